@@ -6,12 +6,17 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W                     # bare: starts its own N child processes
+    python bench.py --gpus 1 --steps 8 --warmup 2 --full              # + sub-benchmarks, rooflines, CPU baselines
 
-The default (mil) line also carries short runs of configs[3] and configs[4] as "gnn" and "vit" sub-objects, each with
-its own roofline and cpu_baseline (--no-sublines to skip).
+A plain run sets up, warms up, times EXACTLY --steps steps and prints ONE JSON line on rank 0: whole-job units/s (bags or
+graphs) with inputs resident in HBM when the timed region starts, and ms_per_step.  --dump-outputs DIR writes what the
+last timed step computed (outputs, loss, parameters and gradients after the step; a fixed seeded sample of the larger
+arrays, 64 MB in all) as DIR/<name>.npy in float32; inputs are seeded, so two builds run with the same arguments can be
+compared file by file.
 
-Prints ONE JSON line on rank 0 (contract in the repo instructions): whole-job units/s (bags or graphs) with
-inputs resident in HBM when the timed region starts, plus
+--full adds everything else: short runs of configs[3], configs[4], the teacher step, the k-NN build and the whole chain
+as "gnn", "vit", "teacher", "knn" and "pipeline" sub-objects of the default (mil) line (--no-sublines to skip), and on
+every line
   "roofline":     the dominant kernel's algorithmic FLOP/s (mil: implicit-GEMM convolution forward + data gradient
                   vs the dense bf16 MFMA peak) or GB/s (gnn: the segmented-sum SpMM vs the HBM peak), from HIP events
                   around every launch of that C-ABI entry INSIDE the timed region, on the stream it is launched on;
@@ -237,7 +242,8 @@ def run_mil(args, world, rank, dev):
                + 0.25 * labels[s].view(B, 1, 1, 1, 1).float()).to(torch.bfloat16) for s in range(n_sets)]
     radiom = [torch.randn(B, R, device=dev, generator=g) + 0.25 * labels[s].view(B, 1).float() for s in range(n_sets)]
 
-    timer = KernelTimer.get()
+    timer = KernelTimer.get() if args.full else None
+    last = {}
 
     def step(i):
         s = i % n_sets
@@ -249,28 +255,35 @@ def run_mil(args, world, rank, dev):
             ops.backward(loss)
         sync.finish()
         opt.step(grad_scale=1.0 / world)
+        last.update((k, v.detach()) for k, v in out.items())
         return loss
 
     # two untimed settle steps (allocator growth, kernel attribute setup) precede the W warm-up steps
     for i in range(2 + args.warmup):
         step(i)
     elapsed, host_s, loss = timed_region(step, args, world, dev, timer, list(CONV_ENTRIES), 2 + args.warmup)
-    conv = timer.stop()
+    if args.dump_outputs and rank == 0:
+        running = torch.cat([v.reshape(-1).float() for k, v in model.state_dict().items() if "running_" in k])
+        dump_outputs(args.dump_outputs, dict(last, loss=loss, params=flat.data, grads=flat.grad, bn_running_stats=running))
     final_loss = float(loss.detach())
-    split = instrumented_pass(step, timer, dev, world, start=2 + args.warmup + args.steps)
+    if args.full:
+        conv = timer.stop()
+        split = instrumented_pass(step, timer, dev, world, start=2 + args.warmup + args.steps)
     ddp.average_buffers(model)           # BatchNorm running statistics are per rank during training
 
     if rank != 0:
         return None
-    conv_ms = sum(ms for _n, _a, ms in conv)
-    conv_fl = sum(conv_entry_flops(n_, a) for n_, a, _ms in conv)
-    n_launch = len(conv)
-    achieved = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
     line = base_line("bags/sec (train step) @ 64x224x224 patches/bag", "bags/s", world * B * args.steps / elapsed,
                      world, args, elapsed, "bf16")
     line["config"] = {"workload": WORKLOAD_MIL, "bags_per_step_per_gpu": B, "global_bags_per_step": B * world,
                       "patches_per_bag": K, "patch": f"3x{S}x{S}", "radiomics_dim": R, "parallelism": f"dp{world}",
                       "host_enqueue_ms_per_step": host_s * 1e3 / args.steps, "final_loss": final_loss}
+    if not args.full:
+        return line
+    conv_ms = sum(ms for _n, _a, ms in conv)
+    conv_fl = sum(conv_entry_flops(n_, a) for n_, a, _ms in conv)
+    n_launch = len(conv)
+    achieved = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
     line["roofline"] = {
         "bound": "mfma", "kernel": "C-ABI entries isic_conv2d_igemm_bf16 + isic_conv2d_igemm_maskadd_bf16 + "
                                    "isic_conv2d_dgrad_bnbwd_bf16 + isic_conv2d_dgrad_pair_bf16 (forward + data gradient of every "
@@ -329,19 +342,33 @@ def run_vit(args, world, rank, dev):
     enc = ViTSmallEncoder(img_size=S).to(dev)
     gen = torch.Generator(device=dev).manual_seed(99 + rank)
     x = torch.randn(n_img, 3, S, S, device=dev, generator=gen)
-    timer = KernelTimer.get()
+    timer = KernelTimer.get() if args.full else None
+    last = {}
 
     def step(i):
-        return enc.run_tokens(x).sum()
+        last["tokens"] = enc.run_tokens(x)
+        return last["tokens"].sum()
 
     for i in range(2 + args.warmup):
         step(i)
-    elapsed, host_s, _ = timed_region(step, args, world, dev, timer, ["isic_gemm_f16", "isic_gemm_f16_stats", "isic_gemm_f16_ln"],
-                                      2 + args.warmup)
-    gemm = timer.stop()
-    split = instrumented_pass(step, timer, dev, world, start=0)
+    elapsed, host_s, total = timed_region(step, args, world, dev, timer, ["isic_gemm_f16", "isic_gemm_f16_stats",
+                                                                          "isic_gemm_f16_ln"], 2 + args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, tokens_sum=total))
+    if args.full:
+        gemm = timer.stop()
+        split = instrumented_pass(step, timer, dev, world, start=0)
     if rank != 0:
         return None
+    line = base_line("images/sec (ViT-S/16 fp16 patch-encoder forward) @ 224x224", "images/s",
+                     world * n_img * args.steps / elapsed, world, args, elapsed, "f16")
+    line["scaling"] = "weak"
+    line["config"] = {"workload": WORKLOAD_VIT, "images_per_step_per_gpu": n_img, "image": f"3x{S}x{S}", "tokens": enc.tokens,
+                      "dim": enc.dim, "depth": enc.depth, "heads": enc.heads, "parallelism": f"replicas{world}",
+                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps,
+                      "whole_forward_algorithmic_tflops": enc.flops_per_image() * n_img * args.steps / elapsed / 1e12}
+    if not args.full:
+        return line
 
     def mnk(name, a):
         """(M, N, K, residual rows read, fp32 statistics bytes) of one launch of the three product entries"""
@@ -363,13 +390,6 @@ def run_vit(args, world, rank, dev):
         by += 2.0 * (M * K + N * K + M * N + rr * N) + sb
     achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
     gbs = by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    line = base_line("images/sec (ViT-S/16 fp16 patch-encoder forward) @ 224x224", "images/s",
-                     world * n_img * args.steps / elapsed, world, args, elapsed, "f16")
-    line["scaling"] = "weak"
-    line["config"] = {"workload": WORKLOAD_VIT, "images_per_step_per_gpu": n_img, "image": f"3x{S}x{S}", "tokens": enc.tokens,
-                      "dim": enc.dim, "depth": enc.depth, "heads": enc.heads, "parallelism": f"replicas{world}",
-                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps,
-                      "whole_forward_algorithmic_tflops": enc.flops_per_image() * n_img * args.steps / elapsed / 1e12}
     # Which roofline binds these GEMMs?  Their arithmetic intensity is 2MNK / 2(MK + NK + MN [+ MN]) = 130-310 FLOP per
     # algorithmic byte at N, K in {384, 1152, 1536} -- below the machine balance of 2.5 PFLOP/s / 8 TB/s = 312 (403 against
     # the 6.2 TB/s a copy reaches): every one of them is HBM-bound by its own operands, so `bound` is "hbm" and the MFMA
@@ -475,7 +495,7 @@ def run_gnn(args, world, rank, dev):
     store = T.GraphStore(records, dev, True, mode=model.graph_mode)
     gidx = torch.Generator(device=dev).manual_seed(7 + rank)
 
-    timer = KernelTimer.get()
+    timer = KernelTimer.get() if args.full else None
 
     # One train step.  On one GPU the whole step (forward, autograd backward, AdamW) is captured into a hipGraph and
     # replayed: ~50 C-ABI launches + ~30 torch kernels for ~1.3 ms of GPU work cost the host more to enqueue than the GPU
@@ -525,11 +545,17 @@ def run_gnn(args, world, rank, dev):
         step(i)
     SPMM = ["isic_spmm_csr_f32", "isic_gemm_f32_ws"]      # the roofline entry + the fp32 GEMMs (second-largest class)
     elapsed, host_s, loss = timed_region(step, args, world, dev, timer, SPMM, 2 + args.warmup)
-    spmm = timer.stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": opt.flat.data, "grads": opt.flat.grad})
     final_loss = float(loss.detach())
     # l1 norm of the parameters after settle + warm-up + timed steps: equal (to the AdamW step-size rounding, 1 ulp) for the
     # captured and the eager launch of the same run -- what the 2-rank rehearsal test compares
     param_l1 = float(opt.flat.data.double().abs().sum())
+    if not args.full:
+        if rank != 0:
+            return None
+        return gnn_line(args, world, elapsed, host_s, final_loss, param_l1, launch_label)
+    spmm = timer.stop()
     measured = "HIP events inside the timed region"
     if captured is not None:
         # a replayed graph has no per-launch host call to bracket: the SAME step is run eagerly right after the timed
@@ -583,12 +609,7 @@ def run_gnn(args, world, rank, dev):
     in_step_ms = ms / max(n_launch, 1)
     achieved = Gs * per_graph / (in_step_ms * 1e-3) / 1e9 if in_step_ms > 0 else 0.0
     b2b = Gs * per_graph * batch_n / (batch_ms * 1e-3) / 1e9 if batch_ms > 0 else 0.0
-    line = base_line("graphs/sec (GNN train step) @ 196-node k-NN patch graphs", "graphs/s",
-                     world * Gs * args.steps / elapsed, world, args, elapsed, "f32")
-    line["config"] = {"workload": WORKLOAD_GNN, "graphs_per_step_per_gpu": Gs, "nodes": N, "feat": D,
-                      "node_radiomics": args.node_radiomics, "hidden": F,
-                      "layers": L, "knn_k": k, "parallelism": f"dp{world}",
-                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps, "final_loss": final_loss}
+    line = gnn_line(args, world, elapsed, host_s, final_loss, param_l1, launch_label)
     line["roofline"] = {
         "bound": "hbm", "kernel": "C-ABI entry isic_spmm_csr_f32 (GCNConv aggregation: neighbour gather + segmented sum, "
                                   "forward and transposed backward)",
@@ -609,10 +630,21 @@ def run_gnn(args, world, rank, dev):
                      "launches": len(gemms), "ms_per_step": gemm_ms / max(args.steps, 1)},
     }
     line["kernel_time"] = split
-    line["config"]["step_launch"] = launch_label
-    line["config"]["param_l1_after_run"] = param_l1
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_gnn(model, records, args.cpu_budget_s)
+    return line
+
+
+def gnn_line(args, world, elapsed, host_s, final_loss, param_l1, launch_label):
+    """The configs[3] line without what --full adds."""
+    Gs = args.graphs_per_step
+    line = base_line("graphs/sec (GNN train step) @ 196-node k-NN patch graphs", "graphs/s",
+                     world * Gs * args.steps / elapsed, world, args, elapsed, "f32")
+    line["config"] = {"workload": WORKLOAD_GNN, "graphs_per_step_per_gpu": Gs, "nodes": args.nodes,
+                      "feat": args.feat + args.node_radiomics, "node_radiomics": args.node_radiomics, "hidden": args.hidden,
+                      "layers": args.gnn_layers, "knn_k": args.knn_k, "parallelism": f"dp{world}",
+                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps, "final_loss": final_loss,
+                      "step_launch": launch_label, "param_l1_after_run": param_l1}
     return line
 
 
@@ -693,7 +725,7 @@ def run_teacher(args, world, rank, dev, H=None, A=None, with_cpu=True):
     xs = [(torch.randn(B, N, D, device=dev, generator=gen) + 0.25 * ys[s].view(B, 1, 1).float()).reshape(B * N, D)
           for s in range(n_sets)]
     offs = BagOffsets.uniform(B, N, dev)
-    timer = KernelTimer.get()
+    timer = KernelTimer.get() if args.full else None
     use_graph = not args.no_graph
     clock = G.StepClock(dev).attach(model, opt) if use_graph else None
 
@@ -730,18 +762,31 @@ def run_teacher(args, world, rank, dev, H=None, A=None, with_cpu=True):
     for i in range(args.warmup):
         step(i)
     elapsed, host_s, loss = timed_region(step, args, world, dev, timer, [], 0)
-    timer.stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": opt.flat.data, "grads": opt.flat.grad})
     final_loss = float(loss.detach())
-    # per-entry durations: the same steps launched eagerly right after the timed region, events around every launch
-    n_inst = min(args.steps, 20)
-    torch.cuda.synchronize()
-    timer.start(None)
-    for i in range(n_inst):
-        eager_step(i)
-    torch.cuda.synchronize()
-    rec = timer.stop()
+    if args.full:
+        timer.stop()
+        # per-entry durations: the same steps launched eagerly right after the timed region, events around every launch
+        n_inst = min(args.steps, 20)
+        torch.cuda.synchronize()
+        timer.start(None)
+        for i in range(n_inst):
+            eager_step(i)
+        torch.cuda.synchronize()
+        rec = timer.stop()
     if rank != 0:
         return None
+    line = base_line("bags/sec (MIL teacher train step) @ 196x768 fp32 latents", "bags/s", world * B * args.steps / elapsed,
+                     world, args, elapsed, "f32")
+    line["config"] = {"workload": WORKLOAD_TEACHER, "bags_per_step_per_gpu": B, "patches_per_bag": N, "feat": D, "hidden": H,
+                      "att_dim": A, "params": sum(p.numel() for p in model.parameters()), "parallelism": f"dp{world}",
+                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps, "final_loss": final_loss,
+                      "step_launch": launch_label}
+    if not args.full:
+        if clock is not None:
+            G.StepClock.detach(model, opt)
+        return line
     split = split_by_class(rec, n_inst)
     head = [(n_, a, m) for n_, a, m in rec if n_.startswith(("isic_gemm_f32", "isic_attn_pool", "isic_colsum"))]
     head_ms = sum(m for _n, _a, m in head) / n_inst
@@ -754,12 +799,6 @@ def run_teacher(args, world, rank, dev, H=None, A=None, with_cpu=True):
     bwd_b = N * D * 4
     step_bytes = B * (fwd_b + bwd_b)
     gbs = step_bytes / (head_ms * 1e-3) / 1e9 if head_ms > 0 else 0.0
-    line = base_line("bags/sec (MIL teacher train step) @ 196x768 fp32 latents", "bags/s", world * B * args.steps / elapsed,
-                     world, args, elapsed, "f32")
-    line["config"] = {"workload": WORKLOAD_TEACHER, "bags_per_step_per_gpu": B, "patches_per_bag": N, "feat": D, "hidden": H,
-                      "att_dim": A, "params": sum(p.numel() for p in model.parameters()), "parallelism": f"dp{world}",
-                      "host_enqueue_ms_per_step": host_s * 1e3 / args.steps, "final_loss": final_loss,
-                      "step_launch": launch_label}
     line["roofline"] = {
         "bound": "hbm", "kernel": "the head's C-ABI entries of one train step: isic_gemm_f32(_ws) (x W1^T + ReLU + dropout, "
                                   "h W2^T, their data / weight gradients), isic_attn_pool_fwd / _bwd, column sums",
@@ -846,7 +885,7 @@ def run_knn(args, world, rank, dev):
     xs = [torch.randn(G_, N, D, device=dev, generator=gen) for _ in range(n_sets)]
     offs = BagOffsets.uniform(G_, N, dev)
     src = {k: torch.arange(N, device=dev).view(1, N, 1).expand(G_, N, k).reshape(G_, -1) for k in ks}
-    timer = KernelTimer.get()
+    timer = KernelTimer.get() if args.full else None
 
     def step(i):
         nn = knn_indices(xs[i % n_sets].view(-1, D), offs, max(ks)).view(G_, N, max(ks))
@@ -857,24 +896,30 @@ def run_knn(args, world, rank, dev):
         return torch.stack([src[8], nn.reshape(G_, -1)], dim=1)
     for i in range(2 + args.warmup):
         step(i)
-        step_k8(i)
-    elapsed, host_s, _ = timed_region(step, args, world, dev, timer, ["isic_knn_graph"], 0)
-    rec = timer.stop()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step_k8(i)
-    torch.cuda.synchronize()
-    k8_elapsed = time.perf_counter() - t0
+        if args.full:
+            step_k8(i)
+    elapsed, host_s, edges = timed_region(step, args, world, dev, timer, ["isic_knn_graph"], 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"edge_index_knn{k}": e for k, e in edges.items()})
+    if args.full:
+        rec = timer.stop()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            step_k8(i)
+        torch.cuda.synchronize()
+        k8_elapsed = time.perf_counter() - t0
     if rank != 0:
         return None
-    ms = sum(m for _n, _a, m in rec)
-    fl = 2.0 * N * N * D * G_ * len(rec)                       # SURVEY.md 8d: 2 N^2 D per image (59 MFLOP at 196 x 768)
-    achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
     line = base_line("graphs/sec (k-NN adjacency build, all ten k of 03_build_graphs.py) @ 196x768 patch embeddings",
                      "graphs/s", world * G_ * args.steps / elapsed, world, args, elapsed, "f32")
     line["config"] = {"workload": WORKLOAD_KNN, "graphs_per_step_per_gpu": G_, "nodes": N, "feat": D, "k_values": ks,
-                      "parallelism": f"replicas{world}", "host_enqueue_ms_per_step": host_s * 1e3 / args.steps,
-                      "k8_only_graphs_per_s": world * G_ * args.steps / k8_elapsed}
+                      "parallelism": f"replicas{world}", "host_enqueue_ms_per_step": host_s * 1e3 / args.steps}
+    if not args.full:
+        return line
+    line["config"]["k8_only_graphs_per_s"] = world * G_ * args.steps / k8_elapsed
+    ms = sum(m for _n, _a, m in rec)
+    fl = 2.0 * N * N * D * G_ * len(rec)                       # SURVEY.md 8d: 2 N^2 D per image (59 MFLOP at 196 x 768)
+    achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
     line["roofline"] = {
         "bound": "mfma", "kernel": "C-ABI entry isic_knn_graph (row norms + per-image distance products x x^T on "
                                    "v_mfma_f32_16x16x4_f32 + top-16 selection, one launch per step)",
@@ -981,6 +1026,9 @@ def run_pipeline(args, world, rank, dev):
         gnn, outs[0], outs[1], outs[1], "knn8", lr=1e-4, epochs=g_epochs, graphs_per_step=256, num_classes=C, device=dev,
         rng=np.random.RandomState(2)))
     total = sum(stages.values())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tokens": tokens, **{f"{name}_params": torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+                                                              for name, m in (("teacher", teacher), ("gnn", gnn))}})
     if world > 1:
         t = torch.tensor([total], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1031,11 +1079,13 @@ def host_threads():
 
 # ----------------------------------------------------------------------------------------------- shared pieces
 def timed_region(step, args, world, dev, timer, names, first):
-    """EXACTLY ``args.steps`` steps between barrier + synchronize on both sides; MAX over ranks."""
+    """EXACTLY ``args.steps`` steps between barrier + synchronize on both sides; MAX over ranks.  ``timer`` (--full only;
+    None otherwise) brackets the launches of the entries ``names`` with HIP events."""
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.start(names)
+    if timer is not None:
+        timer.start(names)
     t0 = time.perf_counter()
     host_s = 0.0
     loss = None
@@ -1048,7 +1098,8 @@ def timed_region(step, args, world, dev, timer, names, first):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    timer.active = False
+    if timer is not None:
+        timer.active = False
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1073,6 +1124,28 @@ def base_line(metric, unit, value, world, args, elapsed, dtype):
     return {"metric": metric, "value": value, "unit": unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": dtype, "data": "synthetic"}
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``dirname/<name>.npy`` in float32, DUMP_BYTES in all.  The smallest
+    arrays are written whole; one larger than its share of what is left becomes a fixed sample of its flattened elements
+    (seed 0, indices ascending), so the same arguments pick the same elements in every build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES - 1024 * len(arrays)                  # the .npy headers
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        t = t.detach().float()
+        cap = left // (len(items) - i) // 4
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 def main():
@@ -1125,6 +1198,11 @@ def main():
     ap.add_argument("--no-sublines", action="store_true",
                     help="mil: do not attach the short configs[3] (gnn) and configs[4] (vit) runs to the line")
     ap.add_argument("--sub-steps", type=int, default=20, help="timed steps of each attached sub-benchmark")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: sub-benchmarks, rooflines, per-class kernel time, "
+                         "CPU baselines (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, 64 MB in all)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1150,20 +1228,23 @@ def main():
     def run_teacher_both(a, w, r, d):
         """the reference's default head (H128 / A64) with its tuned head (H368 / A772) attached as `tuned`"""
         line = run_teacher(a, w, r, d)
+        if not a.full:
+            return line
         release_device_memory()
-        tuned = run_teacher(a, w, r, d, H=368, A=772)
+        tuned = run_teacher(argparse.Namespace(**dict(vars(a), dump_outputs=None)), w, r, d, H=368, A=772)
         if r == 0:
             line["tuned"] = tuned
         return line
     runners = {"mil": run_mil, "gnn": run_gnn, "vit": run_vit, "teacher": run_teacher_both, "knn": run_knn,
                "pipeline": run_pipeline}
     line = runners[args.config](args, world, rank, dev)
-    if args.config == "mil" and not args.no_sublines:
+    if args.config == "mil" and args.full and not args.no_sublines:
         # BASELINE.json configs[3] and configs[4] ride on the SAME line (the driver parses one line): short runs of the
         # graph step and of the ViT encoder, then the reference's OWN hot loop (the teacher step on resident latents) and the
         # adjacency build of 03, each with its own roofline and cpu_baseline
         sub_args = argparse.Namespace(**vars(args))
         sub_args.steps, sub_args.warmup = args.sub_steps, 3
+        sub_args.dump_outputs = None
         sub_args.cpu_budget_s = min(args.cpu_budget_s, 10.0)
         for name in ("gnn", "vit", "teacher", "knn", "pipeline"):
             release_device_memory()

@@ -147,7 +147,7 @@ def test_bare_multi_gpu_launch_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2", "--warmup", "1",
-           "--bags-per-step", "2", "--patches", "4", "--image-size", "64", "--no-cpu-baseline", "--sub-steps", "2",
+           "--bags-per-step", "2", "--patches", "4", "--image-size", "64", "--full", "--no-cpu-baseline", "--sub-steps", "2",
            "--graphs-per-step", "8", "--images-per-step", "8", "--teacher-bags-per-step", "8", "--knn-graphs-per-step", "16", "--pipeline-images", "48"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])

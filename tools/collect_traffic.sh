@@ -18,9 +18,9 @@ mkdir -p $OUT $R/profiles
 cd /tmp && export TMPDIR=/tmp
 for s in $SECTIONS; do
   case $s in
-    mil) ARGS="--config mil --steps 2 --warmup 1 --bags-per-step $B --no-cpu-baseline --no-sublines" ;;
-    gnn) ARGS="--config gnn --steps 4 --warmup 1 --no-cpu-baseline" ;;
-    vit) ARGS="--config vit --steps 2 --warmup 1 --no-cpu-baseline" ;;
+    mil) ARGS="--config mil --steps 2 --warmup 1 --bags-per-step $B --full --no-cpu-baseline --no-sublines" ;;
+    gnn) ARGS="--config gnn --steps 4 --warmup 1 --full --no-cpu-baseline" ;;
+    vit) ARGS="--config vit --steps 2 --warmup 1 --full --no-cpu-baseline" ;;
   esac
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/$s.$c
