@@ -319,6 +319,30 @@ int isic_edge_heterophily_f32(const float* x, const float* probs, const int32_t*
                               float eps, float* h_kl, float* h_dirichlet, float* h_spatial, float* same_class,
                               void* stream);
 
+#define ISIC_SPECTRAL_MAX_NODES 196
+#define ISIC_SEGMENT_MAX_LEN 16384
+
+/* Algebraic connectivity of the heterophily stage (04_measure_heterophily.py:149-159): per graph g,
+ * lambda2[g] (fp64) = second-smallest eigenvalue of L = I - D^-1/2 A D^-1/2 with A = max(C, C^T), C[i][j] = number of
+ * times the directed edge (i, j) occurs (duplicates are summed, :151-152; element-wise max of counts, :153), self loops
+ * dropped (:117-118), D = row sums, d^-1/2 = 0 for a node of degree 0 (:154-156).  nodes == 1 gives 0.0.
+ * The edges of graph g are src/dst[edge_offsets[g] .. edge_offsets[g+1]) with global node ids (g*nodes + local, as
+ * isic_edge_heterophily_f32).  One workgroup per graph in fp64 (Householder tridiagonalisation in LDS + Sturm
+ * multisection): agrees with a dense fp64 eigensolve to ~1e-15.  1 <= nodes <= ISIC_SPECTRAL_MAX_NODES, else
+ * UNSUPPORTED before any device work.  A graph with an edge id outside the graph, or with decreasing / negative offsets,
+ * gets NaN (no fault); the offsets must lie inside src/dst. */
+int isic_laplacian_lambda2_f64(const int64_t* src, const int64_t* dst, const int64_t* edge_offsets, int G, int nodes,
+                               double* lambda2, void* stream);
+/* Per-image summaries of the heterophily stage (_summarize_image, 04_measure_heterophily.py:172-181): for each measure
+ * m < M and segment g < G of values[M][num_edges] (fp32, row stride num_edges), over values[m][edge_offsets[g] ..
+ * edge_offsets[g+1]): mean[m][g], std[m][g] (population, numpy's ddof=0) and median[m][g] (numpy's: the mean of the two
+ * middle values for an even count), fp64, sums in fp64.  An empty segment gives NaN for all three (np.mean([])).
+ * max_segment is a bound on the segment lengths the caller knows without reading the offsets (e.g. the edges per graph);
+ * max_segment > ISIC_SEGMENT_MAX_LEN -> UNSUPPORTED before any device work.  A segment that is longer than
+ * ISIC_SEGMENT_MAX_LEN all the same, or lies outside [0, num_edges), gets NaN. */
+int isic_segment_stats_f32(const float* values, const int64_t* edge_offsets, int64_t num_edges, int M, int G,
+                           int64_t max_segment, double* mean, double* std, double* median, void* stream);
+
 /* CSR-by-destination with GCN symmetric normalisation (PyG GCNConv.gcn_norm as
  * called at 05_train_gnns.py:82,184-185): existing self loops are dropped, one
  * self loop (weight 1, or the dropped loop's weight) is added per node,

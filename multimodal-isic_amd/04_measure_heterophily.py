@@ -1,7 +1,9 @@
 """Drop-in for the numeric part of the reference's ``04_measure_heterophily.py``: the master summary of the
 heterophily measures over all images, folds and graph variants (`build_master_summary`, 04:188-226), computed on
-the MI355X (``measure_heterophily.py``).  The reference's plotting / aggregation section (04:229-589) and its
-hard-coded cluster paths (04:23,560-561) are out of scope: paths are flags here and the output is one CSV.
+the MI355X (``measure_heterophily.py``): each chunk of images is summarised on the device
+(``heterophily_summary_device``) and copied to the host once.  The reference's plotting / aggregation section
+(04:229-589) and its hard-coded cluster paths (04:23,560-561) are out of scope: paths are flags here and the output
+is one CSV.
 
     python 04_measure_heterophily.py --graph-outputs-root graph_outputs --patch-stats-root patch_stats --out-csv h.csv
 """
@@ -11,6 +13,7 @@ import pickle
 
 import numpy as np
 import pandas as pd
+import torch
 
 import measure_heterophily as mh
 
@@ -35,17 +38,20 @@ def build_master_summary(graph_root, patch_root, images_per_launch=64, device="c
                 for lo in range(0, len(merged), images_per_launch):
                     chunk = merged.iloc[lo:lo + images_per_launch]
                     recs = chunk.to_dict("records")
-                    ems = mh.compute_edge_heterophily_batch(
-                        [r["patch_embeddings"] for r in recs], [r["patch_probs"] for r in recs],
-                        [r["dominant_class"] for r in recs], [mh.edge_index_from_variant(r, variant) for r in recs],
-                        device=device)
-                    for r, em in zip(recs, ems):
-                        kind = "grid" if variant.startswith("grid") else ("knn" if variant.startswith("knn") else "random")
-                        meta = {"model_name": r.get("model_name", model), "fold": int(fold), "split": split,
-                                "image_id": r["image_id"], "label": r.get("label"), "graph_variant": variant,
-                                "graph_type": kind,
-                                "graph_param": None if kind == "grid" else int(variant[len(kind):])}      # 04:211-222
-                        rows.append(mh.summarize_image(em, meta))
+                    dev = torch.device(device)
+                    x = torch.as_tensor(np.stack([np.asarray(r["patch_embeddings"], dtype=np.float32) for r in recs])).to(dev)
+                    pp = torch.as_tensor(np.stack([np.asarray(r["patch_probs"], dtype=np.float32) for r in recs])).to(dev)
+                    dom = torch.as_tensor(np.stack([np.asarray(r["dominant_class"], dtype=np.int32) for r in recs])).to(dev)
+                    eis = [torch.as_tensor(np.asarray(mh.edge_index_from_variant(r, variant), dtype=np.int64)).to(dev)
+                           for r in recs]
+                    summary = mh.heterophily_summary_device(x, pp, dom, eis)      # one copy to the host per chunk
+                    kind = "grid" if variant.startswith("grid") else ("knn" if variant.startswith("knn") else "random")
+                    metas = [{"model_name": r.get("model_name", model), "fold": int(fold), "split": split,
+                              "image_id": r["image_id"], "label": r.get("label"), "graph_variant": variant,
+                              "graph_type": kind,
+                              "graph_param": None if kind == "grid" else int(variant[len(kind):])}      # 04:211-222
+                             for r in recs]
+                    rows.extend(mh.summary_records(summary, metas))
     return pd.DataFrame.from_records(rows)
 
 

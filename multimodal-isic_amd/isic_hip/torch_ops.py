@@ -13,6 +13,7 @@ stream)`` of ``ops.DropoutSpec``; a graph is its CSR tensors), as ``custom_op`` 
     z,att = torch.ops.isic_hip.attn_pool(h, W2, b2, w3, b3, offsets, max_bag, heads)   # multi-head attention pool
     p     = torch.ops.isic_hip.softmax_rows(x)
     loss  = torch.ops.isic_hip.cross_entropy(inp, labels, mode)
+    lam2  = torch.ops.isic_hip.laplacian_lambda2(src, dst, edge_offsets, nodes)         # lambda_2 per graph (fp64)
 
 Reference arithmetic: `utils_g_mil.py:49-97` (MIL head), `05_train_gnns.py:168-217` (GraphMIL forward), `model.py:74-83`.
 The module classes keep calling the ``autograd.Function`` forms (same kernels, less dispatcher overhead per launch, and the
@@ -28,6 +29,7 @@ from torch import Tensor
 from torch.library import custom_op
 
 from . import ops as _o
+from . import spectral as _spectral
 from .lib import call
 
 _EMPTY = lambda t: t.new_empty((0,))        # placeholder for "gradient not needed" outputs (custom ops return tensors)
@@ -355,6 +357,19 @@ def _(a, b, trans_a, trans_b, bias, act):
     M = a.shape[1] if trans_a else a.shape[0]
     N = b.shape[0] if trans_b else b.shape[1]
     return a.new_empty((M, N), dtype=torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------- graph spectrum (no autograd)
+@custom_op("isic_hip::laplacian_lambda2", mutates_args=())
+def laplacian_lambda2(src: Tensor, dst: Tensor, edge_offsets: Tensor, nodes: int) -> Tensor:
+    """lambda_2 of I - D^-1/2 max(A, A^T) D^-1/2 per graph (04_measure_heterophily.py:149-159) [G] fp64; src/dst global
+    node ids, edge_offsets[G+1].  Not differentiable (an eigenvalue of integer edge counts)."""
+    return _spectral.laplacian_lambda2(src, dst, edge_offsets, edge_offsets.numel() - 1, int(nodes))
+
+
+@laplacian_lambda2.register_fake
+def _(src, dst, edge_offsets, nodes):
+    return edge_offsets.new_empty((edge_offsets.shape[0] - 1,), dtype=torch.float64)
 
 
 def graph_tensors(graph):

@@ -76,6 +76,13 @@ class DeviceTeacherOutputs:
         y = self.labels.tolist()
         return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i]} for i in range(len(self))]
 
+    def heterophily_summary(self, variant, fold=0, seed=42):
+        """Per-image heterophily summaries of a graph variant (`04_measure_heterophily.py:172-181`) from the resident
+        tensors: ``measure_heterophily.heterophily_summary_device`` on ``x``, ``patch_probs``, ``dominant_class`` and
+        ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host."""
+        import measure_heterophily as mh
+        return mh.heterophily_summary_device(self.x, self.patch_probs, self.dominant_class, self.edge_index(variant, fold, seed))
+
     # ------------------------------------------------------------------ exports (the reference's pickle schemas)
     def teacher_frame(self):
         """`01_train_mil_teacher.py:69-87`: image_id, label, patch_probs, attention, patch_embeddings."""
