@@ -625,4 +625,8 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #ifdef __cplusplus
 }
 #endif
+
+/* The opt-in MXFP8 inference path of the ViT-S/16 encoder: three more entry points, same conventions. */
+#include "isic_hip_mxfp8.h"
+
 #endif /* ISIC_HIP_H */

@@ -47,6 +47,11 @@ def header_path():
     raise IsicHipError("include/isic_hip.h not found next to the package")
 
 
+def extension_header_paths():
+    """Headers isic_hip.h includes for opt-in paths beyond the drop-in surface (include/isic_hip_mxfp8.h)."""
+    return [os.path.join(os.path.dirname(header_path()), "isic_hip_mxfp8.h")]
+
+
 def test_header_path():
     """include/isic_hip_test.h: test / benchmark-only entry points (kernel variants pinned per call)."""
     return os.path.join(os.path.dirname(header_path()), "isic_hip_test.h")
@@ -88,8 +93,11 @@ class _Lib:
         self.public = set(self.protos)                      # the drop-in ABI (include/isic_hip.h)
         if os.path.exists(test_header_path()):
             self.protos.update(parse_header(test_header_path()))
+        self.extension = {}                                 # opt-in entry points of the headers isic_hip.h includes
+        for p in extension_header_paths():
+            self.extension.update(parse_header(p))
         self.fn = {}
-        for name, (restype, args) in self.protos.items():
+        for name, (restype, args) in list(self.protos.items()) + list(self.extension.items()):
             try:
                 f = getattr(self.cdll, name)
             except AttributeError as e:
@@ -134,7 +142,8 @@ def call(name, *args, stream=None):
     None -> NULL.  Raises ``IsicHipError`` on a non-zero return code."""
     L = lib()
     f = L.fn[name]
-    spec = L.protos[name][1]
+    proto = L.protos.get(name) or L.extension[name]
+    spec = proto[1]
     has_stream = bool(spec) and spec[-1][1] == "stream"
     conv = []
     n_user = len(spec) - (1 if has_stream else 0)
@@ -145,6 +154,6 @@ def call(name, *args, stream=None):
     if has_stream:
         conv.append(current_stream() if stream is None else stream)
     rc = f(*conv)
-    if L.protos[name][0] is ctypes.c_int and rc != 0:
+    if proto[0] is ctypes.c_int and rc != 0:
         raise IsicHipError(f"{name} failed: {ERRORS.get(rc, rc)}", code=rc)
     return rc

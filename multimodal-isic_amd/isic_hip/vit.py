@@ -15,6 +15,16 @@ residual stream (`isic_gemm_f16_ln`) and applies the row's (mean, rstd) in its e
 out of the epilogue of the product that WROTE the stream (`isic_gemm_f16_stats`: patch projection, attn.proj, mlp.fc2).
 ``"stats"`` keeps a statistics-only pass (`isic_row_stats_f16`, LayerNorm's two-pass arithmetic) in place of the epilogue
 sums; ``False`` is the layer-by-layer form above.
+
+``precision="mxfp8"`` (opt-in; the default ``"fp16"`` is the path above, unchanged): the four products of every block run
+on the block-scaled FP8 MFMA (`isic_gemm_mxfp8`, OCP MX E4M3 with one E8M0 scale per 32 elements along K, csrc/mxfp8.hip).
+Per block: LayerNorm quantised straight from fp32 (`isic_layernorm_mxfp8_f16`) -> qkv (fp16 out) -> `isic_attention_f16`
+-> `isic_mxfp8_quantize` -> proj (+ residual, fp16 out) -> LayerNorm -> fc1 + GELU (MXFP8 out: the 1536-wide hidden
+activation crosses HBM as 1 byte + 1/32 scale byte per value) -> fc2 (+ residual, fp16 out).  The patch projection
+(raw pixels, 1.3 % of the FLOPs), the attention and the final LayerNorm stay fp16, and so does the residual stream.  The
+LayerNorm is never folded into the product here: the fold multiplies the RAW stream and subtracts mean * c afterwards, and
+with 3 mantissa bits that cancellation loses the signal of rows with a large offset.  Weights are quantised from the fp32
+masters once per weight version.
 """
 from __future__ import annotations
 
@@ -30,11 +40,18 @@ _F16 = torch.float16
 
 class ViTSmallEncoder(nn.Module):
     def __init__(self, img_size=224, patch=16, in_ch=3, dim=384, depth=12, heads=6, mlp_ratio=4, seed=0,
-                 fold_layernorm=True):
+                 fold_layernorm=True, precision="fp16"):
         super().__init__()
         if fold_layernorm not in (True, False, "stats"):
             raise ValueError("fold_layernorm: True, False or 'stats'")
+        if precision not in ("fp16", "mxfp8"):
+            raise ValueError("precision: 'fp16' or 'mxfp8'")
+        if precision == "mxfp8" and fold_layernorm is not True:
+            raise ValueError("precision='mxfp8' runs its LayerNorms as passes of their own: leave fold_layernorm at its default")
+        if precision == "mxfp8" and dim != 384:
+            raise ValueError("precision='mxfp8': dim 384 only (isic_layernorm_mxfp8_f16)")
         self.fold_layernorm = fold_layernorm
+        self.precision = precision
         if dim % 128 != 0 or dim // heads != 64 or patch % 8 != 0 or img_size % patch != 0:
             raise ValueError("ViTSmallEncoder: dim % 128 == 0, head width 64, patch % 8 == 0, img_size % patch == 0")
         self.img_size, self.patch, self.in_ch, self.dim, self.depth, self.heads = img_size, patch, in_ch, dim, depth, heads
@@ -68,6 +85,8 @@ class ViTSmallEncoder(nn.Module):
             p.requires_grad_(False)                    # frozen, as in save_latent.py:51-53
         self._w16 = None                               # fp16 copies of the matrices, made once per weight version
         self._w16_key = None
+        self._wmx = None                               # MXFP8 (q, s) of the block matrices, made once per weight version
+        self._wmx_key = None
         self.eval()
 
     # ------------------------------------------------------------------ timm-named state_dict
@@ -103,6 +122,7 @@ class ViTSmallEncoder(nn.Module):
                         raise RuntimeError(f"size mismatch for {n}: {tuple(src.shape)} vs {tuple(dst.shape)}")
                     dst.copy_(src)
         self._w16_key = None
+        self._wmx_key = None
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     def train(self, mode=True):
@@ -141,6 +161,26 @@ class ViTSmallEncoder(nn.Module):
         self._w16, self._w16_key = w, key
         return w
 
+    def _prepare_mx(self, device):
+        """(q, s) of every block matrix, quantised on the GPU from the fp32 masters (isic_mxfp8_quantize)."""
+        key = tuple((self._get(n).data_ptr(), self._get(n)._version) for n in self._names)
+        if self._wmx is not None and key == self._wmx_key:
+            return self._wmx
+        w = {}
+        for i in range(self.depth):
+            for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
+                n = f"blocks.{i}.{lin}.weight"
+                p = self._get(n).detach().float().contiguous()
+                if p.device != device:
+                    raise IsicHipError("ViTSmallEncoder: move the module to the GPU first (.to('cuda'))")
+                R, K = p.shape
+                q = torch.empty((R, K), device=device, dtype=torch.uint8)
+                s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
+                call("isic_mxfp8_quantize", p, 1, q, s, R, K)
+                w[n] = (q, s)
+        self._wmx, self._wmx_key = w, key
+        return w
+
     @torch.no_grad()
     def run_tokens(self, images, depth=None):
         """images[N,3,H,W] (fp32; other float types are converted) on the GPU -> tokens[N, 196, 384] fp32."""
@@ -150,6 +190,8 @@ class ViTSmallEncoder(nn.Module):
             raise IsicHipError("ViTSmallEncoder runs on the MI355X only (no CPU fallback)")
         dev = images.device
         w = self._prepare(dev)
+        if self.precision == "mxfp8":
+            return self._run_tokens_mx(images, w, self._prepare_mx(dev), depth)
         x_in = images.float().contiguous()
         N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
         M = N * T
@@ -199,6 +241,43 @@ class ViTSmallEncoder(nn.Module):
             linear_res(hid, f"{b}.mlp.fc2", x2, x, st, self.mlp)
         out = torch.empty((M, D), device=dev, dtype=torch.float32)
         call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, 1e-6)
+        return out.view(N, T, D)
+
+    def _run_tokens_mx(self, images, w, wmx, depth):
+        dev = images.device
+        x_in = images.float().contiguous()
+        N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
+        M = N * T
+        K0 = self.in_ch * self.patch * self.patch
+        eps = 1e-6
+        u8 = torch.uint8
+        rows = torch.empty((M, K0), device=dev, dtype=_F16)
+        call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
+        x = torch.empty((M, D), device=dev, dtype=_F16)
+        call("isic_gemm_f16", rows, w["patch_embed.proj.weight"], w["patch_embed.proj.bias"], w["pos_embed"], x, M, D, K0, 0, T)
+        del rows
+        hq, hs = torch.empty((M, D), device=dev, dtype=u8), torch.empty((M, D // 32), device=dev, dtype=u8)
+        qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
+        att = torch.empty((M, D), device=dev, dtype=_F16)
+        midq, mids = torch.empty((M, self.mlp), device=dev, dtype=u8), torch.empty((M, self.mlp // 32), device=dev, dtype=u8)
+        x2 = torch.empty_like(x)
+
+        def gemm(aq, as_, name, res, out, Nout, K, act, outq=None, outs=None):
+            wq, ws = wmx[name + ".weight"]
+            call("isic_gemm_mxfp8", aq, as_, wq, ws, w[name + ".bias"], res, out, outq, outs, M, Nout, K, act, 0)
+
+        for i in range(self.depth if depth is None else depth):
+            b = f"blocks.{i}"
+            call("isic_layernorm_mxfp8_f16", x, w[f"{b}.norm1.weight"], w[f"{b}.norm1.bias"], hq, hs, M, D, eps)
+            gemm(hq, hs, f"{b}.attn.qkv", None, qkv, 3 * D, D, 0)
+            call("isic_attention_f16", qkv, att, N, T, H, D // H)
+            call("isic_mxfp8_quantize", att, 0, hq, hs, M, D)
+            gemm(hq, hs, f"{b}.attn.proj", x, x2, D, D, 0)
+            call("isic_layernorm_mxfp8_f16", x2, w[f"{b}.norm2.weight"], w[f"{b}.norm2.bias"], hq, hs, M, D, eps)
+            gemm(hq, hs, f"{b}.mlp.fc1", None, None, self.mlp, D, 1, midq, mids)
+            gemm(midq, mids, f"{b}.mlp.fc2", x2, x, D, self.mlp, 0)
+        out = torch.empty((M, D), device=dev, dtype=torch.float32)
+        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, eps)
         return out.view(N, T, D)
 
     def forward(self, images):

@@ -134,10 +134,15 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
             return {"image": img, "mask": m}
         datasets = (DermDataset(df_tv, radiomics=None, transform=transform), DermDataset(df_te, radiomics=None, transform=transform))
     loaders = [DataLoader(d, batch_size=batch_size, shuffle=False) for d in datasets]
+    precision = str(config.get("encoder_precision", "fp16")).lower()
+    if precision not in ("fp16", "mxfp8"):
+        raise ValueError(f"encoder_precision: 'fp16' or 'mxfp8', got {precision!r}")
     if str(config.get("encoder", "resnet18")).lower() in ("vit_s16", "vit-s/16", "vit_small_patch16_224"):
         from isic_hip.vit import ViTSmallEncoder                # BASELINE.json configs[4]: ViT-S/16, fp16, 196 x 384 tokens
-        enc = ViTSmallEncoder().to(device)
+        enc = ViTSmallEncoder(precision=precision).to(device)   # "mxfp8": the opt-in MXFP8 products (isic_hip/vit.py)
     else:
+        if precision != "fp16":
+            raise ValueError("encoder_precision='mxfp8' needs encoder: vit_s16 (the ResNet-18 encoder is bf16 only)")
         enc = ResNet18Encoder().to(device)
     ckpt = os.path.join(os.getcwd(), config.get("model_path", "models"), path)
     if os.path.exists(ckpt):
