@@ -49,6 +49,8 @@ struct GemmF16Args {
   // STATS epilogue (SOUT): per row and (slice, wn) the sum and the sum of squares of the 64 rounded outputs this wave
   // holds -> stats_out[m][2 (N / 128)][2]: the LayerNorm statistics of C without another pass over it
   float* stats_out;
+  // GELU == 3: the pre-activation act^-1(C) of the GELU epilogue, rounded to fp16 -> pre_out[M][N] (the backward's aux)
+  unsigned short* pre_out;
 };
 
 __device__ __attribute__((aligned(256))) unsigned char g_g16_zero_page[256];
@@ -67,6 +69,13 @@ __device__ __forceinline__ float g16_hi(unsigned w) { return (float)__builtin_bi
 // erf-GELU (nn.GELU default, timm).  libm's erff: a hand-rolled Abramowitz-Stegun 7.1.26 with an exact reciprocal was
 // measured SLOWER (1.01 vs 0.93 ms for fc1; no GELU at all: 0.87 ms -- the layer is bound by its 1.2 GB output).
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+// d/dv gelu_erf(v) = Phi(v) + v phi(v)
+__device__ __forceinline__ float gelu_erf_grad(float v) {
+  return 0.5f * (1.f + erff(v * 0.70710678118654752f)) + v * 0.39894228040143268f * __expf(-0.5f * v * v);
+}
+
+// GELU: 0 none, 1 erf-GELU, 2 times gelu'(aux) with aux[M][N] read through the residual path (RES; the data gradient of
+// fc1's output, isic_gemm_f16_dgelu), 3 erf-GELU that also writes the fp16 pre-activation (pre_out; the training forward)
 
 template <int GELU, bool RES, bool LNF, bool SOUT>
 __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
       // instruction writes 8 rows x 128 B instead of 16 rows x 64 B: the stores of this epilogue stream at 5.4 instead of
       // 3.2 TB/s (tests/probes/probe_rw.hip) -- they were 40-50 % of a launch.
       float ps1 = 0.f, ps2 = 0.f;                      // SOUT: sums of the row being emitted
-      auto make = [&](int i, int t, const u32x4& rv) -> u32x4 {
+      auto make = [&](int i, int t, const u32x4& rv, u32x4& pre) -> u32x4 {
         u32x4 v;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -242,11 +251,20 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
           } else {
             c = acc[i][2 * t + h] + bv;
           }
-          if (GELU) {
+          if (GELU == 3) {
+            const f16x2 q0 = {(_Float16)c[0], (_Float16)c[1]}, q1 = {(_Float16)c[2], (_Float16)c[3]};
+            pre[2 * h] = __builtin_bit_cast(unsigned, q0);
+            pre[2 * h + 1] = __builtin_bit_cast(unsigned, q1);
+          }
+          if (GELU == 1 || GELU == 3) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) c[e] = gelu_erf(c[e]);
           }
-          if (RES) {
+          if (GELU == 2) {
+            const unsigned lo = rv[2 * h], hi = rv[2 * h + 1];
+            c[0] *= gelu_erf_grad(g16_lo(lo)); c[1] *= gelu_erf_grad(g16_hi(lo));
+            c[2] *= gelu_erf_grad(g16_lo(hi)); c[3] *= gelu_erf_grad(g16_hi(hi));
+          } else if (RES) {
             const unsigned lo = rv[2 * h], hi = rv[2 * h + 1];
             c[0] += g16_lo(lo); c[1] += g16_hi(lo); c[2] += g16_lo(hi); c[3] += g16_hi(hi);
           }
@@ -271,9 +289,10 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
       for (int i = 0; i < 4; ++i) {
         if (RES && i + 1 < 4) res_row(i + 1, nxt);                       // the next row's residual in flight
         ps1 = ps2 = 0.f;
-        const u32x4 v0 = make(i, 0, cur[0]);
+        u32x4 pre0, pre1;
+        const u32x4 v0 = make(i, 0, cur[0], pre0);
         if (GELU) __builtin_amdgcn_sched_barrier(0);                     // one half at a time: erff's temporaries x 16 values spill
-        const u32x4 v1 = make(i, 1, cur[1]);
+        const u32x4 v1 = make(i, 1, cur[1], pre1);
         if (RES) { cur[0] = nxt[0]; cur[1] = nxt[1]; }
         u32x4 da, db;
         isic_pair_rows(v0, v1, odd, da, db);
@@ -281,6 +300,12 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
         const size_t col = (size_t)chan + (odd ? 32 : 0);
         if (mA < a.M) __builtin_nontemporal_store(da, reinterpret_cast<u32x4*>(a.C + (size_t)mA * a.N + col));
         if (mB < a.M) __builtin_nontemporal_store(db, reinterpret_cast<u32x4*>(a.C + (size_t)mB * a.N + col));
+        if (GELU == 3) {
+          u32x4 pa, pb;
+          isic_pair_rows(pre0, pre1, odd, pa, pb);
+          if (mA < a.M) __builtin_nontemporal_store(pa, reinterpret_cast<u32x4*>(a.pre_out + (size_t)mA * a.N + col));
+          if (mB < a.M) __builtin_nontemporal_store(pb, reinterpret_cast<u32x4*>(a.pre_out + (size_t)mB * a.N + col));
+        }
         if (SOUT) {
           // the four fg lanes of a row hold its 64 columns of this wave: fixed-order butterfly, lane fg == 0 writes
           float s1 = ps1, s2 = ps2;
@@ -355,7 +380,7 @@ int isic_gemm_f16_stats(const uint16_t* A, const uint16_t* W, const float* bias,
   GemmF16Args a;
   a.A = A; a.W = W; a.bias = bias; a.res = residual; a.C = C;
   a.M = M; a.N = N; a.K = K; a.act = act; a.res_rows = residual_rows;
-  a.ln_c = nullptr; a.ln_stats = nullptr; a.ln_parts = 0; a.ln_eps = 0.f; a.stats_out = row_stats;
+  a.ln_c = nullptr; a.ln_stats = nullptr; a.ln_parts = 0; a.ln_eps = 0.f; a.stats_out = row_stats; a.pre_out = nullptr;
   const dim3 grid = g16_plan(a);
   hipStream_t s = as_stream(stream);
   if (row_stats) {                                     // the two producers of a LayerNorm input: residual products
@@ -375,10 +400,38 @@ int isic_gemm_f16_ln(const uint16_t* X, const uint16_t* Wg, const float* bias_b,
   GemmF16Args a;
   a.A = X; a.W = Wg; a.bias = bias_b; a.res = nullptr; a.C = C;
   a.M = M; a.N = N; a.K = K; a.act = act; a.res_rows = 0;
-  a.ln_c = ln_c; a.ln_stats = ln_stats; a.ln_parts = ln_parts; a.ln_eps = eps; a.stats_out = nullptr;
+  a.ln_c = ln_c; a.ln_stats = ln_stats; a.ln_parts = ln_parts; a.ln_eps = eps; a.stats_out = nullptr; a.pre_out = nullptr;
   const dim3 grid = g16_plan(a);
   hipStream_t s = as_stream(stream);
   return act == 1 ? launch_g16<1, false, true, false>(a, grid, s) : launch_g16<0, false, true, false>(a, grid, s);
+}
+
+int isic_gemm_f16_dgelu(const uint16_t* A, const uint16_t* W, const uint16_t* aux, uint16_t* C, int M, int N, int K,
+                        void* stream) {
+  ISIC_CHECK_ARG(M >= 0 && N > 0 && K > 0);
+  if (N % GN != 0 || K % 64 != 0) return ISIC_ERR_UNSUPPORTED;
+  if (M == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(A && W && aux && C);
+  GemmF16Args a;
+  a.A = A; a.W = W; a.bias = nullptr; a.res = aux; a.C = C;
+  a.M = M; a.N = N; a.K = K; a.act = 0; a.res_rows = 0;
+  a.ln_c = nullptr; a.ln_stats = nullptr; a.ln_parts = 0; a.ln_eps = 0.f; a.stats_out = nullptr; a.pre_out = nullptr;
+  const dim3 grid = g16_plan(a);
+  return launch_g16<2, true>(a, grid, as_stream(stream));
+}
+
+int isic_gemm_f16_gelu_pre(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* C, uint16_t* pre, int M, int N,
+                           int K, void* stream) {
+  ISIC_CHECK_ARG(M >= 0 && N > 0 && K > 0);
+  if (N % GN != 0 || K % 64 != 0) return ISIC_ERR_UNSUPPORTED;
+  if (M == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(A && W && C && pre);
+  GemmF16Args a;
+  a.A = A; a.W = W; a.bias = bias; a.res = nullptr; a.C = C;
+  a.M = M; a.N = N; a.K = K; a.act = 1; a.res_rows = 0;
+  a.ln_c = nullptr; a.ln_stats = nullptr; a.ln_parts = 0; a.ln_eps = 0.f; a.stats_out = nullptr; a.pre_out = pre;
+  const dim3 grid = g16_plan(a);
+  return launch_g16<3, false>(a, grid, as_stream(stream));
 }
 
 }  // extern "C"

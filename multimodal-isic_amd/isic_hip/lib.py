@@ -48,8 +48,10 @@ def header_path():
 
 
 def extension_header_paths():
-    """Headers isic_hip.h includes for opt-in paths beyond the drop-in surface (include/isic_hip_mxfp8.h)."""
-    return [os.path.join(os.path.dirname(header_path()), "isic_hip_mxfp8.h")]
+    """Headers isic_hip.h includes for opt-in paths beyond the drop-in surface (include/isic_hip_mxfp8.h,
+    include/isic_hip_vit_train.h)."""
+    inc = os.path.dirname(header_path())
+    return [os.path.join(inc, "isic_hip_mxfp8.h"), os.path.join(inc, "isic_hip_vit_train.h")]
 
 
 def test_header_path():

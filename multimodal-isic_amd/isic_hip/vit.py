@@ -25,6 +25,15 @@ activation crosses HBM as 1 byte + 1/32 scale byte per value) -> fc2 (+ residual
 LayerNorm is never folded into the product here: the fold multiplies the RAW stream and subtracts mean * c afterwards, and
 with 3 mantissa bits that cancellation loses the signal of rows with a large offset.  Weights are quantised from the fp32
 masters once per weight version.
+
+``trainable=True`` (opt-in; the default stays the frozen encoder above, bit for bit): the parameters require grad,
+``train()`` works, and the encoder runs the layer-by-layer form (``fold_layernorm=False``).  Under grad, ``forward`` /
+``forward_tokens`` go through ``_ViTFn``: a forward that saves its activations (about 12 KB per token per block: x, LN1(x), qkv,
+the attention output, x2, LN2(x2), fc1's pre-activation and GELU output, fp16) and a native backward
+(include/isic_hip_vit_train.h) that accumulates into ``param.grad``.  The backward runs in fp16 with a power-of-two loss
+scale S = 2^round(8 - log2 amax(d tokens)), one device -> host read per call; every reduction into a parameter gradient
+multiplies by 1/S in fp32, so gradients are exactly scale-equivariant.  An fp16 overflow is not retried: it reaches the
+gradients as inf / NaN, and the backward checks them once at its end and raises ``FloatingPointError``.
 """
 from __future__ import annotations
 
@@ -40,8 +49,14 @@ _F16 = torch.float16
 
 class ViTSmallEncoder(nn.Module):
     def __init__(self, img_size=224, patch=16, in_ch=3, dim=384, depth=12, heads=6, mlp_ratio=4, seed=0,
-                 fold_layernorm=True, precision="fp16"):
+                 fold_layernorm=None, precision="fp16", trainable=False):
         super().__init__()
+        if trainable and precision != "fp16":
+            raise ValueError("trainable=True: fp16 only (no MXFP8 or bf16 training)")
+        if trainable and fold_layernorm not in (None, False):
+            raise ValueError("trainable=True runs the layer-by-layer form: leave fold_layernorm unset (or False)")
+        if fold_layernorm is None:
+            fold_layernorm = not trainable
         if fold_layernorm not in (True, False, "stats"):
             raise ValueError("fold_layernorm: True, False or 'stats'")
         if precision not in ("fp16", "mxfp8"):
@@ -59,7 +74,7 @@ class ViTSmallEncoder(nn.Module):
         self.tokens = (img_size // patch) ** 2
         if self.tokens > 208:
             raise ValueError("ViTSmallEncoder: at most 208 tokens per image (attention kernel)")
-        self.feature_dim = dim
+        self.feature_dim = self.out_dim = dim
         g = torch.Generator().manual_seed(seed)
 
         def P(*shape, scale):
@@ -81,8 +96,11 @@ class ViTSmallEncoder(nn.Module):
             add(f"{b}.mlp.fc1.weight", P(self.mlp, dim, scale=0.02)); add(f"{b}.mlp.fc1.bias", nn.Parameter(torch.zeros(self.mlp)))
             add(f"{b}.mlp.fc2.weight", P(dim, self.mlp, scale=0.02)); add(f"{b}.mlp.fc2.bias", nn.Parameter(torch.zeros(dim)))
         add("norm.weight", nn.Parameter(torch.ones(dim))); add("norm.bias", nn.Parameter(torch.zeros(dim)))
+        self.trainable = bool(trainable)
         for p in self.parameters():
-            p.requires_grad_(False)                    # frozen, as in save_latent.py:51-53
+            p.requires_grad_(self.trainable)           # frozen by default, as in save_latent.py:51-53
+        self.grad_ready_hook = None                    # callable(list_of_param_names) fired as gradients complete (DDP overlap)
+        self._ws = None                                # backward workspace (slabs of the fixed-order reductions)
         self._w16 = None                               # fp16 copies of the matrices, made once per weight version
         self._w16_key = None
         self._wmx = None                               # MXFP8 (q, s) of the block matrices, made once per weight version
@@ -126,6 +144,8 @@ class ViTSmallEncoder(nn.Module):
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     def train(self, mode=True):
+        if self.trainable:
+            return super().train(mode)
         if mode:
             raise IsicHipError("ViTSmallEncoder is a frozen inference encoder (save_latent.py:51-53): no train() mode")
         return super().train(False)
@@ -133,7 +153,9 @@ class ViTSmallEncoder(nn.Module):
     # ------------------------------------------------------------------ forward
     def _prepare(self, device):
         key = tuple((self._get(n).data_ptr(), self._get(n)._version) for n in self._names)
-        if self._w16 is not None and key == self._w16_key:
+        # trainable: rebuilt on every forward -- an optimiser that writes a flat parameter buffer through a raw pointer
+        # (isic_hip.optim.AdamW) bumps neither data_ptr nor _version (ResNet18Encoder.prepare_weights)
+        if self._w16 is not None and key == self._w16_key and not self.trainable:
             return self._w16
         w = {}
         for n in self._names:
@@ -150,7 +172,7 @@ class ViTSmallEncoder(nn.Module):
                 w[n] = p.float().contiguous()                                      # biases, LayerNorm affine: fp32
         # LayerNorm folded into the product that follows it (module docstring): W' fp16, c from the ROUNDED W' (it has to
         # cancel what the MFMAs sum), b' fp32
-        for i in range(self.depth):
+        for i in range(self.depth if self.fold_layernorm is not False else 0):
             for norm, lin in ((f"blocks.{i}.norm1", f"blocks.{i}.attn.qkv"), (f"blocks.{i}.norm2", f"blocks.{i}.mlp.fc1")):
                 W = self._get(lin + ".weight").detach().float()
                 gamma, beta = w[norm + ".weight"], w[norm + ".bias"]
@@ -280,11 +302,168 @@ class ViTSmallEncoder(nn.Module):
         call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, eps)
         return out.view(N, T, D)
 
+    def forward_tokens(self, images):
+        """tokens[N, 196, 384] fp32; differentiable (``_ViTFn``) when the encoder is trainable and grad is enabled."""
+        if self.trainable and torch.is_grad_enabled():
+            return _ViTFn.apply(images, self, *self.parameters())
+        return self.run_tokens(images)
+
     def forward(self, images):
         """Mean-pooled 384-d feature per image (what a MIL bag of patches consumes)."""
-        return self.run_tokens(images).mean(dim=1)
+        return self.forward_tokens(images).mean(dim=1)
+
+    # ------------------------------------------------------------------ training (trainable=True)
+    def _prepare_train(self, device):
+        """fp16 matrices for the forward and their transposes for the data gradients, from the current masters."""
+        w = self._prepare(device)
+        for i in range(self.depth):
+            for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
+                n = f"blocks.{i}.{lin}.weight"
+                w[n + ".t"] = w[n].t().contiguous()
+        return w
+
+    def _workspace(self, nbytes, device):
+        ws = self._ws
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            ws = self._ws = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
+        return ws
+
+    def _grad(self, name):
+        p = self._get(name)
+        if p.grad is None:
+            p.grad = torch.zeros_like(p.data)
+        return p.grad
+
+    def _fire(self, names):
+        if self.grad_ready_hook is not None:
+            self.grad_ready_hook([n.replace(".", "__") for n in names])
+
+    def run_forward_train(self, images):
+        """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
+        if images.dim() != 4 or images.shape[1] != self.in_ch or images.shape[2] != self.img_size or images.shape[3] != self.img_size:
+            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
+        if not images.is_cuda:
+            raise IsicHipError("ViTSmallEncoder runs on the MI355X only (no CPU fallback)")
+        dev = images.device
+        w = self._prepare_train(dev)
+        x_in = images.float().contiguous()
+        N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
+        M = N * T
+        K0 = self.in_ch * self.patch * self.patch
+        eps = 1e-6
+        f32 = torch.float32
+
+        def e16(*shape):
+            return torch.empty(shape, device=dev, dtype=_F16)
+        rows = e16(M, K0)
+        call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
+        x = e16(M, D)
+        call("isic_gemm_f16", rows, w["patch_embed.proj.weight"], w["patch_embed.proj.bias"], w["pos_embed"], x, M, D, K0, 0, T)
+        blocks = []
+        for i in range(self.depth):
+            b = f"blocks.{i}"
+            st1, h1, qkv, att, x2 = torch.empty((M, 2), device=dev, dtype=f32), e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, D)
+            st2, h2, pre, hid, xo = torch.empty((M, 2), device=dev, dtype=f32), e16(M, D), e16(M, self.mlp), e16(M, self.mlp), e16(M, D)
+            call("isic_row_stats_f16", x, st1, M, D, eps)
+            call("isic_layernorm_f16", x, w[f"{b}.norm1.weight"], w[f"{b}.norm1.bias"], h1, None, M, D, eps)
+            call("isic_gemm_f16", h1, w[f"{b}.attn.qkv.weight"], w[f"{b}.attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
+            call("isic_attention_f16", qkv, att, N, T, H, D // H)
+            call("isic_gemm_f16", att, w[f"{b}.attn.proj.weight"], w[f"{b}.attn.proj.bias"], x, x2, M, D, D, 0, 0)
+            call("isic_row_stats_f16", x2, st2, M, D, eps)
+            call("isic_layernorm_f16", x2, w[f"{b}.norm2.weight"], w[f"{b}.norm2.bias"], h2, None, M, D, eps)
+            call("isic_gemm_f16_gelu_pre", h2, w[f"{b}.mlp.fc1.weight"], w[f"{b}.mlp.fc1.bias"], hid, pre, M, self.mlp, D)
+            call("isic_gemm_f16", hid, w[f"{b}.mlp.fc2.weight"], w[f"{b}.mlp.fc2.bias"], x2, xo, M, D, self.mlp, 0, 0)
+            blocks.append(dict(x=x, st1=st1, h1=h1, qkv=qkv, att=att, x2=x2, st2=st2, h2=h2, pre=pre, hid=hid))
+            x = xo
+        stf = torch.empty((M, 2), device=dev, dtype=f32)
+        call("isic_row_stats_f16", x, stf, M, D, eps)
+        out = torch.empty((M, D), device=dev, dtype=f32)
+        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, eps)
+        tape = dict(N=N, rows=rows, blocks=blocks, x=x, stf=stf, w=w)
+        return out.view(N, T, D), tape
+
+    def run_backward(self, tape, dtok):
+        """Accumulates every parameter gradient into ``param.grad`` from d loss / d tokens[N, T, D]."""
+        w, N = tape["w"], tape["N"]
+        T, D, Hm = self.tokens, self.dim, self.mlp
+        M = N * T
+        dev = dtok.device
+        dtok = dtok.float().contiguous()
+        amax = float(dtok.abs().amax())                  # the backward's one device -> host read before its final check
+        if not math.isfinite(amax):
+            raise FloatingPointError("ViTSmallEncoder backward: the incoming gradient is not finite")
+        S = 2.0 ** round(8 - math.log2(amax)) if amax > 0 else 1.0
+        s = 1.0 / S
+        nb = 0
+        for (n_, k_) in ((3 * D, D), (D, D), (Hm, D), (D, Hm), (D, self.in_ch * self.patch ** 2)):
+            nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, n_, k_))
+        nb = max(nb, call("isic_layernorm_bwd_f16_workspace_bytes", M, D), call("isic_colsum_f16_workspace_bytes", N, T * D))
+        ws = self._workspace(nb, dev)
+
+        def wgrad(dy, xin, name, Nout, K):
+            call("isic_gemm_f16_wgrad", dy, xin, self._grad(name + ".weight"), self._grad(name + ".bias"), M, Nout, K, s, 1,
+                 ws, ws.numel())
+
+        def ln_bwd(dy, dy_f32, mul, xin, st, norm, g_in, g, g16):
+            call("isic_layernorm_bwd_f16", dy, dy_f32, mul, xin, st, w[norm + ".weight"], g_in, g, g16,
+                 self._grad(norm + ".weight"), self._grad(norm + ".bias"), M, D, s, 1, ws, ws.numel())
+
+        g = torch.empty((M, D), device=dev, dtype=torch.float32)          # d loss / d residual stream, x S, fp32
+        g16 = torch.empty((M, D), device=dev, dtype=_F16)
+        ln_bwd(dtok, 1, S, tape["x"], tape["stf"], "norm", None, g, g16)
+        self._fire(["norm.weight", "norm.bias"])
+        dmid = torch.empty((M, Hm), device=dev, dtype=_F16)
+        dD = torch.empty((M, D), device=dev, dtype=_F16)
+        dqkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
+        for i in range(self.depth - 1, -1, -1):
+            b, sv = f"blocks.{i}", tape["blocks"][i]
+            wgrad(g16, sv["hid"], f"{b}.mlp.fc2", D, Hm)
+            call("isic_gemm_f16_dgelu", g16, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hm, D)
+            wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hm, D)
+            call("isic_gemm_f16", dmid, w[f"{b}.mlp.fc1.weight.t"], None, None, dD, M, D, Hm, 0, 0)
+            ln_bwd(dD, 0, 1.0, sv["x2"], sv["st2"], f"{b}.norm2", g, g, g16)
+            wgrad(g16, sv["att"], f"{b}.attn.proj", D, D)
+            call("isic_gemm_f16", g16, w[f"{b}.attn.proj.weight.t"], None, None, dD, M, D, D, 0, 0)
+            call("isic_attention_bwd_f16", sv["qkv"], sv["att"], dD, dqkv, N, T, self.heads, D // self.heads)
+            wgrad(dqkv, sv["h1"], f"{b}.attn.qkv", 3 * D, D)
+            call("isic_gemm_f16", dqkv, w[f"{b}.attn.qkv.weight.t"], None, None, dD, M, D, 3 * D, 0, 0)
+            ln_bwd(dD, 0, 1.0, sv["x"], sv["st1"], f"{b}.norm1", g, g, g16)
+            tape["blocks"][i] = None                      # its activations can go
+            self._fire([f"{b}.{n}" for n in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias",
+                                                "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias",
+                                                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")])
+        wgrad(g16, tape["rows"], "patch_embed.proj", D, self.in_ch * self.patch ** 2)
+        call("isic_colsum_f16", g16, self._grad("pos_embed"), N, T * D, s, 1, ws, ws.numel())
+        self._fire(["patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed"])
+        norms = torch._foreach_norm([self._get(n).grad for n in self._names])
+        if not bool(torch.isfinite(torch.stack(norms)).all()):
+            raise FloatingPointError("ViTSmallEncoder backward: non-finite parameter gradient (fp16 overflow in the backward, "
+                                     "or a non-finite gradient accumulated earlier)")
+
+    def train_flops_per_image(self):
+        """Forward + backward products (the patch projection has no data gradient)."""
+        T, D = self.tokens, self.dim
+        return 3 * self.flops_per_image() - 2 * T * D * self.in_ch * self.patch ** 2
 
     def flops_per_image(self):
         T, D, Hm = self.tokens, self.dim, self.mlp
         per_block = 2 * T * (D * 3 * D + D * D + 2 * D * Hm) + 4 * T * T * D
         return 2 * T * D * self.in_ch * self.patch ** 2 + self.depth * per_block
+
+
+class _ViTFn(torch.autograd.Function):
+    """Autograd edge: tokens -> encoder parameter gradients.  The parameters are passed as inputs only so that autograd
+    schedules this node; the kernels accumulate their gradients in place (``param.grad``), hence ``None`` is returned."""
+
+    @staticmethod
+    def forward(ctx, images, enc, *params):
+        tok, tape = enc.run_forward_train(images)
+        ctx.enc, ctx.tape = enc, tape
+        return tok
+
+    @staticmethod
+    def backward(ctx, dtok):
+        enc, tape = ctx.enc, ctx.tape
+        ctx.tape = None
+        enc.run_backward(tape, dtok)
+        return (None, None) + tuple(None for _ in enc.parameters())
