@@ -632,5 +632,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_vit_train.h"
 /* The convolutional front of the ConvMAE-Base patch encoder: more entry points, same conventions. */
 #include "isic_hip_convmae.h"
+/* Training of the ConvMAE-Base encoder (backward of its convolutional front): more entry points, same conventions. */
+#include "isic_hip_convmae_train.h"
 
 #endif /* ISIC_HIP_H */

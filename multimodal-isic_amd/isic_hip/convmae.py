@@ -6,7 +6,7 @@ The reference builds ``convmae_convvit_base_patch16_dec512d8b(with_decoder=False
 ``models_convmae.py`` / ``vision_transformer.py``), which neither the reference nor this tree vendors: PARITY IS UNPINNED,
 as for the ViT-S/16 (isic_hip/vit.py).  ``tests/convmae_ref.py`` is the fp32 torch-CPU restatement it is checked against.
 Parameter names and shapes are the checkpoint's, so a reference checkpoint loads (convolution weights keep their OIHW
-shapes in the state dict).  Inference only, frozen.
+shapes in the state dict).  Frozen by default; ``trainable=True`` fine-tunes it (below).
 
     patch_embed1   Conv2d(3->256, k4 s4) -> LayerNorm -> GELU                       56 x 56 x 256
     blocks1.0-1    CBlock(256): x += conv2(dw5x5(conv1(LN1(x)))); x += fc2(GELU(fc1(LN2(x))))   (1x1 convs, hidden 1024)
@@ -40,6 +40,18 @@ ViT-B stage on ``isic_gemm_f16_ln`` / ``_stats`` and ``isic_attention_f16``.  No
 (``isic_row_stats_f16`` for the first block of a stage, whose input a LayerNorm + GELU wrote).  ``False``: every pre-norm
 is a pass of ``isic_layernorm_add_f16`` followed by a plain product -- the form to compare against when a pretrained
 stream carries rows with large offsets, where the fold's E[x^2] - mean^2 cancels.
+
+``trainable=True`` (opt-in; the default stays the frozen encoder above, bit for bit): the parameters require grad,
+``train()`` works (no dropout or drop-path: the mode changes no arithmetic) and the encoder runs the layer-by-layer form
+(``fold_layernorm=False``).  Under grad, ``forward`` / ``forward_tokens`` go through ``_ConvMAEFn``: a forward that is
+bitwise ``run_tokens`` of the unfolded form and saves its activations (fp16: per CBlock x, LN1(x), conv1's output, the
+depthwise output, x2, LN2(x2), fc1's pre-activation and GELU output; per ViT block the ViT-S set; the three PatchEmbed
+convolution outputs and the two stage outputs; about 0.12 GB per image, 31 GB at 256 images), and a native backward
+(include/isic_hip_convmae_train.h + include/isic_hip_vit_train.h) that accumulates into ``param.grad``.  The backward
+runs in fp16 under a power-of-two loss scale S = 2^round(8 - log2 amax(d tokens)), one device -> host read per call;
+every reduction into a parameter gradient multiplies by 1/S in fp32, so gradients are exactly scale-equivariant.  An
+fp16 overflow is not retried: the backward checks the gradients once at its end and raises ``FloatingPointError``.  The
+training forward does not chunk the batch (``max_batch`` applies to ``run_tokens``).
 
 Memory: the batch runs in chunks of at most ``max_batch`` images (default 256); stage 1 holds about 15 MB of fp16
 activations per image of a chunk (the fc1 output alone is 3136 x 1024 x 2 bytes), 3.9 GB at 256 images.  An image's
@@ -122,8 +134,15 @@ class ConvMAEBaseEncoder(nn.Module):
     img_size, in_ch, tokens = 224, 3, 196
     dims, depths, grids, patches = (256, 384, 768), (2, 2, 11), (56, 28, 14), (4, 2, 2)
 
-    def __init__(self, seed=0, fold_layernorm=True, ln_eps=1e-6, conv_ln_eps=1e-5, heads=12, mlp_ratio=4, max_batch=256):
+    def __init__(self, seed=0, fold_layernorm=None, ln_eps=1e-6, conv_ln_eps=1e-5, heads=12, mlp_ratio=4, max_batch=256,
+                 trainable=False):
         super().__init__()
+        if trainable not in (True, False):
+            raise ValueError("trainable: True or False")
+        if trainable and fold_layernorm not in (None, False):
+            raise ValueError("trainable=True runs the layer-by-layer form: leave fold_layernorm unset (or False)")
+        if fold_layernorm is None:
+            fold_layernorm = not trainable
         if fold_layernorm not in (True, False):
             raise ValueError("fold_layernorm: True or False")
         if max_batch < 1:
@@ -146,8 +165,11 @@ class ConvMAEBaseEncoder(nn.Module):
         self.blocks3 = nn.ModuleList([_Block(d3, d3 * mlp_ratio, ln_eps) for _ in range(self.depths[2])])
         self.norm = nn.LayerNorm(d3, eps=ln_eps)
         self._seeded_init(seed)
+        self.trainable = bool(trainable)
         for p in self.parameters():
-            p.requires_grad_(False)                     # frozen, as in save_latent.py:51-53
+            p.requires_grad_(self.trainable)            # frozen by default, as in save_latent.py:51-53
+        self.grad_ready_hook = None                     # callable(list_of_param_names) fired as gradients complete (DDP overlap)
+        self._ws = None                                 # backward workspace (slabs of the fixed-order reductions)
         self._w16, self._w16_key = None, None
         self.eval()
 
@@ -164,6 +186,8 @@ class ConvMAEBaseEncoder(nn.Module):
                     p.copy_(torch.randn(p.shape, generator=g) / math.sqrt(p[0].numel()))
 
     def train(self, mode=True):
+        if self.trainable:
+            return super().train(mode)
         if mode:
             raise IsicHipError("ConvMAEBaseEncoder is a frozen inference encoder (save_latent.py:51-53): no train() mode")
         return super().train(False)
@@ -179,7 +203,9 @@ class ConvMAEBaseEncoder(nn.Module):
     def _prepare(self, device):
         params = list(self.parameters())
         key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._w16 is not None and key == self._w16_key:
+        # trainable: rebuilt on every forward -- an optimiser that writes a flat parameter buffer through a raw pointer
+        # (isic_hip.optim.AdamW) bumps neither data_ptr nor _version (ViTSmallEncoder._prepare)
+        if self._w16 is not None and key == self._w16_key and not self.trainable:
             return self._w16
         if any(p.device != device for p in params):
             raise IsicHipError("ConvMAEBaseEncoder: move the module to the GPU first (.to('cuda'))")
@@ -368,13 +394,313 @@ class ConvMAEBaseEncoder(nn.Module):
             linear_res(hid, f"{b}.mlp.fc2", x2, x, st, Hd)
         return x
 
-    def forward_tokens(self, images):
-        """tokens[N, 196, 768] fp32 (frozen: no autograd)."""
-        return self.run_tokens(images)
+    def forward_tokens(self, images, depth=None):
+        """tokens[N, 196, 768] fp32; differentiable (``_ConvMAEFn``) when the encoder is trainable and grad is enabled."""
+        if self.trainable and torch.is_grad_enabled():
+            return _ConvMAEFn.apply(images, self, depth, *self.parameters())
+        return self.run_tokens(images, depth=depth)
 
     def forward(self, images):
         """Mean-pooled 768-d feature per image (what a MIL bag of patches consumes)."""
         return self.forward_tokens(images).mean(dim=1)
+
+    # ------------------------------------------------------------------ training (trainable=True)
+    def _check(self, images, depth):
+        if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_ch, self.img_size, self.img_size):
+            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
+        if not images.is_cuda:
+            raise IsicHipError("ConvMAEBaseEncoder runs on the MI355X only (no CPU fallback)")
+        depth = tuple(self.depths) if depth is None else tuple(depth)
+        if len(depth) != 3 or any(not 0 <= d <= m for d, m in zip(depth, self.depths)):
+            raise ValueError(f"depth: three block counts within {self.depths}")
+        return depth
+
+    def _prepare_train(self, device):
+        """fp16 matrices for the forward, their transposes for the data gradients and the depthwise taps reversed."""
+        w = self._prepare(device)
+        for k in [k for k, v in w.items() if k.endswith(".weight") and v.dtype == _F16 and k != "patch_embed1.proj.weight"]:
+            w[k + ".t"] = w[k].t().contiguous()
+        for s, stage in ((0, "blocks1"), (1, "blocks2")):
+            for i in range(self.depths[s]):
+                w[f"{stage}.{i}.attn.weight.rev"] = w[f"{stage}.{i}.attn.weight"].flip(0).contiguous()
+        return w
+
+    def run_forward_train(self, images, depth=None):
+        """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
+        depth = self._check(images, depth)
+        dev = images.device
+        w = self._prepare_train(dev)
+        img = images.float().contiguous()
+        n = img.shape[0]
+        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
+        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        ceps = self.conv_ln_eps
+
+        def e16(*shape):
+            return torch.empty(shape, device=dev, dtype=_F16)
+
+        def patch_embed(rows, name, M, C, K):
+            t, y = e16(M, C), e16(M, C)
+            call("isic_gemm_f16", rows, w[name + ".proj.weight"], w[name + ".proj.bias"], None, t, M, C, K, 0, 0)
+            call("isic_layernorm_add_f16", t, None, None, w[name + ".norm.weight"], w[name + ".norm.bias"], y, None, M, C, 1, ceps)
+            return t, y
+
+        tape = dict(n=n, img=img, depth=depth, w=w)
+        rows = e16(M1, 64)
+        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
+        tape["t1"], x = patch_embed(rows, "patch_embed1", M1, d1, 64)
+        x, tape["blocks1"] = self._cblocks_train(x, w, "blocks1", n, g1, d1, depth[0])
+        tape["x1"] = x
+        rows = e16(M3, 16 * d1)
+        call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 4)
+        s1 = e16(M3, d3)
+        call("isic_gemm_f16", rows, w["stage1_output_decode.weight"], w["stage1_output_decode.bias"], None, s1, M3, d3, 16 * d1, 0, 0)
+        rows = e16(M2, 4 * d1)
+        call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 2)
+        tape["t2"], x = patch_embed(rows, "patch_embed2", M2, d2, 4 * d1)
+        x, tape["blocks2"] = self._cblocks_train(x, w, "blocks2", n, g2, d2, depth[1])
+        tape["x2"] = x
+        rows = e16(M3, 4 * d2)
+        call("isic_patch_rows_nhwc_f16", x, rows, n, g2, g2, d2, 2)
+        s2 = e16(M3, d3)
+        call("isic_gemm_f16", rows, w["stage2_output_decode.weight"], w["stage2_output_decode.bias"], None, s2, M3, d3, 4 * d2, 0, 0)
+        tape["t3"], y3 = patch_embed(rows, "patch_embed3", M3, d3, 4 * d2)
+        del rows
+        x, tape["blocks3"] = self._vit_blocks_train(y3, w, n, depth[2])
+        out = torch.empty((M3, d3), device=dev, dtype=torch.float32)
+        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, M3, d3, 0, self.ln_eps)
+        tape.update(y3=y3, x3=x, s1=s1, s2=s2)
+        return out.view(n, self.tokens, d3), tape
+
+    def _cblocks_train(self, x, w, stage, n, g, C, nblk):
+        dev = x.device
+        M, Hd, eps = n * g * g, C * self.mlp_ratio, self.conv_ln_eps
+        saves = []
+        for i in range(nblk):
+            b = f"{stage}.{i}"
+            h1, dd, m, x2, h2, xo = (torch.empty((M, C), device=dev, dtype=_F16) for _ in range(6))
+            pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
+            call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, C, 0, eps)
+            call("isic_gemm_f16", h1, w[b + ".conv1.weight"], w[b + ".conv1.bias"], None, dd, M, C, C, 0, 0)
+            call("isic_dwconv5x5_f16", dd, w[b + ".attn.weight"], w[b + ".attn.bias"], m, n, g, g, C)
+            call("isic_gemm_f16", m, w[b + ".conv2.weight"], w[b + ".conv2.bias"], x, x2, M, C, C, 0, 0)
+            call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, C, 0, eps)
+            call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, C)
+            call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, xo, M, C, Hd, 0, 0)
+            saves.append(dict(x=x, h1=h1, d=dd, m=m, x2=x2, h2=h2, pre=pre, hid=hid))
+            x = xo
+        return x, saves
+
+    def _vit_blocks_train(self, y3, w, n, nblk):
+        dev = y3.device
+        T, D, H = self.tokens, self.dims[2], self.heads
+        M, Hd, eps = n * T, D * self.mlp_ratio, self.ln_eps
+        x = torch.empty((M, D), device=dev, dtype=_F16)
+        call("isic_gemm_f16", y3, w["patch_embed4.weight"], w["patch_embed4.bias"], w["pos_embed"], x, M, D, D, 0, T)
+        saves = []
+        for i in range(nblk):
+            b = f"blocks3.{i}"
+            h1, att, x2, h2, xo = (torch.empty((M, D), device=dev, dtype=_F16) for _ in range(5))
+            qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
+            pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
+            call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, D, 0, eps)
+            call("isic_gemm_f16", h1, w[b + ".attn.qkv.weight"], w[b + ".attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
+            call("isic_attention_f16", qkv, att, n, T, H, D // H)
+            call("isic_gemm_f16", att, w[b + ".attn.proj.weight"], w[b + ".attn.proj.bias"], x, x2, M, D, D, 0, 0)
+            call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, D, 0, eps)
+            call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, D)
+            call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, xo, M, D, Hd, 0, 0)
+            saves.append(dict(x=x, h1=h1, qkv=qkv, att=att, x2=x2, h2=h2, pre=pre, hid=hid))
+            x = xo
+        return x, saves
+
+    def _workspace(self, nbytes, device):
+        ws = self._ws
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            ws = self._ws = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
+        return ws
+
+    def _fire(self, names):
+        if self.grad_ready_hook is not None:
+            self.grad_ready_hook(list(names))
+
+    def _block_names(self, prefix):
+        return [prefix + "." + k for k, _ in self.get_submodule(prefix).named_parameters()]
+
+    def run_backward(self, tape, dtok):
+        """Accumulates every parameter gradient into ``param.grad`` from d loss / d tokens[N, 196, 768].
+
+        ``grad_ready_hook`` fires with ``norm``, then each ViT block and each CBlock from the last back, then one group
+        with the PatchEmbeds, the stage decoders and ``pos_embed``: their gradients are final earlier, but they sit in
+        front of the blocks in registration order, and a group may only be reported once everything registered after it
+        is final (isic_hip/ddp.py ``mark_ready``)."""
+        w, n, depth = tape["w"], tape["n"], tape["depth"]
+        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
+        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        T, r, ceps = self.tokens, self.mlp_ratio, self.conv_ln_eps
+        dev = dtok.device
+        dtok = dtok.float().contiguous()
+        amax = float(dtok.abs().amax())                  # the backward's one device -> host read before its final check
+        if not math.isfinite(amax):
+            raise FloatingPointError("ConvMAEBaseEncoder backward: the incoming gradient is not finite")
+        S = 2.0 ** round(8 - math.log2(amax)) if amax > 0 else 1.0
+        s = 1.0 / S
+        nb = 0
+        for M, C in ((M1, d1), (M2, d2)):
+            for nk in ((C, C), (r * C, C), (C, r * C)):
+                nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, *nk))
+            nb = max(nb, call("isic_layernorm_add_bwd_f16_workspace_bytes", M, C), call("isic_colsum_f16_workspace_bytes", M, C))
+        for M, nk in ((M3, (d3, 16 * d1)), (M3, (d3, 4 * d2)), (M2, (d2, 4 * d1)), (M1, (d1, 128)), (M3, (3 * d3, d3)),
+                      (M3, (d3, d3)), (M3, (r * d3, d3)), (M3, (d3, r * d3))):
+            nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, *nk))
+        nb = max(nb, call("isic_layernorm_add_bwd_f16_workspace_bytes", M3, d3), call("isic_colsum_f16_workspace_bytes", M3, d3),
+                 call("isic_colsum_f16_workspace_bytes", n, T * d3),
+                 call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g1, g1, d1),
+                 call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g2, g2, d2))
+        ws = self._workspace(nb, dev)
+        params = dict(self.named_parameters())
+        f32 = torch.float32
+
+        def e16(*shape):
+            return torch.empty(shape, device=dev, dtype=_F16)
+
+        def grad(name):
+            p = params[name]
+            if p.grad is None:
+                p.grad = torch.zeros_like(p.data)
+            return p.grad
+
+        def wgrad(dy, xin, name, Nout, K, M):
+            call("isic_gemm_f16_wgrad", dy, xin, grad(name + ".weight"), grad(name + ".bias"), M, Nout, K, s, 1, ws, ws.numel())
+
+        def wgrad_conv(dy, xin, name, Nout, K, M, P, Cin, keep=None):
+            """a P x P patch convolution: the [O][kh][kw][I] gradient of the rows, permuted to the OIHW weight"""
+            tmp = torch.empty((Nout, K), device=dev, dtype=f32)
+            call("isic_gemm_f16_wgrad", dy, xin, tmp, None, M, Nout, K, s, 0, ws, ws.numel())
+            tmp = tmp[:, :keep] if keep is not None else tmp
+            grad(name + ".weight").add_(tmp.reshape(Nout, P, P, Cin).permute(0, 3, 1, 2))
+            call("isic_colsum_f16", dy, grad(name + ".bias"), M, Nout, s, 1, ws, ws.numel())
+
+        def ln_add(dy, dy_f32, mul, xin, a, b, norm, act, eps, g_in, g_out, g16, M, N):
+            call("isic_layernorm_add_bwd_f16", dy, dy_f32, mul, xin, a, b, w[norm + ".weight"], w[norm + ".bias"], act, eps,
+                 g_in, g_out, g16, grad(norm + ".weight"), grad(norm + ".bias"), M, N, s, 1, ws, ws.numel())
+
+        rest = []
+        # ---- norm(x + s1 + s2): one gradient g3 for the stream and both stage decoders
+        g3, g3h = torch.empty((M3, d3), device=dev, dtype=f32), e16(M3, d3)
+        ln_add(dtok, 1, S, tape["x3"], tape["s1"], tape["s2"], "norm", 0, self.ln_eps, None, g3, g3h, M3, d3)
+        self._fire(["norm.weight", "norm.bias"])
+        # ---- stage decoders: s = rows . W^T + b, rows the space-to-depth of the stage output
+        rows2 = e16(M3, 4 * d2)                                             # also the input rows of patch_embed3
+        call("isic_patch_rows_nhwc_f16", tape["x2"], rows2, n, g2, g2, d2, 2)
+        wgrad_conv(g3h, rows2, "stage2_output_decode", d3, 4 * d2, M3, 2, d2)
+        dr2 = e16(M3, 4 * d2)
+        call("isic_gemm_f16", g3h, w["stage2_output_decode.weight.t"], None, None, dr2, M3, 4 * d2, d3, 0, 0)
+        gs2, gs2h = torch.empty((M2, d2), device=dev, dtype=f32), e16(M2, d2)
+        call("isic_patch_rows_bwd_f16", dr2, gs2, None, n, g2, g2, d2, 2, 0)
+        rows = e16(M3, 16 * d1)
+        call("isic_patch_rows_nhwc_f16", tape["x1"], rows, n, g1, g1, d1, 4)
+        wgrad_conv(g3h, rows, "stage1_output_decode", d3, 16 * d1, M3, 4, d1)
+        call("isic_gemm_f16", g3h, w["stage1_output_decode.weight.t"], None, None, rows, M3, 16 * d1, d3, 0, 0)
+        gs1, gs1h = torch.empty((M1, d1), device=dev, dtype=f32), e16(M1, d1)
+        call("isic_patch_rows_bwd_f16", rows, gs1, None, n, g1, g1, d1, 4, 0)
+        del rows
+        rest += self._block_names("stage2_output_decode") + self._block_names("stage1_output_decode")
+        # ---- blocks3, patch_embed4 + pos_embed
+        self._vit_blocks_backward(tape, g3, g3h, ln_add, wgrad, n, depth[2])
+        wgrad(g3h, tape["y3"], "patch_embed4", d3, d3, M3)
+        call("isic_colsum_f16", g3h, grad("pos_embed"), n, T * d3, s, 1, ws, ws.numel())
+        dt3 = e16(M3, d3)
+        call("isic_gemm_f16", g3h, w["patch_embed4.weight.t"], None, None, dt3, M3, d3, d3, 0, 0)
+        rest += self._block_names("patch_embed4") + ["pos_embed"]
+        # ---- patch_embed3: conv -> LN -> GELU; its data gradient joins the stage-2 stream gradient
+        ln_add(dt3, 0, 1.0, tape["t3"], None, None, "patch_embed3.norm", 1, ceps, None, None, g3h, M3, d3)
+        wgrad_conv(g3h, rows2, "patch_embed3.proj", d3, 4 * d2, M3, 2, d2)
+        call("isic_gemm_f16", g3h, w["patch_embed3.proj.weight.t"], None, None, dr2, M3, 4 * d2, d3, 0, 0)
+        call("isic_patch_rows_bwd_f16", dr2, gs2, gs2h, n, g2, g2, d2, 2, 1)
+        del rows2, dr2, dt3, g3, g3h
+        rest += self._block_names("patch_embed3")
+        # ---- blocks2, patch_embed2
+        self._cblocks_backward(tape, "blocks2", gs2, gs2h, grad, ln_add, wgrad, n, g2, d2, depth[1], ws, s)
+        ln_add(gs2, 1, 1.0, tape["t2"], None, None, "patch_embed2.norm", 1, ceps, None, None, gs2h, M2, d2)
+        rows = e16(M2, 4 * d1)
+        call("isic_patch_rows_nhwc_f16", tape["x1"], rows, n, g1, g1, d1, 2)
+        wgrad_conv(gs2h, rows, "patch_embed2.proj", d2, 4 * d1, M2, 2, d1)
+        call("isic_gemm_f16", gs2h, w["patch_embed2.proj.weight.t"], None, None, rows, M2, 4 * d1, d2, 0, 0)
+        call("isic_patch_rows_bwd_f16", rows, gs1, gs1h, n, g1, g1, d1, 2, 1)
+        del rows, gs2, gs2h
+        rest += self._block_names("patch_embed2")
+        # ---- blocks1, the stem (no data gradient; its rows are padded to K = 128 for the weight-gradient GEMM)
+        self._cblocks_backward(tape, "blocks1", gs1, gs1h, grad, ln_add, wgrad, n, g1, d1, depth[0], ws, s)
+        ln_add(gs1, 1, 1.0, tape["t1"], None, None, "patch_embed1.norm", 1, ceps, None, None, gs1h, M1, d1)
+        rows = e16(M1, 128)
+        call("isic_patch_rows_nchw_f32", tape["img"], rows, n, self.in_ch, self.img_size, self.img_size, 4, 128)
+        wgrad_conv(gs1h, rows, "patch_embed1.proj", d1, 128, M1, 4, self.in_ch, keep=16 * self.in_ch)
+        rest += self._block_names("patch_embed1")
+        self._fire(rest)
+        grads = [p.grad for p in self.parameters() if p.grad is not None]
+        norms = torch._foreach_norm(grads)
+        if not bool(torch.isfinite(torch.stack(norms)).all()):
+            raise FloatingPointError("ConvMAEBaseEncoder backward: non-finite parameter gradient (fp16 overflow in the "
+                                     "backward, or a non-finite gradient accumulated earlier)")
+
+    def _vit_blocks_backward(self, tape, g, gh, ln_add, wgrad, n, nblk):
+        w, dev = tape["w"], g.device
+        T, D, H = self.tokens, self.dims[2], self.heads
+        M, Hd, eps = n * T, D * self.mlp_ratio, self.ln_eps
+        dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
+        dD = torch.empty((M, D), device=dev, dtype=_F16)
+        dqkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
+        for i in range(self.depths[2] - 1, nblk - 1, -1):                  # blocks past ``depth`` ran not: no gradient
+            self._fire(self._block_names(f"blocks3.{i}"))
+        for i in range(nblk - 1, -1, -1):
+            b, sv = f"blocks3.{i}", tape["blocks3"][i]
+            wgrad(gh, sv["hid"], f"{b}.mlp.fc2", D, Hd, M)
+            call("isic_gemm_f16_dgelu", gh, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hd, D)
+            wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hd, D, M)
+            call("isic_gemm_f16", dmid, w[f"{b}.mlp.fc1.weight.t"], None, None, dD, M, D, Hd, 0, 0)
+            ln_add(dD, 0, 1.0, sv["x2"], None, None, f"{b}.norm2", 0, eps, g, g, gh, M, D)
+            wgrad(gh, sv["att"], f"{b}.attn.proj", D, D, M)
+            call("isic_gemm_f16", gh, w[f"{b}.attn.proj.weight.t"], None, None, dD, M, D, D, 0, 0)
+            call("isic_attention_bwd_f16", sv["qkv"], sv["att"], dD, dqkv, n, T, H, D // H)
+            wgrad(dqkv, sv["h1"], f"{b}.attn.qkv", 3 * D, D, M)
+            call("isic_gemm_f16", dqkv, w[f"{b}.attn.qkv.weight.t"], None, None, dD, M, D, 3 * D, 0, 0)
+            ln_add(dD, 0, 1.0, sv["x"], None, None, f"{b}.norm1", 0, eps, g, g, gh, M, D)
+            tape["blocks3"][i] = None                        # its activations can go
+            self._fire(self._block_names(b))
+
+    def _cblocks_backward(self, tape, stage, g, gh, grad, ln_add, wgrad, n, gr, C, nblk, ws, s):
+        w, dev = tape["w"], g.device
+        M, Hd, eps = n * gr * gr, C * self.mlp_ratio, self.conv_ln_eps
+        dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
+        dD, dm, dd = (torch.empty((M, C), device=dev, dtype=_F16) for _ in range(3))
+        dw, db = torch.empty((25, C), device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+        s_idx = 0 if stage == "blocks1" else 1
+        for i in range(self.depths[s_idx] - 1, nblk - 1, -1):
+            self._fire(self._block_names(f"{stage}.{i}"))
+        for i in range(nblk - 1, -1, -1):
+            b, sv = f"{stage}.{i}", tape[stage][i]
+            wgrad(gh, sv["hid"], f"{b}.mlp.fc2", C, Hd, M)
+            call("isic_gemm_f16_dgelu", gh, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hd, C)
+            wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hd, C, M)
+            call("isic_gemm_f16", dmid, w[f"{b}.mlp.fc1.weight.t"], None, None, dD, M, C, Hd, 0, 0)
+            ln_add(dD, 0, 1.0, sv["x2"], None, None, f"{b}.norm2", 0, eps, g, g, gh, M, C)
+            wgrad(gh, sv["m"], f"{b}.conv2", C, C, M)
+            call("isic_gemm_f16", gh, w[f"{b}.conv2.weight.t"], None, None, dm, M, C, C, 0, 0)
+            # depthwise 5x5: data gradient = the same convolution with the taps reversed, no bias; weight + bias gradient
+            call("isic_dwconv5x5_f16", dm, w[f"{b}.attn.weight.rev"], None, dd, n, gr, gr, C)
+            call("isic_dwconv5x5_wgrad_f16", sv["d"], dm, dw, db, n, gr, gr, C, s, 0, ws, ws.numel())
+            grad(f"{b}.attn.weight").add_(dw.t().reshape(C, 1, 5, 5))
+            grad(f"{b}.attn.bias").add_(db)
+            wgrad(dd, sv["h1"], f"{b}.conv1", C, C, M)
+            call("isic_gemm_f16", dd, w[f"{b}.conv1.weight.t"], None, None, dD, M, C, C, 0, 0)
+            ln_add(dD, 0, 1.0, sv["x"], None, None, f"{b}.norm1", 0, eps, g, g, gh, M, C)
+            tape[stage][i] = None
+            self._fire(self._block_names(b))
+
+    def train_flops_per_image(self):
+        """Forward + backward products: every product and convolution three times, except the stem's data gradient."""
+        return 3 * self.flops_per_image() - 2 * self.grids[0] ** 2 * self.dims[0] * self.in_ch * 16
 
     def flops_per_image(self):
         """Multiply-adds x 2 of every product and convolution (the stem at its 48 real columns, not the padded 64)."""
@@ -390,3 +716,22 @@ class ConvMAEBaseEncoder(nn.Module):
         f += 2 * T * d3 * d3                                                           # patch_embed4
         f += self.depths[2] * (2 * T * (4 * d3 * d3 + 2 * r * d3 * d3) + 4 * T * T * d3)   # blocks3
         return f
+
+
+class _ConvMAEFn(torch.autograd.Function):
+    """Autograd edge: tokens -> encoder parameter gradients.  The parameters are passed as inputs only so that autograd
+    schedules this node; the kernels accumulate their gradients in place (``param.grad``), hence ``None`` is returned
+    (the images get none either: the stem has no data gradient)."""
+
+    @staticmethod
+    def forward(ctx, images, enc, depth, *params):
+        tok, tape = enc.run_forward_train(images, depth)
+        ctx.enc, ctx.tape = enc, tape
+        return tok
+
+    @staticmethod
+    def backward(ctx, dtok):
+        enc, tape = ctx.enc, ctx.tape
+        ctx.tape = None
+        enc.run_backward(tape, dtok)
+        return (None, None, None) + tuple(None for _ in enc.parameters())

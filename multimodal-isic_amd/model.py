@@ -12,7 +12,8 @@
   attention-MIL teacher head (`utils_g_mil.py:38-105`) -> bag embedding, fused with
   the radiomic MLP (`model.py:74-83`) through the reference's intermediate fusion
   (`model.py:206-216`).  ``encoder="vit_s16"`` puts the ViT-S/16 patch encoder (``isic_hip.vit``, trainable, 384-d
-  token-mean features) in place of ResNet-18.
+  token-mean features) in place of ResNet-18, ``encoder="convmae_base"`` the reference's ConvMAE-Base encoder
+  (``isic_hip.convmae``, trainable, 768-d token-mean features of 224 x 224 patches).
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from isic_hip import ops
 from isic_hip.bags import BagOffsets, as_offsets
 from isic_hip.encoder import LAYERS, ResNet18Encoder
 from isic_hip.vit import ViTSmallEncoder
+from isic_hip.convmae import ConvMAEBaseEncoder
 from utils_g_mil import AttentionMIL_teacher, _DropoutClock
 
 
@@ -172,14 +174,17 @@ class MultiModalMILNet(nn.Module):
         super().__init__()
         if fusion_strategy not in ('concat', 'attention'):
             raise ValueError(f"Unknown fusion_strategy: {fusion_strategy}")
-        if encoder not in ("resnet18", "vit_s16"):
-            raise ValueError(f"Unknown encoder: {encoder!r} (resnet18 or vit_s16)")
+        if encoder not in ("resnet18", "vit_s16", "convmae_base"):
+            raise ValueError(f"Unknown encoder: {encoder!r} (resnet18, vit_s16 or convmae_base)")
         self.fusion_strategy, self.aux_weight = fusion_strategy, float(aux_weight)
         if encoder == "resnet18":
             self.encoder = ResNet18Encoder(layers=encoder_layers, **(encoder_kwargs or {}))
-        else:
+        elif encoder == "vit_s16":
             # the token mean after the final LayerNorm (ViTSmallEncoder.forward), fine-tuned end to end
             self.encoder = ViTSmallEncoder(trainable=True, **(encoder_kwargs or {}))
+        else:
+            # the reference's own encoder (ConvMAEBaseEncoder.forward: the token mean of its latents), 224 x 224 patches
+            self.encoder = ConvMAEBaseEncoder(trainable=True, **(encoder_kwargs or {}))
         self.mil = AttentionMIL_teacher(self.encoder.out_dim, hidden_dim, att_dim, dropout, num_classes)
         self.image_proj = _mlp_ln(hidden_dim, 256, 128, 0.3, 0.2)
         self.radiomics_mlp = _mlp_ln(radiomics_dim, 256, 128, 0.4, 0.3)
@@ -201,7 +206,7 @@ class MultiModalMILNet(nn.Module):
         else:
             offs = as_offsets(offsets, image.device)
         clk, tr = self.dropout_clock, self.training
-        feats = self.encoder(image)                                   # [T, 512] fp32 (vit_s16: [T, 384])
+        feats = self.encoder(image)                                   # [T, 512] fp32 (vit_s16: [T, 384], convmae_base: [T, 768])
         out = self.mil(feats, offs, return_pooled=True)
         img = _run_mlp_ln(self.image_proj, out.pop("pooled"), clk, 0, tr)
         rad = _run_mlp_ln(self.radiomics_mlp, radiomics, clk, 2, tr)
