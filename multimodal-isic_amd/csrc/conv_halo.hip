@@ -103,8 +103,8 @@ __device__ unsigned long long g_halo_stamps[256 * 64 * 4];
 // two stages step S - 1 used and wait for ALL their own DMAs (vmcnt(0): no dummy pieces) in front of barrier S + 1.
 // The next chunk's patch pieces go out at taps 1..6 (not 0..5): a step may hold (chunk c - 1, tap 8) and (chunk c, tap 0),
 // and the buffer of chunk c + 1 is the one chunk c - 1 reads.  Needs Cin % 128 == 0 (an even number of K-tiles per tile).
-// ABL (test entry only): bit 0 = no MFMAs, bit 1 = no fragment reads, bit 2 = no LDS-DMA -- where a tile's time goes
-template <int STATS, bool ADDEND, int KPB, int PRIO, int ABL = 0>
+// With KPB = 2 the multiplying waves also run at a raised wave priority.
+template <int STATS, bool ADDEND, int KPB>
 __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
@@ -163,17 +163,14 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
         if (g >= groups) return;
         const long long pix = (long long)(t_begin + tl) * HM - (a.W + 1) + g * 8 + r8;
         const bool ok = pix >= 0 && pix < a.M;
-        if (!(ABL & 4))
-          halo_glds16(ok ? (const void*)(a.in + (size_t)pix * a.Cin + cc * 64 + gch * 8) : (const void*)zp,
-                      lds0 + (unsigned)(buf * PB + g * 1024));
+        halo_glds16(ok ? (const void*)(a.in + (size_t)pix * a.Cin + cc * 64 + gch * 8) : (const void*)zp,
+                    lds0 + (unsigned)(buf * PB + g * 1024));
       };
       auto weights2 = [&](int tap, int cc, int stage) {
         const unsigned short* s0 = wrow + (size_t)tap * a.Cin + cc * 64;
         const unsigned dst = lds0 + off_w + stage * WSTAGE + sw * 2048;
-        if (!(ABL & 4)) {
-          halo_glds16((const void*)s0, dst);
-          halo_glds16((const void*)(s0 + (size_t)16 * 9 * a.Cin), dst + 1024);
-        }
+        halo_glds16((const void*)s0, dst);
+        halo_glds16((const void*)(s0 + (size_t)16 * 9 * a.Cin), dst + 1024);
       };
 #pragma unroll
       for (int j = 0; j < MAX_PPW; ++j) piece2(j, 0, 0, 0);
@@ -245,7 +242,7 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
   const unsigned boff0 = (unsigned)((wn * 64 + fr) * 128 + ((fg ^ (fr & 7)) << 4));
   const int prow0 = wm * 64 + fr;                        // patch row of tap (0, 0) of this lane's first pixel
 
-  if (PRIO) __builtin_amdgcn_s_setprio(PRIO);             // the multiplying waves win vector-issue arbitration against the staging waves
+  if (KPB == 2) __builtin_amdgcn_s_setprio(1);          // the multiplying waves win vector-issue arbitration against the staging waves
   int gc = 0, gkt = 0;
   for (int tl = 0; tl < ntl; ++tl) {
     const int m0 = (t_begin + tl) * HM;
@@ -295,23 +292,14 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
             bf16x8 af[4], bfr[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              if (ABL & 2) {
-                const unsigned u = aoff[i] + ks, v = boff0 + i;
-                af[i] = __builtin_bit_cast(bf16x8, (u32x4){u, u, u, u});
-                bfr[i] = __builtin_bit_cast(bf16x8, (u32x4){v, v, v, v});
-                asm volatile("" : "+v"(af[i]), "+v"(bfr[i]));
-              } else {
-                af[i] = *reinterpret_cast<const bf16x8*>(smem + (aoff[i] ^ (unsigned)(ks << 6)));
-                bfr[i] = *reinterpret_cast<const bf16x8*>(wst + ((boff0 ^ (unsigned)(ks << 6)) + i * 2048));
-              }
+              af[i] = *reinterpret_cast<const bf16x8*>(smem + (aoff[i] ^ (unsigned)(ks << 6)));
+              bfr[i] = *reinterpret_cast<const bf16x8*>(wst + ((boff0 ^ (unsigned)(ks << 6)) + i * 2048));
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                if (ABL & 1) { if (j == 0) asm volatile("" :: "v"(af[i]), "v"(bfr[i])); }
-                else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-              }
+              for (int j = 0; j < 4; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
           }
           ++tap;
           if (++kw == 3) { kw = 0; ++kh; }
@@ -553,15 +541,15 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
   }
 }
 
-template <int STATS, bool ADDEND, int KPB, int PRIO, int ABL = 0>
+template <int STATS, bool ADDEND, int KPB>
 int launch_halo(const HaloArgs& a, int grid, int lds, hipStream_t stream) {
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_kernel<STATS, ADDEND, KPB, PRIO, ABL>),
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_kernel<STATS, ADDEND, KPB>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((conv_halo_kernel<STATS, ADDEND, KPB, PRIO, ABL>), dim3(grid), dim3(1024), lds, stream, a);
+  hipLaunchKernelGGL((conv_halo_kernel<STATS, ADDEND, KPB>), dim3(grid), dim3(1024), lds, stream, a);
   return ISIC_OK;
 }
 
@@ -603,20 +591,7 @@ int isic_conv_halo_launch(const uint16_t* in, const uint16_t* w, uint16_t* out, 
   // (tools/halo_ab.py, interleaved A/B at 2048 images: l2 +1 %, l3 +2..3.5 %, l4 +3..4 %); experiment 1 = the round-2/3 loop
   const bool two = kpb2_ok && experiment != 1;
   if (two) lds = lds2;
-  if (experiment >= 2) {                                   // timing ablations of the shipped loop (results are garbage): ABL = experiment - 1
-    if (!two || relu_mask || yraw || stat_sum || addend) return ISIC_ERR_UNSUPPORTED;
-    switch (experiment - 1) {
-      case 1: return launch_halo<0, false, 2, 1, 1>(a, grid, lds, stream);
-      case 2: return launch_halo<0, false, 2, 1, 2>(a, grid, lds, stream);
-      case 3: return launch_halo<0, false, 2, 1, 3>(a, grid, lds, stream);
-      case 4: return launch_halo<0, false, 2, 1, 4>(a, grid, lds, stream);
-      case 5: return launch_halo<0, false, 2, 1, 5>(a, grid, lds, stream);
-      case 6: return launch_halo<0, false, 2, 1, 6>(a, grid, lds, stream);
-      case 7: return launch_halo<0, false, 2, 1, 7>(a, grid, lds, stream);
-      default: return ISIC_ERR_UNSUPPORTED;
-    }
-  }
-#define HALO_LAUNCH(S, A) (two ? launch_halo<S, A, 2, 1>(a, grid, lds, stream) : launch_halo<S, A, 1, 0>(a, grid, lds, stream))
+#define HALO_LAUNCH(S, A) (two ? launch_halo<S, A, 2>(a, grid, lds, stream) : launch_halo<S, A, 1>(a, grid, lds, stream))
   if (relu_mask || yraw) {                                 // data gradient feeding a BatchNorm backward (STATS 2)
     if (!relu_mask || !yraw || !stat_sum || !stat_sumsq) return ISIC_ERR_BAD_ARG;
     return addend ? HALO_LAUNCH(2, true) : HALO_LAUNCH(2, false);

@@ -23,15 +23,17 @@
 // through torch, save_latent.py:42-60); BASELINE.json configs[1] names ResNet-18, whose layer table
 // is SURVEY.md 8d.
 //
-// Structure: 256 threads = 4 waves; block tile BM x BN (256x64 as 4x1 waves for Cout = 64,
-// 128x128 as 2x2 waves otherwise), each wave a 64x64 sub-tile = 4x4 MFMA tiles (64 accumulator
-// VGPRs); BK = 64 = one (kh,kw) tap x 64 channels.  Staging is LDS-DMA (global_load_lds, 16 B per
-// lane, no staging VGPRs, no ds_write) into two LDS stages: tile k+1 streams in while tile k is
-// multiplied, one barrier per K-tile, two blocks per CU.  LDS rows are 128 B with a 16-byte-chunk XOR
+// Structure: block tile BM x BN = 256 x 64 (4 x 1 MFMA waves, Cout % 128 != 0) or 256 x 128 (4 x 2 MFMA waves), each
+// MFMA wave a 64x64 sub-tile = 4x4 MFMA tiles (64 accumulator VGPRs); BK = 64 = one (kh,kw) tap x 64 channels.  As many
+// STAGING WAVES run behind the MFMA waves and only issue the LDS-DMA (global_load_lds, 16 B per lane, no staging VGPRs,
+// no ds_write; an LDS-DMA instruction holds its wave for the order of 100 cycles at issue) into NSTAGE LDS stages, so
+// that the MFMA waves only read LDS and multiply: K-tiles kt+1 .. kt+NSTAGE-1 stream in while kt is multiplied, one
+// barrier per K-tile.  NSTAGE = 2 for the 256 x 64 tile, 3 for the 256 x 128 tile (with two stages the DMA latency of
+// every K-tile is exposed behind the barrier).  LDS rows are 128 B with a 16-byte-chunk XOR
 // swizzle applied on the SOURCE side (the DMA writes lane-linearly) so the ds_read_b128 fragment
 // reads are conflict-free; out-of-image taps are fetched from a zero page.  The epilogue transposes
-// through LDS so every global store is a full 16-byte-per-lane row segment.  (Register-staged and
-// 3-stage variants are kept behind ISIC_CONV_MODE for A/B timing; measured slower.)
+// through LDS so every global store is a full 16-byte-per-lane row segment.  (Register staging, a single LDS stage and
+// LDS-DMA issued by the MFMA waves themselves were measured slower: DESIGN.md.)
 #include <stdlib.h>
 
 
@@ -49,12 +51,6 @@ __device__ __forceinline__ float bfbits(unsigned short b) { return __uint_as_flo
 // zero page for LDS-DMA staging: an out-of-image tap row is fetched from here instead of being zero-filled
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
 
-// MODE 0: one LDS stage, register staging      MODE 1: two LDS stages, register staging
-// MODE 2: two LDS stages, LDS-DMA staging       MODE 3: three LDS stages, LDS-DMA, counted vmcnt
-// MODE 4: as MODE 2 with dedicated STAGING WAVES behind the MFMA waves: they only issue the LDS-DMA (an LDS-DMA
-//         instruction holds its wave for the order of 100 cycles at issue), the MFMA waves only read LDS and multiply
-// MODE 5: staging waves and THREE stages (the DMA of K-tile kt+2 is issued while kt is multiplied: with two stages
-//         the DMA latency of every K-tile is exposed behind the barrier); used with the 256 x 128 tile, 8 + 8 waves
 #ifdef IGEMM_STAMPS   // tests/probes/probe_igemm_stamps.hip: per K-tile clocks of one MFMA wave (slots 0-2) and one staging wave (3-6)
 __device__ unsigned long long g_igemm_stamps[256 * 40 * 8];
 #define IG_STAMP(kt, k, who) do { if (threadIdx.x == (who) && blockIdx.x < 256 && blockIdx.y == 0 && (kt) < 40) g_igemm_stamps[(blockIdx.x * 40 + (kt)) * 8 + (k)] = clock64(); } while (0)
@@ -62,20 +58,17 @@ __device__ unsigned long long g_igemm_stamps[256 * 40 * 8];
 #define IG_STAMP(kt, k, who) do { } while (0)
 #endif
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE>
-__global__ __launch_bounds__((MODE >= 4 ? 2 : 1) * WAVES_M * WAVES_N * 64, MODE >= 4 ? 4 : 1) void conv_igemm_kernel(ConvArgsN classes) {
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE>
+__global__ __launch_bounds__(2 * WAVES_M * WAVES_N * 64, 4) void conv_igemm_kernel(ConvArgsN classes) {
   const ConvArgs a = classes.c[blockIdx.z];           // by value: loaded into scalar registers once
   if ((int)(blockIdx.x * BM) >= a.M) return;            // this class has fewer row tiles than the largest one (whole block)
-  constexpr bool DB = (MODE == 1);
-  constexpr bool GLDS = (MODE >= 2);
-  constexpr int NSTAGE = (MODE == 3 || MODE == 5) ? 3 : (MODE == 0 ? 1 : 2);
-  constexpr int MT = WAVES_M * WAVES_N * 64;          // MFMA threads; MODE >= 4: as many staging threads behind them
+  constexpr int MT = WAVES_M * WAVES_N * 64;          // MFMA threads; as many staging threads behind them
   static_assert(BM == WAVES_M * 64 && BN == WAVES_N * 64, "64x64 per wave");
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
   constexpr int CPAD = BN + 8;  // epilogue row stride (elements)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // NSTAGE*STAGE, >= C tile
 
-  const bool stager = MODE >= 4 && threadIdx.x >= MT;
+  const bool stager = threadIdx.x >= MT;
   const int tid = stager ? threadIdx.x - MT : threadIdx.x;   // index inside the role
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -89,7 +82,7 @@ __global__ __launch_bounds__((MODE >= 4 ? 2 : 1) * WAVES_M * WAVES_N * 64, MODE 
   constexpr int RPP = MT / 8;                          // rows staged per pass: 8 threads per 128-byte row
   constexpr int AROWS = BM / RPP, BROWS = BN / RPP;
   const int sr = tid >> 3;
-  const int sc = GLDS ? ((tid & 7) ^ (sr & 7)) : (tid & 7);   // global 16-byte chunk this thread fetches
+  const int sc = (tid & 7) ^ (sr & 7);                // global 16-byte chunk this thread fetches
   const int ds_ = a.down_shift;
   // per-tap uniform offsets: dh(ti) = (oh0*up + kh - pad) >> ds  (exact for the taps of this parity class)
   const int dh0 = (a.oh0 * a.up + a.kh0 - a.pad) >> ds_, dw0 = (a.ow0 * a.up + a.kw0 - a.pad) >> ds_;
@@ -116,34 +109,6 @@ __global__ __launch_bounds__((MODE >= 4 ? 2 : 1) * WAVES_M * WAVES_N * 64, MODE 
 #pragma unroll
   for (int i = 0; i < BROWS; ++i) wrow_ptr[i] = a.w + (size_t)(n0 + sr + RPP * i) * Ktot + sc * 8;
 
-  u32x4 ra0[AROWS], rb0[BROWS];
-  auto gload = [&](int kt, u32x4 (&ra)[AROWS], u32x4 (&rb)[BROWS]) {
-    const int tap = kt / a.ctiles, c0 = (kt - tap * a.ctiles) * BK;
-    const int ti = tap / a.nkw, tj = tap - ti * a.nkw;
-    const int toff = ((dh0 + dstep * ti) * a.Win + (dw0 + dstep * tj)) * a.Cin + c0;          // uniform
-    const int koff = ((a.kh0 + a.kstep * ti) * a.Kw + (a.kw0 + a.kstep * tj)) * a.Cin + c0;     // uniform
-#pragma unroll
-    for (int i = 0; i < AROWS; ++i) {
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (((a_vh[i] >> ti) & (a_vw[i] >> tj)) & 1u) v = *reinterpret_cast<const u32x4*>(a.in + (a_off[i] + toff));
-      ra[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < BROWS; ++i) rb[i] = *reinterpret_cast<const u32x4*>(wrow_ptr[i] + koff);
-  };
-  auto lstore = [&](unsigned char* As, unsigned char* Bs, const u32x4 (&ra)[AROWS], const u32x4 (&rb)[BROWS]) {
-#pragma unroll
-    for (int i = 0; i < AROWS; ++i) {
-      const int r = sr + RPP * i;
-      *reinterpret_cast<u32x4*>(As + r * 128 + ((sc ^ (r & 7)) << 4)) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < BROWS; ++i) {
-      const int r = sr + RPP * i;
-      *reinterpret_cast<u32x4*>(Bs + r * 128 + ((sc ^ (r & 7)) << 4)) = rb[i];
-    }
-  };
-
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -169,10 +134,10 @@ __global__ __launch_bounds__((MODE >= 4 ? 2 : 1) * WAVES_M * WAVES_N * 64, MODE 
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
     }
   };
-  if (GLDS) {
+  {   // K loop, in a scope of its own: the staging state ends before the epilogue (hipcc allocates registers differently without it)
     // LDS-DMA staging (global_load_lds, 16 B per lane): a wave-instruction fills 8 consecutive 128-byte rows
-    // lane-linearly, so lane (r8 = lane>>3, p = lane&7) supplies global chunk p ^ r8 of row 8*g + r8 -- the same
-    // swizzled image the register path builds.  No staging VGPRs, no ds_write; NSTAGE-1 tiles in flight.
+    // lane-linearly, so lane (r8 = lane>>3, p = lane&7) supplies global chunk p ^ r8 of row 8*g + r8 -- the
+    // swizzled image the fragment reads expect.  No staging VGPRs, no ds_write; NSTAGE-1 tiles in flight.
     typedef __attribute__((address_space(3))) void* lds_ptr;
     typedef const __attribute__((address_space(1))) void* gbl_ptr;
     const unsigned char* zp = g_zero_page + (tid & 7) * 16;
@@ -196,79 +161,34 @@ __global__ __launch_bounds__((MODE >= 4 ? 2 : 1) * WAVES_M * WAVES_N * 64, MODE 
       }
     };
     constexpr int LPT = AROWS + BROWS;        // LDS-DMA instructions per wave per K-tile
-    if (MODE >= 4) {
-      // stage of K-tile kt: kt % NSTAGE; the staging waves run NSTAGE-1 tiles ahead of the MFMA waves
-      if (stager) {
+    // stage of K-tile kt: kt % NSTAGE; the staging waves run NSTAGE-1 tiles ahead of the MFMA waves
+    if (stager) {
 #pragma unroll
-        for (int s_ = 0; s_ < NSTAGE - 1; ++s_)
-          if (s_ < a.Ktiles) issue(s_, smem + s_ * STAGE);
-        for (int kt = 0; kt < a.Ktiles; ++kt) {
-          IG_STAMP(kt, 3, MT);
-          // tile kt landed (this wave's rows) when only the younger tiles' DMAs are in flight
-          if (NSTAGE == 3 && kt + 1 < a.Ktiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          IG_STAMP(kt, 4, MT);
-          __builtin_amdgcn_s_barrier();                        // ... every row; and the MFMA waves are done with tile kt-1
-          IG_STAMP(kt, 5, MT);
-          if (kt + NSTAGE - 1 < a.Ktiles) issue(kt + NSTAGE - 1, smem + ((kt + NSTAGE - 1) % NSTAGE) * STAGE);
-          IG_STAMP(kt, 6, MT);
-        }
-        __builtin_amdgcn_s_barrier();                          // matches the MFMA waves' barrier behind the K loop
-        return;                                                // the epilogue belongs to the MFMA waves
-      }
+      for (int s_ = 0; s_ < NSTAGE - 1; ++s_)
+        if (s_ < a.Ktiles) issue(s_, smem + s_ * STAGE);
       for (int kt = 0; kt < a.Ktiles; ++kt) {
-        IG_STAMP(kt, 0, 0);
-        __builtin_amdgcn_s_barrier();
-        IG_STAMP(kt, 1, 0);
-        unsigned char* As = smem + (kt % NSTAGE) * STAGE;
-        compute(As, As + A_BYTES);
-        IG_STAMP(kt, 2, 0);
+        IG_STAMP(kt, 3, MT);
+        // tile kt landed (this wave's rows) when only the younger tiles' DMAs are in flight
+        if (NSTAGE == 3 && kt + 1 < a.Ktiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        IG_STAMP(kt, 4, MT);
+        __builtin_amdgcn_s_barrier();                        // ... every row; and the MFMA waves are done with tile kt-1
+        IG_STAMP(kt, 5, MT);
+        if (kt + NSTAGE - 1 < a.Ktiles) issue(kt + NSTAGE - 1, smem + ((kt + NSTAGE - 1) % NSTAGE) * STAGE);
+        IG_STAMP(kt, 6, MT);
       }
-      __builtin_amdgcn_s_barrier();                            // all MFMA waves are done reading the stages
-    } else {
-#pragma unroll
-    for (int s_ = 0; s_ < NSTAGE - 1; ++s_)
-      if (s_ < a.Ktiles) issue(s_, smem + s_ * STAGE);
+      __builtin_amdgcn_s_barrier();                          // matches the MFMA waves' barrier behind the K loop
+      return;                                                // the epilogue belongs to the MFMA waves
+    }
     for (int kt = 0; kt < a.Ktiles; ++kt) {
-      // tile kt landed when at most the (NSTAGE-2) younger tiles' loads are still outstanding
-      if (NSTAGE == 3 && kt + 1 < a.Ktiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();           // everyone's part landed; everyone is done with stage (kt-1) % NSTAGE
-      if (kt + NSTAGE - 1 < a.Ktiles) issue(kt + NSTAGE - 1, smem + ((kt + NSTAGE - 1) % NSTAGE) * STAGE);
+      IG_STAMP(kt, 0, 0);
+      __builtin_amdgcn_s_barrier();
+      IG_STAMP(kt, 1, 0);
       unsigned char* As = smem + (kt % NSTAGE) * STAGE;
       compute(As, As + A_BYTES);
+      IG_STAMP(kt, 2, 0);
     }
-    __syncthreads();
-    }
-  } else if (DB) {
-    // variant 1: two LDS stages, one register set, one barrier per K-tile
-    if (a.Ktiles > 0) {   // a parity class of a strided data gradient can have no tap at all
-      gload(0, ra0, rb0);
-      lstore(smem, smem + A_BYTES, ra0, rb0);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < a.Ktiles; ++kt) {
-      unsigned char* As = smem + (kt & 1) * STAGE;
-      const bool more = kt + 1 < a.Ktiles;
-      if (more) gload(kt + 1, ra0, rb0);
-      compute(As, As + A_BYTES);
-      if (more) {
-        unsigned char* An = smem + ((kt + 1) & 1) * STAGE;
-        lstore(An, An + A_BYTES, ra0, rb0);
-      }
-      __syncthreads();
-    }
-  } else {
-    // variant 0: one LDS stage, next tile's global loads in flight during the MFMAs
-    if (a.Ktiles > 0) gload(0, ra0, rb0);
-    for (int kt = 0; kt < a.Ktiles; ++kt) {
-      __syncthreads();                      // previous tile fully consumed
-      lstore(smem, smem + A_BYTES, ra0, rb0);
-      __syncthreads();
-      if (kt + 1 < a.Ktiles) gload(kt + 1, ra0, rb0);
-      compute(smem, smem + A_BYTES);
-    }
-    __syncthreads();
+    __builtin_amdgcn_s_barrier();                            // all MFMA waves are done reading the stages
   }
 
   // ---- epilogue.  The MFMAs were issued as D[co][pixel] = W * X^T, so lane (fg, fr) holds, for MFMA tile
@@ -368,46 +288,33 @@ __global__ void weight_prep_kernel(const float* __restrict__ w, unsigned short* 
   }
 }
 
-template <int BM, int BN, int WM, int WN, int MODE>
+template <int BM, int BN, int WM, int WN, int NSTAGE>
 int launch_conv(const ConvArgsN& a, hipStream_t s) {
   constexpr int STAGE = (BM + BN) * BK * 2;
   constexpr int MT = WM * WN * 64;
   constexpr int CBYTES = BM * (BN + 8) * 2 + 2 * MT * 4;
-  constexpr int MAIN = ((MODE == 3 || MODE == 5) ? 3 : (MODE == 0 ? 1 : 2)) * STAGE;
-  constexpr int THREADS = (MODE >= 4 ? 2 : 1) * MT;
+  constexpr int MAIN = NSTAGE * STAGE;
   constexpr int LDS = MAIN > CBYTES ? MAIN : CBYTES;
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, MODE>),
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, NSTAGE>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   int maxM = 0;
   for (int i = 0; i < a.n; ++i) maxM = a.c[i].M > maxM ? a.c[i].M : maxM;
   dim3 grid(ceil_div(maxM, BM), a.c[0].Cout / BN, a.n);
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, MODE>), grid, dim3(THREADS), LDS, s, a);
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NSTAGE>), grid, dim3(2 * MT), LDS, s, a);
   return ISIC_OK;
 }
 
-template <int BM, int BN, int WM, int WN>
-int launch_conv_mode(int mode, const ConvArgsN& a, hipStream_t s) {
-  switch (mode) {
-    case 1: return launch_conv<BM, BN, WM, WN, 1>(a, s);
-    case 2: return launch_conv<BM, BN, WM, WN, 2>(a, s);
-    case 3: return launch_conv<BM, BN, WM, WN, 3>(a, s);
-    case 4: return launch_conv<BM, BN, WM, WN, 4>(a, s);
-    default: return launch_conv<BM, BN, WM, WN, 0>(a, s);
-  }
-}
-
-constexpr int kDefaultConvMode = 5;   // staging waves, three stages, 256 x 128 tile: fastest measured (tools/kernel_bench.py)
 constexpr int kDefaultConvC64 = 2;    // 64 -> 64 3x3 layers: persistent halo kernel (conv_c64.hip)
 
 }  // namespace
 
 int isic_conv3x3_c64_launch(int variant, const uint16_t* in, const uint16_t* w, uint16_t* out, int N, int H, int W,
                             const uint16_t* addend, const uint8_t* addend_mask, double* stat_sum, double* stat_sumsq,
-                            int stat_slots, int experiment, hipStream_t stream);
+                            int stat_slots, hipStream_t stream);
 bool isic_conv_halo_supported(int N, int H, int W, int Cin, int Cout);
 int isic_conv_halo_launch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N, int H, int W, int Cin, int Cout,
                           const uint16_t* addend, const uint8_t* addend_mask, double* stat_sum, double* stat_sumsq,
@@ -417,22 +324,20 @@ int isic_conv_pgemm_launch(const isic_conv::ConvArgsN& classes, hipStream_t stre
 namespace {
 
 // `variant` (include/isic_hip_test.h): 0 = the shipped dispatch.  Otherwise, decimal digits
-//   units: staging MODE of the generic kernel + 1 (0 = default), tens: 64 -> 64 kernels (0 default, 1 generic kernel,
-//   2 tile per block, 3 persistent), hundreds: pixels-staged-once kernel of conv_halo.hip (0 = where profitable,
-//   1 = never, 2 = wherever it is supported), thousands: persistent short-K kernel of conv_pgemm.hip (0 = where
-//   profitable: strided and 1x1 layers, 1 = never, 2 = wherever it is supported).  No global state: the choice travels
-//   with the call.
+//   tens: 64 -> 64 kernels (0 default, 1 generic kernel, 2 tile per block, 3 persistent), hundreds: pixels-staged-once
+//   kernel of conv_halo.hip (0 = where profitable, 1 = never, 2 = wherever it is supported), thousands: persistent short-K
+//   kernel of conv_pgemm.hip (0 = where profitable: strided and 1x1 layers, 1 = never, 2 = wherever it is supported),
+//   ten-thousands: 1 = the one-K-tile loop of conv_halo.hip.  No global state: the choice travels with the call.
 struct ConvVariant {
-  int mode, c64, halo, pgemm, exp;
+  int c64, halo, pgemm, exp;
 };
 inline ConvVariant decode_variant(int v) {
   ConvVariant r;
-  const int m = v % 10, c = (v / 10) % 10;
-  r.mode = m == 0 ? kDefaultConvMode : m - 1;
+  const int c = (v / 10) % 10;
   r.c64 = c == 0 ? kDefaultConvC64 : c - 1;
   r.halo = (v / 100) % 10;
   r.pgemm = (v / 1000) % 10;
-  r.exp = (v / 10000) % 10;          // ten-thousands: a kernel-internal A/B experiment (0 = shipped code)
+  r.exp = (v / 10000) % 10;
   return r;
 }
 
@@ -455,10 +360,9 @@ int conv2d_dispatch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N,
   ISIC_CHECK_ARG((in2 == nullptr) == (w2 == nullptr));
   // a second source exists for the stride-2 3x3 data gradient only (pad' = 1: its even-pixel class has the single tap (1, 1))
   if (in2 && !(Kh == 3 && Kw == 3 && up == 1 && down == 2 && pad == 1 && !addend && !stat_sum)) return ISIC_ERR_UNSUPPORTED;
-  ISIC_CHECK_ARG(variant >= 0 && variant < 100000);
+  ISIC_CHECK_ARG(variant >= 0 && variant < 20000 && variant % 10 == 0);
   const ConvVariant cv = decode_variant(variant);
-  ISIC_CHECK_ARG(cv.mode >= 0 && cv.mode <= 5 && cv.c64 >= 0 && cv.c64 <= 2 && cv.halo >= 0 && cv.halo <= 2 &&
-                 cv.pgemm >= 0 && cv.pgemm <= 2);
+  ISIC_CHECK_ARG(cv.c64 >= 0 && cv.c64 <= 2 && cv.halo >= 0 && cv.halo <= 2 && cv.pgemm >= 0 && cv.pgemm <= 2);
   ISIC_CHECK_ARG(N > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && Kh > 0 && Kw > 0 && up > 0);
   ISIC_CHECK_ARG(down == 1 || down == 2);
   ISIC_CHECK_ARG((stat_sum == nullptr) == (stat_sumsq == nullptr));
@@ -468,8 +372,9 @@ int conv2d_dispatch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N,
   if ((int64_t)N * Hout * Wout * Cout > 0x7FFFFFFFLL || (int64_t)N * Hin * Win * Cin > 0x7FFFFFFFLL) return ISIC_ERR_UNSUPPORTED;
   const bool same3x3 = Kh == 3 && Kw == 3 && up == 1 && down == 1 && pad == 1 && Hin == Hout && Win == Wout;
   if (Cin == 64 && Cout == 64 && same3x3 && cv.c64 != 0) {
+    ISIC_CHECK_ARG(cv.exp == 0);                           // the ten-thousands digit selects a loop of conv_halo.hip only
     const int rc = isic_conv3x3_c64_launch(cv.c64, in, w, out, N, Hin, Win, addend, addend_mask, stat_sum, stat_sumsq,
-                                           stat_slots, cv.exp, as_stream(stream));
+                                           stat_slots, as_stream(stream));
     return rc != ISIC_OK ? rc : isic_launch_status();
   }
   // >= 128-channel 3x3 layers: every input pixel staged once for all nine taps (conv_halo.hip)
@@ -528,16 +433,9 @@ int conv2d_dispatch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N,
     const int rc = isic_conv_pgemm_launch(all, s);
     return rc != ISIC_OK ? rc : isic_launch_status();
   }
-  {
-    int rc;
-    const int mode = cv.mode;
-    if (in2 && mode < 4) return ISIC_ERR_UNSUPPORTED;      // the second source is read by the LDS-DMA staging waves only
-    if (Cout % 128 != 0) rc = launch_conv_mode<256, 64, 4, 1>(mode == 5 ? 4 : mode, all, s);
-    else if (mode == 5) rc = launch_conv<256, 128, 4, 2, 5>(all, s);        // 8 MFMA + 8 staging waves, three stages
-    else rc = launch_conv_mode<128, 128, 2, 2>(mode, all, s);
-    if (rc != ISIC_OK) return rc;
-  }
-  return isic_launch_status();
+  const int rc = Cout % 128 != 0 ? launch_conv<256, 64, 4, 1, 2>(all, s)      // 4 MFMA + 4 staging waves, two stages
+                                  : launch_conv<256, 128, 4, 2, 3>(all, s);    // 8 MFMA + 8 staging waves, three stages
+  return rc != ISIC_OK ? rc : isic_launch_status();
 }
 
 }  // namespace

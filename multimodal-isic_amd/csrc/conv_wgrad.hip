@@ -282,27 +282,16 @@ size_t isic_wgrad_c64_workspace_bytes(int N, int H, int W);
 int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, void* workspace,
                           hipStream_t stream);
 
-// ... and of the 3x3 layers with Cin % 128 == 0, Cout % 32 == 0: 128, 256, 512 channels (conv_wgrad_c128.hip)
-size_t isic_wgrad_c128_workspace_bytes(int N, int H, int W, int Cin, int Cout);
-int isic_wgrad_c128_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int Cin, int Cout,
-                           void* workspace, int xcd_group, hipStream_t stream);
-
-// ... 64 output channels per block (conv_wgrad_c128b.hip): Cin % 128 == 0, Cout % 64 == 0
+// ... of the 3x3 layers with Cin % 128 == 0, Cout % 64 == 0: 128, 256, 512 channels, 64 output channels per block
+// (conv_wgrad_c128b.hip)
 size_t isic_wgrad_c128b_workspace_bytes(int N, int H, int W, int Cin, int Cout);
 int isic_wgrad_c128b_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int Cin, int Cout,
-                            void* workspace, int ablation, hipStream_t stream);
+                            void* workspace, hipStream_t stream);
 
 // ... and of the 3x3 / stride 2 / pad 1 layers with Cin % 64 == 0, Cout % 128 == 0 (conv_wgrad_s2.hip)
 size_t isic_wgrad_s2_workspace_bytes(int N, int Hi, int Wi, int Cin, int Cout);
 int isic_wgrad_s2_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int Hi, int Wi, int Cin, int Cout,
                          void* workspace, hipStream_t stream);
-
-namespace {
-// the all-taps kernels are always used for the shapes they cover (no environment switches, no global state)
-inline bool wgrad_c128_enabled() { return true; }
-constexpr int kWgradC128XcdGroup = 0;      // shipped block order of conv_wgrad_c128.hip (A/B: tools/halo_ab.py --wgrad)
-inline bool wgrad_c64_enabled() { return true; }
-}  // namespace
 
 namespace {
 int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int Hin, int Win, int Cin,
@@ -320,9 +309,7 @@ size_t isic_conv2d_wgrad_workspace_bytes(int N, int Cin, int Hout, int Wout, int
     const size_t c64 = isic_wgrad_c64_workspace_bytes(N, Hout, Wout);
     if (c64 > need) need = c64;
   }
-  if (Cin % 128 == 0 && Cout % 32 == 0 && Kh == 3 && Kw == 3) {   // (a stride-2 layer of these widths asks for more than it uses)
-    const size_t c128 = isic_wgrad_c128_workspace_bytes(N, Hout, Wout, Cin, Cout);
-    if (c128 > need) need = c128;
+  if (Cin % 128 == 0 && Cout % 64 == 0 && Kh == 3 && Kw == 3) {   // (a stride-2 layer of these widths asks for more than it uses)
     const size_t c128b = isic_wgrad_c128b_workspace_bytes(N, Hout, Wout, Cin, Cout);
     if (c128b > need) need = c128b;
   }
@@ -351,20 +338,20 @@ int isic_test_conv2d_wgrad_variant_bf16(const uint16_t* x, const uint16_t* dy, f
 
 namespace {
 
-// variant (include/isic_hip_test.h): 0 = shipped; bit 4 (16) = the 32-output-channel all-taps kernel where the 64-channel
-// one ships, the per-tap kernel where the strided all-taps one ships; bit 0 = that kernel with the OTHER block order; bits 1-3 = its compiled-out parts (timing ablations)
+// variant (include/isic_hip_test.h): 0 = shipped; bit 4 (16) = the per-tap kernel where an all-taps one with Cin % 128 == 0
+// (stride 1) or the strided all-taps one ships; bit 5 (32) = the strided all-taps kernel wherever it supports the shape
 int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int Hin, int Win, int Cin,
                           int Hout, int Wout, int Cout, int Kh, int Kw, int stride, int pad, void* workspace,
                           size_t workspace_bytes, int variant, void* stream) {
   ISIC_CHECK_ARG(x && dy && dw && workspace);
   ISIC_CHECK_ARG(N > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && Kh > 0 && Kw > 0 && stride > 0 && pad >= 0);
   ISIC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0);
+  ISIC_CHECK_ARG((variant & ~(16 | 32)) == 0);
   if (Cin % 64 != 0 || Cout % 64 != 0) return ISIC_ERR_UNSUPPORTED;
   const int64_t M64 = (int64_t)N * Hout * Wout;
   if (M64 > 0x7FFFFFFFLL / 2 || (int64_t)N * Hin * Win * Cin > 0x7FFFFFFFLL || Hout >= 32768 || Wout >= 32768)
     return ISIC_ERR_UNSUPPORTED;   // 32-bit element offsets / 16-bit packed coordinates
-  if (Cin == 64 && Cout == 64 && Kh == 3 && Kw == 3 && stride == 1 && pad == 1 && Hin == Hout && Win == Wout &&
-      wgrad_c64_enabled()) {
+  if (Cin == 64 && Cout == 64 && Kh == 3 && Kw == 3 && stride == 1 && pad == 1 && Hin == Hout && Win == Wout) {
     const size_t need = isic_wgrad_c64_workspace_bytes(N, Hin, Win);
     if (need != 0) {
       if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
@@ -377,17 +364,7 @@ int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int 
     const size_t need = isic_wgrad_c128b_workspace_bytes(N, Hin, Win, Cin, Cout);
     if (need != 0) {
       if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
-      const int rc = isic_wgrad_c128b_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, (variant >> 1) & 7, as_stream(stream));
-      return rc != ISIC_OK ? rc : isic_launch_status();
-    }
-  }
-  if (Cin % 128 == 0 && Cout % 32 == 0 && Kh == 3 && Kw == 3 && stride == 1 && pad == 1 && Hin == Hout && Win == Wout &&
-      wgrad_c128_enabled()) {
-    const size_t need = isic_wgrad_c128_workspace_bytes(N, Hin, Win, Cin, Cout);
-    if (need != 0) {
-      if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
-      const int rc = isic_wgrad_c128_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, (kWgradC128XcdGroup ^ (variant & 1)) | (variant & 14),
-                                            as_stream(stream));
+      const int rc = isic_wgrad_c128b_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, as_stream(stream));
       return rc != ISIC_OK ? rc : isic_launch_status();
     }
   }

@@ -1,6 +1,6 @@
 // Weight gradient of the 3x3 / stride 1 / pad 1 layers with Cin % 128 == 0 and Cout % 64 == 0 (ResNet-18 layer2..4), all
-// nine taps per block, SIXTY-FOUR output channels per block (round 4; conv_wgrad_c128.hip keeps the 32-channel block for
-// Cout % 64 != 0):
+// nine taps per block, SIXTY-FOUR output channels per block (round 4; it replaced a 32-output-channel all-taps kernel,
+// DESIGN.md):
 //
 //   dW[co][kh][kw][ci] = sum over pixels p of  dY[p][co] * X[p + (kh-1, kw-1)][ci]
 //
@@ -19,7 +19,7 @@
 //     dY: now 128-byte pixel rows, granule G of tile pixel P holds channel block G ^ (((P >> 1) & 1) | ((P >> 3) & 1) << 1):
 //     the eight pixels b..b+3, b+8..b+11 a half-wave's transposing read touches land in eight different 32-byte bank groups;
 //   * two stages of 77,824 B; one barrier per tile; per-block partials + a fixed-order reduction: deterministic, no atomics;
-//   * small images packed two / four to a 32-column tile row exactly as in conv_wgrad_c128.hip.
+//   * small images (W <= 15 / W <= 7) packed two / four to a 32-column tile row, at least one empty column between them.
 #include "common.h"
 
 namespace {
@@ -53,8 +53,6 @@ __device__ __forceinline__ void glds16b(const void* gsrc, unsigned lds_dst) {
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
-// ABL (test entry only): bit 0 = no MFMAs, bit 1 = no fragment reads, bit 2 = no LDS-DMA -- where a tile's time goes
-template <int ABL>
 __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
       src = zeros + (unsigned)(lane * 16);
       dst = 0;
     }
-    if (!(ABL & 4)) glds16b(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
+    glds16b(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
   };
 
   // ---------------------------------------------------------------- fragments: wave c = input channels 16c .. 16c+16
@@ -171,7 +169,6 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
     const int nstage = (kk + 1) & 1;
     auto read_frag = [&](unsigned base_lo, unsigned base_hi, int off) -> bf16x8 {
       s16x8_t t;
-      if (ABL & 2) { t.lo = (s16x4){(short)base_lo, (short)off, 1, 2}; t.hi = t.lo; return __builtin_bit_cast(bf16x8, t); }
       t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(base_lo + (unsigned)off));
       t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(base_hi + (unsigned)off));
       return __builtin_bit_cast(bf16x8, t);
@@ -200,8 +197,7 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
           for (int c2 = 0; c2 < 4; ++c2)
-            if (ABL & 1) acc[kh * 3 + kw][c2][0] += __builtin_bit_cast(float, (int)(short)xf[s + kh][kw][0] + (int)(short)yf[c2][1]);
-            else acc[kh * 3 + kw][c2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[s + kh][kw], yf[c2], acc[kh * 3 + kw][c2], 0, 0, 0);
+            acc[kh * 3 + kw][c2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[s + kh][kw], yf[c2], acc[kh * 3 + kw][c2], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);      // a DMA's address arithmetic and the fragment reads stay in their own slot
       }
     }
@@ -273,7 +269,7 @@ size_t isic_wgrad_c128b_workspace_bytes(int N, int H, int W, int Cin, int Cout) 
 
 // called by isic_conv2d_wgrad_bf16 for 3x3, stride 1, pad 1, Cin % 128 == 0, Cout % 64 == 0
 int isic_wgrad_c128b_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int Cin, int Cout,
-                            void* workspace, int ablation, hipStream_t stream) {
+                            void* workspace, hipStream_t stream) {
   WC128BPlan p;
   if (!wc128b_plan(N, H, W, Cin, Cout, p)) return ISIC_ERR_UNSUPPORTED;
   WC128BArgs a;
@@ -282,18 +278,15 @@ int isic_wgrad_c128b_launch(const uint16_t* x, const uint16_t* dy, float* dw, in
   a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.total_tiles = p.total_tiles;
   a.tiles_per_block = p.tiles_per_block; a.blocks_per_pair = p.blocks_per_pair;
   a.Cx = Cin; a.Cy = Cout; a.co_slices = Cout / 64; a.pack = p.pack; a.slot_shift = p.slot_shift; a.Wv = p.Wv;
-  const void* fns[8] = {(const void*)wgrad_c128b_kernel<0>, (const void*)wgrad_c128b_kernel<1>, (const void*)wgrad_c128b_kernel<2>,
-                        (const void*)wgrad_c128b_kernel<3>, (const void*)wgrad_c128b_kernel<4>, (const void*)wgrad_c128b_kernel<5>,
-                        (const void*)wgrad_c128b_kernel<6>, (const void*)wgrad_c128b_kernel<7>};
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [&] {
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
-        return e;
+  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device
+  if (isic_once_per_device(once, [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c128b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LDS_ALL);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   void* kargs[] = {&a};
-  if (hipLaunchKernel(fns[ablation & 7], dim3(p.pairs * p.blocks_per_pair), dim3(512), kargs, LDS_ALL, stream) != hipSuccess)
+  if (hipLaunchKernel(reinterpret_cast<const void*>(wgrad_c128b_kernel), dim3(p.pairs * p.blocks_per_pair), dim3(512), kargs,
+                      LDS_ALL, stream) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   hipLaunchKernelGGL(wgrad_c128b_reduce_kernel, dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
                      p.blocks_per_pair, a.co_slices, Cin);

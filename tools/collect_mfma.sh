@@ -21,7 +21,6 @@ def group(k):
     if "wgrad_c64_kernel" in k: return "wgrad_c64 (64->64 weight gradient)"
     if "wgrad_s2_kernel" in k: return "wgrad_s2 (stride-2 3x3 weight gradients, input staged once per tile)"
     if "wgrad_c128b_kernel" in k: return "wgrad_c128b (>=128-channel 3x3 weight gradients, 64 output channels per block)"
-    if "wgrad_c128_kernel" in k: return "wgrad_c128 (128->128 weight gradient, 32 output channels per block)"
     if "conv_wgrad_kernel" in k: return "conv_wgrad (other weight gradients)"
     if "conv_stem" in k: return "conv_stem (forward + weight gradient)"
     return None

@@ -1,6 +1,7 @@
-"""A/B of kernel-internal experiments of the 3x3 convolution kernels (include/isic_hip_test.h, ten-thousands digit of
-`variant`) inside ONE process: bit-equality with the shipped kernel + HIP-event timing.  Developer tool:
-    python tools/halo_ab.py [--n 2048] [--exps 0,1,2,3] [--layers l2,l3,l4]"""
+"""A/B of the 3x3 convolution kernels inside ONE process: the shipped K loop of conv_halo.hip against the one-K-tile loop
+(include/isic_hip_test.h, ten-thousands digit of `variant`), the downsample-block pair data gradient (--pair) and the
+strided weight gradient (--wgrad-s2); bit-equality with the shipped kernel + HIP-event timing.  Developer tool:
+    python tools/halo_ab.py [--n 2048] [--exps 0,1] [--layers l2,l3,l4] [--addend] [--pair] [--wgrad-s2]"""
 import argparse
 import os
 import sys
@@ -64,27 +65,6 @@ def pair_ab(a):
             print(f"{name} pair dgrad variant {v:4d}: {t:7.4f} ms  {gf / t:7.0f} TF/s alg  {same}", flush=True)
 
 
-def wgrad_ab(a):
-    N = a.n
-    variants = [int(v) for v in a.exps.split(",")]
-    for name in a.layers.split(","):
-        C, h = LAYERS[name]
-        x = torch.randn(N, h, h, C, device=DEV).to(BF)
-        dy = torch.randn(N, h, h, C, device=DEV).to(BF)
-        gf = 2.0 * N * h * h * C * 9 * C / 1e9
-        wsb = torch.empty(call("isic_conv2d_wgrad_workspace_bytes", N, C, h, h, C, 3, 3), device=DEV, dtype=torch.uint8)
-        dws = [torch.zeros(C, C, 3, 3, device=DEV).contiguous(memory_format=torch.channels_last) for _ in variants]
-        fns = [(lambda v=v, dw=dw: call("isic_test_conv2d_wgrad_variant_bf16", x, dy, dw, N, h, h, C, h, h, C, 3, 3, 1, 1, wsb,
-                                        wsb.numel(), v)) for v, dw in zip(variants, dws)]
-        for f in fns:
-            f()
-        torch.cuda.synchronize()
-        ts = interleaved(fns, a.iters)
-        for v, dw, t in zip(variants, dws, ts):
-            same = "bit-equal" if torch.equal(dw, dws[0]) else f"differs max {float((dw - dws[0]).abs().max()):.3e}"
-            print(f"{name} wgrad variant {v:2d}: {t:7.4f} ms  {gf / t:7.0f} TF/s  {same}", flush=True)
-
-
 def wgrad_s2_ab(a):
     """the strided all-taps weight gradient (variant 0) against the per-tap kernel it replaces (variant 16)"""
     N = a.n
@@ -112,17 +92,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--exps", default="0,1", help="conv: 0 = shipped kernel, 1 = the round-3 K loop; --wgrad: variant bits")
+    ap.add_argument("--exps", default="0,1", help="0 = shipped kernel, 1 = the round-3 K loop")
     ap.add_argument("--layers", default="l2,l3,l4")
     ap.add_argument("--addend", action="store_true", help="also the data gradient with a residual-gradient addend")
     ap.add_argument("--pair", action="store_true", help="A/B of the downsample-block pair data gradient: variants 0 and 2000")
     ap.add_argument("--wgrad-s2", action="store_true", help="the strided all-taps weight gradient against the per-tap kernel")
-    ap.add_argument("--wgrad", action="store_true", help="A/B of the weight-gradient block orders instead (isic_test_conv2d_wgrad_variant_bf16)")
     a = ap.parse_args()
     if a.wgrad_s2:
         return wgrad_s2_ab(a)
-    if a.wgrad:
-        return wgrad_ab(a)
     if a.pair:
         return pair_ab(a)
     N = a.n
@@ -136,8 +113,6 @@ def main():
         call("isic_conv_weight_prep_bf16", w, wf, wd, C, C, 3, 3)
         gf = 2.0 * N * h * h * C * 9 * C / 1e9
         modes = [("fwd+stats", wf, True, None), ("dgrad", wd, False, None)] + ([("dgrad+addend", wd, False, add)] if a.addend else [])
-        if max(exps) >= 2:
-            modes = [("dgrad", wd, False, None)]          # the timing ablations exist for the plain data gradient only
         for mode, wt, stats, ad in modes:
             outs, accs, fns, live = [], [], [], []
             for e in exps:

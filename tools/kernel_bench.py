@@ -39,7 +39,9 @@ def main():
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--variant", type=int, default=0,
-                    help="kernel choice pinned per call (include/isic_hip_test.h); 0 = the shipped dispatch")
+                    help="kernel choice of the forward / data-gradient convolutions, pinned per call: the tens, hundreds, "
+                         "thousands and ten-thousands digits of isic_test_conv2d_igemm_variant_bf16 (include/isic_hip_test.h); "
+                         "0 = the shipped dispatch")
     ap.add_argument("--only", default="", help="substring filter on the conv shape names; also skips the extra kernels")
     a = ap.parse_args()
     N = a.n
