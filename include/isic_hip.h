@@ -634,5 +634,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_convmae.h"
 /* Training of the ConvMAE-Base encoder (backward of its convolutional front): more entry points, same conventions. */
 #include "isic_hip_convmae_train.h"
+/* The masked-autoencoder objective of ConvMAE-Base (masking, decoder unshuffle, reconstruction loss): same conventions. */
+#include "isic_hip_mae.h"
 
 #endif /* ISIC_HIP_H */

@@ -41,10 +41,18 @@ constexpr int DW_LR = DW_TH + 4, DW_LC = DW_TW + 4;                 // staged ro
 constexpr int DW_CHUNKS = DW_LR * DW_LC * (DW_CC / 8);             // 16-byte pieces in the tile
 constexpr int DW_PER_T = (DW_CHUNKS + 255) / 256;
 
+// MASK (the MAE's masked CBlock, include/isic_hip_mae.h): keep[n][(h / P) * (W / P) + w / P] flags the token a pixel lies
+// in.  DW_MASK_IN zeroes the removed pixels of x as they are staged (and writes that masked input to xm for the weight
+// gradient: every pixel is inside exactly one tile); DW_MASK_OUT zeroes the removed pixels of y (the data gradient).
+// DW_PLAIN is isic_dwconv5x5_f16, instruction for instruction.
+enum { DW_PLAIN = 0, DW_MASK_IN = 1, DW_MASK_OUT = 2 };
+
+template <int MASK>
 __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short* __restrict__ x,
                                                              const float* __restrict__ wt, const float* __restrict__ bias,
                                                              unsigned short* __restrict__ y, int H, int W, int C,
-                                                             int tiles_w, int tiles_hw) {
+                                                             int tiles_w, int tiles_hw, const unsigned char* __restrict__ keep,
+                                                             int P, unsigned short* __restrict__ xm) {
   __shared__ __attribute__((aligned(16))) u32x4 tile[DW_LR * DW_LC * (DW_CC / 8)];
   const int tid = threadIdx.x;
   const int64_t bid = blockIdx.x;
@@ -62,8 +70,12 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
     const int pix = e >> 3, q = e & 7;
     const int h = h0 - 2 + pix / DW_LC, w = w0 - 2 + pix % DW_LC;
     v[i] = (u32x4){0u, 0u, 0u, 0u};
-    if (e < DW_CHUNKS && h >= 0 && h < H && w >= 0 && w < W)
-      v[i] = *reinterpret_cast<const u32x4*>(xn + ((size_t)h * W + w) * C + q * 8);
+    if (e < DW_CHUNKS && h >= 0 && h < H && w >= 0 && w < W) {
+      if (MASK != DW_MASK_IN || keep[n * (int64_t)((H / P) * (W / P)) + (h / P) * (W / P) + w / P])
+        v[i] = *reinterpret_cast<const u32x4*>(xn + ((size_t)h * W + w) * C + q * 8);
+      if (MASK == DW_MASK_IN && xm && pix / DW_LC >= 2 && pix / DW_LC < DW_TH + 2 && pix % DW_LC >= 2 && pix % DW_LC < DW_TW + 2)
+        *reinterpret_cast<u32x4*>(xm + (size_t)n * H * W * C + c0 + ((size_t)h * W + w) * C + q * 8) = v[i];
+    }
   }
 #pragma unroll
   for (int i = 0; i < DW_PER_T; ++i) {
@@ -112,7 +124,12 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
   unsigned short* yp = y + ((size_t)n * H * W + (size_t)h0 * W + ow) * C + cb;
 #pragma unroll
   for (int r = 0; r < DW_TH; ++r)
-    if (h0 + r < H) *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = cm_pack8(acc[r]);
+    if (h0 + r < H) {
+      if (MASK == DW_MASK_OUT && !keep[n * (int64_t)((H / P) * (W / P)) + ((h0 + r) / P) * (W / P) + ow / P])
+        *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = (u32x4){0u, 0u, 0u, 0u};
+      else
+        *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = cm_pack8(acc[r]);
+    }
 }
 
 // ---------------------------------------------------------------- patch rows
@@ -250,8 +267,8 @@ int isic_dwconv5x5_f16(const uint16_t* x, const float* w_taps, const float* bias
   const int tiles_w = (W + DW_TW - 1) / DW_TW, tiles_h = (H + DW_TH - 1) / DW_TH;
   const int64_t blocks = (int64_t)N * (C / DW_CC) * tiles_w * tiles_h;
   if (blocks > (int64_t)INT32_MAX) return ISIC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(dwconv5x5_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, w_taps, bias, y, H, W,
-                     C, tiles_w, tiles_w * tiles_h);
+  hipLaunchKernelGGL(dwconv5x5_f16_kernel<DW_PLAIN>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, w_taps, bias, y,
+                     H, W, C, tiles_w, tiles_w * tiles_h, nullptr, 1, nullptr);
   return isic_launch_status();
 }
 
@@ -292,6 +309,36 @@ int isic_layernorm_add_f16(const uint16_t* x, const uint16_t* a, const uint16_t*
     hipLaunchKernelGGL(layernorm_add_f16_kernel<2>, grid, dim3(256), 0, as_stream(stream), x, a, b, gamma, beta, y, y_f32, M,
                        N, act, eps);
   return isic_launch_status();
+}
+
+// include/isic_hip_mae.h
+static int dwconv5x5_masked(int mode, const uint16_t* x, const uint8_t* keep, int P, const float* w_taps, const float* bias,
+                            uint16_t* xm, uint16_t* y, int N, int H, int W, int C, void* stream) {
+  ISIC_CHECK_ARG(N >= 0 && H > 0 && W > 0 && C > 0 && P > 0);
+  if (C % DW_CC != 0 || H % P != 0 || W % P != 0) return ISIC_ERR_UNSUPPORTED;
+  if (N == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(x && keep && w_taps && y);
+  const int tiles_w = (W + DW_TW - 1) / DW_TW, tiles_h = (H + DW_TH - 1) / DW_TH;
+  const int64_t blocks = (int64_t)N * (C / DW_CC) * tiles_w * tiles_h;
+  if (blocks > (int64_t)INT32_MAX) return ISIC_ERR_UNSUPPORTED;
+  const unsigned char* k = reinterpret_cast<const unsigned char*>(keep);
+  if (mode == DW_MASK_IN)
+    hipLaunchKernelGGL(dwconv5x5_f16_kernel<DW_MASK_IN>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, w_taps, bias,
+                       y, H, W, C, tiles_w, tiles_w * tiles_h, k, P, xm);
+  else
+    hipLaunchKernelGGL(dwconv5x5_f16_kernel<DW_MASK_OUT>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, w_taps,
+                       bias, y, H, W, C, tiles_w, tiles_w * tiles_h, k, P, nullptr);
+  return isic_launch_status();
+}
+
+int isic_dwconv5x5_masked_f16(const uint16_t* x, const uint8_t* keep, int P, const float* w_taps, const float* bias,
+                              uint16_t* xm, uint16_t* y, int N, int H, int W, int C, void* stream) {
+  return dwconv5x5_masked(DW_MASK_IN, x, keep, P, w_taps, bias, xm, y, N, H, W, C, stream);
+}
+
+int isic_dwconv5x5_masked_dgrad_f16(const uint16_t* dy, const uint8_t* keep, int P, const float* w_taps_rev, uint16_t* dx,
+                                    int N, int H, int W, int C, void* stream) {
+  return dwconv5x5_masked(DW_MASK_OUT, dy, keep, P, w_taps_rev, nullptr, nullptr, dx, N, H, W, C, stream);
 }
 
 }  // extern "C"

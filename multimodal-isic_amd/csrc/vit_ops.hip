@@ -139,14 +139,20 @@ __global__ __launch_bounds__(256) void row_stats_f16_kernel(const unsigned short
 // dimensions a group addresses are chosen so that a lane ends with EIGHT CONSECUTIVE dimensions of its own query
 // (d = 32 (jd >> 1) + 8 (l / 16) + 4 (jd & 1) + r): the result is normalised with the lane's own 1 / sum and leaves in two
 // 16-byte stores, no LDS transpose, no shuffles.
+// Templated on the head width HD in {32, 64} (the MAE decoder's heads are 32 wide): a K / V row is HD * 2 bytes = HD / 8
+// chunks of 16 bytes, swizzled by the same token bits masked to HD / 8 - 1; S^T takes HD / 32 k-steps and O^T HD / 16
+// head-dimension tiles.  HD = 64 is the kernel described above, instruction for instruction.
 constexpr int AT_TMAX = 208, AT_KPAD = 224;                          // tokens padded to 13 x 16 (scores) / 7 x 32 (P.V)
 constexpr int AT_WAVES = 8;
-constexpr int AT_K = AT_TMAX * 128, AT_V = AT_KPAD * 128;
-constexpr int AT_LDS = AT_K + AT_V;
+template <int HD> constexpr int at_lds() { return (AT_TMAX + AT_KPAD) * HD * 2; }
 
+template <int HD>
 __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const unsigned short* __restrict__ qkv,
                                                                           unsigned short* __restrict__ out, int T,
                                                                           int heads, float scale_log2e) {
+  static_assert(HD == 32 || HD == 64, "head width 32 or 64");
+  constexpr int RB = HD * 2, CH = HD / 8, SW = CH - 1, KS = HD / 32, JD = HD / 16;   // row bytes, chunks, swizzle mask
+  constexpr int AT_K = AT_TMAX * RB;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Ks = smem;
   unsigned char* Vs = smem + AT_K;
@@ -154,27 +160,27 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
   const unsigned vs0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)Vs;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int img = blockIdx.x / heads, head = blockIdx.x - img * heads;
-  const int D = heads * 64, ld = 3 * D;                               // qkv row: [q heads*64 | k heads*64 | v heads*64]
-  const unsigned short* base = qkv + (size_t)img * T * ld + head * 64;
+  const int D = heads * HD, ld = 3 * D;                               // qkv row: [q heads*HD | k heads*HD | v heads*HD]
+  const unsigned short* base = qkv + (size_t)img * T * ld + head * HD;
   const int fr = lane & 15, fg = lane >> 4;
   const int qtiles = (T + 15) >> 4;
 
   // ---- this wave's first query fragments (global -> registers), in flight while K and V are staged
-  auto load_q = [&](int qt, f16x8 (&qf)[2]) {
+  auto load_q = [&](int qt, f16x8 (&qf)[KS]) {
     const int q = min(qt * 16 + fr, T - 1);                           // rows >= T: any valid row, never stored
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int ks = 0; ks < KS; ++ks)
       qf[ks] = *reinterpret_cast<const f16x8*>(base + (size_t)q * ld + (ks * 4 + fg) * 8);
   };
-  f16x8 qf[2];
+  f16x8 qf[KS];
   if (wave < qtiles) load_q(wave, qf);
 
   // ---- stage K (swizzled rows of 128 B) and V^T; rows >= T are zero.  All of a thread's loads first, then the stores.
-  constexpr int KV_PER = (AT_KPAD * 8 + AT_WAVES * 64 - 1) / (AT_WAVES * 64);      // 4 vectors of K and of V per thread
+  constexpr int KV_PER = (AT_KPAD * CH + AT_WAVES * 64 - 1) / (AT_WAVES * 64);     // 4 (HD 64) / 2 (HD 32) vectors per thread
   u32x4 kr[KV_PER], vr[KV_PER];
 #pragma unroll
   for (int u = 0; u < KV_PER; ++u) {
-    const int idx = tid + u * AT_WAVES * 64, t = idx >> 3, ch = idx & 7;
+    const int idx = tid + u * AT_WAVES * 64, t = idx / CH, ch = idx % CH;
     kr[u] = (u32x4){0u, 0u, 0u, 0u};
     vr[u] = kr[u];
     if (t < T) {
@@ -184,9 +190,9 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
   }
 #pragma unroll
   for (int u = 0; u < KV_PER; ++u) {
-    const int idx = tid + u * AT_WAVES * 64, t = idx >> 3, ch = idx & 7;
-    if (t < AT_TMAX) *reinterpret_cast<u32x4*>(Ks + t * 128 + ((ch ^ (t & 7)) << 4)) = kr[u];
-    if (t < AT_KPAD) *reinterpret_cast<u32x4*>(Vs + t * 128 + ((ch ^ ((t >> 1) & 7)) << 4)) = vr[u];
+    const int idx = tid + u * AT_WAVES * 64, t = idx / CH, ch = idx % CH;
+    if (t < AT_TMAX) *reinterpret_cast<u32x4*>(Ks + t * RB + ((ch ^ (t & SW)) << 4)) = kr[u];
+    if (t < AT_KPAD) *reinterpret_cast<u32x4*>(Vs + t * RB + ((ch ^ ((t >> 1) & SW)) << 4)) = vr[u];
   }
   __syncthreads();
 
@@ -194,12 +200,12 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
   // head dimensions 32 (jd >> 1) + 8 fp + 4 (jd & 1) + {0..3}: chunk (jd >> 1) * 4 + fp, swizzled by (key >> 1) & 7 (the
   // same for every u and both halves), byte (jd & 1) * 8 inside it.  16 keys x 4 x 8 bytes per instruction spread over half
   // of the banks evenly: the b64 rate.
-  unsigned voff[4];
+  unsigned voff[JD];
   {
-    const int fq = fr >> 2, fp = fr & 3, key = 4 * fg + fq, hsw = (key >> 1) & 7;
+    const int fq = fr >> 2, fp = fr & 3, key = 4 * fg + fq, hsw = (key >> 1) & SW;
 #pragma unroll
-    for (int jd = 0; jd < 4; ++jd)
-      voff[jd] = vs0 + (unsigned)(key * 128 + ((((jd >> 1) * 4 + fp) ^ hsw) << 4) + (jd & 1) * 8);
+    for (int jd = 0; jd < JD; ++jd)
+      voff[jd] = vs0 + (unsigned)(key * RB + ((((jd >> 1) * 4 + fp) ^ hsw) << 4) + (jd & 1) * 8);
   }
   for (int qt = wave; qt < qtiles; qt += AT_WAVES) {
     // ---- S^T tile row: keys x this tile's 16 queries
@@ -209,8 +215,8 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
       const int krow = kt * 16 + fr;
       s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const f16x8 kf = *reinterpret_cast<const f16x8*>(Ks + krow * 128 + (((ks * 4 + fg) ^ (krow & 7)) << 4));
+      for (int ks = 0; ks < KS; ++ks) {
+        const f16x8 kf = *reinterpret_cast<const f16x8*>(Ks + krow * RB + (((ks * 4 + fg) ^ (krow & SW)) << 4));
         s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], s[kt], 0, 0, 0);   // D[key 4fg+r][query fr]
       }
     }
@@ -246,9 +252,9 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
     const float inv = 1.f / sum;                                      // of query fr
 
     // ---- O^T = V^T.P^T: 7 key blocks of 32 (tiles 2u, 2u+1; tile 13 does not exist: zeros), 4 head-dimension tiles of 16
-    f32x4 o[4];
+    f32x4 o[JD];
 #pragma unroll
-    for (int jd = 0; jd < 4; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int jd = 0; jd < JD; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
       f16x8 pf;
@@ -258,17 +264,17 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
         pf[4 + r] = (2 * u + 1 < 13) ? (_Float16)s[2 * u + 1 < 13 ? 2 * u + 1 : 12][r] : (_Float16)0.f;
       }
 #pragma unroll
-      for (int jd = 0; jd < 4; ++jd) {
+      for (int jd = 0; jd < JD; ++jd) {
         s16x8_t t;
-        t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(voff[jd] + (unsigned)(u * 32 * 128)));
-        t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(voff[jd] + (unsigned)(u * 32 * 128 + 16 * 128)));
+        t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(voff[jd] + (unsigned)(u * 32 * RB)));
+        t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)(voff[jd] + (unsigned)(u * 32 * RB + 16 * RB)));
         o[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, t), pf, o[jd], 0, 0, 0);   // D[d-slot 4fg+r][query fr]
       }
     }
     // ---- normalise with the lane's own 1 / sum; dimensions 32t' + 8fg + {0..7} of query fr: two 16-byte stores
     const int q = qt * 16 + fr;
 #pragma unroll
-    for (int tp = 0; tp < 2; ++tp) {
+    for (int tp = 0; tp < HD / 32; ++tp) {
       u32x4 v;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -277,7 +283,7 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
         v[2 * h] = __builtin_bit_cast(unsigned, p0);
         v[2 * h + 1] = __builtin_bit_cast(unsigned, p1);
       }
-      if (q < T) *reinterpret_cast<u32x4*>(out + ((size_t)img * T + q) * D + head * 64 + 32 * tp + 8 * fg) = v;
+      if (q < T) *reinterpret_cast<u32x4*>(out + ((size_t)img * T + q) * D + head * HD + 32 * tp + 8 * fg) = v;
     }
   }
 }
@@ -340,13 +346,29 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
   if (head_dim != 64 || tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, AT_LDS);
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<64>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, at_lds<64>());
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   const float scale_log2e = 0.125f * 1.4426950408889634f;            // 1 / sqrt(64), base-2 exponent
-  hipLaunchKernelGGL(attention_f16_kernel, dim3(n_images * heads), dim3(AT_WAVES * 64), AT_LDS, as_stream(stream), qkv, out, tokens,
-                     heads, scale_log2e);
+  hipLaunchKernelGGL(attention_f16_kernel<64>, dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<64>(), as_stream(stream), qkv,
+                     out, tokens, heads, scale_log2e);
+  return isic_launch_status();
+}
+
+// include/isic_hip_mae.h: the MAE decoder's heads, 32 wide
+int isic_attention_d32_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, void* stream) {
+  ISIC_CHECK_ARG(qkv && out && n_images > 0 && tokens > 0 && heads > 0);
+  if (tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
+  static IsicPerDeviceOnce once;
+  if (isic_once_per_device(once, [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<32>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, at_lds<32>());
+      }) != hipSuccess)
+    return ISIC_ERR_LAUNCH;
+  const float scale_log2e = 0.17677669529663688f * 1.4426950408889634f;   // 1 / sqrt(32), base-2 exponent
+  hipLaunchKernelGGL(attention_f16_kernel<32>, dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<32>(), as_stream(stream), qkv,
+                     out, tokens, heads, scale_log2e);
   return isic_launch_status();
 }
 

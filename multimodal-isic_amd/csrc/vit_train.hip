@@ -332,22 +332,25 @@ __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __res
 //   pass 3 (thread = key j):   dV_j = sum_i P_ij dO_i,  dK_j = scale * sum_i dS_ij Q_i
 // Every sum runs in index order inside one thread: deterministic without atomics.  Q, K, V, dO of the (image, head) sit in
 // LDS as fp16 (4 x T x 128 B, 106.5 KB at T = 208); reads of a row by all lanes are broadcasts.
-constexpr int AB_MAXT = 208, AB_HD = 64, AB_THREADS = 256;
-constexpr int AB_LDS = 4 * AB_MAXT * AB_HD * 2 + 3 * AB_MAXT * 4;
+// Templated on the head width HD in {32, 64} (the MAE decoder's heads are 32 wide); HD = 64 is the kernel as described.
+constexpr int AB_MAXT = 208, AB_THREADS = 256;
+template <int HD> constexpr int ab_lds() { return 4 * AB_MAXT * HD * 2 + 3 * AB_MAXT * 4; }
 
-__device__ __forceinline__ float dot64(const f16x2 (&a)[32], const unsigned short* row) {
+template <int HD>
+__device__ __forceinline__ float dot_hd(const f16x2 (&a)[HD / 2], const unsigned short* row) {
   float s = 0.f;
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < HD / 8; ++c) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(row + 8 * c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_fdot2(a[4 * c + e], __builtin_bit_cast(f16x2, (unsigned)v[e]), s, false);
   }
   return s;
 }
-__device__ __forceinline__ void axpy64(float (&acc)[64], float w, const unsigned short* row) {
+template <int HD>
+__device__ __forceinline__ void axpy_hd(float (&acc)[HD], float w, const unsigned short* row) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < HD / 8; ++c) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(row + 8 * c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -357,17 +360,19 @@ __device__ __forceinline__ void axpy64(float (&acc)[64], float w, const unsigned
     }
   }
 }
-__device__ __forceinline__ void load_row(f16x2 (&r)[32], const unsigned short* p) {
+template <int HD>
+__device__ __forceinline__ void load_row(f16x2 (&r)[HD / 2], const unsigned short* p) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < HD / 8; ++c) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(p + 8 * c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) r[4 * c + e] = __builtin_bit_cast(f16x2, (unsigned)v[e]);
   }
 }
-__device__ __forceinline__ void store_row(unsigned short* p, const float (&a)[64], float mul) {
+template <int HD>
+__device__ __forceinline__ void store_row(unsigned short* p, const float (&a)[HD], float mul) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < HD / 8; ++c) {
     u32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = vt_pack2(a[8 * c + 2 * e] * mul, a[8 * c + 2 * e + 1] * mul);
@@ -375,81 +380,82 @@ __device__ __forceinline__ void store_row(unsigned short* p, const float (&a)[64
   }
 }
 
+template <int HD>
 __global__ __launch_bounds__(AB_THREADS) void attention_bwd_f16_kernel(const unsigned short* __restrict__ qkv,
                                                                        const unsigned short* __restrict__ out,
                                                                        const unsigned short* __restrict__ dout,
                                                                        unsigned short* __restrict__ dqkv, int T, int H) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned short* sQ = reinterpret_cast<unsigned short*>(smem);
-  unsigned short* sK = sQ + AB_MAXT * AB_HD;
-  unsigned short* sV = sK + AB_MAXT * AB_HD;
-  unsigned short* sO = sV + AB_MAXT * AB_HD;                // dO
-  float* sM = reinterpret_cast<float*>(sO + AB_MAXT * AB_HD);
+  unsigned short* sK = sQ + AB_MAXT * HD;
+  unsigned short* sV = sK + AB_MAXT * HD;
+  unsigned short* sO = sV + AB_MAXT * HD;                   // dO
+  float* sM = reinterpret_cast<float*>(sO + AB_MAXT * HD);
   float* sL = sM + AB_MAXT;                                  // 1 / l_i
   float* sD = sL + AB_MAXT;                                  // Delta_i
   const int img = blockIdx.x / H, h = blockIdx.x - img * H;
-  const int D = H * AB_HD, ld = 3 * D;
+  const int D = H * HD, ld = 3 * D;
   const int64_t row0 = (int64_t)img * T;
-  const float sc = 0.125f;
+  const float sc = HD == 64 ? 0.125f : 0.17677669529663688f;       // 1 / sqrt(HD)
   const int tid = threadIdx.x;
-  for (int i = tid; i < T * 8; i += AB_THREADS) {
-    const int t = i >> 3, c = (i & 7) * 8;
-    const unsigned short* base = qkv + (row0 + t) * ld + h * AB_HD + c;
-    *reinterpret_cast<u32x4*>(sQ + t * AB_HD + c) = *reinterpret_cast<const u32x4*>(base);
-    *reinterpret_cast<u32x4*>(sK + t * AB_HD + c) = *reinterpret_cast<const u32x4*>(base + D);
-    *reinterpret_cast<u32x4*>(sV + t * AB_HD + c) = *reinterpret_cast<const u32x4*>(base + 2 * D);
-    *reinterpret_cast<u32x4*>(sO + t * AB_HD + c) = *reinterpret_cast<const u32x4*>(dout + (row0 + t) * D + h * AB_HD + c);
+  for (int i = tid; i < T * (HD / 8); i += AB_THREADS) {
+    const int t = i / (HD / 8), c = (i % (HD / 8)) * 8;
+    const unsigned short* base = qkv + (row0 + t) * ld + h * HD + c;
+    *reinterpret_cast<u32x4*>(sQ + t * HD + c) = *reinterpret_cast<const u32x4*>(base);
+    *reinterpret_cast<u32x4*>(sK + t * HD + c) = *reinterpret_cast<const u32x4*>(base + D);
+    *reinterpret_cast<u32x4*>(sV + t * HD + c) = *reinterpret_cast<const u32x4*>(base + 2 * D);
+    *reinterpret_cast<u32x4*>(sO + t * HD + c) = *reinterpret_cast<const u32x4*>(dout + (row0 + t) * D + h * HD + c);
   }
   __syncthreads();
   const int i = tid;
-  f16x2 a[32], b[32];
+  f16x2 a[HD / 2], b[HD / 2];
   if (i < T) {
     // pass 1
-    load_row(a, sQ + i * AB_HD);
+    load_row<HD>(a, sQ + i * HD);
     float m = -INFINITY, l = 0.f;
     for (int j = 0; j < T; ++j) {
-      const float s = dot64(a, sK + j * AB_HD) * sc;
+      const float s = dot_hd<HD>(a, sK + j * HD) * sc;
       if (s > m) { l = l * __expf(m - s) + 1.f; m = s; }
       else l += __expf(s - m);
     }
-    load_row(b, sO + i * AB_HD);
-    const unsigned short* orow = out + (row0 + i) * D + h * AB_HD;
+    load_row<HD>(b, sO + i * HD);
+    const unsigned short* orow = out + (row0 + i) * D + h * HD;
     float dl = 0.f;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
+    for (int c = 0; c < HD / 8; ++c) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(orow + 8 * c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) dl = __builtin_amdgcn_fdot2(b[4 * c + e], __builtin_bit_cast(f16x2, (unsigned)v[e]), dl, false);
     }
     sM[i] = m; sL[i] = 1.f / l; sD[i] = dl;
     // pass 2
-    float dq[64];
+    float dq[HD];
 #pragma unroll
-    for (int d = 0; d < 64; ++d) dq[d] = 0.f;
+    for (int d = 0; d < HD; ++d) dq[d] = 0.f;
     const float rl = 1.f / l;
     for (int j = 0; j < T; ++j) {
-      const float p = __expf(dot64(a, sK + j * AB_HD) * sc - m) * rl;
-      const float ds = p * (dot64(b, sV + j * AB_HD) - dl);
-      axpy64(dq, ds, sK + j * AB_HD);
+      const float p = __expf(dot_hd<HD>(a, sK + j * HD) * sc - m) * rl;
+      const float ds = p * (dot_hd<HD>(b, sV + j * HD) - dl);
+      axpy_hd<HD>(dq, ds, sK + j * HD);
     }
-    store_row(dqkv + (row0 + i) * ld + h * AB_HD, dq, sc);
+    store_row<HD>(dqkv + (row0 + i) * ld + h * HD, dq, sc);
   }
   __syncthreads();
   if (i < T) {
     // pass 3 (thread = key j = i)
-    load_row(a, sK + i * AB_HD);
-    load_row(b, sV + i * AB_HD);
-    float dk[64], dv[64];
+    load_row<HD>(a, sK + i * HD);
+    load_row<HD>(b, sV + i * HD);
+    float dk[HD], dv[HD];
 #pragma unroll
-    for (int d = 0; d < 64; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
+    for (int d = 0; d < HD; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
     for (int q = 0; q < T; ++q) {
-      const float p = __expf(dot64(a, sQ + q * AB_HD) * sc - sM[q]) * sL[q];
-      const float ds = p * (dot64(b, sO + q * AB_HD) - sD[q]);
-      axpy64(dv, p, sO + q * AB_HD);
-      axpy64(dk, ds, sQ + q * AB_HD);
+      const float p = __expf(dot_hd<HD>(a, sQ + q * HD) * sc - sM[q]) * sL[q];
+      const float ds = p * (dot_hd<HD>(b, sO + q * HD) - sD[q]);
+      axpy_hd<HD>(dv, p, sO + q * HD);
+      axpy_hd<HD>(dk, ds, sQ + q * HD);
     }
-    store_row(dqkv + (row0 + i) * ld + D + h * AB_HD, dk, sc);
-    store_row(dqkv + (row0 + i) * ld + 2 * D + h * AB_HD, dv, 1.f);
+    store_row<HD>(dqkv + (row0 + i) * ld + D + h * HD, dk, sc);
+    store_row<HD>(dqkv + (row0 + i) * ld + 2 * D + h * HD, dv, 1.f);
   }
 }
 
@@ -543,17 +549,35 @@ int isic_layernorm_bwd_f16(const void* dy, int dy_is_f32, float dy_mul, const ui
 int isic_attention_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, uint16_t* dqkv, int n_images,
                            int tokens, int heads, int head_dim, void* stream) {
   ISIC_CHECK_ARG(n_images >= 0 && tokens > 0 && heads > 0 && head_dim > 0);
-  if (head_dim != AB_HD || tokens > AB_MAXT) return ISIC_ERR_UNSUPPORTED;
+  if (head_dim != 64 || tokens > AB_MAXT) return ISIC_ERR_UNSUPPORTED;
   if (n_images == 0) return ISIC_OK;
   ISIC_CHECK_ARG(qkv && out && dout && dqkv);
   static IsicPerDeviceOnce once;
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_f16_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, AB_LDS);
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_f16_kernel<64>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, ab_lds<64>());
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(attention_bwd_f16_kernel, dim3(n_images * heads), dim3(AB_THREADS), AB_LDS, as_stream(stream), qkv, out,
-                     dout, dqkv, tokens, heads);
+  hipLaunchKernelGGL(attention_bwd_f16_kernel<64>, dim3(n_images * heads), dim3(AB_THREADS), ab_lds<64>(), as_stream(stream), qkv,
+                     out, dout, dqkv, tokens, heads);
+  return isic_launch_status();
+}
+
+// include/isic_hip_mae.h: the MAE decoder's heads, 32 wide
+int isic_attention_d32_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, uint16_t* dqkv, int n_images,
+                               int tokens, int heads, void* stream) {
+  ISIC_CHECK_ARG(n_images >= 0 && tokens > 0 && heads > 0);
+  if (tokens > AB_MAXT) return ISIC_ERR_UNSUPPORTED;
+  if (n_images == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(qkv && out && dout && dqkv);
+  static IsicPerDeviceOnce once;
+  if (isic_once_per_device(once, [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_f16_kernel<32>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, ab_lds<32>());
+      }) != hipSuccess)
+    return ISIC_ERR_LAUNCH;
+  hipLaunchKernelGGL(attention_bwd_f16_kernel<32>, dim3(n_images * heads), dim3(AB_THREADS), ab_lds<32>(), as_stream(stream), qkv,
+                     out, dout, dqkv, tokens, heads);
   return isic_launch_status();
 }
 

@@ -425,8 +425,10 @@ class ConvMAEBaseEncoder(nn.Module):
                 w[f"{stage}.{i}.attn.weight.rev"] = w[f"{stage}.{i}.attn.weight"].flip(0).contiguous()
         return w
 
-    def run_forward_train(self, images, depth=None):
-        """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
+    def run_forward_train(self, images, depth=None, masking=None):
+        """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs.
+        ``masking`` (the MAE, isic_hip/convmae_mae.py): dict(keep, ids_keep, ids_restore, L) -> the latent of the L kept
+        tokens per image in ids_keep order (and its fp16 copy as tape["latent16"])."""
         depth = self._check(images, depth)
         dev = images.device
         w = self._prepare_train(dev)
@@ -446,10 +448,14 @@ class ConvMAEBaseEncoder(nn.Module):
             return t, y
 
         tape = dict(n=n, img=img, depth=depth, w=w)
+        keep, L = None, self.tokens
+        if masking is not None:
+            keep, L = masking["keep"], masking["L"]
+            tape.update(keep=keep, ids_restore=masking["ids_restore"], L=L)
         rows = e16(M1, 64)
         call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
         tape["t1"], x = patch_embed(rows, "patch_embed1", M1, d1, 64)
-        x, tape["blocks1"] = self._cblocks_train(x, w, "blocks1", n, g1, d1, depth[0])
+        x, tape["blocks1"] = self._cblocks_train(x, w, "blocks1", n, g1, d1, depth[0], keep)
         tape["x1"] = x
         rows = e16(M3, 16 * d1)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 4)
@@ -458,7 +464,7 @@ class ConvMAEBaseEncoder(nn.Module):
         rows = e16(M2, 4 * d1)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 2)
         tape["t2"], x = patch_embed(rows, "patch_embed2", M2, d2, 4 * d1)
-        x, tape["blocks2"] = self._cblocks_train(x, w, "blocks2", n, g2, d2, depth[1])
+        x, tape["blocks2"] = self._cblocks_train(x, w, "blocks2", n, g2, d2, depth[1], keep)
         tape["x2"] = x
         rows = e16(M3, 4 * d2)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g2, g2, d2, 2)
@@ -466,13 +472,22 @@ class ConvMAEBaseEncoder(nn.Module):
         call("isic_gemm_f16", rows, w["stage2_output_decode.weight"], w["stage2_output_decode.bias"], None, s2, M3, d3, 4 * d2, 0, 0)
         tape["t3"], y3 = patch_embed(rows, "patch_embed3", M3, d3, 4 * d2)
         del rows
-        x, tape["blocks3"] = self._vit_blocks_train(y3, w, n, depth[2])
-        out = torch.empty((M3, d3), device=dev, dtype=torch.float32)
-        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, M3, d3, 0, self.ln_eps)
-        tape.update(y3=y3, x3=x, s1=s1, s2=s2)
-        return out.view(n, self.tokens, d3), tape
+        x = e16(M3, d3)
+        call("isic_gemm_f16", y3, w["patch_embed4.weight"], w["patch_embed4.bias"], w["pos_embed"], x, M3, d3, d3, 0, self.tokens)
+        lat16 = None
+        if masking is not None:                                            # the kept tokens of the stream, s1 and s2
+            xk, s1k, s2k = e16(n * L, d3), e16(n * L, d3), e16(n * L, d3)
+            for a, b in ((x, xk), (s1, s1k), (s2, s2k)):
+                call("isic_gather_rows_f16", a, masking["ids_keep"], b, n, self.tokens, L, d3)
+            x, s1, s2, lat16 = xk, s1k, s2k, e16(n * L, d3)
+        x, tape["blocks3"] = self._vit_blocks_train(x, w, n, depth[2], self._blocks3_spec(L))
+        out = torch.empty((n * L, d3), device=dev, dtype=torch.float32)
+        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], lat16, out, n * L, d3, 0, self.ln_eps)
+        tape.update(y3=y3, x3=x, s1=s1, s2=s2, latent16=lat16)
+        return out.view(n, L, d3), tape
 
-    def _cblocks_train(self, x, w, stage, n, g, C, nblk):
+    def _cblocks_train(self, x, w, stage, n, g, C, nblk, keep=None):
+        """``keep`` (uint8 [n, 196], the MAE's token flags; None: no masking) masks the depthwise 5x5's input per token."""
         dev = x.device
         M, Hd, eps = n * g * g, C * self.mlp_ratio, self.conv_ln_eps
         saves = []
@@ -482,7 +497,13 @@ class ConvMAEBaseEncoder(nn.Module):
             pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
             call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, C, 0, eps)
             call("isic_gemm_f16", h1, w[b + ".conv1.weight"], w[b + ".conv1.bias"], None, dd, M, C, C, 0, 0)
-            call("isic_dwconv5x5_f16", dd, w[b + ".attn.weight"], w[b + ".attn.bias"], m, n, g, g, C)
+            if keep is None:
+                call("isic_dwconv5x5_f16", dd, w[b + ".attn.weight"], w[b + ".attn.bias"], m, n, g, g, C)
+            else:                                       # saved: keep * dd, the input the weight gradient takes
+                dk = torch.empty_like(dd)
+                call("isic_dwconv5x5_masked_f16", dd, keep, g // self.grids[2], w[b + ".attn.weight"], w[b + ".attn.bias"],
+                     dk, m, n, g, g, C)
+                dd = dk
             call("isic_gemm_f16", m, w[b + ".conv2.weight"], w[b + ".conv2.bias"], x, x2, M, C, C, 0, 0)
             call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, C, 0, eps)
             call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, C)
@@ -491,21 +512,39 @@ class ConvMAEBaseEncoder(nn.Module):
             x = xo
         return x, saves
 
-    def _vit_blocks_train(self, y3, w, n, nblk):
-        dev = y3.device
-        T, D, H = self.tokens, self.dims[2], self.heads
-        M, Hd, eps = n * T, D * self.mlp_ratio, self.ln_eps
-        x = torch.empty((M, D), device=dev, dtype=_F16)
-        call("isic_gemm_f16", y3, w["patch_embed4.weight"], w["patch_embed4.bias"], w["pos_embed"], x, M, D, D, 0, T)
+    def _blocks3_spec(self, T):
+        """What ``_vit_blocks_train`` / ``_vit_blocks_backward`` need to know of a stack of pre-norm transformer blocks."""
+        return dict(prefix="blocks3", T=T, D=self.dims[2], H=self.heads, eps=self.ln_eps, total=self.depths[2])
+
+    @staticmethod
+    def _attention(qkv, att, n, T, H, hd):
+        if hd == 64:
+            call("isic_attention_f16", qkv, att, n, T, H, hd)
+        else:
+            call("isic_attention_d32_f16", qkv, att, n, T, H)
+
+    @staticmethod
+    def _attention_bwd(qkv, att, dout, dqkv, n, T, H, hd):
+        if hd == 64:
+            call("isic_attention_bwd_f16", qkv, att, dout, dqkv, n, T, H, hd)
+        else:
+            call("isic_attention_d32_bwd_f16", qkv, att, dout, dqkv, n, T, H)
+
+    def _vit_blocks_train(self, x, w, n, nblk, spec):
+        """The first ``nblk`` blocks ``spec["prefix"].i`` over the stream x[n * T, D] (T tokens per image, head width D / H:
+        64, or 32 for the MAE decoder) -> (the output stream, the saved activations per block)."""
+        dev = x.device
+        T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
+        M, Hd = n * T, D * self.mlp_ratio
         saves = []
         for i in range(nblk):
-            b = f"blocks3.{i}"
+            b = f"{spec['prefix']}.{i}"
             h1, att, x2, h2, xo = (torch.empty((M, D), device=dev, dtype=_F16) for _ in range(5))
             qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
             pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
             call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, D, 0, eps)
             call("isic_gemm_f16", h1, w[b + ".attn.qkv.weight"], w[b + ".attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
-            call("isic_attention_f16", qkv, att, n, T, H, D // H)
+            self._attention(qkv, att, n, T, H, D // H)
             call("isic_gemm_f16", att, w[b + ".attn.proj.weight"], w[b + ".attn.proj.bias"], x, x2, M, D, D, 0, 0)
             call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, D, 0, eps)
             call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, D)
@@ -534,17 +573,34 @@ class ConvMAEBaseEncoder(nn.Module):
         with the PatchEmbeds, the stage decoders and ``pos_embed``: their gradients are final earlier, but they sit in
         front of the blocks in registration order, and a group may only be reported once everything registered after it
         is final (isic_hip/ddp.py ``mark_ready``)."""
-        w, n, depth = tape["w"], tape["n"], tape["depth"]
-        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
-        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
-        T, r, ceps = self.tokens, self.mlp_ratio, self.conv_ln_eps
-        dev = dtok.device
         dtok = dtok.float().contiguous()
         amax = float(dtok.abs().amax())                  # the backward's one device -> host read before its final check
         if not math.isfinite(amax):
             raise FloatingPointError("ConvMAEBaseEncoder backward: the incoming gradient is not finite")
         S = 2.0 ** round(8 - math.log2(amax)) if amax > 0 else 1.0
-        s = 1.0 / S
+        self._encoder_backward(tape, dtok, 1, S, 1.0 / S)
+        self._check_grads()
+
+    def _check_grads(self):
+        grads = [p.grad for p in self.parameters() if p.grad is not None]
+        norms = torch._foreach_norm(grads)
+        if not bool(torch.isfinite(torch.stack(norms)).all()):
+            raise FloatingPointError("ConvMAEBaseEncoder backward: non-finite parameter gradient (fp16 overflow in the "
+                                     "backward, or a non-finite gradient accumulated earlier)")
+
+    def _encoder_backward(self, tape, dy, dy_is_f32, dy_mul, s):
+        """The encoder's backward from dy = d loss / d latent (times dy_mul: then the power-of-two scale S), every
+        parameter-gradient reduction multiplied by s.  With ``tape["ids_restore"]`` (the MAE's masked forward) the latent
+        and blocks3 hold the kept tokens only: their gradients are scattered back onto the 196-token grid (zeros at the
+        removed tokens) for the stage decoders and patch_embed4, and the CBlocks take the masked depthwise gradient."""
+        w, n, depth = tape["w"], tape["n"], tape["depth"]
+        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
+        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        T, r, ceps = self.tokens, self.mlp_ratio, self.conv_ln_eps
+        ids_restore, keep = tape.get("ids_restore"), tape.get("keep")
+        L = tape.get("L", T)
+        Mk = n * L
+        dev = dy.device
         nb = 0
         for M, C in ((M1, d1), (M2, d2)):
             for nk in ((C, C), (r * C, C), (C, r * C)):
@@ -587,27 +643,34 @@ class ConvMAEBaseEncoder(nn.Module):
 
         rest = []
         # ---- norm(x + s1 + s2): one gradient g3 for the stream and both stage decoders
-        g3, g3h = torch.empty((M3, d3), device=dev, dtype=f32), e16(M3, d3)
-        ln_add(dtok, 1, S, tape["x3"], tape["s1"], tape["s2"], "norm", 0, self.ln_eps, None, g3, g3h, M3, d3)
+        g3, g3h = torch.empty((Mk, d3), device=dev, dtype=f32), e16(Mk, d3)
+        ln_add(dy, dy_is_f32, dy_mul, tape["x3"], tape["s1"], tape["s2"], "norm", 0, self.ln_eps, None, g3, g3h, Mk, d3)
         self._fire(["norm.weight", "norm.bias"])
+        gfull = g3h
+        if ids_restore is not None:                                         # the kept rows back onto the token grid
+            gfull = e16(M3, d3)
+            call("isic_scatter_rows_f16", g3h, ids_restore, gfull, n, T, L, d3)
         # ---- stage decoders: s = rows . W^T + b, rows the space-to-depth of the stage output
         rows2 = e16(M3, 4 * d2)                                             # also the input rows of patch_embed3
         call("isic_patch_rows_nhwc_f16", tape["x2"], rows2, n, g2, g2, d2, 2)
-        wgrad_conv(g3h, rows2, "stage2_output_decode", d3, 4 * d2, M3, 2, d2)
+        wgrad_conv(gfull, rows2, "stage2_output_decode", d3, 4 * d2, M3, 2, d2)
         dr2 = e16(M3, 4 * d2)
-        call("isic_gemm_f16", g3h, w["stage2_output_decode.weight.t"], None, None, dr2, M3, 4 * d2, d3, 0, 0)
+        call("isic_gemm_f16", gfull, w["stage2_output_decode.weight.t"], None, None, dr2, M3, 4 * d2, d3, 0, 0)
         gs2, gs2h = torch.empty((M2, d2), device=dev, dtype=f32), e16(M2, d2)
         call("isic_patch_rows_bwd_f16", dr2, gs2, None, n, g2, g2, d2, 2, 0)
         rows = e16(M3, 16 * d1)
         call("isic_patch_rows_nhwc_f16", tape["x1"], rows, n, g1, g1, d1, 4)
-        wgrad_conv(g3h, rows, "stage1_output_decode", d3, 16 * d1, M3, 4, d1)
-        call("isic_gemm_f16", g3h, w["stage1_output_decode.weight.t"], None, None, rows, M3, 16 * d1, d3, 0, 0)
+        wgrad_conv(gfull, rows, "stage1_output_decode", d3, 16 * d1, M3, 4, d1)
+        call("isic_gemm_f16", gfull, w["stage1_output_decode.weight.t"], None, None, rows, M3, 16 * d1, d3, 0, 0)
         gs1, gs1h = torch.empty((M1, d1), device=dev, dtype=f32), e16(M1, d1)
         call("isic_patch_rows_bwd_f16", rows, gs1, None, n, g1, g1, d1, 4, 0)
         del rows
         rest += self._block_names("stage2_output_decode") + self._block_names("stage1_output_decode")
         # ---- blocks3, patch_embed4 + pos_embed
-        self._vit_blocks_backward(tape, g3, g3h, ln_add, wgrad, n, depth[2])
+        self._vit_blocks_backward(tape["blocks3"], w, g3, g3h, ln_add, wgrad, n, depth[2], self._blocks3_spec(L))
+        if ids_restore is not None:
+            call("isic_scatter_rows_f16", g3h, ids_restore, gfull, n, T, L, d3)
+            g3h = gfull
         wgrad(g3h, tape["y3"], "patch_embed4", d3, d3, M3)
         call("isic_colsum_f16", g3h, grad("pos_embed"), n, T * d3, s, 1, ws, ws.numel())
         dt3 = e16(M3, d3)
@@ -618,10 +681,10 @@ class ConvMAEBaseEncoder(nn.Module):
         wgrad_conv(g3h, rows2, "patch_embed3.proj", d3, 4 * d2, M3, 2, d2)
         call("isic_gemm_f16", g3h, w["patch_embed3.proj.weight.t"], None, None, dr2, M3, 4 * d2, d3, 0, 0)
         call("isic_patch_rows_bwd_f16", dr2, gs2, gs2h, n, g2, g2, d2, 2, 1)
-        del rows2, dr2, dt3, g3, g3h
+        del rows2, dr2, dt3, g3, g3h, gfull
         rest += self._block_names("patch_embed3")
         # ---- blocks2, patch_embed2
-        self._cblocks_backward(tape, "blocks2", gs2, gs2h, grad, ln_add, wgrad, n, g2, d2, depth[1], ws, s)
+        self._cblocks_backward(tape, "blocks2", gs2, gs2h, grad, ln_add, wgrad, n, g2, d2, depth[1], ws, s, keep)
         ln_add(gs2, 1, 1.0, tape["t2"], None, None, "patch_embed2.norm", 1, ceps, None, None, gs2h, M2, d2)
         rows = e16(M2, 4 * d1)
         call("isic_patch_rows_nhwc_f16", tape["x1"], rows, n, g1, g1, d1, 2)
@@ -631,30 +694,27 @@ class ConvMAEBaseEncoder(nn.Module):
         del rows, gs2, gs2h
         rest += self._block_names("patch_embed2")
         # ---- blocks1, the stem (no data gradient; its rows are padded to K = 128 for the weight-gradient GEMM)
-        self._cblocks_backward(tape, "blocks1", gs1, gs1h, grad, ln_add, wgrad, n, g1, d1, depth[0], ws, s)
+        self._cblocks_backward(tape, "blocks1", gs1, gs1h, grad, ln_add, wgrad, n, g1, d1, depth[0], ws, s, keep)
         ln_add(gs1, 1, 1.0, tape["t1"], None, None, "patch_embed1.norm", 1, ceps, None, None, gs1h, M1, d1)
         rows = e16(M1, 128)
         call("isic_patch_rows_nchw_f32", tape["img"], rows, n, self.in_ch, self.img_size, self.img_size, 4, 128)
         wgrad_conv(gs1h, rows, "patch_embed1.proj", d1, 128, M1, 4, self.in_ch, keep=16 * self.in_ch)
         rest += self._block_names("patch_embed1")
         self._fire(rest)
-        grads = [p.grad for p in self.parameters() if p.grad is not None]
-        norms = torch._foreach_norm(grads)
-        if not bool(torch.isfinite(torch.stack(norms)).all()):
-            raise FloatingPointError("ConvMAEBaseEncoder backward: non-finite parameter gradient (fp16 overflow in the "
-                                     "backward, or a non-finite gradient accumulated earlier)")
 
-    def _vit_blocks_backward(self, tape, g, gh, ln_add, wgrad, n, nblk):
-        w, dev = tape["w"], g.device
-        T, D, H = self.tokens, self.dims[2], self.heads
-        M, Hd, eps = n * T, D * self.mlp_ratio, self.ln_eps
+    def _vit_blocks_backward(self, saves, w, g, gh, ln_add, wgrad, n, nblk, spec):
+        """Backward of ``_vit_blocks_train``: g (fp32) / gh (its fp16 copy), the gradient of the output stream, become
+        those of the input stream (in place); ``saves[i]`` is dropped once block i is done."""
+        dev = g.device
+        T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
+        M, Hd = n * T, D * self.mlp_ratio
         dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
         dD = torch.empty((M, D), device=dev, dtype=_F16)
         dqkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        for i in range(self.depths[2] - 1, nblk - 1, -1):                  # blocks past ``depth`` ran not: no gradient
-            self._fire(self._block_names(f"blocks3.{i}"))
+        for i in range(spec["total"] - 1, nblk - 1, -1):                    # blocks past ``depth`` ran not: no gradient
+            self._fire(self._block_names(f"{spec['prefix']}.{i}"))
         for i in range(nblk - 1, -1, -1):
-            b, sv = f"blocks3.{i}", tape["blocks3"][i]
+            b, sv = f"{spec['prefix']}.{i}", saves[i]
             wgrad(gh, sv["hid"], f"{b}.mlp.fc2", D, Hd, M)
             call("isic_gemm_f16_dgelu", gh, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hd, D)
             wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hd, D, M)
@@ -662,14 +722,14 @@ class ConvMAEBaseEncoder(nn.Module):
             ln_add(dD, 0, 1.0, sv["x2"], None, None, f"{b}.norm2", 0, eps, g, g, gh, M, D)
             wgrad(gh, sv["att"], f"{b}.attn.proj", D, D, M)
             call("isic_gemm_f16", gh, w[f"{b}.attn.proj.weight.t"], None, None, dD, M, D, D, 0, 0)
-            call("isic_attention_bwd_f16", sv["qkv"], sv["att"], dD, dqkv, n, T, H, D // H)
+            self._attention_bwd(sv["qkv"], sv["att"], dD, dqkv, n, T, H, D // H)
             wgrad(dqkv, sv["h1"], f"{b}.attn.qkv", 3 * D, D, M)
             call("isic_gemm_f16", dqkv, w[f"{b}.attn.qkv.weight.t"], None, None, dD, M, D, 3 * D, 0, 0)
             ln_add(dD, 0, 1.0, sv["x"], None, None, f"{b}.norm1", 0, eps, g, g, gh, M, D)
-            tape["blocks3"][i] = None                        # its activations can go
+            saves[i] = None                                  # its activations can go
             self._fire(self._block_names(b))
 
-    def _cblocks_backward(self, tape, stage, g, gh, grad, ln_add, wgrad, n, gr, C, nblk, ws, s):
+    def _cblocks_backward(self, tape, stage, g, gh, grad, ln_add, wgrad, n, gr, C, nblk, ws, s, keep=None):
         w, dev = tape["w"], g.device
         M, Hd, eps = n * gr * gr, C * self.mlp_ratio, self.conv_ln_eps
         dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
@@ -688,7 +748,11 @@ class ConvMAEBaseEncoder(nn.Module):
             wgrad(gh, sv["m"], f"{b}.conv2", C, C, M)
             call("isic_gemm_f16", gh, w[f"{b}.conv2.weight.t"], None, None, dm, M, C, C, 0, 0)
             # depthwise 5x5: data gradient = the same convolution with the taps reversed, no bias; weight + bias gradient
-            call("isic_dwconv5x5_f16", dm, w[f"{b}.attn.weight.rev"], None, dd, n, gr, gr, C)
+            if keep is None:
+                call("isic_dwconv5x5_f16", dm, w[f"{b}.attn.weight.rev"], None, dd, n, gr, gr, C)
+            else:                                                           # its input was keep * d: so is its gradient
+                call("isic_dwconv5x5_masked_dgrad_f16", dm, keep, gr // self.grids[2], w[f"{b}.attn.weight.rev"], dd, n, gr,
+                     gr, C)
             call("isic_dwconv5x5_wgrad_f16", sv["d"], dm, dw, db, n, gr, gr, C, s, 0, ws, ws.numel())
             grad(f"{b}.attn.weight").add_(dw.t().reshape(C, 1, 5, 5))
             grad(f"{b}.attn.bias").add_(db)
