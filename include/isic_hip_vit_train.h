@@ -1,9 +1,11 @@
 /* libisic_hip.so -- training entry points of the ViT-S/16 patch encoder (included by isic_hip.h).
  *
- * The backward pass of ViTSmallEncoder(trainable=True) (multimodal-isic_amd/isic_hip/vit.py).  Conventions as in
- * isic_hip.h: return 0 or a negative ISIC_ERR_* code, arguments are checked before any device work, device pointers,
- * `stream` last.  fp16 tensors travel as uint16_t bit patterns; gradients are fp32.  They sit in a header of their own so
- * that isic_hip.h keeps listing the drop-in surface of the reference.
+ * The backward pass of a stack of pre-norm transformer blocks (multimodal-isic_amd/isic_hip/transformer.py: the ViT-S/16
+ * encoder, blocks3 of ConvMAE-Base and the MAE decoder); its LayerNorm backward is isic_layernorm_add_bwd_f16
+ * (isic_hip_convmae_train.h).  Conventions as in isic_hip.h: return 0 or a negative ISIC_ERR_* code, arguments are
+ * checked before any device work, device pointers, `stream` last.  fp16 tensors travel as uint16_t bit patterns;
+ * gradients are fp32.  They sit in a header of their own so that isic_hip.h keeps listing the drop-in surface of the
+ * reference.
  *
  * The backward runs on loss-scaled gradients (a power of two S chosen by the caller); `scale` (= 1/S) multiplies every
  * reduction that lands in a parameter gradient, in fp32.  accumulate == 1: out += scale * sum, 0: out = scale * sum.
@@ -31,16 +33,6 @@ int isic_gemm_f16_wgrad(const uint16_t* dY, const uint16_t* X, float* dW, float*
 size_t isic_colsum_f16_workspace_bytes(int64_t rows, int cols);
 int isic_colsum_f16(const uint16_t* x, float* out, int64_t rows, int cols, float scale, int accumulate, void* workspace,
                     size_t workspace_bytes, void* stream);
-/* LayerNorm backward over rows of N (N % 128 == 0, N <= 512, else UNSUPPORTED), from the saved input x[M][N] (fp16) and
- * its row statistics stats[M][2] = (mean, rstd) (isic_row_stats_f16).  dy[M][N] is fp16 (dy_is_f32 == 0) or fp32 (1),
- * multiplied by dy_mul on load (the loss scale of the encoder's output gradient).  With x^ = (x - mean) rstd, g^ = dy gamma:
- *   g_out = g_in + rstd (g^ - mean(g^) - x^ mean(g^ x^))      (fp32; g_in NULL = 0; g_out may alias g_in)
- * and its fp16 copy g_out16; dgamma[N] (+)= scale * sum dy x^, dbeta[N] (+)= scale * sum dy. */
-size_t isic_layernorm_bwd_f16_workspace_bytes(int64_t M, int N);
-int isic_layernorm_bwd_f16(const void* dy, int dy_is_f32, float dy_mul, const uint16_t* x, const float* stats,
-                           const float* gamma, const float* g_in, float* g_out, uint16_t* g_out16, float* dgamma,
-                           float* dbeta, int64_t M, int N, float scale, int accumulate, void* workspace,
-                           size_t workspace_bytes, void* stream);
 /* Backward of isic_attention_f16 per (image, head): from qkv[M][3 D], its output out[M][D] and dout[M][D] (fp16,
  * D = heads * 64) -> dqkv[M][3 D] (fp16, same layout as qkv).  S and P are recomputed from q and k (softmax scale 1/8).
  * head_dim 64 and tokens <= 208, else UNSUPPORTED. */

@@ -89,6 +89,35 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
   return __builtin_bit_cast(unsigned short, h);
 }
 
+// ---------------------------------------------------------------- fp16 pairs <-> f32
+// fp16 tensors travel as 16-bit patterns; a 32-bit word holds two of them, a u32x4 eight.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned f16_pack2(float lo, float hi) {
+  const f16x2 h = {(_Float16)lo, (_Float16)hi};                     // round to nearest even
+  return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[0]; }
+__device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[1]; }
+// both halves of one word from a single bit-cast
+__device__ __forceinline__ void f16_unpack2(unsigned w, float& lo, float& hi) {
+  const f16x2 h = __builtin_bit_cast(f16x2, w);
+  lo = (float)h[0];
+  hi = (float)h[1];
+}
+__device__ __forceinline__ void f16_unpack8(const u32x4 v, float (&f)[8]) {
+  // (element by element through a scalar copy: bit-casting `v[i]` in place read element 0 four times with this hipcc)
+  const unsigned w0 = v[0], w1 = v[1], w2 = v[2], w3 = v[3];
+  f[0] = f16_lo(w0); f[1] = f16_hi(w0); f[2] = f16_lo(w1); f[3] = f16_hi(w1);
+  f[4] = f16_lo(w2); f[5] = f16_hi(w2); f[6] = f16_lo(w3); f[7] = f16_hi(w3);
+}
+__device__ __forceinline__ u32x4 f16_pack8(const float (&f)[8]) {
+  u32x4 v;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = f16_pack2(f[2 * i], f[2 * i + 1]);
+  return v;
+}
+
 // ---------------------------------------------------------------- wave reductions (64 lanes)
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. it waits for every
 // global store the wave has in flight -- a full memory round trip when it follows an epilogue's output stores.

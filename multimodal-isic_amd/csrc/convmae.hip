@@ -8,25 +8,6 @@
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned cm_pack2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};                     // round to nearest even
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ void cm_unpack8(const u32x4 v, float (&f)[8]) {
-  const unsigned w0 = v[0], w1 = v[1], w2 = v[2], w3 = v[3];
-  const f16x2 a = __builtin_bit_cast(f16x2, w0), b = __builtin_bit_cast(f16x2, w1);
-  const f16x2 c = __builtin_bit_cast(f16x2, w2), d = __builtin_bit_cast(f16x2, w3);
-  f[0] = (float)a[0]; f[1] = (float)a[1]; f[2] = (float)b[0]; f[3] = (float)b[1];
-  f[4] = (float)c[0]; f[5] = (float)c[1]; f[6] = (float)d[0]; f[7] = (float)d[1];
-}
-__device__ __forceinline__ u32x4 cm_pack8(const float (&f)[8]) {
-  u32x4 v;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = cm_pack2(f[2 * i], f[2 * i + 1]);
-  return v;
-}
 __device__ __forceinline__ float cm_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 
 // ---------------------------------------------------------------- depthwise 5x5
@@ -111,7 +92,7 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
 #pragma unroll
     for (int r = 0; r < DW_LR; ++r) {
       float f[8];
-      cm_unpack8(tile[(r * DW_LC + col + kw) * 8 + g], f);
+      f16_unpack8(tile[(r * DW_LC + col + kw) * 8 + g], f);
 #pragma unroll
       for (int kh = 0; kh < 5; ++kh) {
         const int oh = r - kh;                                         // compile-time after unrolling
@@ -128,7 +109,7 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
       if (MASK == DW_MASK_OUT && !keep[n * (int64_t)((H / P) * (W / P)) + ((h0 + r) / P) * (W / P) + ow / P])
         *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = (u32x4){0u, 0u, 0u, 0u};
       else
-        *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = cm_pack8(acc[r]);
+        *reinterpret_cast<u32x4*>(yp + (size_t)r * W * C) = f16_pack8(acc[r]);
     }
 }
 
@@ -169,7 +150,7 @@ __global__ __launch_bounds__(256) void patch_rows_nchw_kernel(const float* __res
         f[j] = img[(((size_t)n * C + c) * H + (size_t)(py * P + kh)) * W + (size_t)px * P + kw];
       }
     }
-    *reinterpret_cast<u32x4*>(rows + i * 8) = cm_pack8(f);
+    *reinterpret_cast<u32x4*>(rows + i * 8) = f16_pack8(f);
   }
 }
 
@@ -195,16 +176,16 @@ __global__ __launch_bounds__(256) void layernorm_add_f16_kernel(const unsigned s
       const int q = lane + 64 * i;
       const bool on = q < pieces;
       const size_t off = (size_t)row * N + (size_t)(on ? q : 0) * 8;
-      cm_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
+      f16_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
       if (a) {
         float t[8];
-        cm_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
+        f16_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[i][j] += t[j];
       }
       if (b) {
         float t[8];
-        cm_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
+        f16_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[i][j] += t[j];
       }
@@ -240,7 +221,7 @@ __global__ __launch_bounds__(256) void layernorm_add_f16_kernel(const unsigned s
         o8[j] = act ? cm_gelu(t) : t;
       }
       const size_t off = (size_t)row * N + col;
-      if (y) *reinterpret_cast<u32x4*>(y + off) = cm_pack8(o8);
+      if (y) *reinterpret_cast<u32x4*>(y + off) = f16_pack8(o8);
       if (y32) {
         *reinterpret_cast<f32x4*>(y32 + off) = (f32x4){o8[0], o8[1], o8[2], o8[3]};
         *reinterpret_cast<f32x4*>(y32 + off + 4) = (f32x4){o8[4], o8[5], o8[6], o8[7]};

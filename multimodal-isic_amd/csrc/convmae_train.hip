@@ -1,8 +1,9 @@
 // Backward of the convolutional front of the ConvMAE-Base patch encoder (gfx950, fp16 activations, fp32 arithmetic and
 // gradients): the depthwise 5x5 weight / bias gradient, the backward of the LayerNorm of (x + a + b) with its optional
-// GELU, and depth-to-space (the adjoint of the patch rows).  Everything else of the backward is the ViT-S backward
-// (vit_train.hip) and gemm_f16.  Entry points: include/isic_hip_convmae_train.h; the Python side is isic_hip/convmae.py
-// (trainable=True).
+// GELU, and depth-to-space (the adjoint of the patch rows).  Everything else of the backward is the transformer-block
+// backward (vit_train.hip) and gemm_f16; that one in turn takes its LayerNorm backward from here, for all three trainable
+// encoders (isic_hip/transformer.py).  Entry points: include/isic_hip_convmae_train.h; the Python side is
+// isic_hip/convmae.py (trainable=True).
 //
 // Every reduction that lands in a parameter gradient goes into fp32 slabs, one per block, that a second pass adds in a
 // fixed order and multiplies by `scale`: no float atomics, so the backward is bit-reproducible.
@@ -11,26 +12,6 @@
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned ct_pack2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};                     // round to nearest even
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ void ct_unpack2(unsigned w, float& lo, float& hi) {
-  const f16x2 h = __builtin_bit_cast(f16x2, w);
-  lo = (float)h[0];
-  hi = (float)h[1];
-}
-__device__ __forceinline__ void ct_unpack8(const u32x4 v, float (&f)[8]) {
-  ct_unpack2(v[0], f[0], f[1]); ct_unpack2(v[1], f[2], f[3]); ct_unpack2(v[2], f[4], f[5]); ct_unpack2(v[3], f[6], f[7]);
-}
-__device__ __forceinline__ u32x4 ct_pack8(const float (&f)[8]) {
-  u32x4 v;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = ct_pack2(f[2 * i], f[2 * i + 1]);
-  return v;
-}
 // d/dt of 0.5 t (1 + erf(t / sqrt 2)) = Phi(t) + t phi(t)
 __device__ __forceinline__ float ct_dgelu(float t) {
   return 0.5f * (1.f + erff(t * 0.70710678118654752f)) + t * 0.39894228040143268f * __expf(-0.5f * t * t);
@@ -159,8 +140,8 @@ __global__ __launch_bounds__(256) void dwconv5x5_wgrad_f16_kernel(const unsigned
       u32x2 u = (u32x2){0u, 0u};
       if (col < DG_TW && ow < W && h0 + r < H)
         u = *reinterpret_cast<const u32x2*>(dyn + ((size_t)(h0 + r) * W + ow) * C + g * 4);
-      ct_unpack2(u[0], d[r][0], d[r][1]);
-      ct_unpack2(u[1], d[r][2], d[r][3]);
+      f16_unpack2(u[0], d[r][0], d[r][1]);
+      f16_unpack2(u[1], d[r][2], d[r][3]);
     }
     __syncthreads();
     const unsigned short* ts = reinterpret_cast<const unsigned short*>(tile);
@@ -170,8 +151,8 @@ __global__ __launch_bounds__(256) void dwconv5x5_wgrad_f16_kernel(const unsigned
       for (int kw = 0; kw < 5; ++kw) {
         const u32x2 u = *reinterpret_cast<const u32x2*>(ts + (size_t)(r * DG_LC + colr + kw) * DG_CC + g * 4);
         float f[4];
-        ct_unpack2(u[0], f[0], f[1]);
-        ct_unpack2(u[1], f[2], f[3]);
+        f16_unpack2(u[0], f[0], f[1]);
+        f16_unpack2(u[1], f[2], f[3]);
 #pragma unroll
         for (int kh = 0; kh < 5; ++kh) {
           const int oh = r - kh;                                       // compile-time after unrolling
@@ -269,16 +250,16 @@ __global__ __launch_bounds__(256) void layernorm_add_bwd_f16_kernel(const void* 
       const int q = lane + 64 * i;
       const bool on = q < pieces;
       const size_t off = (size_t)row * N + (size_t)(on ? q : 0) * 8;
-      ct_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
+      f16_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
       if (a) {
         float t[8];
-        ct_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
+        f16_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[i][j] += t[j];
       }
       if (b) {
         float t[8];
-        ct_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
+        f16_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[i][j] += t[j];
       }
@@ -312,7 +293,7 @@ __global__ __launch_bounds__(256) void layernorm_add_bwd_f16_kernel(const void* 
         d[i][0] = lo[0]; d[i][1] = lo[1]; d[i][2] = lo[2]; d[i][3] = lo[3];
         d[i][4] = hi[0]; d[i][5] = hi[1]; d[i][6] = hi[2]; d[i][7] = hi[3];
       } else {
-        ct_unpack8(*reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(dy_) + off), d[i]);
+        f16_unpack8(*reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(dy_) + off), d[i]);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -348,7 +329,7 @@ __global__ __launch_bounds__(256) void layernorm_add_bwd_f16_kernel(const void* 
         *reinterpret_cast<f32x4*>(g_out + off) = (f32x4){o8[0], o8[1], o8[2], o8[3]};
         *reinterpret_cast<f32x4*>(g_out + off + 4) = (f32x4){o8[4], o8[5], o8[6], o8[7]};
       }
-      if (g_out16) *reinterpret_cast<u32x4*>(g_out16 + off) = ct_pack8(o8);
+      if (g_out16) *reinterpret_cast<u32x4*>(g_out16 + off) = f16_pack8(o8);
     }
   }
 #pragma unroll
@@ -384,7 +365,7 @@ __global__ __launch_bounds__(256) void patch_rows_bwd_kernel(const unsigned shor
     const int kh = k / seg, rem = k - kh * seg;
     const size_t off = (((size_t)n * H + (size_t)(py * P + kh)) * W + (size_t)px * P) * C + rem;
     float f[8];
-    ct_unpack8(*reinterpret_cast<const u32x4*>(drows + i * 8), f);
+    f16_unpack8(*reinterpret_cast<const u32x4*>(drows + i * 8), f);
     if (accumulate) {
       const f32x4 lo = *reinterpret_cast<const f32x4*>(dx + off), hi = *reinterpret_cast<const f32x4*>(dx + off + 4);
       f[0] += lo[0]; f[1] += lo[1]; f[2] += lo[2]; f[3] += lo[3];
@@ -392,7 +373,7 @@ __global__ __launch_bounds__(256) void patch_rows_bwd_kernel(const unsigned shor
     }
     *reinterpret_cast<f32x4*>(dx + off) = (f32x4){f[0], f[1], f[2], f[3]};
     *reinterpret_cast<f32x4*>(dx + off + 4) = (f32x4){f[4], f[5], f[6], f[7]};
-    if (dx16) *reinterpret_cast<u32x4*>(dx16 + off) = ct_pack8(f);
+    if (dx16) *reinterpret_cast<u32x4*>(dx16 + off) = f16_pack8(f);
   }
 }
 

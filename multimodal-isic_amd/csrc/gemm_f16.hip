@@ -20,7 +20,6 @@
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int GM = 256, GN = 128;
 constexpr int G_A = GM * 128, G_B = GN * 128, G_STAGE = G_A + G_B;   // bytes per K-tile
@@ -60,12 +59,6 @@ __device__ __forceinline__ void g16_glds16(const void* gsrc, unsigned lds_dst) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ unsigned g16_pack2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};                     // round to nearest even
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float g16_lo(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[0]; }
-__device__ __forceinline__ float g16_hi(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[1]; }
 // erf-GELU (nn.GELU default, timm).  libm's erff: a hand-rolled Abramowitz-Stegun 7.1.26 with an exact reciprocal was
 // measured SLOWER (1.01 vs 0.93 ms for fc1; no GELU at all: 0.87 ms -- the layer is bound by its 1.2 GB output).
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
@@ -262,11 +255,11 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
           }
           if (GELU == 2) {
             const unsigned lo = rv[2 * h], hi = rv[2 * h + 1];
-            c[0] *= gelu_erf_grad(g16_lo(lo)); c[1] *= gelu_erf_grad(g16_hi(lo));
-            c[2] *= gelu_erf_grad(g16_lo(hi)); c[3] *= gelu_erf_grad(g16_hi(hi));
+            c[0] *= gelu_erf_grad(f16_lo(lo)); c[1] *= gelu_erf_grad(f16_hi(lo));
+            c[2] *= gelu_erf_grad(f16_lo(hi)); c[3] *= gelu_erf_grad(f16_hi(hi));
           } else if (RES) {
             const unsigned lo = rv[2 * h], hi = rv[2 * h + 1];
-            c[0] += g16_lo(lo); c[1] += g16_hi(lo); c[2] += g16_lo(hi); c[3] += g16_hi(hi);
+            c[0] += f16_lo(lo); c[1] += f16_hi(lo); c[2] += f16_lo(hi); c[3] += f16_hi(hi);
           }
           const f16x2 p0 = {(_Float16)c[0], (_Float16)c[1]}, p1 = {(_Float16)c[2], (_Float16)c[3]};   // round to nearest even
           v[2 * h] = __builtin_bit_cast(unsigned, p0);

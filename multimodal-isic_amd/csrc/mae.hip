@@ -8,8 +8,6 @@
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 // ---------------------------------------------------------------- row movement
 // One thread per 16-byte piece (8 fp16 channels) of an output row: every output element is written exactly once, no atomics.
 // An index outside [0, T) yields a zero row (never an out-of-bounds read).
@@ -43,11 +41,6 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const unsigned short*
   }
 }
 
-__device__ __forceinline__ unsigned mae_pack2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(unsigned, h);
-}
-
 // out[n][t] = fp16((rank < L ? y[n][rank] : mask_token) + pos[t]), the sum in fp32
 __global__ __launch_bounds__(256) void unshuffle_kernel(const unsigned short* __restrict__ y, const int64_t* __restrict__ ids_restore,
                                                         const float* __restrict__ mask_token, const float* __restrict__ pos,
@@ -60,13 +53,7 @@ __global__ __launch_bounds__(256) void unshuffle_kernel(const unsigned short* __
     const int64_t n = r / T, t = r - n * T, rank = ids_restore[r];
     float f[8];
     if (rank >= 0 && rank < L) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(y + ((n * L + rank) * C) + 8 * c);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f16x2 h = __builtin_bit_cast(f16x2, (unsigned)v[i]);
-        f[2 * i] = (float)h[0];
-        f[2 * i + 1] = (float)h[1];
-      }
+      f16_unpack8(*reinterpret_cast<const u32x4*>(y + ((n * L + rank) * C) + 8 * c), f);
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) f[i] = mask_token[8 * c + i];
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(256) void unshuffle_kernel(const unsigned short* __
     const float* pr = pos + t * C + 8 * c;
     u32x4 o;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = mae_pack2(f[2 * i] + pr[2 * i], f[2 * i + 1] + pr[2 * i + 1]);
+    for (int i = 0; i < 4; ++i) o[i] = f16_pack2(f[2 * i] + pr[2 * i], f[2 * i + 1] + pr[2 * i + 1]);
     *reinterpret_cast<u32x4*>(out + r * C + 8 * c) = o;
   }
 }

@@ -12,26 +12,6 @@ namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_h2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float h_lo(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[0]; }
-__device__ __forceinline__ float h_hi(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[1]; }
-__device__ __forceinline__ void unpack_h8(const u32x4 v, float (&f)[8]) {
-  // (element by element through a scalar copy: bit-casting `v[i]` in place read element 0 four times with this hipcc)
-  const unsigned w0 = v[0], w1 = v[1], w2 = v[2], w3 = v[3];
-  f[0] = h_lo(w0); f[1] = h_hi(w0); f[2] = h_lo(w1); f[3] = h_hi(w1);
-  f[4] = h_lo(w2); f[5] = h_hi(w2); f[6] = h_lo(w3); f[7] = h_hi(w3);
-}
-__device__ __forceinline__ u32x4 pack_h8(const float (&f)[8]) {
-  u32x4 v;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = pack_h2(f[2 * i], f[2 * i + 1]);
-  return v;
-}
 
 // ---------------------------------------------------------------- patches
 // images NCHW (fp32 or bf16/fp16 bits are not mixed here: fp32 in) -> rows [n*gh*gw + py*gw + px][c*P*P + ky*P + kx]
@@ -48,7 +28,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     const float* src = img + (((size_t)n * C + c) * H + (py * P + ky)) * W + px * P + kx;
     const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
     const float f[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    *reinterpret_cast<u32x4*>(out + i * 8) = pack_h8(f);
+    *reinterpret_cast<u32x4*>(out + i * 8) = f16_pack8(f);
   }
 }
 
@@ -70,7 +50,7 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const unsigned short
   for (int j = 0; j < 8; ++j) { g[j] = gamma[col + j]; b[j] = beta[col + j]; }
   for (int64_t row = (int64_t)blockIdx.x * rls + rl; row < M; row += (int64_t)gridDim.x * rls) {
     float f[8];
-    unpack_h8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
+    f16_unpack8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += act ? f[j] : 0.f;
@@ -85,7 +65,7 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const unsigned short
     const float rstd = rsqrtf(v * (1.f / N) + eps);
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = f[j] * rstd * g[j] + b[j];
-    if (act && y) *reinterpret_cast<u32x4*>(y + row * N + col) = pack_h8(f);
+    if (act && y) *reinterpret_cast<u32x4*>(y + row * N + col) = f16_pack8(f);
     if (act && y32) {
       *reinterpret_cast<f32x4*>(y32 + row * N + col) = (f32x4){f[0], f[1], f[2], f[3]};
       *reinterpret_cast<f32x4*>(y32 + row * N + col + 4) = (f32x4){f[4], f[5], f[6], f[7]};
@@ -105,7 +85,7 @@ __global__ __launch_bounds__(256) void row_stats_f16_kernel(const unsigned short
   const int col = (act ? lane : 0) * 8;
   for (int64_t row = (int64_t)blockIdx.x * rls + rl; row < M; row += (int64_t)gridDim.x * rls) {
     float f[8];
-    unpack_h8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
+    f16_unpack8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += act ? f[j] : 0.f;

@@ -1,9 +1,10 @@
-// Backward pass of the ViT-S/16 patch encoder (gfx950, fp16 operands, fp32 arithmetic and gradients): the weight-gradient
-// GEMM, the attention backward, the LayerNorm backward and a column-sum reducer (bias and position-embedding gradients).
-// The data-gradient products and the GELU-derivative epilogue are modes of gemm_f16.hip.  Entry points:
-// include/isic_hip_vit_train.h; the Python side is isic_hip/vit.py (trainable=True).
+// Backward pass of a stack of pre-norm transformer blocks (gfx950, fp16 operands, fp32 arithmetic and gradients): the
+// weight-gradient GEMM, the attention backward and a column-sum reducer (bias and position-embedding gradients).  The
+// data-gradient products and the GELU-derivative epilogue are modes of gemm_f16.hip; the LayerNorm backward is
+// isic_layernorm_add_bwd_f16 (convmae_train.hip), which recomputes the forward's statistics.  Entry points:
+// include/isic_hip_vit_train.h; the Python side is isic_hip/transformer.py, shared by the three trainable encoders.
 //
-// The backward runs on gradients multiplied by a power-of-two loss scale S (vit.py picks it per call); every reduction that
+// The backward runs on gradients multiplied by a power-of-two loss scale S (picked per call); every reduction that
 // lands in a parameter gradient multiplies by `scale` = 1/S in fp32.  Every reduction is split over blocks into fp32 slabs
 // that one more pass adds in a fixed order: no float atomics, so the step is bit-reproducible.
 
@@ -12,15 +13,6 @@
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float vt_lo(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[0]; }
-__device__ __forceinline__ float vt_hi(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[1]; }
-__device__ __forceinline__ unsigned vt_pack2(float lo, float hi) {
-  const f16x2 h = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(unsigned, h);
-}
 
 // ------------------------------------------------------------------ slab reducer
 // out[i] = (accumulate ? out[i] : 0) + scale * sum_{z < S} ws[z][i], z in index order
@@ -69,8 +61,8 @@ __global__ __launch_bounds__(256) void colsum_f16_kernel(const unsigned short* _
     for (int64_t r = r0 + rl; r < r1; r += 32) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(x + r * C + c0);
       const unsigned w0 = v[0], w1 = v[1], w2 = v[2], w3 = v[3];
-      s[0] += vt_lo(w0); s[1] += vt_hi(w0); s[2] += vt_lo(w1); s[3] += vt_hi(w1);
-      s[4] += vt_lo(w2); s[5] += vt_hi(w2); s[6] += vt_lo(w3); s[7] += vt_hi(w3);
+      s[0] += f16_lo(w0); s[1] += f16_hi(w0); s[2] += f16_lo(w1); s[3] += f16_hi(w1);
+      s[4] += f16_lo(w2); s[5] += f16_hi(w2); s[6] += f16_lo(w3); s[7] += f16_hi(w3);
     }
   }
 #pragma unroll
@@ -216,115 +208,6 @@ size_t wgrad_ws_bytes(int64_t M, int N, int K, bool with_bias) {
   return b;
 }
 
-// ------------------------------------------------------------------ LayerNorm backward over rows of N (N % 128 == 0, <= 512)
-// One wave per row: lane l holds the column pairs 2l + 128c, c < N / 128.  Rows are split over a fixed grid of blocks in
-// contiguous chunks; a lane keeps its columns' partial (sum dy x^, sum dy) over its wave's rows, the four waves are added in
-// LDS in index order and each block writes one slab.
-constexpr int LN_MAXC = 4;                  // N <= 512
-constexpr int LN_BLOCKS = 512;
-
-__global__ __launch_bounds__(256) void layernorm_bwd_f16_kernel(const void* __restrict__ dy_, int dy_f32, float dy_mul,
-                                                                const unsigned short* __restrict__ x,
-                                                                const float* __restrict__ stats,
-                                                                const float* __restrict__ gamma,
-                                                                const float* g_in, float* g_out, unsigned short* g_out16,
-                                                                int64_t M, int N, int64_t chunk, float* slab) {
-  __shared__ float red[4][2][512];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nc = N / 128;
-  const float invN = 1.f / (float)N;
-  float pg[LN_MAXC][2] = {}, pb[LN_MAXC][2] = {};
-  float gam[LN_MAXC][2];
-#pragma unroll
-  for (int c = 0; c < LN_MAXC; ++c)
-    if (c < nc) {
-      const f32x2 gv = *reinterpret_cast<const f32x2*>(gamma + 2 * lane + 128 * c);
-      gam[c][0] = gv[0]; gam[c][1] = gv[1];
-    }
-  const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = min(M, r0 + chunk);
-  for (int64_t r = r0 + wave; r < r1; r += 4) {
-    const f32x2 mr = *reinterpret_cast<const f32x2*>(stats + r * 2);
-    const float mean = mr[0], rstd = mr[1];
-    float dy[LN_MAXC][2], xh[LN_MAXC][2];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-      if (c >= nc) break;
-      const int64_t o = r * N + 2 * lane + 128 * c;
-      if (dy_f32) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(dy_) + o);
-        dy[c][0] = v[0] * dy_mul; dy[c][1] = v[1] * dy_mul;
-      } else {
-        const unsigned w = reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(dy_) + o)[0];
-        dy[c][0] = vt_lo(w) * dy_mul; dy[c][1] = vt_hi(w) * dy_mul;
-      }
-      const unsigned xw = reinterpret_cast<const unsigned*>(x + o)[0];
-      xh[c][0] = (vt_lo(xw) - mean) * rstd; xh[c][1] = (vt_hi(xw) - mean) * rstd;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float gh = dy[c][e] * gam[c][e];
-        s1 += gh;
-        s2 = fmaf(gh, xh[c][e], s2);
-        pg[c][e] = fmaf(dy[c][e], xh[c][e], pg[c][e]);
-        pb[c][e] += dy[c][e];
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-    const float a = s1 * invN, bb = s2 * invN;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-      if (c >= nc) break;
-      const int64_t o = r * N + 2 * lane + 128 * c;
-      float g[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) g[e] = rstd * (dy[c][e] * gam[c][e] - a - xh[c][e] * bb);
-      if (g_in) {
-        const f32x2 gi = *reinterpret_cast<const f32x2*>(g_in + o);
-        g[0] += gi[0]; g[1] += gi[1];
-      }
-      *reinterpret_cast<f32x2*>(g_out + o) = (f32x2){g[0], g[1]};
-      reinterpret_cast<unsigned*>(g_out16 + o)[0] = vt_pack2(g[0], g[1]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < LN_MAXC; ++c)
-    if (c < nc) {
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        red[wave][0][2 * lane + 128 * c + e] = pg[c][e];
-        red[wave][1][2 * lane + 128 * c + e] = pb[c][e];
-      }
-    }
-  __syncthreads();
-  for (int i = tid; i < 2 * N; i += 256) {
-    const int which = i / N, col = i - which * N;
-    const float t = ((red[0][which][col] + red[1][which][col]) + red[2][which][col]) + red[3][which][col];
-    slab[((int64_t)blockIdx.x * 2 + which) * N + col] = t;
-  }
-}
-
-struct LnPlan { int G; int64_t chunk; };
-LnPlan ln_plan(int64_t M) {
-  int64_t G = (M + 63) / 64;
-  if (G > LN_BLOCKS) G = LN_BLOCKS;
-  if (G < 1) G = 1;
-  const int64_t chunk = (M + G - 1) / G;
-  return {(int)((M + chunk - 1) / chunk), chunk};
-}
-
-// slab[G][2][N] -> dgamma[n] (+)= scale * sum_g slab[g][0][n], dbeta likewise
-__global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ slab, int G, int N, float* dgamma,
-                                                              float* dbeta, float scale, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * N) return;
-  const int which = i / N, col = i - which * N;
-  float s = 0.f;
-  for (int g = 0; g < G; ++g) s += slab[((int64_t)g * 2 + which) * N + col];
-  float* out = which ? dbeta : dgamma;
-  out[col] = accumulate ? fmaf(scale, s, out[col]) : scale * s;
-}
-
 // ------------------------------------------------------------------ attention backward, one block per (image, head)
 // Scalar fp32 on VALU (fp16 pair dot products on v_dot2): S and P are recomputed from Q and K.
 //   pass 1 (thread = query i): row max m_i and sum l_i of exp(s_ij - m_i), Delta_i = dO_i . O_i
@@ -355,8 +238,8 @@ __device__ __forceinline__ void axpy_hd(float (&acc)[HD], float w, const unsigne
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const unsigned u = v[e];
-      acc[8 * c + 2 * e] = fmaf(w, vt_lo(u), acc[8 * c + 2 * e]);
-      acc[8 * c + 2 * e + 1] = fmaf(w, vt_hi(u), acc[8 * c + 2 * e + 1]);
+      acc[8 * c + 2 * e] = fmaf(w, f16_lo(u), acc[8 * c + 2 * e]);
+      acc[8 * c + 2 * e + 1] = fmaf(w, f16_hi(u), acc[8 * c + 2 * e + 1]);
     }
   }
 }
@@ -375,7 +258,7 @@ __device__ __forceinline__ void store_row(unsigned short* p, const float (&a)[HD
   for (int c = 0; c < HD / 8; ++c) {
     u32x4 v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = vt_pack2(a[8 * c + 2 * e] * mul, a[8 * c + 2 * e + 1] * mul);
+    for (int e = 0; e < 4; ++e) v[e] = f16_pack2(a[8 * c + 2 * e] * mul, a[8 * c + 2 * e + 1] * mul);
     *reinterpret_cast<u32x4*>(p + 8 * c) = v;
   }
 }
@@ -514,36 +397,6 @@ int isic_colsum_f16(const uint16_t* x, float* out, int64_t rows, int cols, float
   if (workspace_bytes < isic_colsum_f16_workspace_bytes(rows, cols) || (workspace_bytes > 0 && !workspace))
     return ISIC_ERR_WORKSPACE;
   return colsum(x, rows, cols, out, scale, accumulate, reinterpret_cast<float*>(workspace), st);
-}
-
-size_t isic_layernorm_bwd_f16_workspace_bytes(int64_t M, int N) {
-  if (M <= 0 || N <= 0) return 0;
-  return (size_t)ln_plan(M).G * 2 * N * sizeof(float);
-}
-
-int isic_layernorm_bwd_f16(const void* dy, int dy_is_f32, float dy_mul, const uint16_t* x, const float* stats,
-                           const float* gamma, const float* g_in, float* g_out, uint16_t* g_out16, float* dgamma,
-                           float* dbeta, int64_t M, int N, float scale, int accumulate, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  ISIC_CHECK_ARG(M >= 0 && N > 0 && (dy_is_f32 == 0 || dy_is_f32 == 1) && (accumulate == 0 || accumulate == 1));
-  if (N % 128 != 0 || N > 128 * LN_MAXC) return ISIC_ERR_UNSUPPORTED;
-  ISIC_CHECK_ARG(gamma && dgamma && dbeta);
-  ISIC_CHECK_ARG(M == 0 || (dy && x && stats && g_out && g_out16));
-  hipStream_t st = as_stream(stream);
-  if (M == 0) {
-    if (accumulate) return ISIC_OK;
-    if (hipMemsetAsync(dgamma, 0, (size_t)N * sizeof(float), st) != hipSuccess) return ISIC_ERR_LAUNCH;
-    return hipMemsetAsync(dbeta, 0, (size_t)N * sizeof(float), st) == hipSuccess ? ISIC_OK : ISIC_ERR_LAUNCH;
-  }
-  if (!workspace || workspace_bytes < isic_layernorm_bwd_f16_workspace_bytes(M, N)) return ISIC_ERR_WORKSPACE;
-  const LnPlan p = ln_plan(M);
-  float* slab = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(layernorm_bwd_f16_kernel, dim3(p.G), dim3(256), 0, st, dy, dy_is_f32, dy_mul, x, stats, gamma, g_in,
-                     g_out, g_out16, M, N, p.chunk, slab);
-  if (isic_launch_status() != ISIC_OK) return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * N + 255) / 256), dim3(256), 0, st, slab, p.G, N, dgamma, dbeta, scale,
-                     accumulate);
-  return isic_launch_status();
 }
 
 int isic_attention_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, uint16_t* dqkv, int n_images,

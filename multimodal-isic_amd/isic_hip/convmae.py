@@ -43,15 +43,16 @@ stream carries rows with large offsets, where the fold's E[x^2] - mean^2 cancels
 
 ``trainable=True`` (opt-in; the default stays the frozen encoder above, bit for bit): the parameters require grad,
 ``train()`` works (no dropout or drop-path: the mode changes no arithmetic) and the encoder runs the layer-by-layer form
-(``fold_layernorm=False``).  Under grad, ``forward`` / ``forward_tokens`` go through ``_ConvMAEFn``: a forward that is
-bitwise ``run_tokens`` of the unfolded form and saves its activations (fp16: per CBlock x, LN1(x), conv1's output, the
-depthwise output, x2, LN2(x2), fc1's pre-activation and GELU output; per ViT block the ViT-S set; the three PatchEmbed
-convolution outputs and the two stage outputs; about 0.12 GB per image, 31 GB at 256 images), and a native backward
-(include/isic_hip_convmae_train.h + include/isic_hip_vit_train.h) that accumulates into ``param.grad``.  The backward
-runs in fp16 under a power-of-two loss scale S = 2^round(8 - log2 amax(d tokens)), one device -> host read per call;
-every reduction into a parameter gradient multiplies by 1/S in fp32, so gradients are exactly scale-equivariant.  An
-fp16 overflow is not retried: the backward checks the gradients once at its end and raises ``FloatingPointError``.  The
-training forward does not chunk the batch (``max_batch`` applies to ``run_tokens``).
+(``fold_layernorm=False``).  Under grad, ``forward`` / ``forward_tokens`` go through ``transformer.EncoderFn``: a
+forward that is bitwise ``run_tokens`` of the unfolded form and saves its activations (fp16: per CBlock x, LN1(x),
+conv1's output, the depthwise output, x2, LN2(x2), fc1's pre-activation and GELU output; per transformer block the set
+of isic_hip/transformer.py; the three PatchEmbed convolution outputs and the two stage outputs; about 0.12 GB per image,
+31 GB at 256 images), and a native backward (include/isic_hip_convmae_train.h + include/isic_hip_vit_train.h) that
+accumulates into ``param.grad``.  The backward runs in fp16 under a power-of-two loss scale S = 2^round(8 - log2 amax(d
+tokens)), one device -> host read per call; every reduction into a parameter gradient multiplies by 1/S in fp32, so
+gradients are exactly scale-equivariant.  An fp16 overflow is not retried: the backward checks the gradients once at its
+end and raises ``FloatingPointError``.  The training forward does not chunk the batch (``max_batch`` applies to
+``run_tokens``).
 
 Memory: the batch runs in chunks of at most ``max_batch`` images (default 256); stage 1 holds about 15 MB of fp16
 activations per image of a chunk (the fc1 output alone is 3136 x 1024 x 2 bytes), 3.9 GB at 256 images.  An image's
@@ -66,6 +67,8 @@ import torch
 from torch import nn
 
 from .lib import IsicHipError, call
+from .transformer import (Backward, EncoderFn, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads,
+                          loss_scale, param_grads)
 
 _F16 = torch.float16
 
@@ -395,9 +398,9 @@ class ConvMAEBaseEncoder(nn.Module):
         return x
 
     def forward_tokens(self, images, depth=None):
-        """tokens[N, 196, 768] fp32; differentiable (``_ConvMAEFn``) when the encoder is trainable and grad is enabled."""
+        """tokens[N, 196, 768] fp32; differentiable (``transformer.EncoderFn``) when the encoder is trainable and grad is enabled."""
         if self.trainable and torch.is_grad_enabled():
-            return _ConvMAEFn.apply(images, self, depth, *self.parameters())
+            return EncoderFn.apply(images, self, (depth,), *self.parameters())
         return self.run_tokens(images, depth=depth)
 
     def forward(self, images):
@@ -480,7 +483,7 @@ class ConvMAEBaseEncoder(nn.Module):
             for a, b in ((x, xk), (s1, s1k), (s2, s2k)):
                 call("isic_gather_rows_f16", a, masking["ids_keep"], b, n, self.tokens, L, d3)
             x, s1, s2, lat16 = xk, s1k, s2k, e16(n * L, d3)
-        x, tape["blocks3"] = self._vit_blocks_train(x, w, n, depth[2], self._blocks3_spec(L))
+        x, tape["blocks3"] = blocks_forward_train(w, x, n, depth[2], self._blocks3_spec(L))
         out = torch.empty((n * L, d3), device=dev, dtype=torch.float32)
         call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], lat16, out, n * L, d3, 0, self.ln_eps)
         tape.update(y3=y3, x3=x, s1=s1, s2=s2, latent16=lat16)
@@ -513,51 +516,8 @@ class ConvMAEBaseEncoder(nn.Module):
         return x, saves
 
     def _blocks3_spec(self, T):
-        """What ``_vit_blocks_train`` / ``_vit_blocks_backward`` need to know of a stack of pre-norm transformer blocks."""
+        """blocks3 over T tokens per image, as isic_hip/transformer.py describes a stack of blocks."""
         return dict(prefix="blocks3", T=T, D=self.dims[2], H=self.heads, eps=self.ln_eps, total=self.depths[2])
-
-    @staticmethod
-    def _attention(qkv, att, n, T, H, hd):
-        if hd == 64:
-            call("isic_attention_f16", qkv, att, n, T, H, hd)
-        else:
-            call("isic_attention_d32_f16", qkv, att, n, T, H)
-
-    @staticmethod
-    def _attention_bwd(qkv, att, dout, dqkv, n, T, H, hd):
-        if hd == 64:
-            call("isic_attention_bwd_f16", qkv, att, dout, dqkv, n, T, H, hd)
-        else:
-            call("isic_attention_d32_bwd_f16", qkv, att, dout, dqkv, n, T, H)
-
-    def _vit_blocks_train(self, x, w, n, nblk, spec):
-        """The first ``nblk`` blocks ``spec["prefix"].i`` over the stream x[n * T, D] (T tokens per image, head width D / H:
-        64, or 32 for the MAE decoder) -> (the output stream, the saved activations per block)."""
-        dev = x.device
-        T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
-        M, Hd = n * T, D * self.mlp_ratio
-        saves = []
-        for i in range(nblk):
-            b = f"{spec['prefix']}.{i}"
-            h1, att, x2, h2, xo = (torch.empty((M, D), device=dev, dtype=_F16) for _ in range(5))
-            qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-            pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
-            call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, D, 0, eps)
-            call("isic_gemm_f16", h1, w[b + ".attn.qkv.weight"], w[b + ".attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
-            self._attention(qkv, att, n, T, H, D // H)
-            call("isic_gemm_f16", att, w[b + ".attn.proj.weight"], w[b + ".attn.proj.bias"], x, x2, M, D, D, 0, 0)
-            call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, D, 0, eps)
-            call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, D)
-            call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, xo, M, D, Hd, 0, 0)
-            saves.append(dict(x=x, h1=h1, qkv=qkv, att=att, x2=x2, h2=h2, pre=pre, hid=hid))
-            x = xo
-        return x, saves
-
-    def _workspace(self, nbytes, device):
-        ws = self._ws
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            ws = self._ws = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
-        return ws
 
     def _fire(self, names):
         if self.grad_ready_hook is not None:
@@ -573,61 +533,48 @@ class ConvMAEBaseEncoder(nn.Module):
         with the PatchEmbeds, the stage decoders and ``pos_embed``: their gradients are final earlier, but they sit in
         front of the blocks in registration order, and a group may only be reported once everything registered after it
         is final (isic_hip/ddp.py ``mark_ready``)."""
-        dtok = dtok.float().contiguous()
-        amax = float(dtok.abs().amax())                  # the backward's one device -> host read before its final check
-        if not math.isfinite(amax):
-            raise FloatingPointError("ConvMAEBaseEncoder backward: the incoming gradient is not finite")
-        S = 2.0 ** round(8 - math.log2(amax)) if amax > 0 else 1.0
-        self._encoder_backward(tape, dtok, 1, S, 1.0 / S)
-        self._check_grads()
+        dtok, S = loss_scale(dtok, type(self).__name__)   # the backward's one device -> host read before its final check
+        bw = Backward(self, tape["w"], param_grads(self), 1.0 / S, self._encoder_workspace_bytes(tape), dtok.device)
+        self._encoder_backward(tape, dtok, 1, S, bw)
+        check_grads(self.parameters(), type(self).__name__)
 
-    def _check_grads(self):
-        grads = [p.grad for p in self.parameters() if p.grad is not None]
-        norms = torch._foreach_norm(grads)
-        if not bool(torch.isfinite(torch.stack(norms)).all()):
-            raise FloatingPointError("ConvMAEBaseEncoder backward: non-finite parameter gradient (fp16 overflow in the "
-                                     "backward, or a non-finite gradient accumulated earlier)")
-
-    def _encoder_backward(self, tape, dy, dy_is_f32, dy_mul, s):
-        """The encoder's backward from dy = d loss / d latent (times dy_mul: then the power-of-two scale S), every
-        parameter-gradient reduction multiplied by s.  With ``tape["ids_restore"]`` (the MAE's masked forward) the latent
-        and blocks3 hold the kept tokens only: their gradients are scattered back onto the 196-token grid (zeros at the
-        removed tokens) for the stage decoders and patch_embed4, and the CBlocks take the masked depthwise gradient."""
-        w, n, depth = tape["w"], tape["n"], tape["depth"]
+    def _encoder_workspace_bytes(self, tape):
+        """The slabs of the largest reduction of ``_encoder_backward``."""
+        w, n = tape["w"], tape["n"]
         (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
         M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
-        T, r, ceps = self.tokens, self.mlp_ratio, self.conv_ln_eps
-        ids_restore, keep = tape.get("ids_restore"), tape.get("keep")
-        L = tape.get("L", T)
-        Mk = n * L
-        dev = dy.device
-        nb = 0
+        T, r = self.tokens, self.mlp_ratio
+        nb = blocks_workspace_bytes(w, n, self._blocks3_spec(tape.get("L", T)))
         for M, C in ((M1, d1), (M2, d2)):
             for nk in ((C, C), (r * C, C), (C, r * C)):
                 nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, *nk))
             nb = max(nb, call("isic_layernorm_add_bwd_f16_workspace_bytes", M, C), call("isic_colsum_f16_workspace_bytes", M, C))
-        for M, nk in ((M3, (d3, 16 * d1)), (M3, (d3, 4 * d2)), (M2, (d2, 4 * d1)), (M1, (d1, 128)), (M3, (3 * d3, d3)),
-                      (M3, (d3, d3)), (M3, (r * d3, d3)), (M3, (d3, r * d3))):
+        for M, nk in ((M3, (d3, 16 * d1)), (M3, (d3, 4 * d2)), (M2, (d2, 4 * d1)), (M1, (d1, 128)), (M3, (d3, d3))):
             nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, *nk))
-        nb = max(nb, call("isic_layernorm_add_bwd_f16_workspace_bytes", M3, d3), call("isic_colsum_f16_workspace_bytes", M3, d3),
-                 call("isic_colsum_f16_workspace_bytes", n, T * d3),
-                 call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g1, g1, d1),
-                 call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g2, g2, d2))
-        ws = self._workspace(nb, dev)
-        params = dict(self.named_parameters())
+        return max(nb, call("isic_layernorm_add_bwd_f16_workspace_bytes", M3, d3), call("isic_colsum_f16_workspace_bytes", M3, d3),
+                   call("isic_colsum_f16_workspace_bytes", n, T * d3),
+                   call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g1, g1, d1),
+                   call("isic_dwconv5x5_wgrad_f16_workspace_bytes", n, g2, g2, d2))
+
+    def _encoder_backward(self, tape, dy, dy_is_f32, dy_mul, bw):
+        """The encoder's backward from dy = d loss / d latent (times dy_mul: then the power-of-two scale S), every
+        parameter-gradient reduction multiplied by ``bw.s`` (transformer.Backward).  With ``tape["ids_restore"]`` (the MAE's
+        masked forward) the latent and blocks3 hold the kept tokens only: their gradients are scattered back onto the
+        196-token grid (zeros at the removed tokens) for the stage decoders and patch_embed4, and the CBlocks take the
+        masked depthwise gradient."""
+        w, n, depth = tape["w"], tape["n"], tape["depth"]
+        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
+        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        T, ceps = self.tokens, self.conv_ln_eps
+        ids_restore, keep = tape.get("ids_restore"), tape.get("keep")
+        L = tape.get("L", T)
+        Mk = n * L
+        dev = dy.device
+        grad, wgrad, ln_add, ws, s = bw.grad, bw.wgrad, bw.ln_add, bw.ws, bw.s
         f32 = torch.float32
 
         def e16(*shape):
             return torch.empty(shape, device=dev, dtype=_F16)
-
-        def grad(name):
-            p = params[name]
-            if p.grad is None:
-                p.grad = torch.zeros_like(p.data)
-            return p.grad
-
-        def wgrad(dy, xin, name, Nout, K, M):
-            call("isic_gemm_f16_wgrad", dy, xin, grad(name + ".weight"), grad(name + ".bias"), M, Nout, K, s, 1, ws, ws.numel())
 
         def wgrad_conv(dy, xin, name, Nout, K, M, P, Cin, keep=None):
             """a P x P patch convolution: the [O][kh][kw][I] gradient of the rows, permuted to the OIHW weight"""
@@ -635,11 +582,7 @@ class ConvMAEBaseEncoder(nn.Module):
             call("isic_gemm_f16_wgrad", dy, xin, tmp, None, M, Nout, K, s, 0, ws, ws.numel())
             tmp = tmp[:, :keep] if keep is not None else tmp
             grad(name + ".weight").add_(tmp.reshape(Nout, P, P, Cin).permute(0, 3, 1, 2))
-            call("isic_colsum_f16", dy, grad(name + ".bias"), M, Nout, s, 1, ws, ws.numel())
-
-        def ln_add(dy, dy_f32, mul, xin, a, b, norm, act, eps, g_in, g_out, g16, M, N):
-            call("isic_layernorm_add_bwd_f16", dy, dy_f32, mul, xin, a, b, w[norm + ".weight"], w[norm + ".bias"], act, eps,
-                 g_in, g_out, g16, grad(norm + ".weight"), grad(norm + ".bias"), M, N, s, 1, ws, ws.numel())
+            bw.colsum(dy, name + ".bias", M, Nout)
 
         rest = []
         # ---- norm(x + s1 + s2): one gradient g3 for the stream and both stage decoders
@@ -667,12 +610,12 @@ class ConvMAEBaseEncoder(nn.Module):
         del rows
         rest += self._block_names("stage2_output_decode") + self._block_names("stage1_output_decode")
         # ---- blocks3, patch_embed4 + pos_embed
-        self._vit_blocks_backward(tape["blocks3"], w, g3, g3h, ln_add, wgrad, n, depth[2], self._blocks3_spec(L))
+        blocks_backward(tape["blocks3"], g3, g3h, bw, n, depth[2], self._blocks3_spec(L), self._fire)
         if ids_restore is not None:
             call("isic_scatter_rows_f16", g3h, ids_restore, gfull, n, T, L, d3)
             g3h = gfull
         wgrad(g3h, tape["y3"], "patch_embed4", d3, d3, M3)
-        call("isic_colsum_f16", g3h, grad("pos_embed"), n, T * d3, s, 1, ws, ws.numel())
+        bw.colsum(g3h, "pos_embed", n, T * d3)
         dt3 = e16(M3, d3)
         call("isic_gemm_f16", g3h, w["patch_embed4.weight.t"], None, None, dt3, M3, d3, d3, 0, 0)
         rest += self._block_names("patch_embed4") + ["pos_embed"]
@@ -684,7 +627,7 @@ class ConvMAEBaseEncoder(nn.Module):
         del rows2, dr2, dt3, g3, g3h, gfull
         rest += self._block_names("patch_embed3")
         # ---- blocks2, patch_embed2
-        self._cblocks_backward(tape, "blocks2", gs2, gs2h, grad, ln_add, wgrad, n, g2, d2, depth[1], ws, s, keep)
+        self._cblocks_backward(tape, "blocks2", gs2, gs2h, bw, n, g2, d2, depth[1], keep)
         ln_add(gs2, 1, 1.0, tape["t2"], None, None, "patch_embed2.norm", 1, ceps, None, None, gs2h, M2, d2)
         rows = e16(M2, 4 * d1)
         call("isic_patch_rows_nhwc_f16", tape["x1"], rows, n, g1, g1, d1, 2)
@@ -694,7 +637,7 @@ class ConvMAEBaseEncoder(nn.Module):
         del rows, gs2, gs2h
         rest += self._block_names("patch_embed2")
         # ---- blocks1, the stem (no data gradient; its rows are padded to K = 128 for the weight-gradient GEMM)
-        self._cblocks_backward(tape, "blocks1", gs1, gs1h, grad, ln_add, wgrad, n, g1, d1, depth[0], ws, s, keep)
+        self._cblocks_backward(tape, "blocks1", gs1, gs1h, bw, n, g1, d1, depth[0], keep)
         ln_add(gs1, 1, 1.0, tape["t1"], None, None, "patch_embed1.norm", 1, ceps, None, None, gs1h, M1, d1)
         rows = e16(M1, 128)
         call("isic_patch_rows_nchw_f32", tape["img"], rows, n, self.in_ch, self.img_size, self.img_size, 4, 128)
@@ -702,35 +645,9 @@ class ConvMAEBaseEncoder(nn.Module):
         rest += self._block_names("patch_embed1")
         self._fire(rest)
 
-    def _vit_blocks_backward(self, saves, w, g, gh, ln_add, wgrad, n, nblk, spec):
-        """Backward of ``_vit_blocks_train``: g (fp32) / gh (its fp16 copy), the gradient of the output stream, become
-        those of the input stream (in place); ``saves[i]`` is dropped once block i is done."""
-        dev = g.device
-        T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
-        M, Hd = n * T, D * self.mlp_ratio
-        dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
-        dD = torch.empty((M, D), device=dev, dtype=_F16)
-        dqkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        for i in range(spec["total"] - 1, nblk - 1, -1):                    # blocks past ``depth`` ran not: no gradient
-            self._fire(self._block_names(f"{spec['prefix']}.{i}"))
-        for i in range(nblk - 1, -1, -1):
-            b, sv = f"{spec['prefix']}.{i}", saves[i]
-            wgrad(gh, sv["hid"], f"{b}.mlp.fc2", D, Hd, M)
-            call("isic_gemm_f16_dgelu", gh, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hd, D)
-            wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hd, D, M)
-            call("isic_gemm_f16", dmid, w[f"{b}.mlp.fc1.weight.t"], None, None, dD, M, D, Hd, 0, 0)
-            ln_add(dD, 0, 1.0, sv["x2"], None, None, f"{b}.norm2", 0, eps, g, g, gh, M, D)
-            wgrad(gh, sv["att"], f"{b}.attn.proj", D, D, M)
-            call("isic_gemm_f16", gh, w[f"{b}.attn.proj.weight.t"], None, None, dD, M, D, D, 0, 0)
-            self._attention_bwd(sv["qkv"], sv["att"], dD, dqkv, n, T, H, D // H)
-            wgrad(dqkv, sv["h1"], f"{b}.attn.qkv", 3 * D, D, M)
-            call("isic_gemm_f16", dqkv, w[f"{b}.attn.qkv.weight.t"], None, None, dD, M, D, 3 * D, 0, 0)
-            ln_add(dD, 0, 1.0, sv["x"], None, None, f"{b}.norm1", 0, eps, g, g, gh, M, D)
-            saves[i] = None                                  # its activations can go
-            self._fire(self._block_names(b))
-
-    def _cblocks_backward(self, tape, stage, g, gh, grad, ln_add, wgrad, n, gr, C, nblk, ws, s, keep=None):
+    def _cblocks_backward(self, tape, stage, g, gh, bw, n, gr, C, nblk, keep=None):
         w, dev = tape["w"], g.device
+        grad, wgrad, ln_add, ws, s = bw.grad, bw.wgrad, bw.ln_add, bw.ws, bw.s
         M, Hd, eps = n * gr * gr, C * self.mlp_ratio, self.conv_ln_eps
         dmid = torch.empty((M, Hd), device=dev, dtype=_F16)
         dD, dm, dd = (torch.empty((M, C), device=dev, dtype=_F16) for _ in range(3))
@@ -781,21 +698,3 @@ class ConvMAEBaseEncoder(nn.Module):
         f += self.depths[2] * (2 * T * (4 * d3 * d3 + 2 * r * d3 * d3) + 4 * T * T * d3)   # blocks3
         return f
 
-
-class _ConvMAEFn(torch.autograd.Function):
-    """Autograd edge: tokens -> encoder parameter gradients.  The parameters are passed as inputs only so that autograd
-    schedules this node; the kernels accumulate their gradients in place (``param.grad``), hence ``None`` is returned
-    (the images get none either: the stem has no data gradient)."""
-
-    @staticmethod
-    def forward(ctx, images, enc, depth, *params):
-        tok, tape = enc.run_forward_train(images, depth)
-        ctx.enc, ctx.tape = enc, tape
-        return tok
-
-    @staticmethod
-    def backward(ctx, dtok):
-        enc, tape = ctx.enc, ctx.tape
-        ctx.tape = None
-        enc.run_backward(tape, dtok)
-        return (None, None, None) + tuple(None for _ in enc.parameters())

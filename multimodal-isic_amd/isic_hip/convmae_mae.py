@@ -28,7 +28,7 @@ check it against.
 
 Launches: the encoder's (isic_hip/convmae.py) with ``isic_dwconv5x5_masked_f16`` in the CBlocks and
 ``isic_gather_rows_f16`` into blocks3; ``isic_mae_unshuffle_f16`` for the mask tokens and the position embedding; the
-decoder blocks through the encoder's own ``_vit_blocks_train`` with ``isic_attention_d32_f16``; ``isic_mae_loss_f16`` for
+decoder blocks through the encoder's own ``transformer.blocks_forward_train`` with ``isic_attention_d32_f16``; ``isic_mae_loss_f16`` for
 the target, the loss and d loss / d pred in one pass.  No CPU fallback.
 
 Training: ``loss.backward()`` runs one native backward (include/isic_hip_mae.h + the encoder's) that accumulates into
@@ -50,6 +50,7 @@ from torch import nn
 
 from .convmae import ConvMAEBaseEncoder, _Block, _F16, sincos_pos_embed
 from .lib import IsicHipError, call
+from .transformer import Backward, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads, param_grads
 
 
 class ConvMAEBase(ConvMAEBaseEncoder):
@@ -166,7 +167,7 @@ class ConvMAEBase(ConvMAEBaseEncoder):
         xd = torch.empty((M, Dd), device=dev, dtype=_F16)
         call("isic_mae_unshuffle_f16", z, m["ids_restore"], w["mask_token"], w["decoder_pos_embed"], xd, n, T, L, Dd)
         del z
-        x, dec_saves = self._vit_blocks_train(xd, w, n, dd, self._decoder_spec())
+        x, dec_saves = blocks_forward_train(w, xd, n, dd, self._decoder_spec())
         hn = torch.empty((M, Dd), device=dev, dtype=_F16)
         call("isic_layernorm_add_f16", x, None, None, w["decoder_norm.weight"], w["decoder_norm.bias"], hn, None, M, Dd, 0,
              self.ln_eps)
@@ -217,7 +218,7 @@ class ConvMAEBase(ConvMAEBaseEncoder):
         xd = torch.empty((n * T, Dd), device=dev, dtype=_F16)
         call("isic_mae_unshuffle_f16", z, ids_restore.to(dev).long().contiguous(), w["mask_token"], w["decoder_pos_embed"],
              xd, n, T, L, Dd)
-        x, _ = self._vit_blocks_train(xd, w, n, self.dec_depth, self._decoder_spec())
+        x, _ = blocks_forward_train(w, xd, n, self.dec_depth, self._decoder_spec())
         hn = torch.empty((n * T, Dd), device=dev, dtype=_F16)
         call("isic_layernorm_add_f16", x, None, None, w["decoder_norm.weight"], w["decoder_norm.bias"], hn, None, n * T, Dd,
              0, self.ln_eps)
@@ -249,54 +250,38 @@ class ConvMAEBase(ConvMAEBaseEncoder):
         enc, dec = tape["enc"], tape["dec"]
         w, n, m = enc["w"], enc["n"], dec["m"]
         T, L, Dd, D, P = self.tokens, m["L"], self.dec_dim, self.dims[2], self.pred_dim
-        M, Mk, r, eps = n * T, n * L, self.mlp_ratio, self.ln_eps
+        M, Mk, eps = n * T, n * L, self.ln_eps
         dev = dec["dpred"].device
         if not math.isfinite(dloss):
             raise FloatingPointError("ConvMAEBase backward: the incoming gradient is not finite")
         s = dloss / dec["S"]
-        nb = max(call("isic_gemm_f16_wgrad_workspace_bytes", M, P, Dd), call("isic_gemm_f16_wgrad_workspace_bytes", Mk, Dd, D),
-                 call("isic_layernorm_add_bwd_f16_workspace_bytes", M, Dd), call("isic_colsum_f16_workspace_bytes", n * (T - L), Dd))
-        for nk in ((3 * Dd, Dd), (Dd, Dd), (r * Dd, Dd), (Dd, r * Dd)):
-            nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, *nk))
-        ws = self._workspace(nb, dev)
-        params = dict(self.named_parameters())
-
-        def grad(name):
-            p = params[name]
-            if p.grad is None:
-                p.grad = torch.zeros_like(p.data)
-            return p.grad
-
-        def wgrad(dy, xin, name, Nout, K, rows):
-            call("isic_gemm_f16_wgrad", dy, xin, grad(name + ".weight"), grad(name + ".bias"), rows, Nout, K, s, 1, ws, ws.numel())
-
-        def ln_add(dy, dy_f32, mul, xin, a, b, norm, act, eps_, g_in, g_out, g16, rows, N):
-            call("isic_layernorm_add_bwd_f16", dy, dy_f32, mul, xin, a, b, w[norm + ".weight"], w[norm + ".bias"], act, eps_,
-                 g_in, g_out, g16, grad(norm + ".weight"), grad(norm + ".bias"), rows, N, s, 1, ws, ws.numel())
-
+        nb = max(self._encoder_workspace_bytes(enc), blocks_workspace_bytes(w, n, self._decoder_spec()),
+                 call("isic_gemm_f16_wgrad_workspace_bytes", M, P, Dd), call("isic_gemm_f16_wgrad_workspace_bytes", Mk, Dd, D),
+                 call("isic_colsum_f16_workspace_bytes", n * (T - L), Dd))
+        bw = Backward(self, w, param_grads(self), s, nb, dev)
         # ---- decoder_pred, decoder_norm
-        wgrad(dec["dpred"], dec["hn"], "decoder_pred", P, Dd, M)
+        bw.wgrad(dec["dpred"], dec["hn"], "decoder_pred", P, Dd, M)
         dh = torch.empty((M, Dd), device=dev, dtype=_F16)
         call("isic_gemm_f16", dec["dpred"], w["decoder_pred.weight.t"], None, None, dh, M, Dd, P, 0, 0)
         g, gh = torch.empty((M, Dd), device=dev, dtype=torch.float32), torch.empty((M, Dd), device=dev, dtype=_F16)
-        ln_add(dh, 0, 1.0, dec["xd_out"], None, None, "decoder_norm", 0, eps, None, g, gh, M, Dd)
+        bw.ln_add(dh, 0, 1.0, dec["xd_out"], None, None, "decoder_norm", 0, eps, None, g, gh, M, Dd)
         del dh
         self._fire(self._block_names("decoder_norm") + self._block_names("decoder_pred"))
         # ---- decoder blocks
-        self._vit_blocks_backward(dec["blocks"], w, g, gh, ln_add, wgrad, n, dec["dd"], self._decoder_spec())
+        blocks_backward(dec["blocks"], g, gh, bw, n, dec["dd"], self._decoder_spec(), self._fire)
         # ---- unshuffle: kept rows back to ids_keep order; mask_token's gradient is the sum over the removed rows
         dz, drem = torch.empty((Mk, Dd), device=dev, dtype=_F16), torch.empty((n * (T - L), Dd), device=dev, dtype=_F16)
         call("isic_mae_unshuffle_bwd_f16", gh, m["ids_shuffle"], dz, drem, n, T, L, Dd)
-        call("isic_colsum_f16", drem, grad("mask_token"), n * (T - L), Dd, s, 1, ws, ws.numel())
+        bw.colsum(drem, "mask_token", n * (T - L), Dd)
         del g, gh, drem
-        wgrad(dz, enc["latent16"], "decoder_embed", Dd, D, Mk)
+        bw.wgrad(dz, enc["latent16"], "decoder_embed", Dd, D, Mk)
         dlat = torch.empty((Mk, D), device=dev, dtype=_F16)
         call("isic_gemm_f16", dz, w["decoder_embed.weight.t"], None, None, dlat, Mk, D, Dd, 0, 0)
         del dz
         self._fire(self._block_names("decoder_embed") + ["mask_token", "decoder_pos_embed"])
         # ---- the encoder, from d latent (already scaled by S)
-        self._encoder_backward(enc, dlat, 0, 1.0, s)
-        self._check_grads()
+        self._encoder_backward(enc, dlat, 0, 1.0, bw)
+        check_grads(self.parameters(), "ConvMAEBase")
 
     def train_flops_per_image(self, mask_ratio=0.75):
         """Algorithmic forward + backward FLOPs of one MAE train step per image (products and convolutions, x 3 except the

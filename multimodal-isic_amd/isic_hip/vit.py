@@ -28,12 +28,15 @@ masters once per weight version.
 
 ``trainable=True`` (opt-in; the default stays the frozen encoder above, bit for bit): the parameters require grad,
 ``train()`` works, and the encoder runs the layer-by-layer form (``fold_layernorm=False``).  Under grad, ``forward`` /
-``forward_tokens`` go through ``_ViTFn``: a forward that saves its activations (about 12 KB per token per block: x, LN1(x), qkv,
-the attention output, x2, LN2(x2), fc1's pre-activation and GELU output, fp16) and a native backward
-(include/isic_hip_vit_train.h) that accumulates into ``param.grad``.  The backward runs in fp16 with a power-of-two loss
-scale S = 2^round(8 - log2 amax(d tokens)), one device -> host read per call; every reduction into a parameter gradient
-multiplies by 1/S in fp32, so gradients are exactly scale-equivariant.  An fp16 overflow is not retried: it reaches the
-gradients as inf / NaN, and the backward checks them once at its end and raises ``FloatingPointError``.
+``forward_tokens`` go through ``transformer.EncoderFn``: patchify, the patch projection (+ pos_embed), then the block
+stack and its backward of isic_hip/transformer.py, which the ConvMAE encoders share.  The forward saves its activations
+(about 12 KB per token per block: x, LN1(x), qkv, the attention output, x2, LN2(x2), fc1's pre-activation and GELU
+output, fp16; no LayerNorm statistics -- the backward recomputes them from x) and the native backward
+(include/isic_hip_vit_train.h, ``isic_layernorm_add_bwd_f16``) accumulates into ``param.grad``.  The backward runs in
+fp16 with a power-of-two loss scale S = 2^round(8 - log2 amax(d tokens)), one device -> host read per call; every
+reduction into a parameter gradient multiplies by 1/S in fp32, so gradients are exactly scale-equivariant.  An fp16
+overflow is not retried: it reaches the gradients as inf / NaN, and the backward checks them once at its end and raises
+``FloatingPointError``.
 """
 from __future__ import annotations
 
@@ -43,6 +46,8 @@ import torch
 from torch import nn
 
 from .lib import IsicHipError, call
+from .transformer import (Backward, EncoderFn, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads,
+                          loss_scale, param_grads)
 
 _F16 = torch.float16
 
@@ -303,9 +308,9 @@ class ViTSmallEncoder(nn.Module):
         return out.view(N, T, D)
 
     def forward_tokens(self, images):
-        """tokens[N, 196, 384] fp32; differentiable (``_ViTFn``) when the encoder is trainable and grad is enabled."""
+        """tokens[N, 196, 384] fp32; differentiable (``transformer.EncoderFn``) when the encoder is trainable and grad is enabled."""
         if self.trainable and torch.is_grad_enabled():
-            return _ViTFn.apply(images, self, *self.parameters())
+            return EncoderFn.apply(images, self, (), *self.parameters())
         return self.run_tokens(images)
 
     def forward(self, images):
@@ -322,21 +327,18 @@ class ViTSmallEncoder(nn.Module):
                 w[n + ".t"] = w[n].t().contiguous()
         return w
 
-    def _workspace(self, nbytes, device):
-        ws = self._ws
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            ws = self._ws = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
-        return ws
-
-    def _grad(self, name):
-        p = self._get(name)
-        if p.grad is None:
-            p.grad = torch.zeros_like(p.data)
-        return p.grad
-
     def _fire(self, names):
         if self.grad_ready_hook is not None:
             self.grad_ready_hook([n.replace(".", "__") for n in names])
+
+    def _spec(self):
+        """The blocks as isic_hip/transformer.py describes a stack of them."""
+        return dict(prefix="blocks", T=self.tokens, D=self.dim, H=self.heads, eps=1e-6, total=self.depth)
+
+    @staticmethod
+    def _layernorm(x, gamma, beta, y, M, D, eps):
+        """``run_tokens``' LayerNorm pass (transformer.blocks_forward_train explains why it is handed in)."""
+        call("isic_layernorm_f16", x, gamma, beta, y, None, M, D, eps)
 
     def run_forward_train(self, images):
         """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
@@ -347,98 +349,38 @@ class ViTSmallEncoder(nn.Module):
         dev = images.device
         w = self._prepare_train(dev)
         x_in = images.float().contiguous()
-        N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
+        N, T, D = x_in.shape[0], self.tokens, self.dim
         M = N * T
         K0 = self.in_ch * self.patch * self.patch
-        eps = 1e-6
-        f32 = torch.float32
-
-        def e16(*shape):
-            return torch.empty(shape, device=dev, dtype=_F16)
-        rows = e16(M, K0)
+        rows = torch.empty((M, K0), device=dev, dtype=_F16)
         call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
-        x = e16(M, D)
+        x = torch.empty((M, D), device=dev, dtype=_F16)
         call("isic_gemm_f16", rows, w["patch_embed.proj.weight"], w["patch_embed.proj.bias"], w["pos_embed"], x, M, D, K0, 0, T)
-        blocks = []
-        for i in range(self.depth):
-            b = f"blocks.{i}"
-            st1, h1, qkv, att, x2 = torch.empty((M, 2), device=dev, dtype=f32), e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, D)
-            st2, h2, pre, hid, xo = torch.empty((M, 2), device=dev, dtype=f32), e16(M, D), e16(M, self.mlp), e16(M, self.mlp), e16(M, D)
-            call("isic_row_stats_f16", x, st1, M, D, eps)
-            call("isic_layernorm_f16", x, w[f"{b}.norm1.weight"], w[f"{b}.norm1.bias"], h1, None, M, D, eps)
-            call("isic_gemm_f16", h1, w[f"{b}.attn.qkv.weight"], w[f"{b}.attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
-            call("isic_attention_f16", qkv, att, N, T, H, D // H)
-            call("isic_gemm_f16", att, w[f"{b}.attn.proj.weight"], w[f"{b}.attn.proj.bias"], x, x2, M, D, D, 0, 0)
-            call("isic_row_stats_f16", x2, st2, M, D, eps)
-            call("isic_layernorm_f16", x2, w[f"{b}.norm2.weight"], w[f"{b}.norm2.bias"], h2, None, M, D, eps)
-            call("isic_gemm_f16_gelu_pre", h2, w[f"{b}.mlp.fc1.weight"], w[f"{b}.mlp.fc1.bias"], hid, pre, M, self.mlp, D)
-            call("isic_gemm_f16", hid, w[f"{b}.mlp.fc2.weight"], w[f"{b}.mlp.fc2.bias"], x2, xo, M, D, self.mlp, 0, 0)
-            blocks.append(dict(x=x, st1=st1, h1=h1, qkv=qkv, att=att, x2=x2, st2=st2, h2=h2, pre=pre, hid=hid))
-            x = xo
-        stf = torch.empty((M, 2), device=dev, dtype=f32)
-        call("isic_row_stats_f16", x, stf, M, D, eps)
-        out = torch.empty((M, D), device=dev, dtype=f32)
-        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, eps)
-        tape = dict(N=N, rows=rows, blocks=blocks, x=x, stf=stf, w=w)
+        x, blocks = blocks_forward_train(w, x, N, self.depth, self._spec(), layernorm=self._layernorm)
+        out = torch.empty((M, D), device=dev, dtype=torch.float32)
+        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, 1e-6)
+        tape = dict(N=N, rows=rows, blocks=blocks, x=x, w=w)
         return out.view(N, T, D), tape
 
     def run_backward(self, tape, dtok):
         """Accumulates every parameter gradient into ``param.grad`` from d loss / d tokens[N, T, D]."""
         w, N = tape["w"], tape["N"]
-        T, D, Hm = self.tokens, self.dim, self.mlp
+        T, D, K0 = self.tokens, self.dim, self.in_ch * self.patch ** 2
         M = N * T
         dev = dtok.device
-        dtok = dtok.float().contiguous()
-        amax = float(dtok.abs().amax())                  # the backward's one device -> host read before its final check
-        if not math.isfinite(amax):
-            raise FloatingPointError("ViTSmallEncoder backward: the incoming gradient is not finite")
-        S = 2.0 ** round(8 - math.log2(amax)) if amax > 0 else 1.0
-        s = 1.0 / S
-        nb = 0
-        for (n_, k_) in ((3 * D, D), (D, D), (Hm, D), (D, Hm), (D, self.in_ch * self.patch ** 2)):
-            nb = max(nb, call("isic_gemm_f16_wgrad_workspace_bytes", M, n_, k_))
-        nb = max(nb, call("isic_layernorm_bwd_f16_workspace_bytes", M, D), call("isic_colsum_f16_workspace_bytes", N, T * D))
-        ws = self._workspace(nb, dev)
-
-        def wgrad(dy, xin, name, Nout, K):
-            call("isic_gemm_f16_wgrad", dy, xin, self._grad(name + ".weight"), self._grad(name + ".bias"), M, Nout, K, s, 1,
-                 ws, ws.numel())
-
-        def ln_bwd(dy, dy_f32, mul, xin, st, norm, g_in, g, g16):
-            call("isic_layernorm_bwd_f16", dy, dy_f32, mul, xin, st, w[norm + ".weight"], g_in, g, g16,
-                 self._grad(norm + ".weight"), self._grad(norm + ".bias"), M, D, s, 1, ws, ws.numel())
-
+        dtok, S = loss_scale(dtok, "ViTSmallEncoder")     # the backward's one device -> host read before its final check
+        nb = max(blocks_workspace_bytes(w, N, self._spec()), call("isic_gemm_f16_wgrad_workspace_bytes", M, D, K0),
+                 call("isic_colsum_f16_workspace_bytes", N, T * D))
+        bw = Backward(self, w, param_grads(self, lambda n: n.replace(".", "__")), 1.0 / S, nb, dev)
         g = torch.empty((M, D), device=dev, dtype=torch.float32)          # d loss / d residual stream, x S, fp32
         g16 = torch.empty((M, D), device=dev, dtype=_F16)
-        ln_bwd(dtok, 1, S, tape["x"], tape["stf"], "norm", None, g, g16)
+        bw.ln_add(dtok, 1, S, tape["x"], None, None, "norm", 0, 1e-6, None, g, g16, M, D)
         self._fire(["norm.weight", "norm.bias"])
-        dmid = torch.empty((M, Hm), device=dev, dtype=_F16)
-        dD = torch.empty((M, D), device=dev, dtype=_F16)
-        dqkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        for i in range(self.depth - 1, -1, -1):
-            b, sv = f"blocks.{i}", tape["blocks"][i]
-            wgrad(g16, sv["hid"], f"{b}.mlp.fc2", D, Hm)
-            call("isic_gemm_f16_dgelu", g16, w[f"{b}.mlp.fc2.weight.t"], sv["pre"], dmid, M, Hm, D)
-            wgrad(dmid, sv["h2"], f"{b}.mlp.fc1", Hm, D)
-            call("isic_gemm_f16", dmid, w[f"{b}.mlp.fc1.weight.t"], None, None, dD, M, D, Hm, 0, 0)
-            ln_bwd(dD, 0, 1.0, sv["x2"], sv["st2"], f"{b}.norm2", g, g, g16)
-            wgrad(g16, sv["att"], f"{b}.attn.proj", D, D)
-            call("isic_gemm_f16", g16, w[f"{b}.attn.proj.weight.t"], None, None, dD, M, D, D, 0, 0)
-            call("isic_attention_bwd_f16", sv["qkv"], sv["att"], dD, dqkv, N, T, self.heads, D // self.heads)
-            wgrad(dqkv, sv["h1"], f"{b}.attn.qkv", 3 * D, D)
-            call("isic_gemm_f16", dqkv, w[f"{b}.attn.qkv.weight.t"], None, None, dD, M, D, 3 * D, 0, 0)
-            ln_bwd(dD, 0, 1.0, sv["x"], sv["st1"], f"{b}.norm1", g, g, g16)
-            tape["blocks"][i] = None                      # its activations can go
-            self._fire([f"{b}.{n}" for n in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias",
-                                                "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias",
-                                                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")])
-        wgrad(g16, tape["rows"], "patch_embed.proj", D, self.in_ch * self.patch ** 2)
-        call("isic_colsum_f16", g16, self._grad("pos_embed"), N, T * D, s, 1, ws, ws.numel())
+        blocks_backward(tape["blocks"], g, g16, bw, N, self.depth, self._spec(), self._fire)
+        bw.wgrad(g16, tape["rows"], "patch_embed.proj", D, K0, M)
+        bw.colsum(g16, "pos_embed", N, T * D)
         self._fire(["patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed"])
-        norms = torch._foreach_norm([self._get(n).grad for n in self._names])
-        if not bool(torch.isfinite(torch.stack(norms)).all()):
-            raise FloatingPointError("ViTSmallEncoder backward: non-finite parameter gradient (fp16 overflow in the backward, "
-                                     "or a non-finite gradient accumulated earlier)")
+        check_grads(self.parameters(), "ViTSmallEncoder")
 
     def train_flops_per_image(self):
         """Forward + backward products (the patch projection has no data gradient)."""
@@ -450,20 +392,3 @@ class ViTSmallEncoder(nn.Module):
         per_block = 2 * T * (D * 3 * D + D * D + 2 * D * Hm) + 4 * T * T * D
         return 2 * T * D * self.in_ch * self.patch ** 2 + self.depth * per_block
 
-
-class _ViTFn(torch.autograd.Function):
-    """Autograd edge: tokens -> encoder parameter gradients.  The parameters are passed as inputs only so that autograd
-    schedules this node; the kernels accumulate their gradients in place (``param.grad``), hence ``None`` is returned."""
-
-    @staticmethod
-    def forward(ctx, images, enc, *params):
-        tok, tape = enc.run_forward_train(images)
-        ctx.enc, ctx.tape = enc, tape
-        return tok
-
-    @staticmethod
-    def backward(ctx, dtok):
-        enc, tape = ctx.enc, ctx.tape
-        ctx.tape = None
-        enc.run_backward(tape, dtok)
-        return (None, None) + tuple(None for _ in enc.parameters())

@@ -86,13 +86,17 @@ def test_dwconv_data_gradient_is_the_reversed_taps_convolution():
     assert (dx.float().cpu() - ref).abs().max() <= 2e-3 * ref.abs().max() + 1e-3
 
 
-@pytest.mark.parametrize("N", [256, 384, 768, 1024])
+@pytest.mark.parametrize("M,N", [pytest.param(300, 256, id="256"), pytest.param(300, 384, id="384"),
+                                 pytest.param(300, 768, id="768"), pytest.param(300, 1024, id="1024"),
+                                 pytest.param(3001, 384, id="3001x384")])
 @pytest.mark.parametrize("addends,dy_f32,act", [(0, 0, 0), (2, 1, 0), (0, 1, 1), (2, 0, 1)])
 @pytest.mark.parametrize("mode", ["alias", "fresh", "f16_only"])
-def test_layernorm_add_bwd_matches_fp32_autograd(N, addends, dy_f32, act, mode):
+def test_layernorm_add_bwd_matches_fp32_autograd(M, N, addends, dy_f32, act, mode):
     """mode "alias": g_in aliases g_out, both outputs, accumulate = 1 (the CBlock / ViT block norms); "fresh": no g_in, both
-    outputs, accumulate = 0; "f16_only": no g_in, no fp32 output, accumulate = 0 (the PatchEmbed norms)."""
-    M, eps, s, mul = 300, 1e-6, 0.5, 4.0
+    outputs, accumulate = 0; "f16_only": no g_in, no fp32 output, accumulate = 0 (the PatchEmbed norms).  M = 300 is 5 slabs
+    of the parameter-gradient reduction; M = 3001 (the ViT-S width) is 47 with a ragged last chunk and rows that are not a
+    multiple of 4."""
+    eps, s, mul = 1e-6, 0.5, 4.0
     g = torch.Generator().manual_seed(N + 10 * addends + act)
     x, a, b = ((torch.randn(M, N, generator=g) * 2 + 0.5).half() for _ in range(3))
     gamma, beta = 1 + 0.1 * torch.randn(N, generator=g), 0.1 * torch.randn(N, generator=g)

@@ -15,8 +15,7 @@ sys.path.insert(0, ROOT)
 from isic_hip import lib  # noqa: E402
 
 NAMES = ("isic_gemm_f16_wgrad_workspace_bytes", "isic_gemm_f16_wgrad", "isic_colsum_f16_workspace_bytes", "isic_colsum_f16",
-         "isic_layernorm_bwd_f16_workspace_bytes", "isic_layernorm_bwd_f16", "isic_attention_bwd_f16",
-         "isic_gemm_f16_dgelu", "isic_gemm_f16_gelu_pre")
+         "isic_attention_bwd_f16", "isic_gemm_f16_dgelu", "isic_gemm_f16_gelu_pre")
 BAD_ARG, UNSUPPORTED, WORKSPACE = -1, -2, -3
 P = 0x10000                                         # a non-NULL pointer value: never dereferenced by a rejected call
 
@@ -63,11 +62,6 @@ def test_attention_bwd_argument_checks_without_a_device():
 
 def test_layernorm_bwd_colsum_and_gemm_mode_argument_checks_without_a_device():
     L = lib.lib().fn
-    ln = L["isic_layernorm_bwd_f16"]
-    assert ln(P, 0, 1.0, P, P, P, None, P, P, P, P, 100, 320, 1.0, 0, P, 1 << 20, None) == UNSUPPORTED
-    assert ln(P, 0, 1.0, P, P, P, None, P, P, P, P, 100, 640, 1.0, 0, P, 1 << 20, None) == UNSUPPORTED
-    assert ln(P, 2, 1.0, P, P, P, None, P, P, P, P, 100, 384, 1.0, 0, P, 1 << 20, None) == BAD_ARG
-    assert ln(P, 0, 1.0, P, P, P, None, P, P, P, P, 100, 384, 1.0, 0, None, 0, None) == WORKSPACE
     cs = L["isic_colsum_f16"]
     assert cs(P, P, 10, 12, 1.0, 0, None, 0, None) == UNSUPPORTED             # cols % 8
     assert cs(P, P, 100000, 384, 1.0, 0, None, 0, None) == WORKSPACE

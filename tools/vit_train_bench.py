@@ -74,9 +74,7 @@ def kernels(a):
     x, h, att, g16, dD = r(M, D), r(M, D), r(M, D), r(M, D), torch.empty(M, D, device=DEV, dtype=F16)
     qkv, dqkv = r(M, 3 * D), torch.empty(M, 3 * D, device=DEV, dtype=F16)
     hid, pre, dmid = r(M, Hm), r(M, Hm), torch.empty(M, Hm, device=DEV, dtype=F16)
-    stats = torch.empty(M, 2, device=DEV)
-    call("isic_row_stats_f16", x, stats, M, D, 1e-6)
-    gam = torch.ones(D, device=DEV)
+    gam, bet = torch.ones(D, device=DEV), torch.zeros(D, device=DEV)
     totals = {}
 
     def rep(cls, name, t, flops=None):
@@ -94,13 +92,11 @@ def kernels(a):
     x2, out = torch.empty_like(x), torch.empty_like(x)
 
     def block_fwd():
-        call("isic_row_stats_f16", x, stats, M, D, 1e-6)
-        call("isic_layernorm_f16", x, gam, b["proj"], h, None, M, D, 1e-6)
+        call("isic_layernorm_f16", x, gam, bet, h, None, M, D, 1e-6)
         call("isic_gemm_f16", h, W["qkv"], b["qkv"], None, qkv, M, 3 * D, D, 0, 0)
         call("isic_attention_f16", qkv, att, a.n, 196, 6, 64)
         call("isic_gemm_f16", att, W["proj"], b["proj"], x, x2, M, D, D, 0, 0)
-        call("isic_row_stats_f16", x2, stats, M, D, 1e-6)
-        call("isic_layernorm_f16", x2, gam, b["proj"], h, None, M, D, 1e-6)
+        call("isic_layernorm_f16", x2, gam, bet, h, None, M, D, 1e-6)
         call("isic_gemm_f16_gelu_pre", h, W["fc1"], b["fc1"], hid, pre, M, Hm, D)
         call("isic_gemm_f16", hid, W["fc2"], b["fc2"], x2, out, M, D, Hm, 0, 0)
     rep("forward", "one block (training form)", timeit(block_fwd, a.iters))
@@ -127,11 +123,11 @@ def kernels(a):
     tf = wf / wt / 1e9
     print(f"  wgrad total: {tf:.0f} TFLOP/s = {tf / PEAK_F16_TFLOPS:.3f} of the dense fp16 peak")
     rep("attn bwd", "6 heads x 196 tokens", timeit(lambda: call("isic_attention_bwd_f16", qkv, att, g16, dqkv, a.n, 196, 6, 64), a.iters))
-    lws = torch.empty(call("isic_layernorm_bwd_f16_workspace_bytes", M, D), device=DEV, dtype=torch.uint8)
+    lws = torch.empty(call("isic_layernorm_add_bwd_f16_workspace_bytes", M, D), device=DEV, dtype=torch.uint8)
     g = torch.zeros(M, D, device=DEV)
     dg, dbt = torch.zeros(D, device=DEV), torch.zeros(D, device=DEV)
-    t = timeit(lambda: call("isic_layernorm_bwd_f16", dD, 0, 1.0, x, stats, gam, g, g, g16, dg, dbt, M, D, 1.0, 1, lws, lws.numel()),
-               a.iters)
+    t = timeit(lambda: call("isic_layernorm_add_bwd_f16", dD, 0, 1.0, x, None, None, gam, bet, 0, 1e-6, g, g, g16, dg, dbt, M, D,
+                            1.0, 1, lws, lws.numel()), a.iters)
     rep("LN bwd", "384 (x2 per block)", t)
     totals["LN bwd"] += t
     print("per class, one block: " + ", ".join(f"{k} {v:.2f} ms" for k, v in totals.items()))
