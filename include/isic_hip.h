@@ -618,7 +618,8 @@ int isic_vit_patchify_f16(const float* images_nchw, uint16_t* rows, int N, int C
 int isic_layernorm_f16(const uint16_t* x, const float* gamma, const float* beta, uint16_t* y, float* y_f32, int64_t M,
                        int N, float eps, void* stream);
 /* Multi-head self-attention over the tokens of one image: qkv[n_images*tokens][3*heads*64] (q | k | v, head-major
- * inside each) -> out[n_images*tokens][heads*64] = softmax(q k^T / 8) v per (image, head).  head_dim 64, tokens <= 208. */
+ * inside each) -> out[n_images*tokens][heads*64] = softmax(q k^T / 8) v per (image, head).  head_dim 64, tokens <= 208,
+ * else UNSUPPORTED; n_images == 0 is a no-op, as in the backward. */
 int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, int head_dim,
                        void* stream);
 

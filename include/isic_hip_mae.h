@@ -29,17 +29,20 @@ int isic_dwconv5x5_masked_f16(const uint16_t* x, const uint8_t* keep, int P, con
 int isic_dwconv5x5_masked_dgrad_f16(const uint16_t* dy, const uint8_t* keep, int P, const float* w_taps_rev, uint16_t* dx,
                                     int N, int H, int W, int C, void* stream);
 /* isic_attention_f16 and isic_attention_bwd_f16 (isic_hip_vit_train.h) with heads 32 wide: softmax scale 1 / sqrt(32),
- * tokens <= 208, else UNSUPPORTED.  qkv[n_images*tokens][3*heads*32], out / dout [n_images*tokens][heads*32]. */
+ * tokens <= 208, else UNSUPPORTED; n_images == 0 is a no-op.  qkv[n_images*tokens][3*heads*32], out / dout
+ * [n_images*tokens][heads*32]. */
 int isic_attention_d32_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, void* stream);
 int isic_attention_d32_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, uint16_t* dqkv, int n_images,
                                int tokens, int heads, void* stream);
 /* Row gather y[n][j] = x[n][ids_keep[n][j]] (x: [N][T][C], y: [N][L][C]) and its adjoint, the scatter
- * x[n][t] = ids_restore[n][t] < L ? y[n][ids_restore[n][t]] : 0 (every row of x written once).  C % 8 == 0. */
+ * x[n][t] = ids_restore[n][t] < L ? y[n][ids_restore[n][t]] : 0 (every row of x written once; a negative rank is a zero
+ * row too).  C % 8 == 0. */
 int isic_gather_rows_f16(const uint16_t* x, const int64_t* ids_keep, uint16_t* y, int N, int T, int L, int C, void* stream);
 int isic_scatter_rows_f16(const uint16_t* y, const int64_t* ids_restore, uint16_t* x, int N, int T, int L, int C,
                           void* stream);
 /* The decoder's unshuffle: out[n][t] = fp16((ids_restore[n][t] < L ? y[n][ids_restore[n][t]] : mask_token) + pos[t]), the
- * sum in fp32 (y fp16 [N][L][C], mask_token fp32 [C], pos fp32 [T][C], out fp16 [N][T][C]).  C % 8 == 0. */
+ * sum in fp32 (y fp16 [N][L][C], mask_token fp32 [C], pos fp32 [T][C], out fp16 [N][T][C]).  A rank outside [0, L), a
+ * negative one included, takes the mask token.  C % 8 == 0. */
 int isic_mae_unshuffle_f16(const uint16_t* y, const int64_t* ids_restore, const float* mask_token, const float* pos,
                            uint16_t* out, int N, int T, int L, int C, void* stream);
 /* Its adjoint, split by ids_shuffle[N][T]: dy_keep[n][j] = dout[n][ids_shuffle[n][j]] for j < L (the kept rows in ids_keep
@@ -53,7 +56,7 @@ int isic_mae_unshuffle_bwd_f16(const uint16_t* dout, const int64_t* ids_shuffle,
  *   loss[0] = sum_{n,t} mask l_{n,t} / mask_sum,  l = mean_k (pred - target)^2            (fp32, on the device)
  *   dpred   = fp16(loss_scale * mask * 2 (pred - target) / (K mask_sum))                  (d loss / d pred, scaled)
  * mask_sum is the caller's sum of mask (> 0).  Both sums run in a fixed order (bit-reproducible); the workspace holds
- * N T per-patch terms.  K <= 1024, H % P == W % P == 0, else UNSUPPORTED. */
+ * N T per-patch terms.  2 <= K <= 1024 (the unbiased variance needs two values), H % P == W % P == 0, else UNSUPPORTED. */
 size_t isic_mae_loss_f16_workspace_bytes(int N, int H, int W, int P);
 int isic_mae_loss_f16(const uint16_t* pred, const float* images, const float* mask, int norm_pix, float mask_sum,
                       float loss_scale, uint16_t* dpred, float* loss, int N, int C, int H, int W, int P, void* workspace,

@@ -194,7 +194,10 @@ __global__ __launch_bounds__(256) void layernorm_add_f16_kernel(const unsigned s
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s * invn;
+    // a true division, not s * invn: the compiler fuses "f - s * invn" into one FMA with the product unrounded, and where
+    // 1 / N is inexact (N = 768: 2 * 768 * fl(1 / 768) = 2 + 2^-24) a constant row no longer cancels to 0 -- times
+    // rstd = 1 / sqrt(eps) that is 6e-5 in x^.  N c / N is exact for every row of equal values c.
+    const float mean = s / (float)N;
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void layernorm_add_bwd_f16_kernel(const void* 
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s * invn;
+    const float mean = s / (float)N;                 // the forward's: a division (convmae.hip, layernorm_add_f16_kernel)
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {

@@ -322,8 +322,10 @@ int isic_row_stats_f16(const uint16_t* x, float* stats, int64_t M, int N, float 
 
 int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, int head_dim,
                        void* stream) {
-  ISIC_CHECK_ARG(qkv && out && n_images > 0 && tokens > 0 && heads > 0);
+  ISIC_CHECK_ARG(n_images >= 0 && tokens > 0 && heads > 0);
   if (head_dim != 64 || tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
+  if (n_images == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(qkv && out);
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
   if (isic_once_per_device(once, [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<64>),
@@ -338,8 +340,10 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 
 // include/isic_hip_mae.h: the MAE decoder's heads, 32 wide
 int isic_attention_d32_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, void* stream) {
-  ISIC_CHECK_ARG(qkv && out && n_images > 0 && tokens > 0 && heads > 0);
+  ISIC_CHECK_ARG(n_images >= 0 && tokens > 0 && heads > 0);
   if (tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
+  if (n_images == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(qkv && out);
   static IsicPerDeviceOnce once;
   if (isic_once_per_device(once, [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<32>),

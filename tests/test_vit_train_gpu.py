@@ -18,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-isic_amd"))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F16 = torch.float16
@@ -46,6 +47,7 @@ def _cos(got, ref):
 @pytest.mark.parametrize("M", [1, 4097, 200704])
 @pytest.mark.parametrize("N,K", [(1152, 384), (384, 1536), (1536, 384), (384, 768)])
 def test_wgrad_matches_fp64(M, N, K):
+    from f16_kernel_ref import wgrad_bound
     g = torch.Generator(device=DEV).manual_seed(M + N + K)
     dY = torch.randn(M, N, device=DEV, generator=g).to(F16)
     X = torch.randn(M, K, device=DEV, generator=g).to(F16)
@@ -55,7 +57,7 @@ def test_wgrad_matches_fp64(M, N, K):
     db = torch.empty(N, device=DEV)
     _call("isic_gemm_f16_wgrad", dY, X, dW, db, M, N, K, s, 0, ws, ws.numel())
     ref = s * (dY.double().t() @ X.double())
-    bound = 1e-4 * s * (dY.double().abs().t() @ X.double().abs()) + 1e-6
+    bound = wgrad_bound(dY, X, s)                       # tests/f16_kernel_ref.py: 1e-4 s |dY|^T |X| + 1e-6
     assert bool(((dW.double() - ref).abs() <= bound).all()), float(((dW.double() - ref).abs() / bound).max())
     refb = s * dY.double().sum(0)
     boundb = 1e-4 * s * dY.double().abs().sum(0) + 1e-6
