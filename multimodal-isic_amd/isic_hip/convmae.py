@@ -66,9 +66,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from .lib import IsicHipError, call
-from .transformer import (Backward, EncoderFn, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads,
-                          loss_scale, param_grads)
+from .lib import call
+from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_workspace_bytes, check_grads,
+                          embed, fold_layernorm, linear_ln, linear_res, loss_scale, param_grads)
 
 _F16 = torch.float16
 
@@ -131,9 +131,10 @@ class _Block(nn.Module):
         self.mlp = _Mlp(dim, hidden)
 
 
-class ConvMAEBaseEncoder(nn.Module):
+class ConvMAEBaseEncoder(Encoder):
     """Frozen ConvMAE-Base encoder (module docstring).  ``run_tokens(images[N,3,224,224]) -> [N, 196, 768]`` fp32."""
 
+    _who = "ConvMAEBaseEncoder"
     img_size, in_ch, tokens = 224, 3, 196
     dims, depths, grids, patches = (256, 384, 768), (2, 2, 11), (56, 28, 14), (4, 2, 2)
 
@@ -188,13 +189,6 @@ class ConvMAEBaseEncoder(nn.Module):
                 else:
                     p.copy_(torch.randn(p.shape, generator=g) / math.sqrt(p[0].numel()))
 
-    def train(self, mode=True):
-        if self.trainable:
-            return super().train(mode)
-        if mode:
-            raise IsicHipError("ConvMAEBaseEncoder is a frozen inference encoder (save_latent.py:51-53): no train() mode")
-        return super().train(False)
-
     def load_state_dict(self, state_dict, strict=True, assign=False):
         """nn.Module semantics (a wrong shape raises, also under strict=False).  A full MAE checkpoint loads with no
         missing keys; its decoder (``decoder_*``, ``mask_token``) comes back as the unexpected keys."""
@@ -210,8 +204,7 @@ class ConvMAEBaseEncoder(nn.Module):
         # (isic_hip.optim.AdamW) bumps neither data_ptr nor _version (ViTSmallEncoder._prepare)
         if self._w16 is not None and key == self._w16_key and not self.trainable:
             return self._w16
-        if any(p.device != device for p in params):
-            raise IsicHipError("ConvMAEBaseEncoder: move the module to the GPU first (.to('cuda'))")
+        self._check_device(params, device)
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         w = {}
 
@@ -245,13 +238,8 @@ class ConvMAEBaseEncoder(nn.Module):
             for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
                 w[f"{b}.{lin}.weight"] = mat(f"{b}.{lin}.weight")
             folds += [(f"{b}.norm1", f"{b}.attn.qkv"), (f"{b}.norm2", f"{b}.mlp.fc1")]
-        # LayerNorm folded into the next product: W' = W diag(gamma) fp16, c from the ROUNDED W', b' = b + W beta (fp32)
         for norm, lin in (folds if self.fold_layernorm else ()):
-            W = sd[lin + ".weight"].float().reshape(sd[lin + ".weight"].shape[0], -1)
-            Wg = (W * w[norm + ".weight"][None, :]).to(_F16).contiguous()
-            w[lin + ".ln_weight"] = Wg
-            w[lin + ".ln_c"] = Wg.float().sum(dim=1).contiguous()
-            w[lin + ".ln_bias"] = (w[lin + ".bias"] + W @ w[norm + ".bias"]).contiguous()
+            fold_layernorm(w, sd[lin + ".weight"], norm, lin)
         self._w16, self._w16_key = w, key
         return w
 
@@ -260,13 +248,7 @@ class ConvMAEBaseEncoder(nn.Module):
     def run_tokens(self, images, depth=None):
         """images[N,3,224,224] (fp32, normalised) on the GPU -> tokens[N, 196, 768] fp32.  ``depth`` = (blocks1, blocks2,
         blocks3) runs only the first blocks of each stage (a test of the composition)."""
-        if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_ch, self.img_size, self.img_size):
-            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
-        if not images.is_cuda:
-            raise IsicHipError("ConvMAEBaseEncoder runs on the MI355X only (no CPU fallback)")
-        depth = tuple(self.depths) if depth is None else tuple(depth)
-        if len(depth) != 3 or any(not 0 <= d <= m for d, m in zip(depth, self.depths)):
-            raise ValueError(f"depth: three block counts within {self.depths}")
+        depth = self._check(images, depth)
         dev = images.device
         w = self._prepare(dev)
         x_in = images.float().contiguous()
@@ -278,12 +260,24 @@ class ConvMAEBaseEncoder(nn.Module):
         return out
 
     def _run_chunk(self, img, w, out, depth):
+        n, fold, spec = img.shape[0], self.fold_layernorm, self._blocks3_spec(self.tokens)
+        y3, s1, s2, _ = self._front(img, w, depth, fold)
+        x, st = embed(w, y3, "patch_embed4", spec, fold)
+        del y3
+        x, _ = blocks_forward(w, x, st, n, depth[2], spec, fold=fold)
+        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, n * self.tokens, self.dims[2], 0,
+             self.ln_eps)
+
+    def _front(self, img, w, depth, fold, save=False, keep=None):
+        """The convolutional front: the stem rows, patch_embed1, blocks1, patch_embed2, blocks2, patch_embed3 and the two
+        stage decoders -> (patch_embed3's tokens [n * 196, 768], s1, s2, tape).  ``save``: tape holds what the backward
+        reads of it (the PatchEmbed convolution outputs t1-t3, the stage outputs x1 / x2, the CBlocks' activations);
+        else it is empty and every activation goes once it has been read.  ``keep``: ``_cblocks``."""
         dev = img.device
         n = img.shape[0]
         (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
         M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
-        T = self.tokens
-        ceps = self.conv_ln_eps
+        tape = {}
 
         def e16(*shape):
             return torch.empty(shape, device=dev, dtype=_F16)
@@ -291,111 +285,84 @@ class ConvMAEBaseEncoder(nn.Module):
         def patch_embed(rows, name, M, C, K):
             t, y = e16(M, C), e16(M, C)
             call("isic_gemm_f16", rows, w[name + ".proj.weight"], w[name + ".proj.bias"], None, t, M, C, K, 0, 0)
-            call("isic_layernorm_add_f16", t, None, None, w[name + ".norm.weight"], w[name + ".norm.bias"], y, None, M, C, 1, ceps)
+            call("isic_layernorm_add_f16", t, None, None, w[name + ".norm.weight"], w[name + ".norm.bias"], y, None, M, C, 1,
+                 self.conv_ln_eps)
+            if save:
+                tape["t" + name[-1]] = t
             return y
+
+        def decode(rows, name, K):
+            s = e16(M3, d3)
+            call("isic_gemm_f16", rows, w[name + ".weight"], w[name + ".bias"], None, s, M3, d3, K, 0, 0)
+            return s
 
         # ---- stage 1: 56 x 56 x 256
         rows = e16(M1, 64)
         call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
         x = patch_embed(rows, "patch_embed1", M1, d1, 64)
         del rows
-        x = self._cblocks(x, w, "blocks1", n, g1, d1, depth[0])
+        x, blocks1 = self._cblocks(x, w, "blocks1", n, g1, d1, depth[0], fold, save, keep)
         rows = e16(M3, 16 * d1)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 4)
-        s1 = e16(M3, d3)
-        call("isic_gemm_f16", rows, w["stage1_output_decode.weight"], w["stage1_output_decode.bias"], None, s1, M3, d3, 16 * d1, 0, 0)
+        s1 = decode(rows, "stage1_output_decode", 16 * d1)
         rows = e16(M2, 4 * d1)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 2)
+        if save:
+            tape.update(blocks1=blocks1, x1=x)
         del x
         # ---- stage 2: 28 x 28 x 384
         x = patch_embed(rows, "patch_embed2", M2, d2, 4 * d1)
         del rows
-        x = self._cblocks(x, w, "blocks2", n, g2, d2, depth[1])
+        x, blocks2 = self._cblocks(x, w, "blocks2", n, g2, d2, depth[1], fold, save, keep)
         rows = e16(M3, 4 * d2)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g2, g2, d2, 2)
+        if save:
+            tape.update(blocks2=blocks2, x2=x)
         del x
-        s2 = e16(M3, d3)
-        call("isic_gemm_f16", rows, w["stage2_output_decode.weight"], w["stage2_output_decode.bias"], None, s2, M3, d3, 4 * d2, 0, 0)
+        s2 = decode(rows, "stage2_output_decode", 4 * d2)
         # ---- stage 3: 196 tokens x 768
-        t3 = patch_embed(rows, "patch_embed3", M3, d3, 4 * d2)
-        del rows
-        x = self._vit_blocks(t3, w, n, depth[2])
-        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, M3, d3, 0, self.ln_eps)
+        return patch_embed(rows, "patch_embed3", M3, d3, 4 * d2), s1, s2, tape
 
-    def _cblocks(self, x, w, stage, n, g, C, nblk):
-        """CBlocks over the NHWC stream x[n*g*g, C] (updated in place; returned)."""
+    def _cblocks(self, x, w, stage, n, g, C, nblk, fold, save=False, keep=None):
+        """``nblk`` CBlocks over the NHWC stream x[n*g*g, C] -> (the output stream, the saved activations per block).
+        ``fold`` / ``save`` as in ``transformer.blocks_forward``: without ``save`` x is updated in place and every block
+        reuses one set of buffers.  ``keep`` (uint8 [n, 196], the MAE's token flags; None: no masking) masks the depthwise
+        5x5's input per token."""
+        if save and fold:
+            raise ValueError("_cblocks: save=True runs the layer-by-layer form (fold=False)")
         dev = x.device
-        M, Hd, eps, fold = n * g * g, C * self.mlp_ratio, self.conv_ln_eps, self.fold_layernorm
+        M, Hd, eps = n * g * g, C * self.mlp_ratio, self.conv_ln_eps
         parts = 2 * C // 128
-        h = torch.empty((M, C), device=dev, dtype=_F16)
-        d = torch.empty_like(h)
-        x2 = torch.empty_like(h)
-        hid = torch.empty((M, Hd), device=dev, dtype=_F16)
         st = st2 = None
-        p_in = 0
         if fold and nblk:
             st = torch.empty((M, parts, 2), device=dev, dtype=torch.float32)
             st2 = torch.empty_like(st)
-            call("isic_row_stats_f16", x, st, M, C, eps)                 # (mean, rstd) of the PatchEmbed output: ln_parts 0
+            call("isic_row_stats_f16", x, st, M, C, eps)      # (mean, rstd) of the PatchEmbed output: block 0 reads 0 parts
+
+        def e16(cols):
+            return torch.empty((M, cols), device=dev, dtype=_F16)
+
+        saves = []
         for i in range(nblk):
             b = f"{stage}.{i}"
-            if fold:
-                call("isic_gemm_f16_ln", x, w[b + ".conv1.ln_weight"], w[b + ".conv1.ln_bias"], w[b + ".conv1.ln_c"], st, p_in,
-                     h, M, C, C, 0, eps)
-                call("isic_dwconv5x5_f16", h, w[b + ".attn.weight"], w[b + ".attn.bias"], d, n, g, g, C)
-                call("isic_gemm_f16_stats", d, w[b + ".conv2.weight"], w[b + ".conv2.bias"], x, x2, st2, M, C, C, 0, 0)
-                call("isic_gemm_f16_ln", x2, w[b + ".mlp.fc1.ln_weight"], w[b + ".mlp.fc1.ln_bias"], w[b + ".mlp.fc1.ln_c"], st2,
-                     parts, hid, M, Hd, C, 1, eps)
-                call("isic_gemm_f16_stats", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, x, st, M, C, Hd, 0, 0)
-                p_in = parts
-            else:
-                call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h, None, M, C, 0, eps)
-                call("isic_gemm_f16", h, w[b + ".conv1.weight"], w[b + ".conv1.bias"], None, d, M, C, C, 0, 0)
-                call("isic_dwconv5x5_f16", d, w[b + ".attn.weight"], w[b + ".attn.bias"], h, n, g, g, C)
-                call("isic_gemm_f16", h, w[b + ".conv2.weight"], w[b + ".conv2.bias"], x, x2, M, C, C, 0, 0)
-                call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h, None, M, C, 0, eps)
-                call("isic_gemm_f16", h, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], None, hid, M, Hd, C, 1, 0)
-                call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, x, M, C, Hd, 0, 0)
-        return x
-
-    def _vit_blocks(self, t3, w, n, nblk):
-        """patch_embed4 (+ pos_embed) and the transformer blocks over t3[n*196, 768] -> the residual stream (fp16)."""
-        dev = t3.device
-        T, D, H = self.tokens, self.dims[2], self.heads
-        M, Hd, eps, fold = n * T, D * self.mlp_ratio, self.ln_eps, self.fold_layernorm
-        parts = 2 * D // 128
-        x = torch.empty((M, D), device=dev, dtype=_F16)
-        x2 = torch.empty_like(x)
-        h = torch.empty_like(x) if not fold else None
-        qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        att = torch.empty_like(x)
-        hid = torch.empty((M, Hd), device=dev, dtype=_F16)
-        st = torch.empty((M, parts, 2), device=dev, dtype=torch.float32) if fold else None
-        st2 = torch.empty_like(st) if fold else None
-
-        def linear_res(a, name, res, out, stats, K, res_rows=0):
-            if fold:
-                call("isic_gemm_f16_stats", a, w[name + ".weight"], w[name + ".bias"], res, out, stats, M, D, K, 0, res_rows)
-            else:
-                call("isic_gemm_f16", a, w[name + ".weight"], w[name + ".bias"], res, out, M, D, K, 0, res_rows)
-
-        def linear_ln(xin, stats, norm, name, out, Nout, act):
-            if fold:
-                call("isic_gemm_f16_ln", xin, w[name + ".ln_weight"], w[name + ".ln_bias"], w[name + ".ln_c"], stats, parts, out,
-                     M, Nout, D, act, eps)
-            else:
-                call("isic_layernorm_add_f16", xin, None, None, w[norm + ".weight"], w[norm + ".bias"], h, None, M, D, 0, eps)
-                call("isic_gemm_f16", h, w[name + ".weight"], w[name + ".bias"], None, out, M, Nout, D, act, 0)
-
-        linear_res(t3, "patch_embed4", w["pos_embed"], x, st, D, res_rows=T)
-        for i in range(nblk):
-            b = f"blocks3.{i}"
-            linear_ln(x, st, f"{b}.norm1", f"{b}.attn.qkv", qkv, 3 * D, 0)
-            call("isic_attention_f16", qkv, att, n, T, H, D // H)
-            linear_res(att, f"{b}.attn.proj", x, x2, st2, D)
-            linear_ln(x2, st2, f"{b}.norm2", f"{b}.mlp.fc1", hid, Hd, 1)
-            linear_res(hid, f"{b}.mlp.fc2", x2, x, st, Hd)
-        return x
+            if save or i == 0:
+                h1, dd, x2, hid = e16(C), e16(C), e16(C), e16(Hd)
+            m, h2, pre, xo = (e16(C), e16(C), e16(Hd), e16(C)) if save else (h1, h1, None, x)
+            linear_ln(w, x, st, parts if i else 0, b + ".norm1", b + ".conv1", h1, dd, 0, eps)
+            if keep is None:
+                call("isic_dwconv5x5_f16", dd, w[b + ".attn.weight"], w[b + ".attn.bias"], m, n, g, g, C)
+            else:                                       # saved: keep * dd, the input the weight gradient takes
+                dk = torch.empty_like(dd)
+                call("isic_dwconv5x5_masked_f16", dd, keep, g // self.grids[2], w[b + ".attn.weight"], w[b + ".attn.bias"],
+                     dk, m, n, g, g, C)
+                dd = dk
+            linear_res(w, m, b + ".conv2", x, x2, st2, fold, eps)
+            linear_ln(w, x2, st2, parts, b + ".norm2", b + ".mlp.fc1", h2, hid, 1, eps, pre=pre)
+            linear_res(w, hid, b + ".mlp.fc2", x2, xo, st, fold, eps)
+            if save:
+                saves.append(dict(x=x, h1=h1, d=dd, m=m, x2=x2, h2=h2, pre=pre, hid=hid))
+            x = xo
+        return x, saves
 
     def forward_tokens(self, images, depth=None):
         """tokens[N, 196, 768] fp32; differentiable (``transformer.EncoderFn``) when the encoder is trainable and grad is enabled."""
@@ -409,10 +376,7 @@ class ConvMAEBaseEncoder(nn.Module):
 
     # ------------------------------------------------------------------ training (trainable=True)
     def _check(self, images, depth):
-        if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_ch, self.img_size, self.img_size):
-            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
-        if not images.is_cuda:
-            raise IsicHipError("ConvMAEBaseEncoder runs on the MI355X only (no CPU fallback)")
+        self._check_images(images)
         depth = tuple(self.depths) if depth is None else tuple(depth)
         if len(depth) != 3 or any(not 0 <= d <= m for d, m in zip(depth, self.depths)):
             raise ValueError(f"depth: three block counts within {self.depths}")
@@ -436,84 +400,23 @@ class ConvMAEBaseEncoder(nn.Module):
         dev = images.device
         w = self._prepare_train(dev)
         img = images.float().contiguous()
-        n = img.shape[0]
-        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
-        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
-        ceps = self.conv_ln_eps
-
-        def e16(*shape):
-            return torch.empty(shape, device=dev, dtype=_F16)
-
-        def patch_embed(rows, name, M, C, K):
-            t, y = e16(M, C), e16(M, C)
-            call("isic_gemm_f16", rows, w[name + ".proj.weight"], w[name + ".proj.bias"], None, t, M, C, K, 0, 0)
-            call("isic_layernorm_add_f16", t, None, None, w[name + ".norm.weight"], w[name + ".norm.bias"], y, None, M, C, 1, ceps)
-            return t, y
-
-        tape = dict(n=n, img=img, depth=depth, w=w)
-        keep, L = None, self.tokens
-        if masking is not None:
-            keep, L = masking["keep"], masking["L"]
-            tape.update(keep=keep, ids_restore=masking["ids_restore"], L=L)
-        rows = e16(M1, 64)
-        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
-        tape["t1"], x = patch_embed(rows, "patch_embed1", M1, d1, 64)
-        x, tape["blocks1"] = self._cblocks_train(x, w, "blocks1", n, g1, d1, depth[0], keep)
-        tape["x1"] = x
-        rows = e16(M3, 16 * d1)
-        call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 4)
-        s1 = e16(M3, d3)
-        call("isic_gemm_f16", rows, w["stage1_output_decode.weight"], w["stage1_output_decode.bias"], None, s1, M3, d3, 16 * d1, 0, 0)
-        rows = e16(M2, 4 * d1)
-        call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 2)
-        tape["t2"], x = patch_embed(rows, "patch_embed2", M2, d2, 4 * d1)
-        x, tape["blocks2"] = self._cblocks_train(x, w, "blocks2", n, g2, d2, depth[1], keep)
-        tape["x2"] = x
-        rows = e16(M3, 4 * d2)
-        call("isic_patch_rows_nhwc_f16", x, rows, n, g2, g2, d2, 2)
-        s2 = e16(M3, d3)
-        call("isic_gemm_f16", rows, w["stage2_output_decode.weight"], w["stage2_output_decode.bias"], None, s2, M3, d3, 4 * d2, 0, 0)
-        tape["t3"], y3 = patch_embed(rows, "patch_embed3", M3, d3, 4 * d2)
-        del rows
-        x = e16(M3, d3)
-        call("isic_gemm_f16", y3, w["patch_embed4.weight"], w["patch_embed4.bias"], w["pos_embed"], x, M3, d3, d3, 0, self.tokens)
+        n, d3 = img.shape[0], self.dims[2]
+        keep, L = (masking["keep"], masking["L"]) if masking is not None else (None, self.tokens)
+        y3, s1, s2, tape = self._front(img, w, depth, False, save=True, keep=keep)
+        tape.update(n=n, img=img, depth=depth, w=w)
+        x, _ = embed(w, y3, "patch_embed4", self._blocks3_spec(L), False)
         lat16 = None
         if masking is not None:                                            # the kept tokens of the stream, s1 and s2
-            xk, s1k, s2k = e16(n * L, d3), e16(n * L, d3), e16(n * L, d3)
+            tape.update(keep=keep, ids_restore=masking["ids_restore"], L=L)
+            xk, s1k, s2k, lat16 = (torch.empty((n * L, d3), device=dev, dtype=_F16) for _ in range(4))
             for a, b in ((x, xk), (s1, s1k), (s2, s2k)):
                 call("isic_gather_rows_f16", a, masking["ids_keep"], b, n, self.tokens, L, d3)
-            x, s1, s2, lat16 = xk, s1k, s2k, e16(n * L, d3)
-        x, tape["blocks3"] = blocks_forward_train(w, x, n, depth[2], self._blocks3_spec(L))
+            x, s1, s2 = xk, s1k, s2k
+        x, tape["blocks3"] = blocks_forward(w, x, None, n, depth[2], self._blocks3_spec(L), save=True)
         out = torch.empty((n * L, d3), device=dev, dtype=torch.float32)
         call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], lat16, out, n * L, d3, 0, self.ln_eps)
         tape.update(y3=y3, x3=x, s1=s1, s2=s2, latent16=lat16)
         return out.view(n, L, d3), tape
-
-    def _cblocks_train(self, x, w, stage, n, g, C, nblk, keep=None):
-        """``keep`` (uint8 [n, 196], the MAE's token flags; None: no masking) masks the depthwise 5x5's input per token."""
-        dev = x.device
-        M, Hd, eps = n * g * g, C * self.mlp_ratio, self.conv_ln_eps
-        saves = []
-        for i in range(nblk):
-            b = f"{stage}.{i}"
-            h1, dd, m, x2, h2, xo = (torch.empty((M, C), device=dev, dtype=_F16) for _ in range(6))
-            pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
-            call("isic_layernorm_add_f16", x, None, None, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, None, M, C, 0, eps)
-            call("isic_gemm_f16", h1, w[b + ".conv1.weight"], w[b + ".conv1.bias"], None, dd, M, C, C, 0, 0)
-            if keep is None:
-                call("isic_dwconv5x5_f16", dd, w[b + ".attn.weight"], w[b + ".attn.bias"], m, n, g, g, C)
-            else:                                       # saved: keep * dd, the input the weight gradient takes
-                dk = torch.empty_like(dd)
-                call("isic_dwconv5x5_masked_f16", dd, keep, g // self.grids[2], w[b + ".attn.weight"], w[b + ".attn.bias"],
-                     dk, m, n, g, g, C)
-                dd = dk
-            call("isic_gemm_f16", m, w[b + ".conv2.weight"], w[b + ".conv2.bias"], x, x2, M, C, C, 0, 0)
-            call("isic_layernorm_add_f16", x2, None, None, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, None, M, C, 0, eps)
-            call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, C)
-            call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, xo, M, C, Hd, 0, 0)
-            saves.append(dict(x=x, h1=h1, d=dd, m=m, x2=x2, h2=h2, pre=pre, hid=hid))
-            x = xo
-        return x, saves
 
     def _blocks3_spec(self, T):
         """blocks3 over T tokens per image, as isic_hip/transformer.py describes a stack of blocks."""

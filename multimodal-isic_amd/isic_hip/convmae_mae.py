@@ -28,8 +28,8 @@ check it against.
 
 Launches: the encoder's (isic_hip/convmae.py) with ``isic_dwconv5x5_masked_f16`` in the CBlocks and
 ``isic_gather_rows_f16`` into blocks3; ``isic_mae_unshuffle_f16`` for the mask tokens and the position embedding; the
-decoder blocks through the encoder's own ``transformer.blocks_forward_train`` with ``isic_attention_d32_f16``; ``isic_mae_loss_f16`` for
-the target, the loss and d loss / d pred in one pass.  No CPU fallback.
+decoder blocks through the encoder's own ``transformer.blocks_forward`` with ``isic_attention_d32_f16``;
+``isic_mae_loss_f16`` for the target, the loss and d loss / d pred in one pass.  No CPU fallback.
 
 Training: ``loss.backward()`` runs one native backward (include/isic_hip_mae.h + the encoder's) that accumulates into
 every ``param.grad``.  The loss kernel writes d loss / d pred already multiplied by the power-of-two loss scale
@@ -50,7 +50,7 @@ from torch import nn
 
 from .convmae import ConvMAEBaseEncoder, _Block, _F16, sincos_pos_embed
 from .lib import IsicHipError, call
-from .transformer import Backward, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads, param_grads
+from .transformer import Backward, blocks_backward, blocks_forward, blocks_workspace_bytes, check_grads, param_grads
 
 
 class ConvMAEBase(ConvMAEBaseEncoder):
@@ -148,40 +148,52 @@ class ConvMAEBase(ConvMAEBaseEncoder):
     def _loss_scale(self, mask_sum):
         return 2.0 ** (round(math.log2(self.pred_dim * mask_sum)) + 4)
 
-    def _run_mae(self, images, mask_ratio, noise, depth, decoder_depth):
-        depth = self._check(images, depth)
-        dd = self.dec_depth if decoder_depth is None else int(decoder_depth)
-        if not 0 <= dd <= self.dec_depth:
-            raise ValueError(f"decoder_depth: 0..{self.dec_depth}")
-        n, dev = images.shape[0], images.device
-        m = self.random_masking(n, mask_ratio, noise, dev)
-        L, T, Dd, P = m["L"], self.tokens, self.dec_dim, self.pred_dim
-        if L == T:
-            raise ValueError("mask_ratio removes no token: the reconstruction loss has no term (use forward_encoder)")
-        latent, tape = self.run_forward_train(images, depth, masking=m)
-        w = tape["w"]
-        Mk, M = n * L, n * T
-        z = torch.empty((Mk, Dd), device=dev, dtype=_F16)
-        call("isic_gemm_f16", tape["latent16"], w["decoder_embed.weight"], w["decoder_embed.bias"], None, z, Mk, Dd,
-             self.dims[2], 0, 0)
+    def _decoder(self, w, lat16, ids_restore, n, L, dd):
+        """The decoder over the first ``dd`` blocks: latent (fp16 rows [n * L, 768]) -> (pred fp16 [n * 196, 768], what the
+        backward reads of it).  ``forward_decoder`` drops the second result; its blocks run in the saving form all the
+        same, so that it stays ``forward``'s launch sequence (fc1 through ``isic_gemm_f16_gelu_pre``)."""
+        T, Dd, P, dev = self.tokens, self.dec_dim, self.pred_dim, lat16.device
+        M = n * T
+        z = torch.empty((n * L, Dd), device=dev, dtype=_F16)
+        call("isic_gemm_f16", lat16, w["decoder_embed.weight"], w["decoder_embed.bias"], None, z, n * L, Dd, self.dims[2], 0, 0)
         xd = torch.empty((M, Dd), device=dev, dtype=_F16)
-        call("isic_mae_unshuffle_f16", z, m["ids_restore"], w["mask_token"], w["decoder_pos_embed"], xd, n, T, L, Dd)
+        call("isic_mae_unshuffle_f16", z, ids_restore, w["mask_token"], w["decoder_pos_embed"], xd, n, T, L, Dd)
         del z
-        x, dec_saves = blocks_forward_train(w, xd, n, dd, self._decoder_spec())
+        x, saves = blocks_forward(w, xd, None, n, dd, self._decoder_spec(), save=True)
         hn = torch.empty((M, Dd), device=dev, dtype=_F16)
         call("isic_layernorm_add_f16", x, None, None, w["decoder_norm.weight"], w["decoder_norm.bias"], hn, None, M, Dd, 0,
              self.ln_eps)
         pred = torch.empty((M, P), device=dev, dtype=_F16)
         call("isic_gemm_f16", hn, w["decoder_pred.weight"], w["decoder_pred.bias"], None, pred, M, P, Dd, 0, 0)
-        mask_sum = float(n * (T - L))
-        S = self._loss_scale(mask_sum)
+        return pred, dict(dd=dd, xd_out=x, hn=hn, blocks=saves)
+
+    def _loss(self, pred, img, mask, mask_sum, S):
+        """-> (loss[1] fp32, S d loss / d pred fp16) of pred (fp16 rows) against img (fp32), one launch."""
+        n, dev = img.shape[0], img.device
         loss, dpred = torch.empty(1, device=dev, dtype=torch.float32), torch.empty_like(pred)
         nb = call("isic_mae_loss_f16_workspace_bytes", n, self.img_size, self.img_size, self.patch)
         ws = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
-        call("isic_mae_loss_f16", pred, tape["img"], m["mask"], int(self.norm_pix_loss), mask_sum, S, dpred, loss, n,
-             self.in_ch, self.img_size, self.img_size, self.patch, ws, ws.numel())
-        dec = dict(dd=dd, m=m, xd_out=x, hn=hn, blocks=dec_saves, dpred=dpred, S=S)
-        return loss.view(()), pred.view(n, T, P), m, latent, dict(enc=tape, dec=dec)
+        call("isic_mae_loss_f16", pred, img, mask, int(self.norm_pix_loss), mask_sum, S, dpred, loss, n, self.in_ch,
+             self.img_size, self.img_size, self.patch, ws, ws.numel())
+        return loss, dpred
+
+    def _run_mae(self, images, mask_ratio, noise, depth, decoder_depth):
+        depth = self._check(images, depth)
+        dd = self.dec_depth if decoder_depth is None else int(decoder_depth)
+        if not 0 <= dd <= self.dec_depth:
+            raise ValueError(f"decoder_depth: 0..{self.dec_depth}")
+        n = images.shape[0]
+        m = self.random_masking(n, mask_ratio, noise, images.device)
+        L, T = m["L"], self.tokens
+        if L == T:
+            raise ValueError("mask_ratio removes no token: the reconstruction loss has no term (use forward_encoder)")
+        latent, tape = self.run_forward_train(images, depth, masking=m)
+        pred, dec = self._decoder(tape["w"], tape["latent16"], m["ids_restore"], n, L, dd)
+        mask_sum = float(n * (T - L))
+        S = self._loss_scale(mask_sum)
+        loss, dpred = self._loss(pred, tape["img"], m["mask"], mask_sum, S)
+        dec.update(m=m, dpred=dpred, S=S)
+        return loss.view(()), pred.view(n, T, self.pred_dim), m, latent, dict(enc=tape, dec=dec)
 
     def forward(self, imgs, mask_ratio=0.75, noise=None, lesion_mask=None, depth=None, decoder_depth=None):
         """-> (loss, pred[N, 196, 768] fp32, mask[N, 196]); ``loss.backward()`` fills every ``param.grad`` (native).
@@ -211,19 +223,8 @@ class ConvMAEBase(ConvMAEBaseEncoder):
         if not latent.is_cuda:
             raise IsicHipError("ConvMAEBase runs on the MI355X only (no CPU fallback)")
         dev = latent.device
-        w = self._prepare(dev)
-        lat16 = latent.reshape(n * L, D).to(_F16).contiguous()
-        z = torch.empty((n * L, Dd), device=dev, dtype=_F16)
-        call("isic_gemm_f16", lat16, w["decoder_embed.weight"], w["decoder_embed.bias"], None, z, n * L, Dd, D, 0, 0)
-        xd = torch.empty((n * T, Dd), device=dev, dtype=_F16)
-        call("isic_mae_unshuffle_f16", z, ids_restore.to(dev).long().contiguous(), w["mask_token"], w["decoder_pos_embed"],
-             xd, n, T, L, Dd)
-        x, _ = blocks_forward_train(w, xd, n, self.dec_depth, self._decoder_spec())
-        hn = torch.empty((n * T, Dd), device=dev, dtype=_F16)
-        call("isic_layernorm_add_f16", x, None, None, w["decoder_norm.weight"], w["decoder_norm.bias"], hn, None, n * T, Dd,
-             0, self.ln_eps)
-        pred = torch.empty((n * T, P), device=dev, dtype=_F16)
-        call("isic_gemm_f16", hn, w["decoder_pred.weight"], w["decoder_pred.bias"], None, pred, n * T, P, Dd, 0, 0)
+        pred, _ = self._decoder(self._prepare(dev), latent.reshape(n * L, D).to(_F16).contiguous(),
+                                ids_restore.to(dev).long().contiguous(), n, L, self.dec_depth)
         return pred.float().view(n, T, P)
 
     @torch.no_grad()
@@ -236,13 +237,7 @@ class ConvMAEBase(ConvMAEBaseEncoder):
         mask_sum = float(mask.sum())
         if mask_sum <= 0:
             raise ValueError("forward_loss: the mask removes no token")
-        dev = imgs.device
-        p16 = pred.to(_F16).contiguous()
-        loss, dpred = torch.empty(1, device=dev, dtype=torch.float32), torch.empty_like(p16)
-        nb = call("isic_mae_loss_f16_workspace_bytes", n, self.img_size, self.img_size, self.patch)
-        ws = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
-        call("isic_mae_loss_f16", p16, imgs.float().contiguous(), mask, int(self.norm_pix_loss), mask_sum, 1.0, dpred, loss,
-             n, self.in_ch, self.img_size, self.img_size, self.patch, ws, ws.numel())
+        loss, _ = self._loss(pred.to(_F16).contiguous(), imgs.float().contiguous(), mask, mask_sum, 1.0)
         return loss.view(())
 
     # ------------------------------------------------------------------ backward

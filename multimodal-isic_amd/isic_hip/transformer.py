@@ -1,17 +1,20 @@
-"""The training path of a stack of pre-norm transformer blocks, fp16 on gfx950 -- shared by ``ViTSmallEncoder``
-(isic_hip/vit.py), ``ConvMAEBaseEncoder`` (blocks3, isic_hip/convmae.py) and the MAE decoder (isic_hip/convmae_mae.py).
+"""A stack of pre-norm transformer blocks, fp16 on gfx950: its one forward (inference and training) and its backward --
+shared by ``ViTSmallEncoder`` (isic_hip/vit.py), ``ConvMAEBaseEncoder`` (blocks3, isic_hip/convmae.py) and the MAE decoder
+(isic_hip/convmae_mae.py).
 
 A block is x2 = x + proj(attention(qkv(LN1(x)))), out = x2 + fc2(GELU(fc1(LN2(x2)))) with timm's parameter names
 (``BLOCK_PARAMS``).  A stack is described by ``spec = dict(prefix, T, D, H, eps, total)``: the blocks are ``prefix.i``,
 i < total, in the weight dict ``w``; T tokens per image, width D, H heads of 64 (``isic_attention_f16``) or 32
 (``isic_attention_d32_f16``), LayerNorm eps; the MLP width is fc1's.  The stream is fp16 rows [n * T, D].
 
-Forward: ``isic_layernorm_add_f16`` (the ViT-S/16 hands in ``isic_layernorm_f16``, its frozen forward's kernel: the two are
+Forward (``blocks_forward``), layer by layer: ``isic_layernorm_add_f16`` (the ViT-S/16 hands in ``isic_layernorm_f16``, its frozen forward's kernel: the two are
 the same two-pass arithmetic, but the compiler fuses the mean subtraction and the first squares into FMAs in one and not
-in the other, and their outputs differ in the last bit), ``isic_gemm_f16`` (residual in the epilogue), the attention, and
-``isic_gemm_f16_gelu_pre`` for fc1.  It saves per block x, LN1(x), qkv, the attention output, x2, LN2(x2), fc1's
-pre-activation and GELU output (fp16), and no LayerNorm statistics: ``isic_layernorm_add_bwd_f16`` recomputes (mean, rstd)
-from x in fp32.
+in the other, and their outputs differ in the last bit), ``isic_gemm_f16`` (residual in the epilogue; GELU for fc1) and
+the attention.  ``fold``: the pre-norms have no pass of their own (``isic_gemm_f16_ln`` on row statistics from
+``isic_gemm_f16_stats`` or ``isic_row_stats_f16``; isic_hip/vit.py has the algebra, ``fold_layernorm`` the weights).
+``save`` (training): fc1 through ``isic_gemm_f16_gelu_pre``, and per block x, LN1(x), qkv, the attention output, x2,
+LN2(x2), fc1's pre-activation and GELU output (fp16) are kept, and no LayerNorm statistics:
+``isic_layernorm_add_bwd_f16`` recomputes (mean, rstd) from x in fp32.
 
 Backward: on gradients multiplied by a power-of-two loss scale S (``loss_scale``); every reduction into a parameter
 gradient multiplies by s = 1/S in fp32 and accumulates into ``param.grad`` (``Backward``), so gradients are exactly
@@ -23,8 +26,9 @@ from __future__ import annotations
 import math
 
 import torch
+from torch import nn
 
-from .lib import call
+from .lib import IsicHipError, call
 
 _F16 = torch.float16
 
@@ -51,28 +55,91 @@ def layernorm_add(x, gamma, beta, y, M, D, eps):
     call("isic_layernorm_add_f16", x, None, None, gamma, beta, y, None, M, D, 0, eps)
 
 
-def blocks_forward_train(w, x, n, nblk, spec, layernorm=layernorm_add):
+def fold_layernorm(w, W, norm, lin):
+    """LayerNorm ``norm`` folded into the product ``lin`` that follows it (isic_hip/vit.py has the algebra), from the fp32
+    master W of ``lin``: W' = W diag(gamma) in fp16, c from the ROUNDED W' (it has to cancel what the MFMAs sum),
+    b' = b + W beta in fp32."""
+    W = W.float().reshape(W.shape[0], -1)
+    Wg = (W * w[norm + ".weight"][None, :]).to(_F16).contiguous()
+    w[lin + ".ln_weight"] = Wg
+    w[lin + ".ln_c"] = Wg.float().sum(dim=1).contiguous()
+    w[lin + ".ln_bias"] = (w[lin + ".bias"] + W @ w[norm + ".bias"]).contiguous()
+
+
+def linear_res(w, a, name, res, out, st, fold, eps, res_rows=0):
+    """out = a . W^T + b + res (``res_rows`` > 0: res repeats every ``res_rows`` rows) and, into ``st``, the LayerNorm
+    statistics of out's rows for the product that reads it: partial sums per 64-column group out of the epilogue
+    (``fold`` True), or (mean, rstd) from a statistics-only pass (``"stats"``)."""
+    (M, K), N = a.shape, out.shape[1]
+    if fold is True:
+        call("isic_gemm_f16_stats", a, w[name + ".weight"], w[name + ".bias"], res, out, st, M, N, K, 0, res_rows)
+    else:
+        call("isic_gemm_f16", a, w[name + ".weight"], w[name + ".bias"], res, out, M, N, K, 0, res_rows)
+        if fold == "stats":
+            call("isic_row_stats_f16", out, st, M, N, eps)
+
+
+def linear_ln(w, xin, st, parts, norm, name, h, out, act, eps, layernorm=layernorm_add, pre=None):
+    """out = act(LayerNorm ``norm`` (xin) . W^T + b).  With xin's row statistics ``st`` (``parts`` partial sums per row; 0:
+    (mean, rstd)) the LayerNorm is folded into the product; ``st`` None: a ``layernorm`` pass into h and a plain product,
+    which also leaves fc1's pre-activation in ``pre`` if given (for the backward)."""
+    (M, K), Nout = xin.shape, out.shape[1]
+    if st is not None:
+        call("isic_gemm_f16_ln", xin, w[name + ".ln_weight"], w[name + ".ln_bias"], w[name + ".ln_c"], st, parts, out, M, Nout,
+             K, act, eps)
+        return
+    layernorm(xin, w[norm + ".weight"], w[norm + ".bias"], h, M, K, eps)
+    if pre is not None:
+        call("isic_gemm_f16_gelu_pre", h, w[name + ".weight"], w[name + ".bias"], out, pre, M, Nout, K)
+    else:
+        call("isic_gemm_f16", h, w[name + ".weight"], w[name + ".bias"], None, out, M, Nout, K, act, 0)
+
+
+def embed(w, a, name, spec, fold):
+    """The product that writes the stream ahead of block 0: a . ``name``^T + b + pos_embed -> (the stream, its row
+    statistics for ``blocks_forward``: None when ``fold`` is False)."""
+    M, D = a.shape[0], spec["D"]
+    x = torch.empty((M, D), device=a.device, dtype=_F16)
+    st = None
+    if fold is not False:
+        st = torch.empty((M, 2 * D // 128 if fold is True else 1, 2), device=a.device, dtype=torch.float32)
+    linear_res(w, a, name, w["pos_embed"], x, st, fold, spec["eps"], res_rows=w["pos_embed"].shape[0])
+    return x, st
+
+
+def blocks_forward(w, x, st, n, nblk, spec, fold=False, save=False, layernorm=layernorm_add):
     """The first ``nblk`` blocks of the stack over the stream x[n * T, D] -> (the output stream, the saved activations per
-    block).  ``layernorm(x, gamma, beta, y, M, D, eps)`` is the pre-norm pass: a caller whose frozen forward runs another
-    LayerNorm kernel hands that one in, so that the training forward stays that forward bit for bit."""
+    block).  ``fold`` False: the layer-by-layer form; True / ``"stats"``: the pre-norms folded into qkv and fc1
+    (``fold_layernorm``), on the row statistics ``st`` of x that the product which wrote x left (``embed``).  ``save``
+    False (inference): the stream ping-pongs between x and one second buffer, every block reuses one LN / qkv /
+    attention / hidden buffer, and x is overwritten.  ``save`` True (training; the layer-by-layer form only): fresh
+    tensors per block, fc1 through ``isic_gemm_f16_gelu_pre``, x is kept.  ``layernorm(x, gamma, beta, y, M, D, eps)`` is
+    the pre-norm pass: a caller whose frozen forward runs another LayerNorm kernel hands that one in."""
+    if save and fold is not False:
+        raise ValueError("blocks_forward: save=True runs the layer-by-layer form (fold=False)")
     dev = x.device
     T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
     M = n * T
+    parts = 2 * D // 128 if fold is True else 0
+    st2 = torch.empty_like(st) if fold is not False else None
+
+    def e16(cols):
+        return torch.empty((M, cols), device=dev, dtype=_F16)
+
     saves = []
     for i in range(nblk):
         b = f"{spec['prefix']}.{i}"
         Hd = w[b + ".mlp.fc1.weight"].shape[0]
-        h1, att, x2, h2, xo = (torch.empty((M, D), device=dev, dtype=_F16) for _ in range(5))
-        qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        pre, hid = (torch.empty((M, Hd), device=dev, dtype=_F16) for _ in range(2))
-        layernorm(x, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h1, M, D, eps)
-        call("isic_gemm_f16", h1, w[b + ".attn.qkv.weight"], w[b + ".attn.qkv.bias"], None, qkv, M, 3 * D, D, 0, 0)
+        if save or i == 0:
+            h1, qkv, att, x2, hid = e16(D) if fold is False else None, e16(3 * D), e16(D), e16(D), e16(Hd)
+        h2, pre, xo = (e16(D), e16(Hd), e16(D)) if save else (h1, None, x)
+        linear_ln(w, x, st, parts, b + ".norm1", b + ".attn.qkv", h1, qkv, 0, eps, layernorm)
         _attention(qkv, att, n, T, H, D // H)
-        call("isic_gemm_f16", att, w[b + ".attn.proj.weight"], w[b + ".attn.proj.bias"], x, x2, M, D, D, 0, 0)
-        layernorm(x2, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h2, M, D, eps)
-        call("isic_gemm_f16_gelu_pre", h2, w[b + ".mlp.fc1.weight"], w[b + ".mlp.fc1.bias"], hid, pre, M, Hd, D)
-        call("isic_gemm_f16", hid, w[b + ".mlp.fc2.weight"], w[b + ".mlp.fc2.bias"], x2, xo, M, D, Hd, 0, 0)
-        saves.append(dict(x=x, h1=h1, qkv=qkv, att=att, x2=x2, h2=h2, pre=pre, hid=hid))
+        linear_res(w, att, b + ".attn.proj", x, x2, st2, fold, eps)
+        linear_ln(w, x2, st2, parts, b + ".norm2", b + ".mlp.fc1", h2, hid, 1, eps, layernorm, pre)
+        linear_res(w, hid, b + ".mlp.fc2", x2, xo, st, fold, eps)
+        if save:
+            saves.append(dict(x=x, h1=h1, qkv=qkv, att=att, x2=x2, h2=h2, pre=pre, hid=hid))
         x = xo
     return x, saves
 
@@ -129,7 +196,7 @@ class Backward:
 
 
 def blocks_backward(saves, g, gh, bw, n, nblk, spec, fire):
-    """Backward of ``blocks_forward_train``: g (fp32) / gh (its fp16 copy), the gradient of the output stream, become those
+    """Backward of ``blocks_forward(save=True)``: g (fp32) / gh (its fp16 copy), the gradient of the output stream, become those
     of the input stream (in place); ``saves[i]`` is dropped once block i is done.  ``fire(names)`` is told the parameters
     of each finished block (``prefix.i.`` + ``BLOCK_PARAMS``), from the last block back."""
     dev, w = g.device, bw.w
@@ -176,6 +243,25 @@ def check_grads(params, who):
     if not bool(torch.isfinite(torch.stack(norms)).all()):
         raise FloatingPointError(f"{who} backward: non-finite parameter gradient (fp16 overflow in the backward, or a "
                                  "non-finite gradient accumulated earlier)")
+
+
+class Encoder(nn.Module):
+    """What the fp16 patch encoders share: frozen unless ``trainable``, images[N, in_ch, img_size, img_size] on the GPU."""
+
+    def train(self, mode=True):
+        if mode and not self.trainable:
+            raise IsicHipError(f"{self._who} is a frozen inference encoder (save_latent.py:51-53): no train() mode")
+        return super().train(mode)
+
+    def _check_images(self, images):
+        if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_ch, self.img_size, self.img_size):
+            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
+        if not images.is_cuda:
+            raise IsicHipError(f"{self._who} runs on the MI355X only (no CPU fallback)")
+
+    def _check_device(self, params, device):
+        if any(p.device != device for p in params):
+            raise IsicHipError(f"{self._who}: move the module to the GPU first (.to('cuda'))")
 
 
 class EncoderFn(torch.autograd.Function):

@@ -45,14 +45,16 @@ import math
 import torch
 from torch import nn
 
-from .lib import IsicHipError, call
-from .transformer import (Backward, EncoderFn, blocks_backward, blocks_forward_train, blocks_workspace_bytes, check_grads,
-                          loss_scale, param_grads)
+from .lib import call
+from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_workspace_bytes, check_grads,
+                          embed, fold_layernorm, loss_scale, param_grads)
 
 _F16 = torch.float16
 
 
-class ViTSmallEncoder(nn.Module):
+class ViTSmallEncoder(Encoder):
+    _who = "ViTSmallEncoder"
+
     def __init__(self, img_size=224, patch=16, in_ch=3, dim=384, depth=12, heads=6, mlp_ratio=4, seed=0,
                  fold_layernorm=None, precision="fp16", trainable=False):
         super().__init__()
@@ -148,13 +150,6 @@ class ViTSmallEncoder(nn.Module):
         self._wmx_key = None
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
-    def train(self, mode=True):
-        if self.trainable:
-            return super().train(mode)
-        if mode:
-            raise IsicHipError("ViTSmallEncoder is a frozen inference encoder (save_latent.py:51-53): no train() mode")
-        return super().train(False)
-
     # ------------------------------------------------------------------ forward
     def _prepare(self, device):
         key = tuple((self._get(n).data_ptr(), self._get(n)._version) for n in self._names)
@@ -162,11 +157,10 @@ class ViTSmallEncoder(nn.Module):
         # (isic_hip.optim.AdamW) bumps neither data_ptr nor _version (ResNet18Encoder.prepare_weights)
         if self._w16 is not None and key == self._w16_key and not self.trainable:
             return self._w16
+        self._check_device(self.parameters(), device)
         w = {}
         for n in self._names:
             p = self._get(n).detach()
-            if p.device != device:
-                raise IsicHipError("ViTSmallEncoder: move the module to the GPU first (.to('cuda'))")
             if n == "patch_embed.proj.weight":
                 w[n] = p.reshape(self.dim, -1).to(_F16).contiguous()
             elif n == "pos_embed":
@@ -175,16 +169,9 @@ class ViTSmallEncoder(nn.Module):
                 w[n] = p.to(_F16).contiguous()
             else:
                 w[n] = p.float().contiguous()                                      # biases, LayerNorm affine: fp32
-        # LayerNorm folded into the product that follows it (module docstring): W' fp16, c from the ROUNDED W' (it has to
-        # cancel what the MFMAs sum), b' fp32
-        for i in range(self.depth if self.fold_layernorm is not False else 0):
+        for i in range(self.depth if self.fold_layernorm is not False else 0):      # module docstring
             for norm, lin in ((f"blocks.{i}.norm1", f"blocks.{i}.attn.qkv"), (f"blocks.{i}.norm2", f"blocks.{i}.mlp.fc1")):
-                W = self._get(lin + ".weight").detach().float()
-                gamma, beta = w[norm + ".weight"], w[norm + ".bias"]
-                Wg = (W * gamma[None, :]).to(_F16).contiguous()
-                w[lin + ".ln_weight"] = Wg
-                w[lin + ".ln_c"] = Wg.float().sum(dim=1).contiguous()
-                w[lin + ".ln_bias"] = (w[lin + ".bias"] + W @ beta).contiguous()
+                fold_layernorm(w, self._get(lin + ".weight").detach(), norm, lin)
         self._w16, self._w16_key = w, key
         return w
 
@@ -198,8 +185,6 @@ class ViTSmallEncoder(nn.Module):
             for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
                 n = f"blocks.{i}.{lin}.weight"
                 p = self._get(n).detach().float().contiguous()
-                if p.device != device:
-                    raise IsicHipError("ViTSmallEncoder: move the module to the GPU first (.to('cuda'))")
                 R, K = p.shape
                 q = torch.empty((R, K), device=device, dtype=torch.uint8)
                 s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
@@ -208,80 +193,40 @@ class ViTSmallEncoder(nn.Module):
         self._wmx, self._wmx_key = w, key
         return w
 
+    def _patch_stream(self, images, w, fold):
+        """patchify and the patch projection (+ pos_embed) -> (the residual stream x[N * 196, 384] fp16, its row statistics
+        as ``fold`` has them (transformer.embed), the patch rows: the backward's input, else to be dropped)."""
+        x_in = images.float().contiguous()
+        rows = torch.empty((x_in.shape[0] * self.tokens, self.in_ch * self.patch * self.patch), device=x_in.device, dtype=_F16)
+        call("isic_vit_patchify_f16", x_in, rows, x_in.shape[0], self.in_ch, self.img_size, self.img_size, self.patch)
+        return embed(w, rows, "patch_embed.proj", self._spec(), fold) + (rows,)
+
+    def _final_norm(self, x, w, N):
+        out = torch.empty((N * self.tokens, self.dim), device=x.device, dtype=torch.float32)
+        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, N * self.tokens, self.dim, 1e-6)
+        return out.view(N, self.tokens, self.dim)
+
     @torch.no_grad()
     def run_tokens(self, images, depth=None):
         """images[N,3,H,W] (fp32; other float types are converted) on the GPU -> tokens[N, 196, 384] fp32."""
-        if images.dim() != 4 or images.shape[1] != self.in_ch or images.shape[2] != self.img_size or images.shape[3] != self.img_size:
-            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
-        if not images.is_cuda:
-            raise IsicHipError("ViTSmallEncoder runs on the MI355X only (no CPU fallback)")
-        dev = images.device
-        w = self._prepare(dev)
+        self._check_images(images)
+        w = self._prepare(images.device)
         if self.precision == "mxfp8":
-            return self._run_tokens_mx(images, w, self._prepare_mx(dev), depth)
-        x_in = images.float().contiguous()
-        N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
-        M = N * T
-        K0 = self.in_ch * self.patch * self.patch
-        rows = torch.empty((M, K0), device=dev, dtype=_F16)
-        call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
-        x = torch.empty((M, D), device=dev, dtype=_F16)
-        fold = self.fold_layernorm
-        eps = 1e-6
-        h = torch.empty((M, D), device=dev, dtype=_F16) if fold is False else None
-        qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        att = torch.empty((M, D), device=dev, dtype=_F16)
-        hid = torch.empty((M, self.mlp), device=dev, dtype=_F16)
-        x2 = torch.empty_like(x)
-        # row statistics of x / x2: partial sums per 64-column group out of the producing epilogue (fold True), or
-        # (mean, rstd) from a statistics-only pass ("stats")
-        parts = 2 * D // 128 if fold is True else 0
-        st = torch.empty((M, max(parts, 1), 2), device=dev, dtype=torch.float32) if fold is not False else None
-        st2 = torch.empty_like(st) if fold is not False else None
-
-        def linear_res(a, name, res, out, stats, K, res_rows=0):
-            """out = a . W^T + b + res; the LayerNorm statistics of out on the way when the next product wants them"""
-            if fold is True:
-                call("isic_gemm_f16_stats", a, w[name + ".weight"], w[name + ".bias"], res, out, stats, M, D, K, 0, res_rows)
-            else:
-                call("isic_gemm_f16", a, w[name + ".weight"], w[name + ".bias"], res, out, M, D, K, 0, res_rows)
-                if fold == "stats":
-                    call("isic_row_stats_f16", out, stats, M, D, eps)
-
-        def linear_ln(xin, stats, norm, name, out, Nout, act):
-            """out = act(LayerNorm(xin) . W^T + b)"""
-            if fold is False:
-                call("isic_layernorm_f16", xin, w[norm + ".weight"], w[norm + ".bias"], h, None, M, D, eps)
-                call("isic_gemm_f16", h, w[name + ".weight"], w[name + ".bias"], None, out, M, Nout, D, act, 0)
-            else:
-                call("isic_gemm_f16_ln", xin, w[name + ".ln_weight"], w[name + ".ln_bias"], w[name + ".ln_c"], stats, parts, out,
-                     M, Nout, D, act, eps)
-
-        linear_res(rows, "patch_embed.proj", w["pos_embed"], x, st, K0, res_rows=T)
+            return self._run_tokens_mx(images, w, self._prepare_mx(images.device), depth)
+        fold, N = self.fold_layernorm, images.shape[0]
+        x, st, rows = self._patch_stream(images, w, fold)
         del rows
-        for i in range(self.depth if depth is None else depth):
-            b = f"blocks.{i}"
-            linear_ln(x, st, f"{b}.norm1", f"{b}.attn.qkv", qkv, 3 * D, 0)
-            call("isic_attention_f16", qkv, att, N, T, H, D // H)
-            linear_res(att, f"{b}.attn.proj", x, x2, st2, D)
-            linear_ln(x2, st2, f"{b}.norm2", f"{b}.mlp.fc1", hid, self.mlp, 1)
-            linear_res(hid, f"{b}.mlp.fc2", x2, x, st, self.mlp)
-        out = torch.empty((M, D), device=dev, dtype=torch.float32)
-        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, 1e-6)
-        return out.view(N, T, D)
+        x, _ = blocks_forward(w, x, st, N, self.depth if depth is None else depth, self._spec(), fold=fold,
+                              layernorm=self._layernorm)
+        return self._final_norm(x, w, N)
 
     def _run_tokens_mx(self, images, w, wmx, depth):
         dev = images.device
-        x_in = images.float().contiguous()
-        N, T, D, H = x_in.shape[0], self.tokens, self.dim, self.heads
+        N, T, D, H = images.shape[0], self.tokens, self.dim, self.heads
         M = N * T
-        K0 = self.in_ch * self.patch * self.patch
         eps = 1e-6
         u8 = torch.uint8
-        rows = torch.empty((M, K0), device=dev, dtype=_F16)
-        call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
-        x = torch.empty((M, D), device=dev, dtype=_F16)
-        call("isic_gemm_f16", rows, w["patch_embed.proj.weight"], w["patch_embed.proj.bias"], w["pos_embed"], x, M, D, K0, 0, T)
+        x, _, rows = self._patch_stream(images, w, False)
         del rows
         hq, hs = torch.empty((M, D), device=dev, dtype=u8), torch.empty((M, D // 32), device=dev, dtype=u8)
         qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
@@ -303,9 +248,7 @@ class ViTSmallEncoder(nn.Module):
             call("isic_layernorm_mxfp8_f16", x2, w[f"{b}.norm2.weight"], w[f"{b}.norm2.bias"], hq, hs, M, D, eps)
             gemm(hq, hs, f"{b}.mlp.fc1", None, None, self.mlp, D, 1, midq, mids)
             gemm(midq, mids, f"{b}.mlp.fc2", x2, x, D, self.mlp, 0)
-        out = torch.empty((M, D), device=dev, dtype=torch.float32)
-        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, eps)
-        return out.view(N, T, D)
+        return self._final_norm(x, w, N)
 
     def forward_tokens(self, images):
         """tokens[N, 196, 384] fp32; differentiable (``transformer.EncoderFn``) when the encoder is trainable and grad is enabled."""
@@ -337,30 +280,17 @@ class ViTSmallEncoder(nn.Module):
 
     @staticmethod
     def _layernorm(x, gamma, beta, y, M, D, eps):
-        """``run_tokens``' LayerNorm pass (transformer.blocks_forward_train explains why it is handed in)."""
+        """The LayerNorm pass of this encoder's blocks (isic_hip/transformer.py explains why it is handed in)."""
         call("isic_layernorm_f16", x, gamma, beta, y, None, M, D, eps)
 
     def run_forward_train(self, images):
         """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
-        if images.dim() != 4 or images.shape[1] != self.in_ch or images.shape[2] != self.img_size or images.shape[3] != self.img_size:
-            raise ValueError(f"expected images[N,{self.in_ch},{self.img_size},{self.img_size}], got {tuple(images.shape)}")
-        if not images.is_cuda:
-            raise IsicHipError("ViTSmallEncoder runs on the MI355X only (no CPU fallback)")
-        dev = images.device
-        w = self._prepare_train(dev)
-        x_in = images.float().contiguous()
-        N, T, D = x_in.shape[0], self.tokens, self.dim
-        M = N * T
-        K0 = self.in_ch * self.patch * self.patch
-        rows = torch.empty((M, K0), device=dev, dtype=_F16)
-        call("isic_vit_patchify_f16", x_in, rows, N, self.in_ch, self.img_size, self.img_size, self.patch)
-        x = torch.empty((M, D), device=dev, dtype=_F16)
-        call("isic_gemm_f16", rows, w["patch_embed.proj.weight"], w["patch_embed.proj.bias"], w["pos_embed"], x, M, D, K0, 0, T)
-        x, blocks = blocks_forward_train(w, x, N, self.depth, self._spec(), layernorm=self._layernorm)
-        out = torch.empty((M, D), device=dev, dtype=torch.float32)
-        call("isic_layernorm_f16", x, w["norm.weight"], w["norm.bias"], None, out, M, D, 1e-6)
-        tape = dict(N=N, rows=rows, blocks=blocks, x=x, w=w)
-        return out.view(N, T, D), tape
+        self._check_images(images)
+        w = self._prepare_train(images.device)
+        N = images.shape[0]
+        x, _, rows = self._patch_stream(images, w, False)
+        x, blocks = blocks_forward(w, x, None, N, self.depth, self._spec(), save=True, layernorm=self._layernorm)
+        return self._final_norm(x, w, N), dict(N=N, rows=rows, blocks=blocks, x=x, w=w)
 
     def run_backward(self, tape, dtok):
         """Accumulates every parameter gradient into ``param.grad`` from d loss / d tokens[N, T, D]."""

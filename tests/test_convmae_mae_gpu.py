@@ -204,6 +204,21 @@ def test_ratio_zero_is_the_trainable_encoder():
     assert torch.equal(lat, tok) and not bool(mask.any()) and torch.equal(rest.cpu(), torch.arange(196).expand(2, 196))
 
 
+def test_forward_is_encoder_then_decoder_then_loss():
+    """forward() and the three public stages run the same launches: composed, they give forward()'s pred and loss bit for bit."""
+    img = _images(2, 4).to(DEV)
+    noise = torch.rand(2, 196, generator=torch.Generator().manual_seed(8)).to(DEV)
+    for norm_pix in (False, True):
+        m, _ = _model(2, norm_pix)
+        with torch.no_grad():
+            loss, pred, mask = m(img, mask_ratio=0.75, noise=noise)
+            lat, mask2, ids_restore = m.forward_encoder(img, 0.75, noise=noise)
+            pred2 = m.forward_decoder(lat, ids_restore)
+            loss2 = m.forward_loss(img, pred2, mask2)
+        assert math.isfinite(float(loss)) and float(loss) > 0
+        assert torch.equal(mask2, mask) and torch.equal(pred2, pred) and torch.equal(loss2, loss)
+
+
 def _grads_vs_ref(depth, dd, norm_pix, n, seed):
     import convmae_mae_ref as mr
     m, p = _model(seed, norm_pix)
