@@ -637,5 +637,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_convmae_train.h"
 /* The masked-autoencoder objective of ConvMAE-Base (masking, decoder unshuffle, reconstruction loss): same conventions. */
 #include "isic_hip_mae.h"
+/* The batch transform of the MAE fine-tune from a device-resident uint8 image pool: one more entry point, same conventions. */
+#include "isic_hip_augment.h"
 
 #endif /* ISIC_HIP_H */

@@ -13,6 +13,11 @@ What changes:
     (``isic_mask_patch_flags_f32``), and the per-patch Python double loop of ``build_patch_level_df`` (`:109-154`)
     replaced by array operations that produce the same rows in the same order.
 
+  * ``device_resize: true`` (opt-in) moves the resize off the CPU: the loader hands over the decoded uint8 arrays
+    (``isic_hip.augment.uint8_transform``), each batch is uploaded as a small ``ImagePool``, and ``isic_augment_u8`` with
+    identity parameters produces the normalised 224 x 224 images and the nearest-neighbour masks the patch flags are
+    computed from.  ``datasets`` must then yield uint8 arrays (``isic_hip.augment.SyntheticDermPixels``).
+
 ``extract_latents(config, path, remove_background=False, datasets=None)`` keeps the reference's signature and return
 tuple; ``datasets=(train_val_dataset, test_dataset)`` lets a caller hand in any dataset with the ``DermDataset`` dict
 contract (`dataset.py:45-56`) -- the synthetic one below when there are no image files.
@@ -96,6 +101,19 @@ def build_patch_level_df(latent_raw_df, remove=True):
     return df, (int(keep.sum()) if remove else 0)
 
 
+def _device_resized(loader, device):
+    """Batches of a loader that hands over lists of uint8 items -> the dict batches of the default path, image and mask made
+    on the device by one ``isic_augment_u8`` launch with identity parameters."""
+    from isic_hip import augment as ag
+    for items in loader:
+        pool = ag.ImagePool.from_arrays([(it["image"], it["mask"]) for it in items], device)
+        box, op = ag.identity_params(pool.hw_host)
+        images, masks = ag.augment(pool, torch.arange(len(pool)), box, op, size=224, mean=MEAN, std=STD)
+        yield {"image": images, "mask": masks, "target": torch.stack([torch.as_tensor(it["target"]) for it in items]),
+               "image_path": [it["image_path"] for it in items],
+               "segmentation_path": [it["segmentation_path"] for it in items]}
+
+
 def _extract_from_loader(encoder, loader, device):
     pooled_list, raw_list = [], []
     for batch in loader:
@@ -123,6 +141,7 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
     seed = config.get("seed", 42)
     np.random.seed(seed)
     torch.manual_seed(seed)
+    device_resize = bool(config.get("device_resize", False))
     if datasets is None:
         from dataset import DermDataset
         df_tv, df_te = pd.read_pickle(config["dir"]["df"]), pd.read_pickle(config["dir"]["df_test"])
@@ -134,8 +153,14 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
             m = torch.from_numpy(np.ascontiguousarray(mask)).float()[None, None]
             m = torch.nn.functional.interpolate(m, size=(224, 224), mode="nearest")[0, 0]
             return {"image": img, "mask": m}
+        if device_resize:
+            from isic_hip.augment import uint8_transform as transform
         datasets = (DermDataset(df_tv, radiomics=None, transform=transform), DermDataset(df_te, radiomics=None, transform=transform))
-    loaders = [DataLoader(d, batch_size=batch_size, shuffle=False) for d in datasets]
+    if device_resize:
+        loaders = [_device_resized(DataLoader(d, batch_size=batch_size, shuffle=False, collate_fn=list), device)
+                   for d in datasets]
+    else:
+        loaders = [DataLoader(d, batch_size=batch_size, shuffle=False) for d in datasets]
     precision = str(config.get("encoder_precision", "fp16")).lower()
     if precision not in ("fp16", "mxfp8"):
         raise ValueError(f"encoder_precision: 'fp16' or 'mxfp8', got {precision!r}")

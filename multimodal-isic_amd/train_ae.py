@@ -10,9 +10,23 @@ loads through ``model_path``.
 
 Config keys (``training_plan.parameters``; the committed config.yml has none of them, so these defaults apply):
 ``masking_ratio`` 0.75, ``eval_masking_ratio`` 0.75, ``norm_pix_loss`` False, ``batch_size`` 64, ``epochs`` 100,
-``fold`` 0, ``include_lesion_mask`` False (True raises: ``ConvMAEBase`` does not define ``lesion_mask``).
-``--synthetic`` trains on ``save_latent.SyntheticDermImages`` (no dataset needed).  Not ported: Neptune logging, the
-latent-space and reconstruction plots, the ISIC2019 CSV merge and ``concat_patch_moments``.
+``fold`` 0, ``include_lesion_mask`` False (True raises: ``ConvMAEBase`` does not define ``lesion_mask``),
+``device_augment`` False.  ``--synthetic`` trains on ``save_latent.SyntheticDermImages`` (no dataset needed).
+
+Augmentation.  The reference trains under ``RandomResizedCrop(224, scale=(0.5, 1.0), ratio=(0.75, 1.33))``, horizontal and
+vertical flips and ``RandomRotate90`` (each with probability 0.5), then ``Normalize`` (``train_ae.py:88-100``), and
+validates under ``Resize(224)``, ``Normalize`` (``:102-105``).  The default path here does NOT augment: it trains on the
+validation transform (decode, square crop, bilinear resize to 224 and normalise on the CPU, per image and per epoch), so
+every epoch sees the same pixels.  ``device_augment: true`` (``--device-augment``) is the reference's training
+distribution: the decoded uint8 images are uploaded once (``isic_hip.augment.ImagePool``), each step draws its images
+from the same class-balanced sampler and its crop / flip / rotation parameters from a generator seeded with ``seed``
+(``sample_params``), and one HIP launch (``isic_augment_u8``) produces the batch; validation batches come from the same
+launch with identity parameters.  The crop boxes follow RandomResizedCrop's algorithm, but albumentations' random
+stream cannot be reproduced, and its fixed-point uint8 resize is not pinned (include/isic_hip_augment.h).  With
+``--synthetic`` it trains on ``isic_hip.augment.SyntheticDermPixels``.
+
+Not ported: Neptune logging, the latent-space and reconstruction plots, the ISIC2019 CSV merge and
+``concat_patch_moments``; the colour augmentations the reference has commented out.
 """
 from __future__ import annotations
 
@@ -35,7 +49,7 @@ from isic_hip.convmae_mae import convmae_convvit_base_patch16_dec512d8b  # noqa:
 
 SPLITS = 10
 DEFAULTS = dict(masking_ratio=0.75, eval_masking_ratio=0.75, norm_pix_loss=False, batch_size=64, epochs=100, fold=0,
-                include_lesion_mask=False)
+                include_lesion_mask=False, device_augment=False)
 
 
 def plan(config):
@@ -65,9 +79,25 @@ def optimizers(model):
     return [optim.AdamW(enc, lr=1e-5, **kw), optim.AdamW(dec, lr=1e-3, **kw)]
 
 
-def train(config, dataset, labels, out_dir, checkpoint=None, log=print):
-    """-> (path of the saved best state, [(train_loss, val_loss) per epoch])."""
+def _chunks(ids, size):
+    return [ids[i:i + size] for i in range(0, len(ids), size)]
+
+
+def device_batches(pool, ids, batch_size, generator=None):
+    """Batches of ``pool`` images ``ids`` through ``isic_augment_u8``: augmented with parameters drawn from ``generator``, or
+    (``generator=None``) the plain resize to 224 x 224."""
+    from isic_hip import augment as ag
+    for chunk in _chunks(list(ids), batch_size):
+        hw = pool.hw_host[chunk]
+        box, op = ag.sample_params(hw, generator) if generator is not None else ag.identity_params(hw)
+        yield ag.augment(pool, chunk, box, op, want_mask=False)[0]
+
+
+def train(config, dataset, labels, out_dir, checkpoint=None, log=print, device_augment=False):
+    """-> (path of the saved best state, [(train_loss, val_loss) per epoch]).  With ``device_augment`` (or the config key
+    of that name) ``dataset`` yields uint8 arrays (``isic_hip.augment.uint8_transform`` / ``SyntheticDermPixels``)."""
     p = plan(config)
+    device_augment = bool(device_augment or p["device_augment"])
     if p["include_lesion_mask"]:
         raise ValueError("include_lesion_mask: the lesion_mask argument of the reference's MAE fork is undefined here")
     seed = int(config.get("seed", 42))
@@ -75,9 +105,21 @@ def train(config, dataset, labels, out_dir, checkpoint=None, log=print):
     np.random.seed(seed)
     torch.manual_seed(seed)
     tr, va = split(labels, int(p["fold"]), seed)
-    train_loader = DataLoader(Subset(dataset, tr.tolist()), batch_size=int(p["batch_size"]),
-                              sampler=balanced_sampler(np.asarray(labels)[tr]))
-    val_loader = DataLoader(Subset(dataset, va.tolist()), batch_size=64, shuffle=False)
+    if device_augment:
+        from isic_hip.augment import ImagePool
+        pool = ImagePool.from_dataset(dataset, device)                      # decoded once; every batch is one launch
+        sampler = balanced_sampler(np.asarray(labels)[tr])
+        params = torch.Generator().manual_seed(seed)
+        n_train, n_val = len(tr), len(va)
+        train_batches = lambda: device_batches(pool, [int(tr[i]) for i in sampler], int(p["batch_size"]), params)
+        val_batches = lambda: device_batches(pool, va.tolist(), 64)
+    else:
+        train_loader = DataLoader(Subset(dataset, tr.tolist()), batch_size=int(p["batch_size"]),
+                                  sampler=balanced_sampler(np.asarray(labels)[tr]))
+        val_loader = DataLoader(Subset(dataset, va.tolist()), batch_size=64, shuffle=False)
+        n_train, n_val = len(train_loader.dataset), len(val_loader.dataset)
+        train_batches = lambda: (batch["image"].to(device) for batch in train_loader)
+        val_batches = lambda: (batch["image"].to(device) for batch in val_loader)
     model = convmae_convvit_base_patch16_dec512d8b(norm_pix_loss=bool(p["norm_pix_loss"])).to(device)
     if checkpoint:
         sd = torch.load(checkpoint, map_location=device, weights_only=False)
@@ -87,24 +129,22 @@ def train(config, dataset, labels, out_dir, checkpoint=None, log=print):
     for epoch in range(int(p["epochs"])):
         model.train()
         run = 0.0
-        for batch in train_loader:
+        for images in train_batches():
             for o in opts:
                 o.zero_grad()
-            images = batch["image"].to(device)
             loss, _, _ = model(images, mask_ratio=float(p["masking_ratio"]))
             loss.backward()
             for o in opts:
                 o.step()
             run += float(loss) * images.shape[0]
-        train_loss = run / len(train_loader.dataset)
+        train_loss = run / n_train
         model.eval()
         run = 0.0
         with torch.no_grad():
-            for batch in val_loader:
-                images = batch["image"].to(device)
+            for images in val_batches():
                 loss, _, _ = model(images, mask_ratio=float(p["eval_masking_ratio"]))
                 run += float(loss) * images.shape[0]
-        val_loss = run / len(val_loader.dataset)
+        val_loss = run / n_val
         history.append((train_loss, val_loss))
         log(f"Epoch [{epoch + 1}/{p['epochs']}], Train Loss: {train_loss:.4f}, Val Loss: {val_loss:.4f}")
         if val_loss < best:
@@ -122,6 +162,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", default=os.path.join(HERE, "config.yml"))
     ap.add_argument("--synthetic", action="store_true", help="train on save_latent.SyntheticDermImages")
+    ap.add_argument("--device-augment", action="store_true",
+                    help="the reference's training augmentation, on the device from a resident uint8 pool")
     ap.add_argument("--n-images", type=int, default=256, help="synthetic images")
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
@@ -136,9 +178,13 @@ def main(argv=None):
         params["epochs"] = a.epochs
     if a.batch_size is not None:
         params["batch_size"] = a.batch_size
+    if a.device_augment:
+        params["device_augment"] = True
+    device_augment = bool(params.get("device_augment", False))
     if a.synthetic:
+        from isic_hip.augment import SyntheticDermPixels
         from save_latent import SyntheticDermImages
-        ds = SyntheticDermImages(n=a.n_images)
+        ds = (SyntheticDermPixels if device_augment else SyntheticDermImages)(n=a.n_images)
         labels = [i % ds.classes for i in range(len(ds))]
     else:
         import pandas as pd
@@ -152,6 +198,8 @@ def main(argv=None):
             img = (img - torch.tensor(MEAN).view(3, 1, 1)) / torch.tensor(STD).view(3, 1, 1)
             return {"image": img, "mask": torch.from_numpy(np.ascontiguousarray(mask)).float()}
 
+        if device_augment:
+            from isic_hip.augment import uint8_transform as transform
         ds = DermDataset(df, radiomics=None, transform=transform)
         labels = list(df["dx"])
     train(config, ds, labels, a.out_dir, checkpoint=a.checkpoint or None)
