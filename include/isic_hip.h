@@ -639,5 +639,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_mae.h"
 /* The batch transform of the MAE fine-tune from a device-resident uint8 image pool: one more entry point, same conventions. */
 #include "isic_hip_augment.h"
+/* ResNet-18 layer1: BatchNorm backward's apply pass formed inside the weight gradient: two more entry points, same conventions. */
+#include "isic_hip_wgrad_bnbwd.h"
 
 #endif /* ISIC_HIP_H */

@@ -281,6 +281,12 @@ WgradPlan wgrad_plan(int N, int Cin, int Hout, int Wout, int Cout, int Kh, int K
 size_t isic_wgrad_c64_workspace_bytes(int N, int H, int W);
 int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, void* workspace,
                           hipStream_t stream);
+// ... with dY formed on the way from the BatchNorm backward's operands (isic_conv2d_wgrad_bnbwd_bf16)
+int isic_wgrad_c64_bnbwd_launch(const uint16_t* x, const uint16_t* g, const uint16_t* c, const uint8_t* relu_mask,
+                                const float* mean, const float* rstd, const float* gamma, const double* dgamma,
+                                const double* dbeta, const float* scale, const float* shift, uint16_t* dc, float* dw,
+                                float* dgamma_f32, float* dbeta_f32, int N, int H, int W, void* workspace,
+                                hipStream_t stream);
 
 // ... of the 3x3 layers with Cin % 128 == 0, Cout % 64 == 0: 128, 256, 512 channels, 64 output channels per block
 // (conv_wgrad_c128b.hip)
@@ -325,6 +331,34 @@ int isic_conv2d_wgrad_bf16(const uint16_t* x, const uint16_t* dy, float* dw, int
                            size_t workspace_bytes, void* stream) {
   return conv2d_wgrad_dispatch(x, dy, dw, N, Hin, Win, Cin, Hout, Wout, Cout, Kh, Kw, stride, pad, workspace, workspace_bytes,
                                0, stream);
+}
+
+size_t isic_conv2d_wgrad_bnbwd_supported(int N, int H, int W, int Cin, int Cout, int Kh, int Kw, int stride, int pad,
+                                         int has_mask) {
+  (void)has_mask;                                          // both mask forms are built
+  if (N <= 0 || H <= 0 || W <= 0 || Cin != 64 || Cout != 64 || Kh != 3 || Kw != 3 || stride != 1 || pad != 1) return 0;
+  if ((int64_t)N * H * W * 64 > 0x7FFFFFFFLL || H >= 32768 || W >= 32768) return 0;      // the limits of isic_conv2d_wgrad_bf16
+  return isic_wgrad_c64_workspace_bytes(N, H, W) != 0 ? 1 : 0;
+}
+
+int isic_conv2d_wgrad_bnbwd_bf16(const uint16_t* x, const uint16_t* dz, const uint16_t* c, const uint8_t* relu_mask,
+                                 const float* mean, const float* rstd, const float* gamma, const double* sum_dz,
+                                 const double* sum_dzx, const float* scale, const float* shift, uint16_t* dc, float* dw,
+                                 float* dgamma_f32, float* dbeta_f32, int N, int H, int W, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  ISIC_CHECK_ARG(x && dz && c && mean && rstd && gamma && sum_dz && sum_dzx && dc && dw && workspace);
+  ISIC_CHECK_ARG(N > 0 && H > 0 && W > 0);
+  ISIC_CHECK_ARG((scale == nullptr) == (shift == nullptr));
+  ISIC_CHECK_ARG((dgamma_f32 == nullptr) == (dbeta_f32 == nullptr));
+  ISIC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0);
+  ISIC_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(c) |
+                   reinterpret_cast<uintptr_t>(dc)) & 15) == 0);
+  if (!relu_mask && !scale) return ISIC_ERR_UNSUPPORTED;   // no ReLU / mask from the output: the two-launch form
+  if (!isic_conv2d_wgrad_bnbwd_supported(N, H, W, 64, 64, 3, 3, 1, 1, relu_mask != nullptr)) return ISIC_ERR_UNSUPPORTED;
+  if (workspace_bytes < isic_wgrad_c64_workspace_bytes(N, H, W)) return ISIC_ERR_WORKSPACE;
+  const int rc = isic_wgrad_c64_bnbwd_launch(x, dz, c, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, scale, shift, dc, dw,
+                                             dgamma_f32, dbeta_f32, N, H, W, workspace, as_stream(stream));
+  return rc != ISIC_OK ? rc : isic_launch_status();
 }
 
 int isic_test_conv2d_wgrad_variant_bf16(const uint16_t* x, const uint16_t* dy, float* dw, int N, int Hin, int Win, int Cin,

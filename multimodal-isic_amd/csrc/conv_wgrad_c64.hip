@@ -14,8 +14,12 @@
 // the K axis (pixels) is the row axis of the NHWC images in LDS.
 // The partial gradients of the blocks go to the workspace with plain stores and are summed by a second kernel in
 // a fixed order: the result does not depend on the scheduling (no atomics).
+//
+// wgrad_c64_kernel<2> / <3> are the same kernel with the BatchNorm-backward apply pass folded into its staging waves: dY
+// does not exist yet, the staging waves form it from the incoming gradient and the convolution output (see BNBWD below).
 
 #include "common.h"
+#include "pool_grad.h"
 
 namespace {
 
@@ -38,6 +42,16 @@ struct WC64Args {
   int N, H, W, tiles_y, tiles_x, total_tiles, tiles_per_block;
 };
 
+// BNBWD: dY = kA * dz + (kB * c + kD) per channel, dz = relu_mask ? g : 0 (isic_bn_bwd_apply*_bf16, encoder_ops.hip)
+struct WC64BnArgs : WC64Args {        // dy = g, the gradient of the BatchNorm(+ReLU) output
+  const unsigned short* c;            // the BatchNorm input (this layer's raw convolution output)
+  const unsigned char* mask;          // MODE 3: one bit per element
+  const float *mean, *rstd, *gamma, *scale, *shift;   // scale, shift: MODE 2 (mask recomputed from c)
+  const double *dgamma, *dbeta;       // the reduced sums
+  unsigned short* dc;                 // dY is also written out (the data gradient reads it next)
+  float *dgamma_f32, *dbeta_f32;
+};
+
 __device__ __attribute__((aligned(256))) unsigned char g_wc64_zeros[2048];
 
 __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {   // see conv_wgrad.hip
@@ -46,6 +60,35 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {   /
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
+// Register loads the compiler must not count: its waits would drain the LDS-DMAs in flight beside them.  The data is
+// there after the counted wait of wc64_landed*, which names every destination.
+__device__ __forceinline__ u32x4 wc64_load16(const void* gsrc) {
+  u32x4 v;
+  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(gsrc) : "memory");
+  return v;
+}
+__device__ __forceinline__ unsigned wc64_load1(const void* gsrc) {
+  unsigned v;
+  asm volatile("global_load_ubyte %0, %1, off" : "=v"(v) : "v"(gsrc) : "memory");
+  return v;
+}
+template <int N>
+__device__ __forceinline__ void wc64_landed(u32x4 (&g)[4], u32x4 (&c)[4]) {
+  asm volatile("s_waitcnt vmcnt(%8)"
+               : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3])
+               : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wc64_landed(u32x4 (&g)[4], u32x4 (&c)[4], unsigned (&m)[4]) {
+  asm volatile("s_waitcnt vmcnt(%12)"
+               : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]),
+                 "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3])
+               : "n"(N) : "memory");
+}
+template <int V> struct WC64Int { static constexpr int value = V; };
+template <int MODE> struct WC64Mode { typedef WC64BnArgs Args; };
+template <> struct WC64Mode<0> { typedef WC64Args Args; };
+
 #ifdef WC64_STAMPS   // tests/probes: per tile clock before the wait, after the barrier, after the MFMAs (wave 0, 256 blocks x 64 tiles)
 __device__ unsigned long long g_wc64_stamps[256 * 64 * 4];
 #define WC64_STAMP(kk, k) do { if (threadIdx.x == 512 && blockIdx.x < 256 && (kk) < 64) g_wc64_stamps[(blockIdx.x * 64 + (kk)) * 4 + (k)] = clock64(); } while (0)
@@ -53,7 +96,10 @@ __device__ unsigned long long g_wc64_stamps[256 * 64 * 4];
 #define WC64_STAMP(kk, k) do { } while (0)
 #endif
 
-__global__ __launch_bounds__(768) void wgrad_c64_kernel(WC64Args a) {
+// MODE 0: dY is read (WC64Args).  MODE 2 / 3: dY is formed by the staging waves (WC64BnArgs), ReLU mask recomputed from
+// c * scale + shift / read from the 1-bit mask -- the modes of bn_bwd_apply_kernel.
+template <int MODE>
+__global__ __launch_bounds__(768) void wgrad_c64_kernel(typename WC64Mode<MODE>::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
@@ -111,6 +157,7 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(WC64Args a) {
           row_ok = (unsigned)(tl.y0 - 1 + j) < (unsigned)a.H; okc = okx; lanev = lane_p;
           dst = (unsigned)((j * XP + 8 * p) * 128);
         } else if (j < 10) {                           // dY row j - 6, block p
+          if constexpr (MODE != 0) continue;           // formed in registers instead: commit_dy below
           rowaddr = yrow + (unsigned long long)((j - 6) * W128);
           row_ok = (unsigned)(tl.y0 + j - 6) < (unsigned)a.H; okc = oky; lanev = lane_p;
           dst = (unsigned)(X_BYTES + ((j - 6) * 4 + p) * 1024);
@@ -128,6 +175,121 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(WC64Args a) {
         glds16(reinterpret_cast<const void*>(src), real ? sbase + dst : lds0 + SCRATCH);   // padding: zeros -> scratch
       }
     };
+    if constexpr (MODE != 0) {
+      // ------------------------------------------------------------- BNBWD: the four dY groups go through registers
+      // Each lane loads the 16 bytes of g and c (and its mask byte) the DMA would have copied, forms its 8 values of dY,
+      // writes them to the LDS slot the DMA filled and to global memory.  The lane's 8 channels never change.
+      // Order on the wave's memory queue (loads, stores and DMAs retire in issue order):
+      //   prologue  D(0) L(0) D(1) L(1) | wait L(0), commit 0 -> S(0)
+      //   step kk   barrier | D(kk+2) L(kk+2) | wait L(kk+1), commit kk+1 -> S(kk+1)
+      // D = the 8 X-patch DMAs, L = the NLD register loads, S = up to 4 dY stores.  When step kk waits, L(kk+1) is
+      // followed by S(kk), D(kk+2), L(kk+2): "at most 8 + NLD outstanding" retires L(kk+1) whether or not S(kk) was
+      // issued (a wave whose lanes are all outside the image skips it), and with it the older D(kk+1).  Tile kk+1 is
+      // then complete in LDS once its ds_writes are (lgkmcnt(0) before the barrier).  L(kk+2) stays in flight while
+      // tile kk+1 is committed; its registers are the set tile kk used.
+      constexpr int NLD = MODE == 3 ? 12 : 8;
+      const int cg = (int)((lane_p & 127u) >> 4);
+      float kA[8], kB[8], kD[8], sc[8], sh[8];
+      {
+        const float inv_rows = 1.f / (float)((int64_t)a.N * a.H * a.W);
+        if (blockIdx.x == 0 && p == 0 && a.dgamma_f32) {
+          a.dgamma_f32[lane] += (float)a.dgamma[lane];
+          a.dbeta_f32[lane] += (float)a.dbeta[lane];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {                 // bn_bwd_apply_kernel's constants, with the one contraction the
+#pragma clang fp contract(off)                        // compiler makes there written out (a * b - c * d has two)
+          const int c = cg * 8 + j;
+          const float mu = a.mean[c], rs = a.rstd[c], k1 = a.gamma[c] * rs;
+          const float k2 = (float)a.dbeta[c] * inv_rows, k3 = (float)a.dgamma[c] * inv_rows;
+          kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * __builtin_fmaf(k3 * rs, mu, -k2);
+          sc[j] = MODE == 2 ? a.scale[c] : 0.f; sh[j] = MODE == 2 ? a.shift[c] : 0.f;
+        }
+        // the constants are in registers before the first DMA: the compiler's own wait for their loads (it counts only
+        // those) would otherwise fall into the pipeline and drain it
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(kA[j]), "+v"(kB[j]), "+v"(kD[j]), "+v"(sc[j]), "+v"(sh[j]));
+      }
+      u32x4 rg[2][4], rc[2][4];
+      unsigned rm[2][4];
+      // byte offset of the lane's 16 bytes of row j of the tile (the source the DMA used), validity of the pixel
+      auto dy_off = [&](const Tile& tl, int j, bool& ok) -> long long {
+        ok = (unsigned)(tl.x0 + 8 * p + r8) < (unsigned)a.W && (unsigned)(tl.y0 + j) < (unsigned)a.H;
+        return ((((long long)tl.n * a.H + tl.y0 + j) * a.W + tl.x0 + 8 * p) << 7) + (long long)lane_p;
+      };
+      auto load_dy = [&](const Tile& tl, bool live, auto SET) {
+        constexpr int S = decltype(SET)::value;
+#pragma unroll
+        for (int j = 0; j < WT_H; ++j) {
+          bool ok;
+          const long long off = dy_off(tl, j, ok);
+          ok = ok && live;                             // out-of-image lanes read the zero page: the count stays fixed
+          const unsigned char* zp = g_wc64_zeros + lane_p;
+          rg[S][j] = wc64_load16(ok ? reinterpret_cast<const unsigned char*>(a.dy) + off : zp);
+          rc[S][j] = wc64_load16(ok ? reinterpret_cast<const unsigned char*>(a.c) + off : zp);
+          if constexpr (MODE == 3) rm[S][j] = wc64_load1(ok ? a.mask + (off >> 4) : zp);
+        }
+      };
+      auto commit_dy = [&](const Tile& tl, int stage, auto SET) {
+        constexpr int S = decltype(SET)::value;
+        if constexpr (MODE == 3) wc64_landed<8 + NLD>(rg[S], rc[S], rm[S]);
+        else wc64_landed<8 + NLD>(rg[S], rc[S]);
+        const unsigned sdy = lds0 + (unsigned)stage * STAGE + (unsigned)(X_BYTES + p * 1024 + lane * 16);
+#pragma unroll
+        for (int j = 0; j < WT_H; ++j) {
+          bool ok;
+          const long long off = dy_off(tl, j, ok);
+          float g[8], xv[8], yv[8], o[8];
+          isic_pool::unpack8(rg[S][j], g);
+          isic_pool::unpack8(rc[S][j], xv);
+          if constexpr (MODE == 2) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) yv[e] = __builtin_fmaf(xv[e], sc[e], sh[e]);
+          } else {
+            const unsigned m = rm[S][j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) yv[e] = ((m >> e) & 1u) ? 1.f : 0.f;
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
+            o[e] = __builtin_fmaf(kA[e], dz, __builtin_fmaf(kB[e], xv[e], kD[e]));   // the apply pass's two FMAs
+          }
+          u32x4 v = isic_pool::pack8(o);
+          if (!ok) v = (u32x4){0u, 0u, 0u, 0u};       // padding pixels are zeros in LDS, as the DMA left them
+          *(__attribute__((address_space(3))) u32x4*)(size_t)(sdy + (unsigned)(j * 4 * 1024)) = v;
+          if (ok) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(a.dc) + off));
+        }
+      };
+      Tile next = ahead;                               // the tile committed next
+      issue_tile(ahead, 0, true);
+      load_dy(ahead, true, WC64Int<0>());
+      advance(ahead);
+      issue_tile(ahead, 1, ntl > 1);
+      load_dy(ahead, ntl > 1, WC64Int<1>());
+      advance(ahead);
+      commit_dy(next, 0, WC64Int<0>());
+      advance(next);
+      auto step = [&](int kk, auto SET) {             // SET: register set of tile kk (free), the other holds tile kk+1
+        constexpr int S = decltype(SET)::value;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's part of tile kk is in LDS
+        __builtin_amdgcn_s_barrier();                 // the MFMA waves are done with stage (kk+2)%3 = (kk-1)%3
+        issue_tile(ahead, (kk + 2) % NSTAGE, kk + 2 < ntl);
+        load_dy(ahead, kk + 2 < ntl, WC64Int<S>());
+        advance(ahead);
+        if (kk + 1 < ntl) {
+          commit_dy(next, (kk + 1) % NSTAGE, WC64Int<S ^ 1>());
+          advance(next);
+        }
+      };
+      for (int kk = 0; kk < ntl; kk += 2) {
+        step(kk, WC64Int<0>());
+        if (kk + 1 >= ntl) break;
+        step(kk + 1, WC64Int<1>());
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // nothing of this wave is in flight when it ends
+      return;
+    }
     issue_tile(ahead, 0, true);
     advance(ahead);
     issue_tile(ahead, 1, ntl > 1);
@@ -279,11 +441,40 @@ int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int 
   const int grid = wc64_blocks(N, H, W, &a.tiles_per_block);
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c64_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   LDS_TOTAL);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(wgrad_c64_kernel, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  hipLaunchKernelGGL(wgrad_c64_kernel<0>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  hipLaunchKernelGGL(wgrad_c64_reduce_kernel, dim3(DW_ELEMS / 64), dim3(256), 0, stream, a.partial, dw, grid);
+  return ISIC_OK;
+}
+
+// called by isic_conv2d_wgrad_bnbwd_bf16: the same launch with dY = BatchNorm backward of (g, c) formed on the way
+// (relu_mask given: its bits are the ReLU mask; otherwise it is recomputed from c * scale + shift); dY is also left in dc
+int isic_wgrad_c64_bnbwd_launch(const uint16_t* x, const uint16_t* g, const uint16_t* c, const uint8_t* relu_mask,
+                                const float* mean, const float* rstd, const float* gamma, const double* dgamma,
+                                const double* dbeta, const float* scale, const float* shift, uint16_t* dc, float* dw,
+                                float* dgamma_f32, float* dbeta_f32, int N, int H, int W, void* workspace,
+                                hipStream_t stream) {
+  WC64BnArgs a;
+  a.x = x; a.dy = g; a.partial = reinterpret_cast<float*>(workspace);
+  a.N = N; a.H = H; a.W = W;
+  a.tiles_y = ceil_div(H, WT_H); a.tiles_x = ceil_div(W, WT_W);
+  a.total_tiles = N * a.tiles_y * a.tiles_x;
+  a.c = c; a.mask = relu_mask; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.scale = scale; a.shift = shift;
+  a.dgamma = dgamma; a.dbeta = dbeta; a.dc = dc; a.dgamma_f32 = dgamma_f32; a.dbeta_f32 = dbeta_f32;
+  const int grid = wc64_blocks(N, H, W, &a.tiles_per_block);
+  static IsicPerDeviceOnce once[2];
+  const int m = relu_mask ? 1 : 0;
+  if (isic_once_per_device(once[m], [m] {
+        return hipFuncSetAttribute(m ? reinterpret_cast<const void*>(wgrad_c64_kernel<3>)
+                                     : reinterpret_cast<const void*>(wgrad_c64_kernel<2>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+      }) != hipSuccess)
+    return ISIC_ERR_LAUNCH;
+  if (m) hipLaunchKernelGGL(wgrad_c64_kernel<3>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  else hipLaunchKernelGGL(wgrad_c64_kernel<2>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
   hipLaunchKernelGGL(wgrad_c64_reduce_kernel, dim3(DW_ELEMS / 64), dim3(256), 0, stream, a.partial, dw, grid);
   return ISIC_OK;
 }

@@ -100,7 +100,11 @@ class ResNet18Encoder(nn.Module):
         # downsample blocks: both stride-2 data gradients in one launch (A/B attribute; one bf16 rounding less than two launches)
         self.pair_downsample_gradient = True
         self.fold_shortcut_norm = True      # downsample blocks: the shortcut's BatchNorm output is not materialised (training)
+        # layer1 (64 -> 64): BatchNorm backward's apply pass inside the weight gradient that consumes its output
+        # (isic_conv2d_wgrad_bnbwd_bf16: bit-identical, one pass over two tensors and one launch less per convolution)
+        self.fuse_bn_apply_wgrad = True
         self._tape_fused = False      # fusion mode of the tape being replayed (recorded at forward time)
+        self._tape_apply_wgrad = False
         self.grad_ready_hook = None   # callable(list_of_param_names) fired as gradients complete (DDP overlap)
 
     # parameters are registered under dotted torchvision names via nested holder modules
@@ -397,6 +401,40 @@ class ResNet18Encoder(nn.Module):
              dres, self._grad_buffer(gamma), self._grad_buffer(beta))
         return dx, dres
 
+    def _bn_bwd_wgrad(self, dy, c, st, name, x, conv, mask_from_x=False):
+        """``_bn_bwd`` (with ReLU, no residual gradient) and ``_conv_wgrad(x, dc, conv)`` of the convolution ``conv`` that
+        made ``c`` from ``x``, the apply pass formed inside the weight-gradient kernel.  Returns dc, or None when the two
+        launches have to run: the weight gradients are on the side stream (dc is needed on this one), the tape was not
+        recorded for it, or no fused kernel serves the layer."""
+        if not self._tape_apply_wgrad or self.wgrad_stream:
+            return None
+        mean, rstd, scale, shift = st[:4]
+        mask = st[4] if (len(st) > 4 and not mask_from_x) else None
+        if mask is None and not mask_from_x:
+            return None
+        sp = self.specs[conv]
+        N, H, W, C = c.shape
+        if tuple(x.shape) != tuple(c.shape) or not call("isic_conv2d_wgrad_bnbwd_supported", N, H, W, sp.cin, sp.cout, sp.k,
+                                                        sp.k, sp.stride, sp.pad, int(mask is not None)):
+            return None
+        p = self._get(conv + ".weight")
+        gw = self._grad_buffer(p)
+        if not gw.is_contiguous(memory_format=torch.channels_last):
+            raise IsicHipError(f"{conv}.weight.grad must be channels_last ([O][Kh][Kw][I] memory)")
+        gamma, beta = self._get(name + ".weight"), self._get(name + ".bias")
+        rows = N * H * W
+        acc = self._zeros64((2, C), c.device)
+        if mask is not None:
+            call("isic_bn_bwd_reduce_mask_bf16", dy, c, mask, mean, rstd, rows, C, acc[0], acc[1])
+            scale = shift = None
+        else:
+            call("isic_bn_bwd_reduce_bf16", dy, c, None, mean, rstd, rows, C, 1, scale, shift, acc[0], acc[1])
+        dc = _empty(c.shape, c)
+        ws = self._workspace(call("isic_conv2d_wgrad_workspace_bytes", N, C, H, W, C, sp.k, sp.k), c.device)
+        call("isic_conv2d_wgrad_bnbwd_bf16", x, dy, c, mask, mean, rstd, gamma.data, acc[1], acc[0], scale, shift, dc, gw,
+             self._grad_buffer(gamma), self._grad_buffer(beta), N, H, W, ws, ws.numel())
+        return dc
+
     def _fire(self, names):
         if self.grad_ready_hook is not None:
             # the hook hands gradients to the collective stream, which waits for the stream it is called on:
@@ -458,20 +496,27 @@ class ResNet18Encoder(nn.Module):
                        and self._maskadd_ok(c1.shape, f"{pre}.conv1", tuple(x.shape)))
         if g_sums is not None:
             dc2, dres = self._bn_bwd_from_sums(g, c2, st2, f"{pre}.bn2", g_sums), g      # the residual gradient IS dz
+            self._conv_wgrad(a1, dc2, f"{pre}.conv2")
         else:
-            dc2, dres = self._bn_bwd(g, c2, out, st2, f"{pre}.bn2", True, not masked_join)
-        self._conv_wgrad(a1, dc2, f"{pre}.conv2")
+            dc2 = self._bn_bwd_wgrad(g, c2, st2, f"{pre}.bn2", a1, f"{pre}.conv2") if masked_join else None
+            dres = None
+            if dc2 is None:
+                dc2, dres = self._bn_bwd(g, c2, out, st2, f"{pre}.bn2", True, not masked_join)
+                self._conv_wgrad(a1, dc2, f"{pre}.conv2")
         if len(st1) > 4 and self._dgrad_bnbwd_ok(dc2.shape, f"{pre}.conv2", tuple(a1.shape)):
             dz1, sums1 = self._conv_dgrad_bnbwd(dc2, f"{pre}.conv2", tuple(a1.shape), st1[4], c1)
             del dc2
             dc1 = self._bn_bwd_from_sums(dz1, c1, st1, f"{pre}.bn1", sums1)
             del dz1
+            self._conv_wgrad(x, dc1, f"{pre}.conv1")
         else:
             da1 = self._conv_dgrad(dc2, f"{pre}.conv2", tuple(a1.shape))
             del dc2
-            dc1, _ = self._bn_bwd(da1, c1, a1, st1, f"{pre}.bn1", True, False, mask_from_x=True)
+            dc1 = self._bn_bwd_wgrad(da1, c1, st1, f"{pre}.bn1", x, f"{pre}.conv1", mask_from_x=True)
+            if dc1 is None:
+                dc1, _ = self._bn_bwd(da1, c1, a1, st1, f"{pre}.bn1", True, False, mask_from_x=True)
+                self._conv_wgrad(x, dc1, f"{pre}.conv1")
             del da1
-        self._conv_wgrad(x, dc1, f"{pre}.conv1")
         names = [f"{pre}.conv2.weight", f"{pre}.bn2.weight", f"{pre}.bn2.bias", f"{pre}.conv1.weight",
                  f"{pre}.bn1.weight", f"{pre}.bn1.bias"]
         dx_sums = None
@@ -513,7 +558,8 @@ class ResNet18Encoder(nn.Module):
         csel = _empty((N, Hp, Wp, 64), c) if save else None    # raw stem output at each window's argmax (bn1 backward sums)
         call("isic_bn_relu_maxpool3x3s2_fwd_sel_bf16", c, st0[2], st0[3], p, am, csel, N, Ho, Wo, 64, Hp, Wp)
         tape = {"x0": x0, "stem": (c, st0, am, csel, (N, Ho, Wo, 64)), "blocks": [],
-                "fused_bn_backward": bool(self.fuse_bn_backward)} if save else None
+                "fused_bn_backward": bool(self.fuse_bn_backward),
+                "fused_bn_apply_wgrad": bool(self.fuse_bn_apply_wgrad)} if save else None
         x = p
         for pre, ds in self.blocks:
             x, saved = self.block_forward(x, pre, ds)
@@ -565,6 +611,7 @@ class ResNet18Encoder(nn.Module):
             raise IsicHipError("encoder backward needs train() mode (batch-statistics BatchNorm)")
         N, Hf, Wf, Cf = tape["final_shape"]
         self._tape_fused = bool(tape.get("fused_bn_backward", False))
+        self._tape_apply_wgrad = bool(tape.get("fused_bn_apply_wgrad", False))
         self._arena_reset(dfeat.device)
         g = torch.empty((N, Hf, Wf, Cf), device=dfeat.device, dtype=_BF16)
         call("isic_avgpool_bwd_bf16", dfeat.float().contiguous(), g, N, Hf * Wf, Cf)
