@@ -641,5 +641,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_augment.h"
 /* ResNet-18 layer1: BatchNorm backward's apply pass formed inside the weight gradient: two more entry points, same conventions. */
 #include "isic_hip_wgrad_bnbwd.h"
+/* ResNet-18 downsample blocks: BatchNorm backward of bn2 and of the shortcut's norm in one reduce and one apply pass: two more entry points, same conventions. */
+#include "isic_hip_bn_pair.h"
 
 #endif /* ISIC_HIP_H */

@@ -309,6 +309,104 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   }
 }
 
+// ---------------------------------------------------------------- downsample block: bn2 and the shortcut's BatchNorm together
+// Both norms of a downsample block receive the same gradient dz = mask ? dy : 0 (out = relu(bn2(c2) + bn_d(cd))).  The pair
+// kernels are bn_bwd_reduce_kernel<3> + bn_bwd_reduce_kernel<0> and bn_bwd_apply_kernel<3> + bn_bwd_apply_kernel<0> in one
+// walk each: same launch geometry, same thread -> (row, channel group) mapping, same expressions in the same order, so
+// every partial sum and every output is the value those launches give -- and dz is never written out and read back.
+__global__ __launch_bounds__(256) void bn_bwd_reduce_pair_kernel(const unsigned short* __restrict__ dy,
+                                                                  const unsigned short* __restrict__ x,
+                                                                  const unsigned char* __restrict__ relu_mask,
+                                                                  const float* __restrict__ mean,
+                                                                  const float* __restrict__ rstd,
+                                                                  const unsigned short* __restrict__ x2,
+                                                                  const float* __restrict__ mean2,
+                                                                  const float* __restrict__ rstd2, int64_t rows, int C,
+                                                                  double* __restrict__ sum_dzx, double* __restrict__ sum_dz,
+                                                                  double* __restrict__ sum_dzx2) {
+  const int tid = threadIdx.x, cgs = C >> 3, cg = tid % cgs, rl = tid / cgs, rls = 256 / cgs;
+  float acc[3][8], mu[8], rs[8], mu2[8], rs2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    acc[0][j] = 0.f; acc[1][j] = 0.f; acc[2][j] = 0.f;
+    mu[j] = mean[cg * 8 + j]; rs[j] = rstd[cg * 8 + j]; mu2[j] = mean2[cg * 8 + j]; rs2[j] = rstd2[cg * 8 + j];
+  }
+  const int64_t per_block = ((rows + gridDim.x - 1) / gridDim.x + rls - 1) / rls * rls;   // contiguous rows: bn_bwd_reduce_kernel
+  const int64_t r_end = min(rows, ((int64_t)blockIdx.x + 1) * per_block);
+#pragma unroll 2
+  for (int64_t r = (int64_t)blockIdx.x * per_block + rl; r < r_end; r += rls) {
+    float g[8], xv[8], x2v[8];
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + r * C + cg * 8)), g);
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + r * C + cg * 8)), xv);
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + r * C + cg * 8)), x2v);
+    const unsigned m = relu_mask[r * (C >> 3) + cg];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float dz = ((m >> j) & 1u) ? g[j] : 0.f;
+      // fmaf spelled out: the kernels this replaces compile to one fused multiply-add per term, and a bit-identical sum
+      // must not depend on the compiler contracting every one of these the same way
+      acc[0][j] = fmaf(dz, (xv[j] - mu[j]) * rs[j], acc[0][j]);
+      acc[1][j] += dz;
+      acc[2][j] = fmaf(dz, (x2v[j] - mu2[j]) * rs2[j], acc[2][j]);
+    }
+  }
+  double* const dst[3] = {sum_dzx, sum_dz, sum_dzx2};
+  block_reduce_to_global<3>(acc, C, dst);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(
+    const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x, const unsigned char* __restrict__ relu_mask,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const double* __restrict__ sum_dzx, const double* __restrict__ sum_dz, const unsigned short* __restrict__ x2,
+    const float* __restrict__ mean2, const float* __restrict__ rstd2, const float* __restrict__ gamma2,
+    const double* __restrict__ sum_dzx2, int64_t rows, int C, unsigned short* __restrict__ dx,
+    unsigned short* __restrict__ dx2, float* __restrict__ dgamma_f32, float* __restrict__ dbeta_f32,
+    float* __restrict__ dgamma2_f32, float* __restrict__ dbeta2_f32) {
+  const int cgs = C >> 3;
+  const int64_t nvec = rows * cgs;
+  const float inv_rows = 1.f / (float)rows;
+  if (blockIdx.x == 0) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      if (dgamma_f32) { dgamma_f32[c] += (float)sum_dzx[c]; dbeta_f32[c] += (float)sum_dz[c]; }
+      if (dgamma2_f32) { dgamma2_f32[c] += (float)sum_dzx2[c]; dbeta2_f32[c] += (float)sum_dz[c]; }
+    }
+  }
+  const int cg = threadIdx.x % cgs;
+  float kA[8], kB[8], kD[8], kA2[8], kB2[8], kD2[8];      // as in bn_bwd_apply_kernel, once per norm; sum dz is shared
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = cg * 8 + j;
+    const float k2 = (float)sum_dz[c] * inv_rows;
+    {
+      const float mu = mean[c], rs = rstd[c], k1 = gamma[c] * rs, k3 = (float)sum_dzx[c] * inv_rows;
+      kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * fmaf(k3 * rs, mu, -k2);       // fmaf: see bn_bwd_reduce_pair_kernel
+    }
+    {
+      const float mu = mean2[c], rs = rstd2[c], k1 = gamma2[c] * rs, k3 = (float)sum_dzx2[c] * inv_rows;
+      kA2[j] = k1; kB2[j] = -k1 * k3 * rs; kD2[j] = k1 * fmaf(k3 * rs, mu, -k2);
+    }
+  }
+  const int64_t base = (int64_t)blockIdx.x * (256 * FLAT_BWD) + threadIdx.x;     // flat: see bn_apply_kernel
+#pragma unroll
+  for (int u = 0; u < FLAT_BWD; ++u) {
+    const int64_t i = base + u * 256;
+    if (i >= nvec) break;
+    float g[8], xv[8], x2v[8], o[8], o2[8];
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + i * 8)), g);
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8)), xv);
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + i * 8)), x2v);
+    const unsigned m = relu_mask[i];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float dz = ((m >> j) & 1u) ? g[j] : 0.f;
+      o[j] = fmaf(kA[j], dz, fmaf(kB[j], xv[j], kD[j]));
+      o2[j] = fmaf(kA2[j], dz, fmaf(kB2[j], x2v[j], kD2[j]));
+    }
+    __builtin_nontemporal_store(pack8(o), reinterpret_cast<u32x4*>(dx + i * 8));
+    __builtin_nontemporal_store(pack8(o2), reinterpret_cast<u32x4*>(dx2 + i * 8));
+  }
+}
+
 // ---------------------------------------------------------------- stem: BatchNorm backward fed by the pooled gradient
 // The gradient of the stem activation is the 3x3/2 max-pool backward of the pooled gradient gp through argmax; it is
 // not materialised.  A thread owns the 2x2 input pixels (2a+dy, 2b+dx) of one 8-channel group: they are covered by the
@@ -789,6 +887,34 @@ int isic_bn_bwd_apply_mask_bf16(const uint16_t* dy, const uint16_t* x, const uin
   hipLaunchKernelGGL(bn_bwd_apply_kernel<3>, dim3(grid_for(nvec, 256 * FLAT_BWD, STREAM_CAP)), dim3(256), 0, as_stream(stream), dy, x, nullptr,
                      relu_mask, mean, rstd, gamma, dgamma, dbeta, rows, C, 1, nullptr, nullptr, dx, d_residual, dgamma_f32,
                      dbeta_f32);
+  return isic_launch_status();
+}
+
+int isic_bn_bwd_reduce_pair_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
+                                 const float* rstd, const uint16_t* x2, const float* mean2, const float* rstd2, int64_t rows,
+                                 int C, double* sum_dzx, double* sum_dz, double* sum_dzx2, void* stream) {
+  ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && x2 && mean2 && rstd2 && sum_dzx && sum_dz && sum_dzx2 && rows > 0 &&
+                 C > 0);
+  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;
+  const int rls = 256 / (C / 8);
+  hipLaunchKernelGGL(bn_bwd_reduce_pair_kernel, dim3(grid_for(rows, rls * 8, 2048)), dim3(256), 0, as_stream(stream), dy, x,
+                     relu_mask, mean, rstd, x2, mean2, rstd2, rows, C, sum_dzx, sum_dz, sum_dzx2);
+  return isic_launch_status();
+}
+
+int isic_bn_bwd_apply_pair_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
+                                const float* rstd, const float* gamma, const double* sum_dzx, const double* sum_dz,
+                                const uint16_t* x2, const float* mean2, const float* rstd2, const float* gamma2,
+                                const double* sum_dzx2, int64_t rows, int C, uint16_t* dx, uint16_t* dx2, float* dgamma_f32,
+                                float* dbeta_f32, float* dgamma2_f32, float* dbeta2_f32, void* stream) {
+  ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && gamma && sum_dzx && sum_dz && x2 && mean2 && rstd2 && gamma2 &&
+                 sum_dzx2 && dx && dx2 && rows > 0 && C > 0 && C % 8 == 0);
+  ISIC_CHECK_ARG((dgamma_f32 == nullptr) == (dbeta_f32 == nullptr) && (dgamma2_f32 == nullptr) == (dbeta2_f32 == nullptr));
+  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
+  const int64_t nvec = rows * (C / 8);
+  hipLaunchKernelGGL(bn_bwd_apply_pair_kernel, dim3(grid_for(nvec, 256 * FLAT_BWD, STREAM_CAP)), dim3(256), 0,
+                     as_stream(stream), dy, x, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, x2, mean2, rstd2, gamma2, sum_dzx2,
+                     rows, C, dx, dx2, dgamma_f32, dbeta_f32, dgamma2_f32, dbeta2_f32);
   return isic_launch_status();
 }
 

@@ -100,6 +100,7 @@ class ResNet18Encoder(nn.Module):
         # downsample blocks: both stride-2 data gradients in one launch (A/B attribute; one bf16 rounding less than two launches)
         self.pair_downsample_gradient = True
         self.fold_shortcut_norm = True      # downsample blocks: the shortcut's BatchNorm output is not materialised (training)
+        self.pair_shortcut_norm_backward = True   # downsample blocks: bn2 and the shortcut norm go backward in one reduce + one apply pass (bit-identical; A/B attribute)
         # layer1 (64 -> 64): BatchNorm backward's apply pass inside the weight gradient that consumes its output
         # (isic_conv2d_wgrad_bnbwd_bf16: bit-identical, one pass over two tensors and one launch less per convolution)
         self.fuse_bn_apply_wgrad = True
@@ -401,6 +402,28 @@ class ResNet18Encoder(nn.Module):
              dres, self._grad_buffer(gamma), self._grad_buffer(beta))
         return dx, dres
 
+    def _bn_bwd_pair(self, g, c2, st2, name2, cd, std, named):
+        """BatchNorm backward of a downsample block's bn2 (ReLU mask bits in ``st2``) and of its shortcut's norm, which
+        receive the same gradient: one reduce and one apply pass over (g, mask, c2, cd) instead of two each with the masked
+        gradient written out in between.  Returns (dc2, dcd), or None when the entry does not serve the channel count."""
+        N, H, W, C = c2.shape
+        rows = N * H * W
+        gamma2, beta2 = self._get(name2 + ".weight"), self._get(name2 + ".bias")
+        gammad, betad = self._get(named + ".weight"), self._get(named + ".bias")
+        acc = self._zeros64((3, C), c2.device)              # sum dz * xhat(c2), sum dz, sum dz * xhat(cd)
+        try:
+            call("isic_bn_bwd_reduce_pair_bf16", g, c2, st2[4], st2[0], st2[1], cd, std[0], std[1], rows, C, acc[0], acc[1],
+                 acc[2])
+        except IsicHipError as e:
+            if e.code != ERR_UNSUPPORTED:
+                raise
+            return None
+        dc2, dcd = _empty(c2.shape, c2), _empty(cd.shape, cd)
+        call("isic_bn_bwd_apply_pair_bf16", g, c2, st2[4], st2[0], st2[1], gamma2.data, acc[0], acc[1], cd, std[0], std[1],
+             gammad.data, acc[2], rows, C, dc2, dcd, self._grad_buffer(gamma2), self._grad_buffer(beta2),
+             self._grad_buffer(gammad), self._grad_buffer(betad))
+        return dc2, dcd
+
     def _bn_bwd_wgrad(self, dy, c, st, name, x, conv, mask_from_x=False):
         """``_bn_bwd`` (with ReLU, no residual gradient) and ``_conv_wgrad(x, dc, conv)`` of the convolution ``conv`` that
         made ``c`` from ``x``, the apply pass formed inside the weight-gradient kernel.  Returns dc, or None when the two
@@ -494,6 +517,7 @@ class ResNet18Encoder(nn.Module):
         masked_join = (self.mask_identity_gradient and not ds and g_sums is None and len(st2) > 4 and
                        not (prev is not None and len(prev[6]) > 4 and self._dgrad_bnbwd_ok(c1.shape, f"{pre}.conv1", tuple(x.shape)))
                        and self._maskadd_ok(c1.shape, f"{pre}.conv1", tuple(x.shape)))
+        dcd = None                    # downsample block: the shortcut norm's backward, when bn2's pass formed it as well
         if g_sums is not None:
             dc2, dres = self._bn_bwd_from_sums(g, c2, st2, f"{pre}.bn2", g_sums), g      # the residual gradient IS dz
             self._conv_wgrad(a1, dc2, f"{pre}.conv2")
@@ -501,7 +525,12 @@ class ResNet18Encoder(nn.Module):
             dc2 = self._bn_bwd_wgrad(g, c2, st2, f"{pre}.bn2", a1, f"{pre}.conv2") if masked_join else None
             dres = None
             if dc2 is None:
-                dc2, dres = self._bn_bwd(g, c2, out, st2, f"{pre}.bn2", True, not masked_join)
+                pair = (self._bn_bwd_pair(g, c2, st2, f"{pre}.bn2", cd, std, f"{pre}.downsample.1")
+                        if ds and self.pair_shortcut_norm_backward and len(st2) > 4 else None)
+                if pair is not None:
+                    dc2, dcd = pair
+                else:
+                    dc2, dres = self._bn_bwd(g, c2, out, st2, f"{pre}.bn2", True, not masked_join)
                 self._conv_wgrad(a1, dc2, f"{pre}.conv2")
         if len(st1) > 4 and self._dgrad_bnbwd_ok(dc2.shape, f"{pre}.conv2", tuple(a1.shape)):
             dz1, sums1 = self._conv_dgrad_bnbwd(dc2, f"{pre}.conv2", tuple(a1.shape), st1[4], c1)
@@ -521,7 +550,8 @@ class ResNet18Encoder(nn.Module):
                  f"{pre}.bn1.weight", f"{pre}.bn1.bias"]
         dx_sums = None
         if ds:
-            dcd, _ = self._bn_bwd(dres, cd, None, std, f"{pre}.downsample.1", False, False)
+            if dcd is None:
+                dcd, _ = self._bn_bwd(dres, cd, None, std, f"{pre}.downsample.1", False, False)
             self._conv_wgrad(x, dcd, f"{pre}.downsample.0")
             dx = self._conv_dgrad_pair(dc1, f"{pre}.conv1", dcd, f"{pre}.downsample.0", tuple(x.shape))
             names += [f"{pre}.downsample.0.weight", f"{pre}.downsample.1.weight", f"{pre}.downsample.1.bias"]
