@@ -14,6 +14,7 @@
 // XOR-swizzled 128-byte LDS rows written lane-linearly by the DMA, D[co][pixel] accumulators).
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -39,16 +40,6 @@ struct C64Args {
 };
 
 __device__ __attribute__((aligned(256))) unsigned char g_c64_zero_page[256];
-
-__device__ __forceinline__ float bfb(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
-
-// 16-byte-per-lane LDS-DMA in inline asm (see conv_wgrad.hip): keeps the loads out of hipcc's vmcnt bookkeeping,
-// the tap loop below counts them itself.  M0 (the DMA's LDS base) is saved and restored inside the statement.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 #ifdef C64_STAMPS   // tests/probes/probe_c64_stamps.hip: per-block phase timestamps
 __device__ unsigned long long g_c64_stamps[8192 * 4];
@@ -85,14 +76,14 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(C64Args a) {
     const int yy = y0 - 1 + py, xx = x0 - 1 + px;
     const bool ok = pp < PPIX && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
     const void* src = ok ? (const void*)(a.in + (((size_t)n * a.H + yy) * a.W + xx) * 64 + gch * 8) : (const void*)zp;
-    glds16(src, patch_lds + g * 1024);
+    isic_glds16(src, patch_lds + g * 1024);
   }
   // weights of one tap: 64 rows x 128 B = 8 DMA groups, 2 per wave; row co = 8g + l/8, chunk (l%8) ^ (co&7) = gch
   const unsigned short* wsrc = a.w + (size_t)(wave * 8 + r8) * 576 + gch * 8;
   auto issue_w = [&](int tap) {
     const unsigned stage = wst_lds + (tap % WSTAGES) * WSTAGE;
-    glds16(wsrc + tap * 64, stage + wave * 1024);
-    glds16(wsrc + 32 * 576 + tap * 64, stage + (wave + 4) * 1024);
+    isic_glds16(wsrc + tap * 64, stage + wave * 1024);
+    isic_glds16(wsrc + 32 * 576 + tap * 64, stage + (wave + 4) * 1024);
   };
   issue_w(0); issue_w(1); issue_w(2);
 
@@ -165,10 +156,7 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(C64Args a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const u32x2 v = *reinterpret_cast<const u32x2*>(Cs + crow0 + i * 16 * CPAD + j * 16);
-        acc[i][j][0] += __uint_as_float(v[0] << 16);
-        acc[i][j][1] += __uint_as_float(v[0] & 0xFFFF0000u);
-        acc[i][j][2] += __uint_as_float(v[1] << 16);
-        acc[i][j][3] += __uint_as_float(v[1] & 0xFFFF0000u);
+        isic_add_bf16x4(acc[i][j], v[0], v[1]);
       }
     lds_barrier();
   }
@@ -177,10 +165,7 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(C64Args a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       u32x2 v = {0u, 0u};                                // pixels outside the image stay exact zeros (statistics!)
-      if (valid[i]) {
-        v[0] = (unsigned)f32_to_bf16_bits(acc[i][j][0]) | ((unsigned)f32_to_bf16_bits(acc[i][j][1]) << 16);
-        v[1] = (unsigned)f32_to_bf16_bits(acc[i][j][2]) | ((unsigned)f32_to_bf16_bits(acc[i][j][3]) << 16);
-      }
+      if (valid[i]) v = isic_pack_bf16x4(acc[i][j]);
       *reinterpret_cast<u32x2*>(Cs + crow0 + i * 16 * CPAD + j * 16) = v;
     }
   lds_barrier();
@@ -189,7 +174,7 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(C64Args a) {
     float s = 0.f, q = 0.f;
 #pragma unroll 16
     for (int r = part * 64; r < (part + 1) * 64; ++r) {
-      const float v = bfb(Cs[r * CPAD + col]);
+      const float v = bf16_bits_to_f32(Cs[r * CPAD + col]);
       s += v; q += v * v;
     }
     float* red = reinterpret_cast<float*>(smem + 256 * CPAD * 2);
@@ -266,39 +251,6 @@ __device__ unsigned long long g_c64p_stamps[256 * 32 * 4];
 #define C64P_STAMP(kk, k) do { } while (0)
 #endif
 
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {     // one v_cvt_pk_bf16_f32 (round to nearest even)
-  const f32x2_t f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-// sum over the 16 lanes of a DPP row (the lanes of one fg group), result in every lane: row_ror 8, 4, 2, 1
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-  return v;
-}
-// LDS-DMA / store with a wave-uniform 64-bit base (SGPR pair) and a 32-bit per-lane byte offset
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// (the s_nop covers the hazard "VMEM store of more than 64 bits followed by a write of its data VGPRs", which the
-//  compiler cannot see through the asm statement)
-// Ordinary stores, not non-temporal ones (late round 4).  The two waves of a SIMD write the two 64-byte halves of a pixel
-// row half a tile apart; non-temporal, each half goes to memory by itself (64-byte segments stream at 3.2 TB/s against 5.4
-// for whole lines, profiles/r03_probe_rw.txt), cached, the L2 joins them: dgrad + addend 1.356 -> 1.295 ms, dgrad 0.951 ->
-// 0.939 ms, forward with statistics unchanged (interleaved A/B, 4096 images).
-__device__ __forceinline__ void store16_s(void* sbase, unsigned voff, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void store16_v(void* ptr, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(ptr), "v"(v) : "memory");
-}
-
 template <bool STATS, bool ADDEND>
 __global__ __launch_bounds__(512) void conv3x3_c64p_kernel(C64PArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -356,7 +308,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64p_kernel(C64PArgs a) {
     const bool real = live && ddst[j] != 0xFFFFFFFFu;
     const bool ok = real && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
     const unsigned char* src = (ok ? origin + doff[j] : g_c64_zeros) + lane_src;
-    glds16(src, real ? lds0 + (unsigned)buf * P_BUF + ddst[j] : lds0 + P_SCRATCH);
+    isic_glds16(src, real ? lds0 + (unsigned)buf * P_BUF + ddst[j] : lds0 + P_SCRATCH);
   };
   auto issue_patch = [&](const Tile& tl, int buf, bool live) {
 #pragma unroll
@@ -439,27 +391,21 @@ __global__ __launch_bounds__(512) void conv3x3_c64p_kernel(C64PArgs a) {
         f32x4 c = acc[i][j];
         if (ADDEND) {
           const unsigned lo = ad[i][2 * j], hi = ad[i][2 * j + 1], bits = amb[i] >> (4 * j);
-          c[0] += (bits & 1u) ? __uint_as_float(lo << 16) : 0.f;
-          c[1] += (bits & 2u) ? __uint_as_float(lo & 0xFFFF0000u) : 0.f;
-          c[2] += (bits & 4u) ? __uint_as_float(hi << 16) : 0.f;
-          c[3] += (bits & 8u) ? __uint_as_float(hi & 0xFFFF0000u) : 0.f;
+          isic_add_bf16x4_masked(c, lo, hi, bits);
         }
-        const unsigned w0 = pack_bf16x2(c[0], c[1]), w1 = pack_bf16x2(c[2], c[3]);
+        const unsigned w0 = isic_pack_bf16x2(c[0], c[1]), w1 = isic_pack_bf16x2(c[2], c[3]);
         v[2 * j] = w0;
         v[2 * j + 1] = w1;
         if (STATS && valid) {                                            // statistics of the ROUNDED outputs
-          const float r0 = __uint_as_float(w0 << 16), r1 = __uint_as_float(w0 & 0xFFFF0000u);
-          const float r2 = __uint_as_float(w1 << 16), r3 = __uint_as_float(w1 & 0xFFFF0000u);
-          s8[4 * j + 0] += r0; q8[4 * j + 0] += r0 * r0;
-          s8[4 * j + 1] += r1; q8[4 * j + 1] += r1 * r1;
-          s8[4 * j + 2] += r2; q8[4 * j + 2] += r2 * r2;
-          s8[4 * j + 3] += r3; q8[4 * j + 3] += r3 * r3;
+          float r[4];
+          isic_unpack_bf16x4(w0, w1, r);
+          isic_sum_sumsq4(s8 + 4 * j, q8 + 4 * j, r);
         }
       }
       // exactly one store per M-tile is ISSUED whatever the validity (see CNT_TOP)
-      if (seg == 0) store16_s(a.out + off, lane_out, v);
-      else if (seg == 1) store16_s(g_c64_sink, (unsigned)lane * 16, v);
-      else store16_v(valid ? (void*)(reinterpret_cast<unsigned char*>(a.out + off) + lane_out) : (void*)(g_c64_sink + lane * 16), v);
+      if (seg == 0) isic_store16_s(a.out + off, lane_out, v);
+      else if (seg == 1) isic_store16_s(g_c64_sink, (unsigned)lane * 16, v);
+      else isic_store16_v(valid ? (void*)(reinterpret_cast<unsigned char*>(a.out + off) + lane_out) : (void*)(g_c64_sink + lane * 16), v);
     }
   };
 
@@ -520,7 +466,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64p_kernel(C64PArgs a) {
     // lanes of one fg group (a DPP row of 16) hold the same channels for different pixels; 4 pixel-group waves per half
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const float s = row16_sum(s8[c]), q = row16_sum(q8[c]);
+      const float s = isic_row16_sum(s8[c]), q = isic_row16_sum(q8[c]);
       // DETERMINISTIC (round 3): every (pixel-group wave, channel) value has ONE writer and its own LDS word; the four
       // pixel-group waves are added below in a fixed order (LDS atomics added them in arrival order: run-to-run noise
       // in the last fp32 bits of the statistics, which 17 bf16 layers amplify to per cent in the gradients)

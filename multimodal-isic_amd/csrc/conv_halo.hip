@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -61,25 +62,6 @@ __device__ __attribute__((aligned(256))) unsigned char g_halo_zero_page[256];
 
 __device__ __forceinline__ unsigned fdiv40(unsigned n, unsigned long long magic) {
   return (unsigned)(((unsigned long long)n * magic) >> 40);
-}
-// 16-byte-per-lane LDS-DMA in inline asm: outside hipcc's vmcnt bookkeeping (the staging waves count by hand).
-__device__ __forceinline__ void halo_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-typedef __attribute__((ext_vector_type(2))) float hf32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 hbf16x2;
-__device__ __forceinline__ unsigned halo_pack2(float lo, float hi) {     // one v_cvt_pk_bf16_f32 (round to nearest even)
-  const hf32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, hbf16x2));
-}
-__device__ __forceinline__ float halo_row16_sum(float v) {               // sum over the 16 lanes of a DPP row
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-  return v;
 }
 
 #ifdef HALO_STAMPS   // tests/probes/probe_halo_stamps.hip: per-tile phase timestamps of MFMA wave 0 of the first 256 blocks
@@ -141,7 +123,7 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
       const long long pix = (long long)(t_begin + tl) * HM - (a.W + 1) + g * 8 + r8;
       const bool ok = real && pix >= 0 && pix < a.M;
       const void* src = ok ? (const void*)(a.in + (size_t)pix * a.Cin + cc * 64 + gch * 8) : (const void*)zp;
-      halo_glds16(src, real ? lds0 + (unsigned)(buf * PB + g * 1024) : scr);
+      isic_glds16(src, real ? lds0 + (unsigned)(buf * PB + g * 1024) : scr);
     };
     // weights of K-tile (tap, cc): stage rows sr = 16*sw + 8*t + r8 (t = 0, 1: the wave's two DMA groups).  Stage row
     // wn*64 + j*16 + rho feeds row rho of MFMA tile j of channel half wn and holds output channel
@@ -152,8 +134,8 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
     auto weights = [&](int tap, int cc, int stage, bool live) {
       const unsigned short* s0 = wrow + (size_t)tap * a.Cin + cc * 64;
       const unsigned dst = lds0 + off_w + stage * WSTAGE + sw * 2048;
-      halo_glds16(live ? (const void*)s0 : (const void*)zp, live ? dst : scr);
-      halo_glds16(live ? (const void*)(s0 + (size_t)16 * 9 * a.Cin) : (const void*)zp, live ? dst + 1024 : scr);
+      isic_glds16(live ? (const void*)s0 : (const void*)zp, live ? dst : scr);
+      isic_glds16(live ? (const void*)(s0 + (size_t)16 * 9 * a.Cin) : (const void*)zp, live ? dst + 1024 : scr);
     };
 
     if constexpr (KPB == 2) {
@@ -163,14 +145,14 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
         if (g >= groups) return;
         const long long pix = (long long)(t_begin + tl) * HM - (a.W + 1) + g * 8 + r8;
         const bool ok = pix >= 0 && pix < a.M;
-        halo_glds16(ok ? (const void*)(a.in + (size_t)pix * a.Cin + cc * 64 + gch * 8) : (const void*)zp,
+        isic_glds16(ok ? (const void*)(a.in + (size_t)pix * a.Cin + cc * 64 + gch * 8) : (const void*)zp,
                     lds0 + (unsigned)(buf * PB + g * 1024));
       };
       auto weights2 = [&](int tap, int cc, int stage) {
         const unsigned short* s0 = wrow + (size_t)tap * a.Cin + cc * 64;
         const unsigned dst = lds0 + off_w + stage * WSTAGE + sw * 2048;
-        halo_glds16((const void*)s0, dst);
-        halo_glds16((const void*)(s0 + (size_t)16 * 9 * a.Cin), dst + 1024);
+        isic_glds16((const void*)s0, dst);
+        isic_glds16((const void*)(s0 + (size_t)16 * 9 * a.Cin), dst + 1024);
       };
 #pragma unroll
       for (int j = 0; j < MAX_PPW; ++j) piece2(j, 0, 0, 0);
@@ -395,28 +377,25 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
             f32x4 c = acc[i][2 * t + h];
             if (ADDEND) {
               const unsigned lo = ad[t][2 * h], hi = ad[t][2 * h + 1];
-              c[0] += __uint_as_float(lo << 16);
-              c[1] += __uint_as_float(lo & 0xFFFF0000u);
-              c[2] += __uint_as_float(hi << 16);
-              c[3] += __uint_as_float(hi & 0xFFFF0000u);
+              isic_add_bf16x4(c, lo, hi);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) c[e] = ((bits >> (4 * h + e)) & 1u) ? c[e] : 0.f;
-            const unsigned w0 = halo_pack2(c[0], c[1]), w1 = halo_pack2(c[2], c[3]);
+            const unsigned w0 = isic_pack_bf16x2(c[0], c[1]), w1 = isic_pack_bf16x2(c[2], c[3]);
             res[t][2 * h] = w0;
             res[t][2 * h + 1] = w1;
             const unsigned ylo = yv[i & 1][t][2 * h], yhi = yv[i & 1][t][2 * h + 1];
-            const float r0 = __uint_as_float(w0 << 16), r1 = __uint_as_float(w0 & 0xFFFF0000u);       // the ROUNDED dz
-            const float r2 = __uint_as_float(w1 << 16), r3 = __uint_as_float(w1 & 0xFFFF0000u);
-            s8[4 * h + 0] = r0; q8[4 * h + 0] = r0 * __uint_as_float(ylo << 16);
-            s8[4 * h + 1] = r1; q8[4 * h + 1] = r1 * __uint_as_float(ylo & 0xFFFF0000u);
-            s8[4 * h + 2] = r2; q8[4 * h + 2] = r2 * __uint_as_float(yhi << 16);
-            s8[4 * h + 3] = r3; q8[4 * h + 3] = r3 * __uint_as_float(yhi & 0xFFFF0000u);
+            float r[4];                                      // the ROUNDED dz; the second sum is dz * y, not dz * dz
+            isic_unpack_bf16x4(w0, w1, r);
+            s8[4 * h + 0] = r[0]; q8[4 * h + 0] = r[0] * __uint_as_float(ylo << 16);
+            s8[4 * h + 1] = r[1]; q8[4 * h + 1] = r[1] * __uint_as_float(ylo & 0xFFFF0000u);
+            s8[4 * h + 2] = r[2]; q8[4 * h + 2] = r[2] * __uint_as_float(yhi << 16);
+            s8[4 * h + 3] = r[3]; q8[4 * h + 3] = r[3] * __uint_as_float(yhi & 0xFFFF0000u);
           }
           float mine = 0.f;
 #pragma unroll
           for (int c = 0; c < 8; ++c) {
-            const float sv = halo_row16_sum(s8[c]), qv = halo_row16_sum(q8[c]);
+            const float sv = isic_row16_sum(s8[c]), qv = isic_row16_sum(q8[c]);
             mine = fr == c ? sv : mine;
             mine = fr == 8 + c ? qv : mine;
           }
@@ -471,21 +450,15 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
           f32x4 c = acc[i][2 * t + h];
           if (ADDEND) {
             const unsigned lo = ad[i][t][2 * h], hi = ad[i][t][2 * h + 1], bits = amb[i][t] >> (4 * h);
-            c[0] += (bits & 1u) ? __uint_as_float(lo << 16) : 0.f;
-            c[1] += (bits & 2u) ? __uint_as_float(lo & 0xFFFF0000u) : 0.f;
-            c[2] += (bits & 4u) ? __uint_as_float(hi << 16) : 0.f;
-            c[3] += (bits & 8u) ? __uint_as_float(hi & 0xFFFF0000u) : 0.f;
+            isic_add_bf16x4_masked(c, lo, hi, bits);
           }
-          const unsigned w0 = halo_pack2(c[0], c[1]), w1 = halo_pack2(c[2], c[3]);
+          const unsigned w0 = isic_pack_bf16x2(c[0], c[1]), w1 = isic_pack_bf16x2(c[2], c[3]);
           v[2 * h] = w0;
           v[2 * h + 1] = w1;
           if (STATS == 1 && valid) {                     // statistics of the ROUNDED outputs
-            const float r0 = __uint_as_float(w0 << 16), r1 = __uint_as_float(w0 & 0xFFFF0000u);
-            const float r2 = __uint_as_float(w1 << 16), r3 = __uint_as_float(w1 & 0xFFFF0000u);
-            s8[t][4 * h + 0] += r0; q8[t][4 * h + 0] += r0 * r0;
-            s8[t][4 * h + 1] += r1; q8[t][4 * h + 1] += r1 * r1;
-            s8[t][4 * h + 2] += r2; q8[t][4 * h + 2] += r2 * r2;
-            s8[t][4 * h + 3] += r3; q8[t][4 * h + 3] += r3 * r3;
+            float r[4];
+            isic_unpack_bf16x4(w0, w1, r);
+            isic_sum_sumsq4(s8[t] + 4 * h, q8[t] + 4 * h, r);
           }
         }
         vv[t] = v;
@@ -513,7 +486,7 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
         float mine = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          const float sv = halo_row16_sum(s8[t][c]), qv = halo_row16_sum(q8[t][c]);
+          const float sv = isic_row16_sum(s8[t][c]), qv = isic_row16_sum(q8[t][c]);
           mine = fr == c ? sv : mine;
           mine = fr == 8 + c ? qv : mine;
         }

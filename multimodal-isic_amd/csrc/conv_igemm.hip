@@ -38,6 +38,7 @@
 
 
 #include "common.h"
+#include "mfma_tile.h"
 #include "conv_args.h"
 
 namespace {
@@ -45,8 +46,6 @@ namespace {
 using namespace isic_conv;
 
 constexpr int BK = 64;  // bf16 elements per K-tile (128 bytes per LDS row)
-
-__device__ __forceinline__ float bfbits(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
 
 // zero page for LDS-DMA staging: an out-of-image tap row is fetched from here instead of being zero-filled
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
@@ -219,10 +218,7 @@ __global__ __launch_bounds__(2 * WAVES_M * WAVES_N * 64, 4) void conv_igemm_kern
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const u32x2 v = *reinterpret_cast<const u32x2*>(Cs + crow0 + i * 16 * CPAD + j * 16);
-        acc[i][j][0] += __uint_as_float(v[0] << 16);
-        acc[i][j][1] += __uint_as_float(v[0] & 0xFFFF0000u);
-        acc[i][j][2] += __uint_as_float(v[1] << 16);
-        acc[i][j][3] += __uint_as_float(v[1] & 0xFFFF0000u);
+        isic_add_bf16x4(acc[i][j], v[0], v[1]);
       }
     lds_barrier();
   }
@@ -230,10 +226,7 @@ __global__ __launch_bounds__(2 * WAVES_M * WAVES_N * 64, 4) void conv_igemm_kern
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      u32x2 v;
-      v[0] = (unsigned)f32_to_bf16_bits(acc[i][j][0]) | ((unsigned)f32_to_bf16_bits(acc[i][j][1]) << 16);
-      v[1] = (unsigned)f32_to_bf16_bits(acc[i][j][2]) | ((unsigned)f32_to_bf16_bits(acc[i][j][3]) << 16);
-      *reinterpret_cast<u32x2*>(Cs + crow0 + i * 16 * CPAD + j * 16) = v;
+      *reinterpret_cast<u32x2*>(Cs + crow0 + i * 16 * CPAD + j * 16) = isic_pack_bf16x4(acc[i][j]);
     }
   lds_barrier();
   if (a.stat_sum) {
@@ -245,7 +238,7 @@ __global__ __launch_bounds__(2 * WAVES_M * WAVES_N * 64, 4) void conv_igemm_kern
     float s = 0.f, q = 0.f;
 #pragma unroll 16
     for (int r = part * RPP; r < (part + 1) * RPP; ++r) {
-      const float v = bfbits(Cs[r * CPAD + col]);
+      const float v = bf16_bits_to_f32(Cs[r * CPAD + col]);
       s += v; q += v * v;
     }
     float* red = reinterpret_cast<float*>(smem + BM * CPAD * 2);   // behind the C tile: 2*MT floats

@@ -23,6 +23,7 @@
 // save_latent.py:42-60); BASELINE.json configs[1] names ResNet-18 (SURVEY.md 8d layer table).
 
 #include "common.h"
+#include "mfma_tile.h"
 #include "conv_args.h"
 
 namespace {
@@ -43,24 +44,6 @@ struct PGemmArgs {
 
 __device__ __attribute__((aligned(256))) unsigned char g_pg_zero_page[256];
 
-__device__ __forceinline__ void pg_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-typedef __attribute__((ext_vector_type(2))) float pf32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 pbf16x2;
-__device__ __forceinline__ unsigned pg_pack2(float lo, float hi) {
-  const pf32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, pbf16x2));
-}
-__device__ __forceinline__ float pg_row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-  return v;
-}
 
 // PN = 64 (round 2, for convolutions with 64 outputs -- the data gradient of the 64 -> 128 stride-2 layer): the MFMA
 // waves stay 4 x 2 but own 64 x 32 (4 x 2 tiles), a stage holds 64 weight rows (one DMA piece per staging wave).
@@ -150,13 +133,13 @@ __global__ __launch_bounds__(1024) void conv_pgemm_kernel(PGemmArgs pa) {
       for (int i = 0; i < 4; ++i) {
         const bool ok = live && (((a_vh[i] >> ti) & (a_vw[i] >> tj)) & 1u);
         const void* src = ok ? (const void*)(inp + (a_off[i] + toff)) : (const void*)zp;
-        pg_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
+        isic_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
       }
       if (PN == 128) {
-        pg_glds16(live ? (const void*)(wp + koff) : (const void*)zp, live ? sbase + P_A + sw * 2048 : scr);
-        pg_glds16(live ? (const void*)(wp + koff + wstep) : (const void*)zp, live ? sbase + P_A + sw * 2048 + 1024 : scr);
+        isic_glds16(live ? (const void*)(wp + koff) : (const void*)zp, live ? sbase + P_A + sw * 2048 : scr);
+        isic_glds16(live ? (const void*)(wp + koff + wstep) : (const void*)zp, live ? sbase + P_A + sw * 2048 + 1024 : scr);
       } else {
-        pg_glds16(live ? (const void*)(wp + koff) : (const void*)zp, live ? sbase + P_A + sw * 1024 : scr);
+        isic_glds16(live ? (const void*)(wp + koff) : (const void*)zp, live ? sbase + P_A + sw * 1024 : scr);
       }
     };
 
@@ -260,21 +243,15 @@ __global__ __launch_bounds__(1024) void conv_pgemm_kernel(PGemmArgs pa) {
             f32x4 c = acc[i][2 * t + h];
             if (ADDEND) {
               const unsigned lo = ad[i][t][2 * h], hi = ad[i][t][2 * h + 1];
-              c[0] += __uint_as_float(lo << 16);
-              c[1] += __uint_as_float(lo & 0xFFFF0000u);
-              c[2] += __uint_as_float(hi << 16);
-              c[3] += __uint_as_float(hi & 0xFFFF0000u);
+              isic_add_bf16x4(c, lo, hi);
             }
-            const unsigned w0 = pg_pack2(c[0], c[1]), w1 = pg_pack2(c[2], c[3]);
+            const unsigned w0 = isic_pack_bf16x2(c[0], c[1]), w1 = isic_pack_bf16x2(c[2], c[3]);
             v[2 * h] = w0;
             v[2 * h + 1] = w1;
             if (STATS && valid[i]) {                       // statistics of the ROUNDED outputs
-              const float r0 = __uint_as_float(w0 << 16), r1 = __uint_as_float(w0 & 0xFFFF0000u);
-              const float r2 = __uint_as_float(w1 << 16), r3 = __uint_as_float(w1 & 0xFFFF0000u);
-              s8[4 * h + 0] += r0; q8[4 * h + 0] += r0 * r0;
-              s8[4 * h + 1] += r1; q8[4 * h + 1] += r1 * r1;
-              s8[4 * h + 2] += r2; q8[4 * h + 2] += r2 * r2;
-              s8[4 * h + 3] += r3; q8[4 * h + 3] += r3 * r3;
+              float r[4];
+              isic_unpack_bf16x4(w0, w1, r);
+              isic_sum_sumsq4(s8 + 4 * h, q8 + 4 * h, r);
             }
           }
           // ordinary stores (late round 4): a wave writes a pixel's 64-byte segment per instruction, its partner -- the next t or the
@@ -288,7 +265,7 @@ __global__ __launch_bounds__(1024) void conv_pgemm_kernel(PGemmArgs pa) {
           float mine = 0.f;
 #pragma unroll
           for (int c = 0; c < 8; ++c) {
-            const float sv = pg_row16_sum(s8[c]), qv = pg_row16_sum(q8[c]);
+            const float sv = isic_row16_sum(s8[c]), qv = isic_row16_sum(q8[c]);
             mine = fr == c ? sv : mine;
             mine = fr == 8 + c ? qv : mine;
           }

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_tile.h"
 #include "pool_grad.h"
 
 namespace {
@@ -140,9 +141,7 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(StemArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int p = (wave * 2 + i) * 16 + fi;
-        u32x2 v;
-        v[0] = (unsigned)f32_to_bf16_bits(acc[i][j][0]) | ((unsigned)f32_to_bf16_bits(acc[i][j][1]) << 16);
-        v[1] = (unsigned)f32_to_bf16_bits(acc[i][j][2]) | ((unsigned)f32_to_bf16_bits(acc[i][j][3]) << 16);
+        const u32x2 v = isic_pack_bf16x4(acc[i][j]);
         *reinterpret_cast<u32x2*>(Cs + p * CPAD + j * 16 + fg * 4) = v;
         if (a.stat_sum) {
           const bool in = (oy0 + wave * 2 + i < a.Hout) && (ox0 + fi < a.Wout);
@@ -373,19 +372,16 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
         const int oyl = 2 * al + (p >> 1), oxl = 2 * bw + (p & 1);
         const bool in = inside || ((oy0 + oyl < a.Hout) && (ox0 + oxl < a.Wout));
         const unsigned lo = xr[p][2 * H_], hi = xr[p][2 * H_ + 1];
-        const float xv[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xFFFF0000u), __uint_as_float(hi << 16),
-                             __uint_as_float(hi & 0xFFFF0000u)};
-        float o[4];
+        float xv[4];
+        isic_unpack_bf16x4(lo, hi, xv);
+        f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float dz = (xv[j] * sc[j] + sh[j] > 0.f) ? g[p][j] : 0.f;
           o[j] = kA[j] * dz + (kB[j] * xv[j] + kD[j]);
           if (!inside) o[j] = in ? o[j] : 0.f;
         }
-        u32x2 v;
-        v[0] = (unsigned)f32_to_bf16_bits(o[0]) | ((unsigned)f32_to_bf16_bits(o[1]) << 16);
-        v[1] = (unsigned)f32_to_bf16_bits(o[2]) | ((unsigned)f32_to_bf16_bits(o[3]) << 16);
-        *reinterpret_cast<u32x2*>(Ys + (oyl * TW + oxl) * YROW + cg * 16 + H_ * 8) = v;
+        *reinterpret_cast<u32x2*>(Ys + (oyl * TW + oxl) * YROW + cg * 16 + H_ * 8) = isic_pack_bf16x4(o);
       }
     };
     half(std::integral_constant<int, 0>{});

@@ -27,6 +27,7 @@
 // split order.  DETERMINISTIC (round 3): the fp32 row atomics this replaces added the splits in arrival order, so two
 // identical steps gave different last bits in 6 of ResNet-18's 20 weight gradients.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -54,16 +55,6 @@ __global__ void wgrad_table_kernel(int2* __restrict__ tab, int M, int Hout, int 
   e.x = ((n * Hin + ho * stride - pad) * Win + wo * stride - pad) * Cin;
   e.y = (ho << 16) | wo;
   tab[m] = e;
-}
-
-// One LDS-DMA instruction from inline asm: 64 lanes x 16 B from per-lane global addresses to the wave-uniform LDS
-// byte address `lds_dst` (+ lane*16).  Issued from asm so that hipcc neither counts it in vmcnt nor fences the
-// following ds_read_tr with a vmcnt(0) drain (it does for the builtin form in this kernel); completion is
-// tracked by the loop's own s_waitcnt.  M0 (the DMA's LDS base) is saved and restored inside the statement.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // zero page: rows past the end of the pixel range and out-of-image taps are fetched from here
@@ -146,8 +137,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
       const void* sa = inr ? (const void*)(a.dy + (size_t)m * a.Cout + co0 + gchunk * 8) : (const void*)zp;
       const void* sb = okx ? (const void*)(a.x + (ex + tapoff)) : (const void*)zp;
       const unsigned dst = stage + (unsigned)((wave_u * RPI + RSTEP * i) * ROWB);
-      glds16(sa, dst);
-      glds16(sb, dst + OPB);
+      isic_glds16(sa, dst);
+      isic_glds16(sb, dst + OPB);
     }
   };
 

@@ -21,6 +21,7 @@
 //   * two stages of 77,824 B; one barrier per tile; per-block partials + a fixed-order reduction: deterministic, no atomics;
 //   * small images (W <= 15 / W <= 7) packed two / four to a 32-column tile row, at least one empty column between them.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -46,12 +47,6 @@ struct WC128BArgs {
 };
 
 __device__ __attribute__((aligned(256))) unsigned char g_wc128b_zeros[2048];
-
-__device__ __forceinline__ void glds16b(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -127,7 +122,7 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
       src = zeros + (unsigned)(lane * 16);
       dst = 0;
     }
-    glds16b(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
+    isic_glds16(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
   };
 
   // ---------------------------------------------------------------- fragments: wave c = input channels 16c .. 16c+16

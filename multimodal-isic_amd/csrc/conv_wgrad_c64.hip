@@ -19,6 +19,7 @@
 // does not exist yet, the staging waves form it from the incoming gradient and the convolution output (see BNBWD below).
 
 #include "common.h"
+#include "mfma_tile.h"
 #include "pool_grad.h"
 
 namespace {
@@ -53,12 +54,6 @@ struct WC64BnArgs : WC64Args {        // dy = g, the gradient of the BatchNorm(+
 };
 
 __device__ __attribute__((aligned(256))) unsigned char g_wc64_zeros[2048];
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {   // see conv_wgrad.hip
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 // Register loads the compiler must not count: its waits would drain the LDS-DMAs in flight beside them.  The data is
 // there after the counted wait of wc64_landed*, which names every destination.
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(typename WC64Mode<MODE>:
         // per-lane select of two wave-uniform addresses, half by half (out-of-image lanes read a zero page)
         const unsigned lo = ok ? (unsigned)rowaddr : (unsigned)zeros, hi = ok ? (unsigned)(rowaddr >> 32) : (unsigned)(zeros >> 32);
         const unsigned long long src = (((unsigned long long)hi << 32) | lo) + lanev;
-        glds16(reinterpret_cast<const void*>(src), real ? sbase + dst : lds0 + SCRATCH);   // padding: zeros -> scratch
+        isic_glds16(reinterpret_cast<const void*>(src), real ? sbase + dst : lds0 + SCRATCH);   // padding: zeros -> scratch
       }
     };
     if constexpr (MODE != 0) {

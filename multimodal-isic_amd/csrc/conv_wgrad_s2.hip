@@ -25,6 +25,7 @@
 // The reference has no convolution kernel of its own (un-vendored encoder, save_latent.py:42-60); ResNet-18 layer table:
 // SURVEY.md 8d.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -51,12 +52,6 @@ struct WS2Args {
 };
 
 __device__ __attribute__((aligned(256))) unsigned char g_ws2_zeros[2048];
-
-__device__ __forceinline__ void glds16s(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 
 __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
       src = zeros + (unsigned)(lane * 16);
       dst = 0;
     }
-    glds16s(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
+    isic_glds16(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
   };
 
   // ---------------------------------------------------------------- fragments: wave = (ci block c, co half hh)

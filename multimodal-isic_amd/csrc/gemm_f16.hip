@@ -16,10 +16,9 @@
 // this build's definition of the ViT-S/16 named by BASELINE.json (oracle/vit.py restates it on the CPU in fp32).
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GM = 256, GN = 128;
 constexpr int G_A = GM * 128, G_B = GN * 128, G_STAGE = G_A + G_B;   // bytes per K-tile
@@ -54,11 +53,6 @@ struct GemmF16Args {
 
 __device__ __attribute__((aligned(256))) unsigned char g_g16_zero_page[256];
 
-__device__ __forceinline__ void g16_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // erf-GELU (nn.GELU default, timm).  libm's erff: a hand-rolled Abramowitz-Stegun 7.1.26 with an exact reciprocal was
 // measured SLOWER (1.01 vs 0.93 ms for fc1; no GELU at all: 0.87 ms -- the layer is bound by its 1.2 GB output).
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
@@ -119,10 +113,10 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const void* src = (live && a_ok[i]) ? (const void*)(a_ptr[i] + koff) : (const void*)zp;
-        g16_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
+        isic_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
       }
-      g16_glds16(live ? (const void*)(wrow + koff) : (const void*)zp, live ? sbase + G_A + sw * 2048 : scr);
-      g16_glds16(live ? (const void*)(wrow + koff + (size_t)16 * a.K) : (const void*)zp, live ? sbase + G_A + sw * 2048 + 1024 : scr);
+      isic_glds16(live ? (const void*)(wrow + koff) : (const void*)zp, live ? sbase + G_A + sw * 2048 : scr);
+      isic_glds16(live ? (const void*)(wrow + koff + (size_t)16 * a.K) : (const void*)zp, live ? sbase + G_A + sw * 2048 + 1024 : scr);
     };
     int itile = 0, ikt = 0;
     tile_rows(0);
@@ -147,7 +141,6 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
     // the block's biases in LDS (read back per 4 columns in the epilogue: no registers held across the K loop)
     float* bias_all = reinterpret_cast<float*>(smem + off_scr + 1024);
     float* cn_all = bias_all + G_MAXSPB * GN;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2* rowst = reinterpret_cast<f32x2*>(cn_all + G_MAXSPB * GN);     // [GM] (rstd, mean * rstd) of the current row tile
     if (tid < spb * GN) {
       bias_all[tid] = a.bias ? a.bias[nbase + tid] : 0.f;

@@ -26,6 +26,7 @@
 // Shapes the DMA path cannot take (a dimension that is not a multiple of 4 floats, unaligned pointers) and small products
 // stay on gemm_f32.hip's kernel: isic_gemm_f32_ws decides.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -51,11 +52,6 @@ struct G32Args {
 
 __device__ __attribute__((aligned(256))) unsigned char g_g32_zero_page[256];
 
-__device__ __forceinline__ void g32_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // Row indices of a gathered operand are read with SCALAR loads (lgkmcnt): the staging waves count vmcnt by hand, a vector
 // load among their LDS-DMAs would break the count.  The address is wave-uniform by construction.
 typedef int g32_i8 __attribute__((ext_vector_type(8)));
@@ -163,7 +159,7 @@ __global__ __launch_bounds__(1024) void gemm_f32p_kernel(G32Args a) {
             roff = (size_t)g32_sload1(a.arow + k0 + sw + 8 * i) * a.lda - (size_t)(sw + 8 * i) * a.lda;
           src = (in && a_ok[i]) ? (const void*)(a_ptr[i] + roff) : (const void*)zp;
         }
-        g32_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
+        isic_glds16(src, live ? sbase + (unsigned)((sw + 8 * i) * 1024) : scr);
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(1024) void gemm_f32p_kernel(G32Args a) {
           const int k = 2 * (2 * sw + t) + (lane >> 5);
           src = (live && b_ok[t] && k0 + k < a.K) ? (const void*)(b_ptr[t] + (size_t)k0 * a.ldb) : (const void*)zp;
         }
-        g32_glds16(src, live ? sbase + P_A + (unsigned)((2 * sw + t) * 1024) : scr);
+        isic_glds16(src, live ? sbase + P_A + (unsigned)((2 * sw + t) * 1024) : scr);
       }
     };
     int itile = 0, ikt = 0;

@@ -21,6 +21,7 @@
 //     is set to +inf and d is symmetric bit for bit; the row norms need no pass of their own.
 //   * summation order of x_i . x_j: identical to knn_kernel's (k-steps of 16, the four MFMAs of a step take k = 4 fg + j).
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -39,11 +40,6 @@ struct KnnGramArgs {
   int G, D, k;
 };
 
-__device__ __forceinline__ void kg_glds16(const void* gsrc, unsigned lds_dst) {     // outside hipcc's vmcnt bookkeeping
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 template <int CTRL>
 __device__ __forceinline__ float kg_dpp_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
       row = row < 0 ? 0 : row;
       const unsigned char* src = reinterpret_cast<const unsigned char*>(a.x + (size_t)(N > 0 ? lo + row : 0) * a.D) +
                                  (size_t)ikc * 128 + src_chunk;
-      kg_glds16(src, dst + h * 1024);
+      isic_glds16(src, dst + h * 1024);
     }
     if (++ikc == nchunks) { ikc = 0; ++ig; }
   };

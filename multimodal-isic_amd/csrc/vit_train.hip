@@ -12,8 +12,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // ------------------------------------------------------------------ slab reducer
 // out[i] = (accumulate ? out[i] : 0) + scale * sum_{z < S} ws[z][i], z in index order
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ ws, int S, int64_t n, float* out,
