@@ -643,5 +643,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_wgrad_bnbwd.h"
 /* ResNet-18 downsample blocks: BatchNorm backward of bn2 and of the shortcut's norm in one reduce and one apply pass: two more entry points, same conventions. */
 #include "isic_hip_bn_pair.h"
+/* The opt-in MXFP8 inference path of the ConvMAE-Base encoder (LayerNorm, depthwise 5x5 and patch rows with MXFP8 outputs): three more entry points, same conventions. */
+#include "isic_hip_convmae_mxfp8.h"
 
 #endif /* ISIC_HIP_H */

@@ -40,11 +40,12 @@ def build(force=False, verbose=True, jobs=None):
     """Compile every ``csrc/*.hip`` and link the shared library.  Returns its path."""
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    # *.inc: kernel templates / device helpers that two translation units share (convmae_kernels.inc, mx_quant.inc)
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers += [os.path.join(os.path.dirname(PKG), "include", h)
                 for h in ("isic_hip.h", "isic_hip_mxfp8.h", "isic_hip_vit_train.h", "isic_hip_convmae.h",
                           "isic_hip_convmae_train.h", "isic_hip_mae.h", "isic_hip_augment.h", "isic_hip_wgrad_bnbwd.h",
-                          "isic_hip_bn_pair.h")]
+                          "isic_hip_bn_pair.h", "isic_hip_convmae_mxfp8.h")]
     todo, objs = [], []
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")

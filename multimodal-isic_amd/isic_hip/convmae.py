@@ -1,4 +1,4 @@
-"""ConvMAE-Base patch encoder, fp16 on gfx950 -- the encoder the reference makes its patch latents with.
+"""ConvMAE-Base patch encoder, fp16 (or, opt-in, MXFP8) on gfx950 -- the encoder the reference makes its patch latents with.
 
 The reference builds ``convmae_convvit_base_patch16_dec512d8b(with_decoder=False)``, loads a checkpoint of its
 ``train_ae.py`` with ``strict=False`` and runs ``forward(images, mask_ratio=0) -> latent[B, 196, 768]``
@@ -40,6 +40,30 @@ ViT-B stage on ``isic_gemm_f16_ln`` / ``_stats`` and ``isic_attention_f16``.  No
 (``isic_row_stats_f16`` for the first block of a stage, whose input a LayerNorm + GELU wrote).  ``False``: every pre-norm
 is a pass of ``isic_layernorm_add_f16`` followed by a plain product -- the form to compare against when a pretrained
 stream carries rows with large offsets, where the fold's E[x^2] - mean^2 cancels.
+
+``precision="mxfp8"`` (opt-in, inference only; the default ``"fp16"`` is the path above, bit for bit): every product but
+the stem's runs on the block-scaled FP8 MFMA (``isic_gemm_mxfp8``; OCP MX E4M3, one E8M0 scale per 32 elements along K,
+csrc/mxfp8.hip), and the launch in front of a product writes its operand as MXFP8 straight from fp32 values
+(include/isic_hip_convmae_mxfp8.h).  MX(.) = quantised, fp16(.) = rounded to fp16, the rounding points in order:
+    stem        unchanged (K = 48 padded to 64 is no multiple of 128): fp16 rows, ``isic_gemm_f16``, LayerNorm + GELU -> fp16 x
+    CBlock      h = MX(LN1(x)) (``isic_layernorm_act_mxfp8_f16``); d = fp16(conv1(h)); m = MX(dw5x5(d) + b)
+                (``isic_dwconv5x5_mxfp8_f16``); x2 = fp16(x + conv2(m)); h2 = MX(LN2(x2)); hid = MX(GELU(fc1(h2))) (the
+                product's MXFP8 output: the 1024 / 1536-wide hidden map crosses HBM at 1 + 1/32 byte per value);
+                x = fp16(x2 + fc2(hid))
+    stage outputs  ``isic_patch_rows_mxfp8_nhwc_f16`` per consumer: stage 1 with P = 4 (stage1_output_decode) and P = 2
+                (patch_embed2), stage 2 with P = 2 once (stage2_output_decode and patch_embed3); decoders -> fp16 s1, s2
+    patch_embed2   product -> fp16, ``isic_layernorm_add_f16`` + GELU -> fp16 x;   patch_embed3: product -> fp16, then
+                MX(GELU(LN(.))) (its only reader is patch_embed4);   patch_embed4: + pos_embed (fp16) -> fp16 x
+    blocks3     the ViT's MXFP8 block at D = 768 (isic_hip/vit.py): LN -> MX, qkv -> fp16, ``isic_attention_f16``,
+                ``isic_mxfp8_quantize``, proj + residual -> fp16, LN -> MX, fc1 + GELU -> MX, fc2 + residual -> fp16
+    output      norm(x + s1 + s2) -> fp32, unchanged
+The LayerNorms are passes of their own (no fold, no row statistics: isic_hip/vit.py says why), so ``fold_layernorm=False``
+and ``trainable=True`` are ``ValueError`` with it.  The product matrices are quantised on the GPU from the fp32 masters in
+their [O][kh][kw][I] row order, once per weight version (``load_state_dict`` invalidates them); biases, LayerNorm
+affines and the depthwise taps stay fp32, ``pos_embed`` fp16.  ``max_batch`` and ``depth`` work as for fp16, and an
+image's tokens do not depend on its batch or chunk.  ``tests/convmae_mxfp8_ref.py`` is the CPU emulation of these
+rounding points: 0.091 relative Frobenius error and a minimum per-token cosine of 0.9946 against the fp32 restatement
+(fp16: 1.1e-3).
 
 ``trainable=True`` (opt-in; the default stays the frozen encoder above, bit for bit): the parameters require grad,
 ``train()`` works (no dropout or drop-path: the mode changes no arithmetic) and the encoder runs the layer-by-layer form
@@ -132,17 +156,24 @@ class _Block(nn.Module):
 
 
 class ConvMAEBaseEncoder(Encoder):
-    """Frozen ConvMAE-Base encoder (module docstring).  ``run_tokens(images[N,3,224,224]) -> [N, 196, 768]`` fp32."""
+    """Frozen ConvMAE-Base encoder (module docstring).  ``run_tokens(images[N,3,224,224]) -> [N, 196, 768]`` fp32.
+    ``precision``: ``"fp16"`` (default) or ``"mxfp8"`` (the products on the block-scaled FP8 MFMA; inference only)."""
 
     _who = "ConvMAEBaseEncoder"
     img_size, in_ch, tokens = 224, 3, 196
     dims, depths, grids, patches = (256, 384, 768), (2, 2, 11), (56, 28, 14), (4, 2, 2)
 
     def __init__(self, seed=0, fold_layernorm=None, ln_eps=1e-6, conv_ln_eps=1e-5, heads=12, mlp_ratio=4, max_batch=256,
-                 trainable=False):
+                 trainable=False, precision="fp16"):
         super().__init__()
         if trainable not in (True, False):
             raise ValueError("trainable: True or False")
+        if precision not in ("fp16", "mxfp8"):
+            raise ValueError("precision: 'fp16' or 'mxfp8'")
+        if precision == "mxfp8" and trainable:
+            raise ValueError("trainable=True: fp16 only (no MXFP8 training)")
+        if precision == "mxfp8" and fold_layernorm not in (None, True):
+            raise ValueError("precision='mxfp8' runs its LayerNorms as passes of their own: leave fold_layernorm at its default")
         if trainable and fold_layernorm not in (None, False):
             raise ValueError("trainable=True runs the layer-by-layer form: leave fold_layernorm unset (or False)")
         if fold_layernorm is None:
@@ -156,6 +187,7 @@ class ConvMAEBaseEncoder(Encoder):
             raise ValueError("ConvMAEBaseEncoder: head width 64 (isic_attention_f16)")
         self.fold_layernorm, self.ln_eps, self.conv_ln_eps = fold_layernorm, float(ln_eps), float(conv_ln_eps)
         self.heads, self.mlp_ratio, self.max_batch = heads, mlp_ratio, int(max_batch)
+        self.precision = precision
         self.feature_dim = self.out_dim = d3
         self.patch_embed1 = _PatchEmbed(self.in_ch, d1, 4, conv_ln_eps)
         self.patch_embed2 = _PatchEmbed(d1, d2, 2, conv_ln_eps)
@@ -175,6 +207,7 @@ class ConvMAEBaseEncoder(Encoder):
         self.grad_ready_hook = None                     # callable(list_of_param_names) fired as gradients complete (DDP overlap)
         self._ws = None                                 # backward workspace (slabs of the fixed-order reductions)
         self._w16, self._w16_key = None, None
+        self._wmx, self._wmx_key = None, None           # MXFP8 (q, s) of the product matrices, once per weight version
         self.eval()
 
     def _seeded_init(self, seed):
@@ -193,7 +226,7 @@ class ConvMAEBaseEncoder(Encoder):
         """nn.Module semantics (a wrong shape raises, also under strict=False).  A full MAE checkpoint loads with no
         missing keys; its decoder (``decoder_*``, ``mask_token``) comes back as the unexpected keys."""
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
-        self._w16_key = None
+        self._w16_key = self._wmx_key = None
         return out
 
     # ------------------------------------------------------------------ weights, once per weight version
@@ -238,9 +271,29 @@ class ConvMAEBaseEncoder(Encoder):
             for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
                 w[f"{b}.{lin}.weight"] = mat(f"{b}.{lin}.weight")
             folds += [(f"{b}.norm1", f"{b}.attn.qkv"), (f"{b}.norm2", f"{b}.mlp.fc1")]
-        for norm, lin in (folds if self.fold_layernorm else ()):
+        for norm, lin in (folds if self.fold_layernorm and self.precision == "fp16" else ()):
             fold_layernorm(w, sd[lin + ".weight"], norm, lin)
         self._w16, self._w16_key = w, key
+        return w
+
+    def _prepare_mx(self, device):
+        """(q, s) of every product matrix but the stem's, quantised on the GPU (isic_mxfp8_quantize) from the fp32 masters
+        in the row order of the patch rows ([O][kh][kw][I]: a block is 32 input channels of one kernel position)."""
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._wmx is not None and key == self._wmx_key:
+            return self._wmx
+        w = {}
+        for name, v in self.state_dict().items():
+            if v.dim() < 2 or name in ("pos_embed", "patch_embed1.proj.weight") or name.endswith(".attn.weight"):
+                continue
+            t = v.detach().float()
+            t = (t.permute(0, 2, 3, 1).reshape(t.shape[0], -1) if t.dim() == 4 else t).contiguous()
+            R, K = t.shape
+            q = torch.empty((R, K), device=device, dtype=torch.uint8)
+            s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
+            call("isic_mxfp8_quantize", t, 1, q, s, R, K)
+            w[name] = (q, s)
+        self._wmx, self._wmx_key = w, key
         return w
 
     # ------------------------------------------------------------------ forward
@@ -251,13 +304,101 @@ class ConvMAEBaseEncoder(Encoder):
         depth = self._check(images, depth)
         dev = images.device
         w = self._prepare(dev)
+        wmx = self._prepare_mx(dev) if self.precision == "mxfp8" else None
         x_in = images.float().contiguous()
         N = x_in.shape[0]
         out = torch.empty((N, self.tokens, self.out_dim), device=dev, dtype=torch.float32)
         for s in range(0, N, self.max_batch):
             e = min(N, s + self.max_batch)
-            self._run_chunk(x_in[s:e], w, out[s:e], depth)
+            if wmx is None:
+                self._run_chunk(x_in[s:e], w, out[s:e], depth)
+            else:
+                self._run_chunk_mx(x_in[s:e], w, wmx, out[s:e], depth)
         return out
+
+    def _run_chunk_mx(self, img, w, wmx, out, depth):
+        """The ``precision="mxfp8"`` forward of one chunk (module docstring): every product but the stem's on
+        ``isic_gemm_mxfp8``, its operand written as MXFP8 by the launch before it."""
+        dev = img.device
+        n, T, heads, r = img.shape[0], self.tokens, self.heads, self.mlp_ratio
+        (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
+        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        ceps, eps = self.conv_ln_eps, self.ln_eps
+
+        def e16(*shape):
+            return torch.empty(shape, device=dev, dtype=_F16)
+
+        def mx(M, K):
+            return (torch.empty((M, K), device=dev, dtype=torch.uint8), torch.empty((M, K // 32), device=dev, dtype=torch.uint8))
+
+        def gemm(a, name, M, Nout, K, out=None, out_mx=None, act=0, res=None, res_rows=0):
+            (wq, ws), (oq, os_) = wmx[name + ".weight"], out_mx or (None, None)
+            call("isic_gemm_mxfp8", a[0], a[1], wq, ws, w[name + ".bias"], res, out, oq, os_, M, Nout, K, act, res_rows)
+            return out
+
+        def ln_mx(x, name, h, M, C, act, e):
+            call("isic_layernorm_act_mxfp8_f16", x, w[name + ".weight"], w[name + ".bias"], h[0], h[1], M, C, act, e)
+
+        def patch_rows(x, g, C, P):
+            rows = mx(n * (g // P) ** 2, P * P * C)
+            call("isic_patch_rows_mxfp8_nhwc_f16", x, rows[0], rows[1], n, g, g, C, P)
+            return rows
+
+        def cblocks(x, stage, g, C, nblk):
+            M, Hd = n * g * g, C * r
+            if nblk:
+                h, m, hid, d, x2 = mx(M, C), mx(M, C), mx(M, Hd), e16(M, C), e16(M, C)
+            for i in range(nblk):
+                b = f"{stage}.{i}"
+                ln_mx(x, b + ".norm1", h, M, C, 0, ceps)
+                gemm(h, b + ".conv1", M, C, C, out=d)
+                call("isic_dwconv5x5_mxfp8_f16", d, w[b + ".attn.weight"], w[b + ".attn.bias"], m[0], m[1], n, g, g, C)
+                gemm(m, b + ".conv2", M, C, C, out=x2, res=x)
+                ln_mx(x2, b + ".norm2", h, M, C, 0, ceps)
+                gemm(h, b + ".mlp.fc1", M, Hd, C, out_mx=hid, act=1)
+                gemm(hid, b + ".mlp.fc2", M, C, Hd, out=x, res=x2)
+            return x
+
+        def patch_embed(rows, name, M, C, K):
+            t, y = gemm(rows, name + ".proj", M, C, K, out=e16(M, C)), e16(M, C)
+            call("isic_layernorm_add_f16", t, None, None, w[name + ".norm.weight"], w[name + ".norm.bias"], y, None, M, C, 1, ceps)
+            return y
+
+        # ---- stage 1: the stem stays fp16 (K = 48 padded to 64 is no multiple of 128)
+        rows, t, x = e16(M1, 64), e16(M1, d1), e16(M1, d1)
+        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
+        call("isic_gemm_f16", rows, w["patch_embed1.proj.weight"], w["patch_embed1.proj.bias"], None, t, M1, d1, 64, 0, 0)
+        call("isic_layernorm_add_f16", t, None, None, w["patch_embed1.norm.weight"], w["patch_embed1.norm.bias"], x, None, M1, d1,
+             1, ceps)
+        del rows, t
+        x = cblocks(x, "blocks1", g1, d1, depth[0])
+        s1 = gemm(patch_rows(x, g1, d1, 4), "stage1_output_decode", M3, d3, 16 * d1, out=e16(M3, d3))
+        rows = patch_rows(x, g1, d1, 2)
+        del x
+        # ---- stage 2
+        x = cblocks(patch_embed(rows, "patch_embed2", M2, d2, 4 * d1), "blocks2", g2, d2, depth[1])
+        rows = patch_rows(x, g2, d2, 2)                               # shared by the stage decoder and patch_embed3
+        del x
+        s2 = gemm(rows, "stage2_output_decode", M3, d3, 4 * d2, out=e16(M3, d3))
+        # ---- stage 3: patch_embed3's LayerNorm + GELU feeds patch_embed4 only, so it leaves as MXFP8
+        t = gemm(rows, "patch_embed3.proj", M3, d3, 4 * d2, out=e16(M3, d3))
+        del rows
+        h = mx(M3, d3)
+        ln_mx(t, "patch_embed3.norm", h, M3, d3, 1, ceps)
+        x = gemm(h, "patch_embed4", M3, d3, d3, out=t, res=w["pos_embed"], res_rows=T)
+        if depth[2]:
+            qkv, att, x2, hid = e16(M3, 3 * d3), e16(M3, d3), e16(M3, d3), mx(M3, r * d3)
+        for i in range(depth[2]):
+            b = f"blocks3.{i}"
+            ln_mx(x, b + ".norm1", h, M3, d3, 0, eps)
+            gemm(h, b + ".attn.qkv", M3, 3 * d3, d3, out=qkv)
+            call("isic_attention_f16", qkv, att, n, T, heads, d3 // heads)
+            call("isic_mxfp8_quantize", att, 0, h[0], h[1], M3, d3)
+            gemm(h, b + ".attn.proj", M3, d3, d3, out=x2, res=x)
+            ln_mx(x2, b + ".norm2", h, M3, d3, 0, eps)
+            gemm(h, b + ".mlp.fc1", M3, r * d3, d3, out_mx=hid, act=1)
+            gemm(hid, b + ".mlp.fc2", M3, d3, r * d3, out=x, res=x2)
+        call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, n * T, d3, 0, eps)
 
     def _run_chunk(self, img, w, out, depth):
         n, fold, spec = img.shape[0], self.fold_layernorm, self._blocks3_spec(self.tokens)

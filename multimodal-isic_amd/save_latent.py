@@ -5,8 +5,9 @@ What changes:
   * the encoder.  The reference runs an un-vendored ConvMAE conv-ViT (`save_latent.py:17-18,42-60`) whose code and
     weights are not in the tree.  ``encoder: convmae_base`` selects this build's restatement of it
     (``isic_hip.convmae.ConvMAEBaseEncoder``, 196 x 768 tokens; a checkpoint of the reference's ``train_ae.py`` loads into
-    it).  The default frozen encoder is the ResNet-18 of this build truncated after layer3
-    (``ResNet18Encoder.run_tokens``): 14 x 14 = 196 tokens of 256 channels for a 224 x 224 image, one per 16 x 16-pixel
+    it; ``encoder_precision: mxfp8`` runs its products on the block-scaled FP8 MFMA, on a GPU device only -- as for
+    ``encoder: vit_s16``, the one other encoder that takes it).  The default frozen encoder is the ResNet-18 of this
+    build truncated after layer3 (``ResNet18Encoder.run_tokens``): 14 x 14 = 196 tokens of 256 channels for a 224 x 224 image, one per 16 x 16-pixel
     patch -- the reference's token geometry (`:77`).  There is no random masking, so ``ids_keep = ids_restore =
     arange(196)`` (the reference passes ``mask_ratio=0``: every patch is kept, in shuffled order);
   * batched inference in HBM, the lesion-mask -> patch-flag step (`:73-87`) as one HIP launch
@@ -166,10 +167,11 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
         raise ValueError(f"encoder_precision: 'fp16' or 'mxfp8', got {precision!r}")
     name = str(config.get("encoder", "resnet18")).lower()
     if name in ("convmae_base", "convmae", "convmae_convvit_base_patch16"):
-        if precision != "fp16":
-            raise ValueError("encoder_precision must be 'fp16' for encoder: convmae_base (no MXFP8 path for it)")
-        from isic_hip.convmae import ConvMAEBaseEncoder          # the reference's encoder: 196 x 768 tokens, fp16
-        enc = ConvMAEBaseEncoder().to(device)
+        if precision == "mxfp8" and device.type != "cuda":
+            raise ValueError("encoder_precision='mxfp8' with encoder: convmae_base runs on gfx950's block-scaled MFMA: "
+                             f"it needs a GPU device, got device: {str(device)!r}")
+        from isic_hip.convmae import ConvMAEBaseEncoder          # the reference's encoder: 196 x 768 tokens
+        enc = ConvMAEBaseEncoder(precision=precision).to(device)  # "mxfp8": the opt-in MXFP8 products (isic_hip/convmae.py)
     elif name in ("vit_s16", "vit-s/16", "vit_small_patch16_224"):
         from isic_hip.vit import ViTSmallEncoder                # BASELINE.json configs[4]: ViT-S/16, fp16, 196 x 384 tokens
         enc = ViTSmallEncoder(precision=precision).to(device)   # "mxfp8": the opt-in MXFP8 products (isic_hip/vit.py)

@@ -5,8 +5,11 @@ time of each stage (blocks1, blocks2, blocks3 and the rest: patch embeddings, de
 with the stages cut off (``run_tokens(depth=...)``); the depthwise 5x5 convolution's GB/s over compulsory bytes (x read
 once, y written once) against the 6.3 TB/s measured copy rate; and products' TFLOP/s as a fraction of the ~2.5 PF dense
 fp16 MFMA peak.
+``--precision mxfp8`` measures the opt-in MXFP8 path instead; ``--precision both`` runs the fp16 and the MXFP8 forward of
+the same images alternately inside every round of one process and prints both medians, the range over the rounds and
+their ratio, then the three MXFP8 kernels of the convolutional front against their algorithmic bytes.
 Developer tool:
-    python tools/convmae_bench.py [--sizes 256 1024 2048] [--iters 3] [--repeats 3]"""
+    python tools/convmae_bench.py [--sizes 256 1024 2048] [--iters 3] [--repeats 3] [--precision fp16|mxfp8|both]"""
 import argparse
 import os
 import statistics
@@ -49,34 +52,51 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 1024, 2048])
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--precision", choices=("fp16", "mxfp8", "both"), default="fp16")
     a = ap.parse_args()
-    enc = ConvMAEBaseEncoder().to(DEV)
+    paths = ("fp16", "mxfp8") if a.precision == "both" else (a.precision,)
+    encs = {p: ConvMAEBaseEncoder(precision=p).to(DEV) for p in paths}
+    enc = encs[paths[0]]
     g = torch.Generator(device=DEV).manual_seed(0)
     xs = {n: torch.randn(n, 3, 224, 224, device=DEV, generator=g) for n in a.sizes}
     cuts = {"stems": (0, 0, 0), "blocks1": (2, 0, 0), "blocks2": (2, 2, 0), "full": (2, 2, 11)}
-    times = {(n, c): [] for n in a.sizes for c in cuts}
+    times = {(p, n, c): [] for p in paths for n in a.sizes for c in cuts}
     for r in range(a.repeats):
         for n in a.sizes:
             for c, d in cuts.items():
-                times[(n, c)].append(timeit(lambda: enc.run_tokens(xs[n], depth=d), a.iters))
-        print(f"round {r}: " + ", ".join(f"{n} images {times[(n, 'full')][-1]:.1f} ms" for n in a.sizes), flush=True)
+                for p in paths:                                   # the precisions alternate inside a round
+                    times[(p, n, c)].append(timeit(lambda: encs[p].run_tokens(xs[n], depth=d), a.iters))
+        print(f"round {r}: " + ", ".join(f"{p} {n} images {times[(p, n, 'full')][-1]:.1f} ms" for n in a.sizes for p in paths),
+              flush=True)
     fl = enc.flops_per_image()
     sf = stage_flops(enc)
     print(f"ConvMAE-Base: {fl / 1e9:.1f} GFLOP per image; max_batch {enc.max_batch}")
     for n in a.sizes:
-        m = {c: statistics.median(times[(n, c)]) for c in cuts}
-        st = {"patch embeds / decodes / norm": m["stems"], "blocks1": m["blocks1"] - m["stems"],
-              "blocks2": m["blocks2"] - m["blocks1"], "blocks3": m["full"] - m["blocks2"]}
-        tf = fl * n / m["full"] / 1e9
-        print(f"{n:5d} images: {m['full']:.1f} ms (median) = {n / m['full'] * 1e3:.0f} images/s, {tf:.0f} TFLOP/s "
-              f"= {tf / PEAK_F16_TFLOPS:.3f} of the dense fp16 peak")
-        for k, v in st.items():
-            extra = ""
-            if k in sf:
-                t = sf[k] * n / v / 1e9
-                extra = f"  {t:6.0f} TFLOP/s ({t / PEAK_F16_TFLOPS:.3f} of peak)"
-            print(f"    {k:30s} {v:8.2f} ms{extra}")
-    kernels(a)
+        med = {}
+        for p in paths:
+            m = med[p] = {c: statistics.median(times[(p, n, c)]) for c in cuts}
+            full = times[(p, n, "full")]
+            st = {"patch embeds / decodes / norm": m["stems"], "blocks1": m["blocks1"] - m["stems"],
+                  "blocks2": m["blocks2"] - m["blocks1"], "blocks3": m["full"] - m["blocks2"]}
+            tf = fl * n / m["full"] / 1e9
+            print(f"{n:5d} images, {p}: {m['full']:.1f} ms (median of {a.repeats}, range {min(full):.1f} - {max(full):.1f}) = "
+                  f"{n / m['full'] * 1e3:.0f} images/s, {tf:.0f} TFLOP/s = {tf / PEAK_F16_TFLOPS:.3f} of the dense fp16 peak")
+            for k, v in st.items():
+                extra = ""
+                if k in sf:
+                    t = sf[k] * n / v / 1e9
+                    extra = f"  {t:6.0f} TFLOP/s ({t / PEAK_F16_TFLOPS:.3f} of peak)"
+                print(f"    {k:30s} {v:8.2f} ms{extra}")
+        if len(paths) == 2:
+            f, q = med["fp16"], med["mxfp8"]
+            stages = (("stems", None), ("blocks1", "stems"), ("blocks2", "blocks1"), ("full", "blocks2"))
+            ratio = ", ".join(f"{c if c != 'full' else 'blocks3'} {(f[c] - (f[b] if b else 0)) / (q[c] - (q[b] if b else 0)):.2f}x"
+                              for c, b in stages)
+            print(f"{n:5d} images: mxfp8 / fp16 speed-up (medians) {f['full'] / q['full']:.3f}x; per stage: {ratio}")
+    if a.precision in ("fp16", "both"):
+        kernels(a)
+    if a.precision in ("mxfp8", "both"):
+        mxfp8_kernels(a)
 
 
 def kernels(a):
@@ -101,6 +121,37 @@ def kernels(a):
         tf = 2.0 * M * N * K / t / 1e9
         print(f"  gemm_f16 {name:24s} {t:7.3f} ms {tf:6.0f} TFLOP/s = {tf / PEAK_F16_TFLOPS:.3f} of peak")
         del A, C
+
+
+def mxfp8_kernels(a):
+    """the three MXFP8 kernels of the convolutional front at the encoder's shapes, against their algorithmic bytes (the
+    fp16 input read once, one byte per element and one scale byte per 32 written) and the measured copy rate"""
+    n, u8 = 256, torch.uint8
+    print(f"mxfp8 single launches at {n} images (one chunk); bytes = fp16 in + 1 B / element + 1 B / 32 out:")
+
+    def report(name, t, elems):
+        gbs = elems * (2 + 1 + 1 / 32) / t / 1e6
+        print(f"  {name:38s} {t * 1e3:7.1f} us, {gbs:6.0f} GB/s = {gbs / 1e3 / COPY_TBS:.2f} of {COPY_TBS} TB/s")
+    for H, C in ((56, 256), (28, 384)):
+        M = n * H * H
+        x = (torch.randn(M, C, device=DEV) * 0.5).to(F16)
+        q, s = torch.empty(M, C, device=DEV, dtype=u8), torch.empty(M, C // 32, device=DEV, dtype=u8)
+        w, b = torch.randn(25, C, device=DEV) * 0.2, torch.zeros(C, device=DEV)
+        gam, bet = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+        t = timeit(lambda: call("isic_dwconv5x5_mxfp8_f16", x, w, b, q, s, n, H, H, C), a.iters * 4)
+        report(f"dwconv5x5 -> mxfp8 {H}x{H}x{C}", t, M * C)
+        t = timeit(lambda: call("isic_layernorm_act_mxfp8_f16", x, gam, bet, q, s, M, C, 0, 1e-5), a.iters * 4)
+        report(f"layernorm -> mxfp8 {M} x {C}", t, M * C)
+        for P in ((4, 2) if H == 56 else (2,)):
+            t = timeit(lambda: call("isic_patch_rows_mxfp8_nhwc_f16", x, q, s, n, H, H, C, P), a.iters * 4)
+            report(f"patch rows -> mxfp8 {H}x{H}x{C} P={P}", t, M * C)
+        del x, q, s
+    M, C = n * 196, 768
+    x = (torch.randn(M, C, device=DEV) * 0.5).to(F16)
+    q, s = torch.empty(M, C, device=DEV, dtype=u8), torch.empty(M, C // 32, device=DEV, dtype=u8)
+    gam, bet = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+    t = timeit(lambda: call("isic_layernorm_act_mxfp8_f16", x, gam, bet, q, s, M, C, 1, 1e-5), a.iters * 4)
+    report(f"layernorm + GELU -> mxfp8 {M} x {C}", t, M * C)
 
 
 if __name__ == "__main__":
