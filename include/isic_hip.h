@@ -85,7 +85,8 @@ int isic_gemm_f32_add_ws(int transA, int transB, int M, int N, int K, const floa
 /* out[n] = sum_m X[m,n] (+ beta*out): bias gradients of the layers above. */
 int isic_colsum_f32(const float* X, int M, int N, int ldx, float* out, float beta, void* stream);
 /* ... with a workspace (isic_colsum_f32_workspace_bytes(M, N) bytes; may be NULL / 0): the row chunks of a tall matrix
- * are then added in chunk order instead of through fp32 atomics -- bit-reproducible. */
+ * are then added in chunk order instead of through fp32 atomics -- bit-reproducible, for every N and ldx (the size covers
+ * both the 16-byte-vector kernel and the scalar one that N, ldx or X not a multiple of 4 floats falls back to). */
 size_t isic_colsum_f32_workspace_bytes(int M, int N);
 int isic_colsum_f32_ws(const float* X, int M, int N, int ldx, float* out, float beta, void* workspace,
                        size_t workspace_bytes, void* stream);
@@ -154,7 +155,10 @@ int isic_relu_dropout_fwd_clk_f32(float* x, int64_t n, uint32_t drop_threshold, 
  * Replaces utils_g_mil.py:72-97 (AttentionMIL_teacher), utils_g_mil.py:32-33
  * (AttentionMIL) and the multi-head pool 05_train_gnns.py:205-213.
  * Any output pointer may be NULL (skipped) except att.  max_bag >= the longest
- * bag (the per-bag scores live in LDS: max_bag*heads <= ~30k); H <= 1024, C <= 16. */
+ * bag (the per-bag scores live in LDS: max_bag*heads <= ~30k); H <= 1024, C <= 16.
+ * Any number of heads: the forward runs them in groups of 4, one launch each, the later launches adding into z.
+ * EMPTY BAGS (offsets[b] == offsets[b+1], anywhere, the last bag and max_bag == 0 included) are allowed: such a bag
+ * reads no row of h / t and writes no row of att / patch_*; z[b,:] = 0, bag_logits[b,:] = 0, bag_probs[b,:] = 1 / C. */
 int isic_attn_pool_fwd(const float* h, const float* t, const float* w3, const float* b3, const float* W4,
                        const float* b4, const int64_t* offsets, int B, int H, int A, int heads, int C, int max_bag,
                        float* att, float* z, float* patch_logits, float* patch_probs, float* bag_logits,
@@ -165,7 +169,9 @@ int isic_attn_pool_fwd(const float* h, const float* t, const float* w3, const fl
  *   d_u[T,heads*A]: gradient w.r.t. the PRE-tanh attention hidden (ds * w3 * (1-t^2))
  *   d_s[T,heads]: gradient of the raw scores, d_P[T,C]: gradient of patch logits
  * The weight gradients follow with isic_gemm_f32 / isic_colsum_f32
- * (dW4 = d_P^T h, dw3 = d_s^T t, dW2 = d_u^T h ...). */
+ * (dW4 = d_P^T h, dw3 = d_s^T t, dW2 = d_u^T h ...).
+ * heads <= 4 (one launch holds every head; ISIC_ERR_UNSUPPORTED beyond, before any device work).  An empty bag reads and
+ * writes no row; its row of param_sums is zero. */
 int isic_attn_pool_bwd(const float* h, const float* t, const float* att, const float* patch_logits,
                        const float* w3, const float* W4, const int64_t* offsets, int B, int H, int A, int heads,
                        int C, int max_bag, const float* d_bag_logits, const float* d_z, float* d_h,
@@ -185,7 +191,10 @@ int isic_attn_pool_bwd_sums(const float* h, const float* t, const float* att, co
  * y = dropout(relu?(LN(x) * gamma + beta)) + residual      rows of length N.
  * Replaces 05_train_gnns.py:187-199 (LayerNorm -> relu -> dropout -> +h_prev)
  * and model.py:75-82 (Linear -> LayerNorm -> ReLU -> Dropout).
- * Saves mean[M], rstd[M] for backward.  residual may be NULL. */
+ * Saves mean[M], rstd[M] for backward.  residual may be NULL.
+ * Dropout element index: row * N + j.  The forward takes ANY row length N > 0 (N in {64, 128, 256} with 16-byte aligned
+ * x, y, gamma, beta, residual runs the vector kernel, everything else one wave per row); the backward forms take
+ * N <= 1024 and return ISIC_ERR_UNSUPPORTED beyond, before any device work. */
 int isic_layernorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
                        float* mean, float* rstd, int M, int N, float eps, int relu, uint32_t drop_threshold,
                        float drop_scale, uint64_t seed, uint64_t stream_id, void* stream);
@@ -281,7 +290,10 @@ int isic_mask_patch_flags_f32(const float* mask, uint8_t* flags, int64_t B, int 
  * bwd: de[nnz,H] = d logit (workspace and output), dqd = d loss / d qd, dks = d loss / d ks (mode 0: including the
  * value path, v == ks), dv = d loss / d v (mode 1 only), datt[H,F] += d loss / d att (mode 0 only; zero it first; any
  * H, F: kept in registers across rows while H * ceil(F/64) <= 16 -- the reference class defaults, hidden 256 x 4 heads,
- * included -- one atomic per element and row beyond that). */
+ * included -- one atomic per element and row beyond that; either way the waves' sums meet through fp32 atomics, so datt is
+ * the one output here that is not bit-reproducible).
+ * For information, not a limit: a destination row of up to 512 stored entries keeps its per-edge logits / gradients in
+ * LDS; a longer row (isic_gat_bwd likewise) parks them in alpha / de in global memory between its two sweeps. */
 int isic_edge_attn_fwd(int mode, const float* ks, const float* qd, const float* v, const float* att, const int32_t* rowptr,
                        const int32_t* col, const float* bias, float* out, float* alpha, int64_t N, int H, int F,
                        float negative_slope, float scale, uint32_t drop_threshold, float drop_scale, uint64_t seed,

@@ -210,9 +210,11 @@ __global__ void gemm_scale_kernel(float* __restrict__ C, int M, int N, int ldc, 
 }
 
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, int M, int N, int ldx,
-                                                      float* __restrict__ out, float beta, int rows_per_block) {
+                                                      float* __restrict__ out, float beta, int rows_per_block,
+                                                      float* __restrict__ partial) {
   // one block per 64 columns x row chunk; 4 waves stride the rows; deterministic tree over waves.  With more than
-  // one row chunk (gridDim.y > 1) the chunk sums are atomically added to the pre-scaled output.
+  // one row chunk (gridDim.y > 1) the chunk sums are parked in `partial` ([gridDim.y][N], added in chunk order by
+  // colsum_reduce_kernel) or, without a workspace, atomically added to the pre-scaled output.
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = blockIdx.x * 64 + lane;
@@ -224,7 +226,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
   __syncthreads();
   if (wave == 0 && col < N) {
     float t = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-    if (gridDim.y > 1) atomicAdd(out + col, t);
+    if (partial) partial[(size_t)blockIdx.y * N + col] = t;
+    else if (gridDim.y > 1) atomicAdd(out + col, t);
     else out[col] = beta != 0.f ? beta * out[col] + t : t;
   }
 }
@@ -535,9 +538,27 @@ int isic_multi_copy_f32(int nseg, float* const* dst, const float* const* src, co
   return isic_launch_status();
 }
 
+// Row chunks of the scalar colsum_kernel (N, ldx or the pointer not a multiple of 4 floats): M >= 8192 rows are cut into up
+// to 1024 / ceil(N / 64) chunks of >= 1024 rows.  The launch and the workspace size both take the count from here.
+static int colsum_scalar_chunks(int M, int N) {
+  int chunks = 1;
+  const int colblocks = ceil_div(N, 64);
+  if (M >= 8192 && colblocks < 256) {
+    chunks = (1024 + colblocks - 1) / colblocks;
+    if (chunks > M / 1024) chunks = M / 1024;
+    if (chunks < 1) chunks = 1;
+  }
+  const int rows_per_block = ceil_div(M > 0 ? M : 1, chunks);
+  return ceil_div(M > 0 ? M : 1, rows_per_block);
+}
+
 size_t isic_colsum_f32_workspace_bytes(int M, int N) {
-  if (M < 1024 || N <= 0 || N % 4 != 0) return 0;
-  return (size_t)96 * N * sizeof(float) + 256;             // at most 96 row chunks (colsum4_kernel's launch shape)
+  if (M < 1024 || N <= 0) return 0;
+  // at most 96 row chunks on the vector path (colsum4_kernel's launch shape), colsum_scalar_chunks on the scalar one
+  int chunks = 96;
+  const int c = colsum_scalar_chunks(M, N);
+  if (c > chunks) chunks = c;
+  return (size_t)chunks * N * sizeof(float) + 256;
 }
 
 int isic_colsum_f32(const float* X, int M, int N, int ldx, float* out, float beta, void* stream) {
@@ -574,23 +595,22 @@ int isic_colsum_f32_ws(const float* X, int M, int N, int ldx, float* out, float 
     return isic_launch_status();
   }
   // few column blocks x many rows (bias gradients over all the nodes of a batch): split the rows over blockIdx.y
-  int chunks = 1;
   const int colblocks = ceil_div(N, 64);
-  if (M >= 8192 && colblocks < 256) {
-    chunks = (1024 + colblocks - 1) / colblocks;
-    if (chunks > M / 1024) chunks = M / 1024;
-    if (chunks < 1) chunks = 1;
-  }
+  const int chunks = colsum_scalar_chunks(M, N);
   const int rows_per_block = ceil_div(M > 0 ? M : 1, chunks);
-  chunks = ceil_div(M > 0 ? M : 1, rows_per_block);
   if (chunks == 1) {
     hipLaunchKernelGGL(colsum_small_kernel, dim3(colblocks), dim3(1024), 0, as_stream(stream), X, M, N, ldx, out, beta);
     return isic_launch_status();
   }
-  if (chunks > 1)
+  float* partial = nullptr;                                        // deterministic path, as above
+  if (workspace && workspace_bytes >= (size_t)chunks * N * sizeof(float)) partial = reinterpret_cast<float*>(workspace);
+  if (!partial)
     hipLaunchKernelGGL(gemm_scale_kernel, dim3(1), dim3(256), 0, as_stream(stream), out, 1, N, N, beta);
   hipLaunchKernelGGL(colsum_kernel, dim3(colblocks, chunks), dim3(256), 0, as_stream(stream), X, M, N, ldx, out, beta,
-                     rows_per_block);
+                     rows_per_block, partial);
+  if (partial)
+    hipLaunchKernelGGL(colsum_reduce_kernel, dim3(ceil_div(N, 16)), dim3(256), 0, as_stream(stream), partial, chunks, N, out,
+                       beta);
   return isic_launch_status();
 }
 
