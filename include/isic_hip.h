@@ -293,7 +293,9 @@ int isic_mask_patch_flags_f32(const float* mask, uint8_t* flags, int64_t B, int 
  * included -- one atomic per element and row beyond that; either way the waves' sums meet through fp32 atomics, so datt is
  * the one output here that is not bit-reproducible).
  * For information, not a limit: a destination row of up to 512 stored entries keeps its per-edge logits / gradients in
- * LDS; a longer row (isic_gat_bwd likewise) parks them in alpha / de in global memory between its two sweeps. */
+ * LDS; a longer row (isic_gat_bwd likewise) parks them in alpha / de in global memory between its two sweeps.
+ * These are the concat=True forms; the head mean of concat=False (out [N,F], bias [F]) is isic_edge_attn_fwd_mean /
+ * isic_edge_attn_bwd_mean of isic_hip_attn_mean.h. */
 int isic_edge_attn_fwd(int mode, const float* ks, const float* qd, const float* v, const float* att, const int32_t* rowptr,
                        const int32_t* col, const float* bias, float* out, float* alpha, int64_t N, int H, int F,
                        float negative_slope, float scale, uint32_t drop_threshold, float drop_scale, uint64_t seed,
@@ -396,7 +398,9 @@ int isic_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* va
  *   alpha (counter-based, element index = slot*H + h), out[dst,h,:] = sum alpha x'[src,h,:] + bias.
  * x' is [N, H*F]; alpha[nnz, H] (pre-dropout) is saved for the backward pass, which returns
  * d x' (aggregation + score paths), d al, d ar and uses de[nnz,H] as scratch; the att_src /
- * att_dst gradients follow as dal^T x' / dar^T x' per head (isic_gemm_f32). */
+ * att_dst gradients follow as dal^T x' / dar^T x' per head (isic_gemm_f32).
+ * concat=False (the mean over heads, out [N,F], bias [F]): isic_gat_fwd_mean / isic_gat_bwd_mean of
+ * isic_hip_attn_mean.h, after the same isic_gat_scores. */
 int isic_gat_scores(const float* xp, const float* att_src, const float* att_dst, float* al, float* ar, int64_t N, int H,
                     int F, void* stream);
 int isic_gat_fwd(const float* xp, const float* al, const float* ar, const int32_t* rowptr, const int32_t* col,
@@ -657,5 +661,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_bn_pair.h"
 /* The opt-in MXFP8 inference path of the ConvMAE-Base encoder (LayerNorm, depthwise 5x5 and patch rows with MXFP8 outputs): three more entry points, same conventions. */
 #include "isic_hip_convmae_mxfp8.h"
+/* Head-averaged attention (concat=False) of GATConv / GATv2Conv / TransformerConv, the mean formed inside the kernels: four more entry points, same conventions. */
+#include "isic_hip_attn_mean.h"
 
 #endif /* ISIC_HIP_H */

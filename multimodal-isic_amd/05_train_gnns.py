@@ -83,9 +83,10 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
     """`05:305-358` (model configuration of the reference call site, `05:310-326`)."""
     set_seed(args.seed + fold)
     model = GraphMIL(input_dim=input_dim, gnn_type=args.gnn if isinstance(args.gnn, str) else args.gnn[0],
-                     gnn_hidden=args.hidden_dim, gnn_layers=args.num_layers, gnn_dropout=args.dropout, gnn_heads=4,
-                     gnn_concat=True, att_dim=128, att_heads=4, pool_dropout=0.2, classifier_dim=128,
-                     classifier_light=True, num_classes=num_classes, use_residual=True, use_layer_norm=True).to(device)
+                     gnn_hidden=args.hidden_dim, gnn_layers=args.num_layers, gnn_dropout=args.dropout,
+                     gnn_heads=args.gnn_heads, gnn_concat=args.gnn_concat, att_dim=128, att_heads=4, pool_dropout=0.2,
+                     classifier_dim=128, classifier_light=True, num_classes=num_classes, use_residual=True,
+                     use_layer_norm=True).to(device)
     model.set_dropout_state(args.seed + fold, 0)
     return T.train_gnn_fold(model, train_records, val_records, test_records, lr=args.learning_rate,
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
@@ -126,6 +127,9 @@ def parse_args(argv=None):
     p.add_argument("--variants", nargs="*", default=graph_variants())
     p.add_argument("--folds", nargs="*", type=int, default=list(range(1)))
     p.add_argument("--gnn", nargs="+", choices=GNN_TYPES, default=["mlp", "gcn", "gcnii", "graphsage", "gin", "gat"])
+    p.add_argument("--gnn-heads", type=int, default=4, help="heads of gat / gatv2 / transformer (reference call site: 4)")
+    p.add_argument("--no-gnn-concat", dest="gnn_concat", action="store_false",
+                   help="average the attention heads instead of concatenating them (PyG concat=False)")
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--patience", type=int, default=16)
     p.add_argument("--min-delta", type=float, default=1e-6)

@@ -12,7 +12,11 @@
 // rows -- no atomics, no scatter.  Backward is a destination sweep (d logit per edge, the destination-side gradient)
 // and a source sweep over the transposed CSR (source-side and value gradients), linked by perm_t.  Only the tiny
 // d att[H,F] of GATv2 is reduced across rows: persistent blocks keep it in registers and add it once.
+//
+// MEAN = true is ``concat=False``: out[dst,:] = (1/H) sum_h out[dst,h,:] + bias[:], formed by the wave that owns the row
+// (head_mean.inc), and the backward reads dout[N,F]; nothing of width H*F exists on the output side.
 #include "common.h"
+#include "head_mean.inc"
 
 namespace {
 
@@ -35,7 +39,7 @@ __device__ __forceinline__ float edge_logit(const float* __restrict__ ks_row, co
 }
 
 // forward: wave per destination row.  alpha[nnz,H] receives the PRE-dropout attention.
-template <int MODE>
+template <int MODE, bool MEAN>
 __global__ __launch_bounds__(256) void edge_attn_fwd_kernel(const float* __restrict__ ks, const float* __restrict__ qd,
                                                              const float* __restrict__ v, const float* __restrict__ att,
                                                              const int* __restrict__ rowptr, const int* __restrict__ col,
@@ -49,6 +53,8 @@ __global__ __launch_bounds__(256) void edge_attn_fwd_kernel(const float* __restr
   if (i >= N) return;
   const int b = rowptr[i], e = rowptr[i + 1];
   const bool in_lds = (e - b) <= MAXE;
+  HeadMeanRow hm;                                                  // MEAN: the row's sum over heads
+  const bool hm_regs = head_mean_in_regs(F);
   for (int h = 0; h < H; ++h) {
     const float* qrow = qd + (i * H + h) * F;
     const float* att_h = att ? att + h * F : nullptr;
@@ -66,7 +72,7 @@ __global__ __launch_bounds__(256) void edge_attn_fwd_kernel(const float* __restr
     if (in_lds) __builtin_amdgcn_wave_barrier();
     else __threadfence();
     const float inv = e > b ? 1.f / s : 0.f;
-    for (int f0 = lane; f0 < F; f0 += 64) {
+    for (int f0 = lane, q = 0; f0 < F; f0 += 64, ++q) {
       float acc = 0.f;
       for (int p = b; p < e; ++p) {
         const float lg = in_lds ? slog[wave][p - b] : __builtin_nontemporal_load(&alpha[(int64_t)p * H + h]);
@@ -74,7 +80,8 @@ __global__ __launch_bounds__(256) void edge_attn_fwd_kernel(const float* __restr
         if (thr) a = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? a * dscale : 0.f;
         acc += a * v[((int64_t)col[p] * H + h) * F + f0];
       }
-      out[(i * H + h) * F + f0] = acc + (bias ? bias[h * F + f0] : 0.f);
+      if (MEAN) hm.add(acc, out + i * F + f0, q, h, hm_regs);
+      else out[(i * H + h) * F + f0] = acc + (bias ? bias[h * F + f0] : 0.f);
     }
     __builtin_amdgcn_wave_barrier();                               // every lane has read the logits
     for (int p = b + lane; p < e; p += 64) {
@@ -83,11 +90,12 @@ __global__ __launch_bounds__(256) void edge_attn_fwd_kernel(const float* __restr
     }
     __builtin_amdgcn_wave_barrier();                               // slog is reused by the next head
   }
+  if (MEAN) hm.finish(out + i * F, bias, 1.f / (float)H, F, lane, hm_regs);
 }
 
 // backward sweep 1: persistent blocks, wave per destination row.  de[nnz,H] = d logit; dqd[N,H,F] = destination-side
 // gradient (d q for DOT, d xr for GATv2); datt[H,F] (GATv2) accumulated in registers over all rows of the wave.
-template <int MODE>
+template <int MODE, bool MEAN>
 __global__ __launch_bounds__(256) void edge_attn_bwd_dst_kernel(const float* __restrict__ dout, const float* __restrict__ ks,
                                                                  const float* __restrict__ qd, const float* __restrict__ v,
                                                                  const float* __restrict__ att, const float* __restrict__ alpha,
@@ -110,14 +118,13 @@ __global__ __launch_bounds__(256) void edge_attn_bwd_dst_kernel(const float* __r
   for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < N; i += (int64_t)gridDim.x * 4) {
     const int b = rowptr[i], e = rowptr[i + 1];
     const bool in_lds = (e - b) <= MAXE;
+    HeadMeanDout<MEAN> hd(dout + i * F, F, H, lane);               // MEAN: row i of dout[N,F], read once for all heads
     for (int h = 0; h < H; ++h) {
-      const float* drow = dout + (i * H + h) * F;
+      const float* drow = dout + (MEAN ? i : i * H + h) * F;
       float dot = 0.f;
       for (int p = b; p < e; ++p) {
         const float* vr = v + ((int64_t)col[p] * H + h) * F;
-        float d = 0.f;
-        for (int f = lane; f < F; f += 64) d += drow[f] * vr[f];
-        d = wave_sum(d);
+        float d = hd.dot(drow, vr, F, lane);
         if (thr) d = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? d * dscale : 0.f;
         dot += alpha[(int64_t)p * H + h] * d;
         if (lane == 0) {
@@ -127,9 +134,20 @@ __global__ __launch_bounds__(256) void edge_attn_bwd_dst_kernel(const float* __r
       }
       if (in_lds) __builtin_amdgcn_wave_barrier();
       else __threadfence();
-      for (int p = b + lane; p < e; p += 64) {
-        const float da = in_lds ? sda[wave][p - b] : __builtin_nontemporal_load(&de[(int64_t)p * H + h]);
-        de[(int64_t)p * H + h] = alpha[(int64_t)p * H + h] * (da - dot);      // softmax backward
+      if (!MEAN) {
+        for (int p = b + lane; p < e; p += 64) {
+          const float da = in_lds ? sda[wave][p - b] : __builtin_nontemporal_load(&de[(int64_t)p * H + h]);
+          de[(int64_t)p * H + h] = alpha[(int64_t)p * H + h] * (da - dot);      // softmax backward
+        }
+      } else if (in_lds) {
+        // the same, one loop per parking place: in the <DOT, MEAN> kernel this hipcc merges the two loads of the loop above
+        // into one flat load through a pointer that is LDS or global, and then cannot select it for gfx950
+        for (int p = b + lane; p < e; p += 64) de[(int64_t)p * H + h] = alpha[(int64_t)p * H + h] * (sda[wave][p - b] - dot);
+      } else {
+        for (int p = b + lane; p < e; p += 64) {
+          const float da = __builtin_nontemporal_load(&de[(int64_t)p * H + h]);
+          de[(int64_t)p * H + h] = alpha[(int64_t)p * H + h] * (da - dot);
+        }
       }
       __threadfence();                                             // d logit of this row is re-read just below
       const float* qrow = qd + (i * H + h) * F;
@@ -171,7 +189,7 @@ __global__ __launch_bounds__(256) void edge_attn_bwd_dst_kernel(const float* __r
 
 // backward sweep 2, wave per source row (transposed CSR): dks[N,H,F] (source-side logit gradient; for GATv2 the value
 // gradient is added, v == xl) and dv[N,H,F] (DOT only).
-template <int MODE>
+template <int MODE, bool MEAN>
 __global__ __launch_bounds__(256) void edge_attn_bwd_src_kernel(const float* __restrict__ dout, const float* __restrict__ ks,
                                                                  const float* __restrict__ qd, const float* __restrict__ att,
                                                                  const float* __restrict__ alpha, const float* __restrict__ de,
@@ -193,7 +211,7 @@ __global__ __launch_bounds__(256) void edge_attn_bwd_src_kernel(const float* __r
         const int64_t dst = col_t[pt];
         float a = alpha[(int64_t)p * H + h];
         if (thr) a = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? a * dscale : 0.f;
-        gv += a * dout[(dst * H + h) * F + f0];
+        gv += a * dout[MEAN ? dst * F + f0 : (dst * H + h) * F + f0];
         const float g = de[(int64_t)p * H + h];
         if (MODE == EA_GATV2) {
           const float sv = ksv + qd[(dst * H + h) * F + f0];
@@ -202,6 +220,7 @@ __global__ __launch_bounds__(256) void edge_attn_bwd_src_kernel(const float* __r
           gk += g * qd[(dst * H + h) * F + f0] * scale;
         }
       }
+      if (MEAN) gv *= 1.f / (float)H;                              // the mean's factor, once on the sum
       if (MODE == EA_GATV2) dks[(s * H + h) * F + f0] = gk + gv;
       else { dks[(s * H + h) * F + f0] = gk; dv[(s * H + h) * F + f0] = gv; }
     }
@@ -287,30 +306,64 @@ __global__ __launch_bounds__(256) void fa_bwd_src_kernel(const float* __restrict
   }
 }
 
-template <int MODE>
+template <int MODE, bool MEAN>
 int launch_fwd(const float* ks, const float* qd, const float* v, const float* att, const int32_t* rowptr, const int32_t* col,
                const float* bias, float* out, float* alpha, int64_t N, int H, int F, float slope, float scale, uint32_t thr,
                float dscale, uint64_t seed, uint64_t stream_id, hipStream_t s) {
-  hipLaunchKernelGGL((edge_attn_fwd_kernel<MODE>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, ks, qd, v, att, rowptr, col,
+  hipLaunchKernelGGL((edge_attn_fwd_kernel<MODE, MEAN>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, ks, qd, v, att, rowptr, col,
                      bias, out, alpha, N, H, F, slope, scale, thr, dscale, (unsigned long long)seed,
                      (unsigned long long)stream_id);
   return isic_launch_status();
 }
 
-template <int MODE>
+template <int MODE, bool MEAN>
 int launch_bwd(const float* dout, const float* ks, const float* qd, const float* v, const float* att, const float* alpha,
                const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t,
                float* de, float* dqd, float* dks, float* dv, float* datt, int64_t N, int H, int F, float slope, float scale,
                uint32_t thr, float dscale, uint64_t seed, uint64_t stream_id, hipStream_t s) {
   int64_t blocks = (N + 3) / 4;
   if (blocks > 2048) blocks = 2048;                                // persistent: d att lives in registers across rows
-  hipLaunchKernelGGL((edge_attn_bwd_dst_kernel<MODE>), dim3((unsigned)blocks), dim3(256), 0, s, dout, ks, qd, v, att, alpha,
+  hipLaunchKernelGGL((edge_attn_bwd_dst_kernel<MODE, MEAN>), dim3((unsigned)blocks), dim3(256), 0, s, dout, ks, qd, v, att, alpha,
                      rowptr, col, de, dqd, datt, N, H, F, slope, scale, thr, dscale, (unsigned long long)seed,
                      (unsigned long long)stream_id);
-  hipLaunchKernelGGL((edge_attn_bwd_src_kernel<MODE>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, dout, ks, qd, att, alpha,
+  hipLaunchKernelGGL((edge_attn_bwd_src_kernel<MODE, MEAN>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, dout, ks, qd, att, alpha,
                      de, rowptr_t, col_t, perm_t, dks, dv, N, H, F, slope, scale, thr, dscale, (unsigned long long)seed,
                      (unsigned long long)stream_id);
   return isic_launch_status();
+}
+
+template <bool MEAN>
+int edge_attn_fwd(int mode, const float* ks, const float* qd, const float* v, const float* att, const int32_t* rowptr,
+                       const int32_t* col, const float* bias, float* out, float* alpha, int64_t N, int H, int F,
+                       float negative_slope, float scale, uint32_t drop_threshold, float drop_scale, uint64_t seed,
+                       uint64_t stream_id, void* stream) {
+  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0 && (mode == EA_GATV2 || mode == EA_DOT));
+  if (N == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(ks && qd && v && rowptr && col && out && alpha && (mode != EA_GATV2 || att));
+  hipStream_t s = as_stream(stream);
+  return mode == EA_GATV2 ? launch_fwd<EA_GATV2, MEAN>(ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale,
+                                                 drop_threshold, drop_scale, seed, stream_id, s)
+                          : launch_fwd<EA_DOT, MEAN>(ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale,
+                                               drop_threshold, drop_scale, seed, stream_id, s);
+}
+
+template <bool MEAN>
+int edge_attn_bwd(int mode, const float* dout, const float* ks, const float* qd, const float* v, const float* att,
+                       const float* alpha, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t,
+                       const int32_t* col_t, const int32_t* perm_t, float* de, float* dqd, float* dks, float* dv, float* datt,
+                       int64_t N, int H, int F, float negative_slope, float scale, uint32_t drop_threshold, float drop_scale,
+                       uint64_t seed, uint64_t stream_id, void* stream) {
+  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0 && (mode == EA_GATV2 || mode == EA_DOT));
+  if (N == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(dout && ks && qd && v && alpha && rowptr && col && rowptr_t && col_t && perm_t && de && dqd && dks);
+  ISIC_CHECK_ARG(mode == EA_GATV2 ? (att && datt) : (dv != nullptr));
+  hipStream_t s = as_stream(stream);
+  return mode == EA_GATV2 ? launch_bwd<EA_GATV2, MEAN>(dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd,
+                                                 dks, dv, datt, N, H, F, negative_slope, scale, drop_threshold, drop_scale,
+                                                 seed, stream_id, s)
+                          : launch_bwd<EA_DOT, MEAN>(dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd, dks,
+                                               dv, datt, N, H, F, negative_slope, scale, drop_threshold, drop_scale, seed,
+                                               stream_id, s);
 }
 
 }  // namespace
@@ -321,14 +374,8 @@ int isic_edge_attn_fwd(int mode, const float* ks, const float* qd, const float* 
                        const int32_t* col, const float* bias, float* out, float* alpha, int64_t N, int H, int F,
                        float negative_slope, float scale, uint32_t drop_threshold, float drop_scale, uint64_t seed,
                        uint64_t stream_id, void* stream) {
-  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0 && (mode == EA_GATV2 || mode == EA_DOT));
-  if (N == 0) return ISIC_OK;
-  ISIC_CHECK_ARG(ks && qd && v && rowptr && col && out && alpha && (mode != EA_GATV2 || att));
-  hipStream_t s = as_stream(stream);
-  return mode == EA_GATV2 ? launch_fwd<EA_GATV2>(ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale,
-                                                 drop_threshold, drop_scale, seed, stream_id, s)
-                          : launch_fwd<EA_DOT>(ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale,
-                                               drop_threshold, drop_scale, seed, stream_id, s);
+  return edge_attn_fwd<false>(mode, ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale, drop_threshold,
+                       drop_scale, seed, stream_id, stream);
 }
 
 int isic_edge_attn_bwd(int mode, const float* dout, const float* ks, const float* qd, const float* v, const float* att,
@@ -336,17 +383,25 @@ int isic_edge_attn_bwd(int mode, const float* dout, const float* ks, const float
                        const int32_t* col_t, const int32_t* perm_t, float* de, float* dqd, float* dks, float* dv, float* datt,
                        int64_t N, int H, int F, float negative_slope, float scale, uint32_t drop_threshold, float drop_scale,
                        uint64_t seed, uint64_t stream_id, void* stream) {
-  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0 && (mode == EA_GATV2 || mode == EA_DOT));
-  if (N == 0) return ISIC_OK;
-  ISIC_CHECK_ARG(dout && ks && qd && v && alpha && rowptr && col && rowptr_t && col_t && perm_t && de && dqd && dks);
-  ISIC_CHECK_ARG(mode == EA_GATV2 ? (att && datt) : (dv != nullptr));
-  hipStream_t s = as_stream(stream);
-  return mode == EA_GATV2 ? launch_bwd<EA_GATV2>(dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd,
-                                                 dks, dv, datt, N, H, F, negative_slope, scale, drop_threshold, drop_scale,
-                                                 seed, stream_id, s)
-                          : launch_bwd<EA_DOT>(dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd, dks,
-                                               dv, datt, N, H, F, negative_slope, scale, drop_threshold, drop_scale, seed,
-                                               stream_id, s);
+  return edge_attn_bwd<false>(mode, dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd, dks, dv, datt, N,
+                       H, F, negative_slope, scale, drop_threshold, drop_scale, seed, stream_id, stream);
+}
+
+int isic_edge_attn_fwd_mean(int mode, const float* ks, const float* qd, const float* v, const float* att, const int32_t* rowptr,
+                       const int32_t* col, const float* bias, float* out, float* alpha, int64_t N, int H, int F,
+                       float negative_slope, float scale, uint32_t drop_threshold, float drop_scale, uint64_t seed,
+                       uint64_t stream_id, void* stream) {
+  return edge_attn_fwd<true>(mode, ks, qd, v, att, rowptr, col, bias, out, alpha, N, H, F, negative_slope, scale, drop_threshold,
+                       drop_scale, seed, stream_id, stream);
+}
+
+int isic_edge_attn_bwd_mean(int mode, const float* dout, const float* ks, const float* qd, const float* v, const float* att,
+                       const float* alpha, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t,
+                       const int32_t* col_t, const int32_t* perm_t, float* de, float* dqd, float* dks, float* dv, float* datt,
+                       int64_t N, int H, int F, float negative_slope, float scale, uint32_t drop_threshold, float drop_scale,
+                       uint64_t seed, uint64_t stream_id, void* stream) {
+  return edge_attn_bwd<true>(mode, dout, ks, qd, v, att, alpha, rowptr, col, rowptr_t, col_t, perm_t, de, dqd, dks, dv, datt, N,
+                       H, F, negative_slope, scale, drop_threshold, drop_scale, seed, stream_id, stream);
 }
 
 int isic_fa_fwd(const float* x, const float* x0, const float* al, const float* ar, const int32_t* rowptr, const int32_t* col,

@@ -11,7 +11,11 @@
 // then an online-softmax weighted sum of coalesced neighbour rows -- no atomics, no scatter.  The
 // backward pass is two such sweeps: by destination (d alpha -> d e, d ar) and by source through the
 // transposed CSR (d x', d al), linked by the edge permutation perm_t the CSR build emits.
+//
+// MEAN = true is ``concat=False``: out[dst,:] = (1/H) sum_h out[dst,h,:] + bias[:], formed by the wave that owns the row
+// (head_mean.inc), and the backward reads dout[N,F]; nothing of width H*F exists on the output side.
 #include "common.h"
+#include "head_mean.inc"
 
 namespace {
 
@@ -39,6 +43,7 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict
 }
 
 // forward: wave per destination row
+template <bool MEAN>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(const float* __restrict__ xp, const float* __restrict__ al,
                                                        const float* __restrict__ ar, const int* __restrict__ rowptr,
                                                        const int* __restrict__ col, const float* __restrict__ bias,
@@ -49,6 +54,8 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const float* __restrict__ 
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= N) return;
   const int b = rowptr[i], e = rowptr[i + 1];
+  HeadMeanRow hm;                                   // MEAN: the row's sum over heads
+  const bool hm_regs = head_mean_in_regs(F);
   for (int h = 0; h < H; ++h) {
     const float ari = ar[i * H + h];
     // pass 1 (lanes over edges): row max and sum of exp
@@ -59,7 +66,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const float* __restrict__ 
     for (int p = b + lane; p < e; p += 64) s += expf(lrelu(al[(int64_t)col[p] * H + h] + ari, slope) - m);
     s = wave_sum(s);
     // pass 2 (lanes over features): weighted sum of neighbour rows
-    for (int f0 = lane; f0 < F; f0 += 64) {
+    for (int f0 = lane, q = 0; f0 < F; f0 += 64, ++q) {
       float acc = 0.f;
       for (int p = b; p < e; ++p) {
         const int src = col[p];
@@ -68,12 +75,15 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const float* __restrict__ 
         if (thr) a = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? a * scale : 0.f;
         acc += a * xp[((int64_t)src * H + h) * F + f0];
       }
-      out[(i * H + h) * F + f0] = acc + (bias ? bias[h * F + f0] : 0.f);
+      if (MEAN) hm.add(acc, out + i * F + f0, q, h, hm_regs);
+      else out[(i * H + h) * F + f0] = acc + (bias ? bias[h * F + f0] : 0.f);
     }
   }
+  if (MEAN) hm.finish(out + i * F, bias, 1.f / (float)H, F, lane, hm_regs);
 }
 
 // backward sweep 1, wave per destination row: d e (per edge, per head) and d ar
+template <bool MEAN>
 __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(const float* __restrict__ dout, const float* __restrict__ xp,
                                                            const float* __restrict__ alpha, const float* __restrict__ al,
                                                            const float* __restrict__ ar, const int* __restrict__ rowptr,
@@ -88,15 +98,14 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(const float* __restric
   if (i >= N) return;
   const int b = rowptr[i], e = rowptr[i + 1];
   const bool in_lds = (e - b) <= MAXE;
+  HeadMeanDout<MEAN> hd(dout + i * F, F, H, lane);  // MEAN: row i of dout[N,F], read once for all heads
   for (int h = 0; h < H; ++h) {
-    const float* drow = dout + (i * H + h) * F;
+    const float* drow = dout + (MEAN ? i : i * H + h) * F;
     // d alpha_p = m_p * <dout[i,h,:], x'[src_p,h,:]> ; parked per edge, and sum_k alpha_k d alpha_k accumulated
     float dot = 0.f;
     for (int p = b; p < e; ++p) {
       const float* xr = xp + ((int64_t)col[p] * H + h) * F;
-      float d = 0.f;
-      for (int f = lane; f < F; f += 64) d += drow[f] * xr[f];
-      d = wave_sum(d);
+      float d = hd.dot(drow, xr, F, lane);
       if (thr) d = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? d * scale : 0.f;
       dot += alpha[(int64_t)p * H + h] * d;
       if (lane == 0) {
@@ -123,6 +132,7 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(const float* __restric
 }
 
 // backward sweep 2, wave per source row (transposed CSR): d al and d x'
+template <bool MEAN>
 __global__ __launch_bounds__(256) void gat_bwd_src_kernel(const float* __restrict__ dout, const float* __restrict__ alpha,
                                                            const float* __restrict__ de, const float* __restrict__ dar,
                                                            const int* __restrict__ rowptr_t, const int* __restrict__ col_t,
@@ -143,15 +153,50 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(const float* __restric
     const float gr = dar[s * H + h];
     for (int f0 = lane; f0 < F; f0 += 64) {
       float acc = g * att_src[h * F + f0] + gr * att_dst[h * F + f0];
+      float gv = 0.f;                               // MEAN: sum alpha_d dout[dst,:], scaled by 1/H once
       for (int pt = b; pt < e; ++pt) {
         const int p = perm_t[pt];
         float a = alpha[(int64_t)p * H + h];
         if (thr) a = philox_word((unsigned long long)p * H + h, seed, stream_id) >= thr ? a * scale : 0.f;
-        acc += a * dout[((int64_t)col_t[pt] * H + h) * F + f0];
+        if (MEAN) gv += a * dout[(int64_t)col_t[pt] * F + f0];
+        else acc += a * dout[((int64_t)col_t[pt] * H + h) * F + f0];
       }
-      dxp[(s * H + h) * F + f0] = acc;
+      dxp[(s * H + h) * F + f0] = MEAN ? acc + gv * (1.f / (float)H) : acc;
     }
   }
+}
+
+template <bool MEAN>
+int gat_fwd(const float* xp, const float* al, const float* ar, const int32_t* rowptr, const int32_t* col, const float* bias,
+            float* out, float* alpha, int64_t N, int H, int F, float negative_slope, uint32_t drop_threshold,
+            float drop_scale, uint64_t seed, uint64_t stream_id, void* stream) {
+  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0);
+  if (N == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(xp && al && ar && rowptr && col && out && alpha);
+  hipLaunchKernelGGL(gat_fwd_kernel<MEAN>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, as_stream(stream), xp, al, ar,
+                     rowptr, col, bias, out, alpha, N, H, F, negative_slope, drop_threshold, drop_scale,
+                     (unsigned long long)seed, (unsigned long long)stream_id);
+  return isic_launch_status();
+}
+
+template <bool MEAN>
+int gat_bwd(const float* dout, const float* xp, const float* alpha, const float* al, const float* ar, const float* att_src,
+            const float* att_dst, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t,
+            const int32_t* perm_t, float* de, float* dar, float* dal, float* dxp, int64_t N, int H, int F,
+            float negative_slope, uint32_t drop_threshold, float drop_scale, uint64_t seed, uint64_t stream_id,
+            void* stream) {
+  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0);
+  if (N == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(dout && xp && alpha && al && ar && att_src && att_dst && rowptr && col && rowptr_t && col_t && perm_t &&
+                 de && dar && dal && dxp);
+  const dim3 grid((unsigned)((N + 3) / 4));
+  hipLaunchKernelGGL(gat_bwd_dst_kernel<MEAN>, grid, dim3(256), 0, as_stream(stream), dout, xp, alpha, al, ar, rowptr, col,
+                     de, dar, N, H, F, negative_slope, drop_threshold, drop_scale, (unsigned long long)seed,
+                     (unsigned long long)stream_id);
+  hipLaunchKernelGGL(gat_bwd_src_kernel<MEAN>, grid, dim3(256), 0, as_stream(stream), dout, alpha, de, dar, rowptr_t, col_t,
+                     perm_t, att_src, att_dst, dxp, dal, N, H, F, drop_threshold, drop_scale, (unsigned long long)seed,
+                     (unsigned long long)stream_id);
+  return isic_launch_status();
 }
 
 }  // namespace
@@ -171,13 +216,8 @@ int isic_gat_scores(const float* xp, const float* att_src, const float* att_dst,
 int isic_gat_fwd(const float* xp, const float* al, const float* ar, const int32_t* rowptr, const int32_t* col,
                  const float* bias, float* out, float* alpha, int64_t N, int H, int F, float negative_slope,
                  uint32_t drop_threshold, float drop_scale, uint64_t seed, uint64_t stream_id, void* stream) {
-  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0);
-  if (N == 0) return ISIC_OK;
-  ISIC_CHECK_ARG(xp && al && ar && rowptr && col && out && alpha);
-  hipLaunchKernelGGL(gat_fwd_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, as_stream(stream), xp, al, ar, rowptr,
-                     col, bias, out, alpha, N, H, F, negative_slope, drop_threshold, drop_scale,
-                     (unsigned long long)seed, (unsigned long long)stream_id);
-  return isic_launch_status();
+  return gat_fwd<false>(xp, al, ar, rowptr, col, bias, out, alpha, N, H, F, negative_slope, drop_threshold, drop_scale, seed,
+                 stream_id, stream);
 }
 
 int isic_gat_bwd(const float* dout, const float* xp, const float* alpha, const float* al, const float* ar,
@@ -185,18 +225,24 @@ int isic_gat_bwd(const float* dout, const float* xp, const float* alpha, const f
                  const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, float* de, float* dar, float* dal,
                  float* dxp, int64_t N, int H, int F, float negative_slope, uint32_t drop_threshold, float drop_scale,
                  uint64_t seed, uint64_t stream_id, void* stream) {
-  ISIC_CHECK_ARG(N >= 0 && H > 0 && F > 0);
-  if (N == 0) return ISIC_OK;
-  ISIC_CHECK_ARG(dout && xp && alpha && al && ar && att_src && att_dst && rowptr && col && rowptr_t && col_t && perm_t &&
-                 de && dar && dal && dxp);
-  const dim3 grid((unsigned)((N + 3) / 4));
-  hipLaunchKernelGGL(gat_bwd_dst_kernel, grid, dim3(256), 0, as_stream(stream), dout, xp, alpha, al, ar, rowptr, col, de,
-                     dar, N, H, F, negative_slope, drop_threshold, drop_scale, (unsigned long long)seed,
-                     (unsigned long long)stream_id);
-  hipLaunchKernelGGL(gat_bwd_src_kernel, grid, dim3(256), 0, as_stream(stream), dout, alpha, de, dar, rowptr_t, col_t,
-                     perm_t, att_src, att_dst, dxp, dal, N, H, F, drop_threshold, drop_scale, (unsigned long long)seed,
-                     (unsigned long long)stream_id);
-  return isic_launch_status();
+  return gat_bwd<false>(dout, xp, alpha, al, ar, att_src, att_dst, rowptr, col, rowptr_t, col_t, perm_t, de, dar, dal, dxp, N,
+                 H, F, negative_slope, drop_threshold, drop_scale, seed, stream_id, stream);
+}
+
+int isic_gat_fwd_mean(const float* xp, const float* al, const float* ar, const int32_t* rowptr, const int32_t* col,
+                 const float* bias, float* out, float* alpha, int64_t N, int H, int F, float negative_slope,
+                 uint32_t drop_threshold, float drop_scale, uint64_t seed, uint64_t stream_id, void* stream) {
+  return gat_fwd<true>(xp, al, ar, rowptr, col, bias, out, alpha, N, H, F, negative_slope, drop_threshold, drop_scale, seed,
+                 stream_id, stream);
+}
+
+int isic_gat_bwd_mean(const float* dout, const float* xp, const float* alpha, const float* al, const float* ar,
+                 const float* att_src, const float* att_dst, const int32_t* rowptr, const int32_t* col,
+                 const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, float* de, float* dar, float* dal,
+                 float* dxp, int64_t N, int H, int F, float negative_slope, uint32_t drop_threshold, float drop_scale,
+                 uint64_t seed, uint64_t stream_id, void* stream) {
+  return gat_bwd<true>(dout, xp, alpha, al, ar, att_src, att_dst, rowptr, col, rowptr_t, col_t, perm_t, de, dar, dal, dxp, N,
+                 H, F, negative_slope, drop_threshold, drop_scale, seed, stream_id, stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,11 @@ so the following LayerNorm rejects the layer's output, and ``fagcn`` is called a
 ``layer(h, edge_index, edge_weight)`` (`:184-185`) whereas the layer takes ``(x, x_0, edge_index)``.
 Here ``gatv2`` widens like ``gat`` and ``fagcn`` receives ``x_0`` = the projected input (as ``gcnii``).
 
+``gnn_concat=False`` (half of the reference's graph search space, `tune_mil.py:173-178`) averages the heads of ``gat`` /
+``gatv2`` / ``transformer`` instead of concatenating them: the layers' output, the LayerNorms, the attention pool and the
+classifier are ``gnn_hidden`` wide, the mean is formed inside the attention kernels (``isic_*_mean``), and with an
+``input_proj`` the residual of `05:197-198` is active on every layer.
+
 Beyond the reference: ``forward`` also takes a batch of graphs (``offsets`` + global node ids,
 or a prebuilt ``GraphBatch``) and returns ``probs[G, C]``.
 """
@@ -79,13 +84,13 @@ class _GATConvParams(nn.Module):
 
 
 class _GATv2ConvParams(nn.Module):
-    """PyG ``GATv2Conv(in, F, heads=H, concat=True)``: ``att`` [1,H,F] (Glorot), ``bias`` [H*F] (zeros),
-    ``lin_l`` / ``lin_r`` Linear(in, H*F) with bias (Glorot weights, zero biases)."""
+    """PyG ``GATv2Conv(in, F, heads=H, concat)``: ``att`` [1,H,F] (Glorot), ``bias`` [H*F] (zeros; [F] when not
+    concatenating), ``lin_l`` / ``lin_r`` Linear(in, H*F) with bias (Glorot weights, zero biases)."""
 
-    def __init__(self, in_dim, out_dim, heads):
+    def __init__(self, in_dim, out_dim, heads, concat=True):
         super().__init__()
         self.att = nn.Parameter(torch.empty(1, heads, out_dim))
-        self.bias = nn.Parameter(torch.zeros(heads * out_dim))
+        self.bias = nn.Parameter(torch.zeros(heads * out_dim if concat else out_dim))
         self.lin_l = nn.Linear(in_dim, heads * out_dim, bias=True)
         self.lin_r = nn.Linear(in_dim, heads * out_dim, bias=True)
         for t in (self.att, self.lin_l.weight, self.lin_r.weight):
@@ -96,16 +101,18 @@ class _GATv2ConvParams(nn.Module):
 
 
 class _TransformerConvParams(nn.Module):
-    """PyG ``TransformerConv(in, F, heads=H, concat=True, beta=True)``: ``lin_key`` / ``lin_query`` / ``lin_value`` /
-    ``lin_skip`` Linear(in, H*F) with bias, ``lin_beta`` Linear(3*H*F, 1, bias=False)."""
+    """PyG ``TransformerConv(in, F, heads=H, concat, beta=True)``: ``lin_key`` / ``lin_query`` / ``lin_value`` Linear(in, H*F)
+    with bias; ``lin_skip`` Linear(in, W) with bias and ``lin_beta`` Linear(3*W, 1, bias=False), W = H*F when concatenating
+    and F when averaging the heads (the gate then acts on [N,F])."""
 
-    def __init__(self, in_dim, out_dim, heads):
+    def __init__(self, in_dim, out_dim, heads, concat=True):
         super().__init__()
+        width = heads * out_dim if concat else out_dim
         self.lin_key = nn.Linear(in_dim, heads * out_dim)
         self.lin_query = nn.Linear(in_dim, heads * out_dim)
         self.lin_value = nn.Linear(in_dim, heads * out_dim)
-        self.lin_skip = nn.Linear(in_dim, heads * out_dim)
-        self.lin_beta = nn.Linear(3 * heads * out_dim, 1, bias=False)
+        self.lin_skip = nn.Linear(in_dim, width)
+        self.lin_beta = nn.Linear(3 * width, 1, bias=False)
         self.heads, self.out_dim = heads, out_dim
 
 
@@ -164,20 +171,14 @@ class GraphMIL(nn.Module):
                     raise ValueError("GCNII requires a constant hidden dimension across layers")
                 layer = _GCN2ConvParams(out_dim, gcnii_alpha, gcnii_theta, i + 1)
             elif self.gnn_type == 'gat':                                         # 05:83-86
-                if not gnn_concat:
-                    raise NotImplementedError("GATConv(concat=False) is not built on the HIP path")
                 layer = _GATConvParams(in_dim, out_dim, gnn_heads, gnn_concat)
-                out_dim *= gnn_heads
+                out_dim *= gnn_heads if gnn_concat else 1
             elif self.gnn_type == 'gatv2':                                       # 05:99-101 (+ the widening of :86)
-                if not gnn_concat:
-                    raise NotImplementedError("GATv2Conv(concat=False) is not built on the HIP path")
-                layer = _GATv2ConvParams(in_dim, out_dim, gnn_heads)
-                out_dim *= gnn_heads
+                layer = _GATv2ConvParams(in_dim, out_dim, gnn_heads, gnn_concat)
+                out_dim *= gnn_heads if gnn_concat else 1
             elif self.gnn_type == 'transformer':                                 # 05:94-98
-                if not gnn_concat:
-                    raise NotImplementedError("TransformerConv(concat=False) is not built on the HIP path")
-                layer = _TransformerConvParams(in_dim, out_dim, gnn_heads)
-                out_dim *= gnn_heads
+                layer = _TransformerConvParams(in_dim, out_dim, gnn_heads, gnn_concat)
+                out_dim *= gnn_heads if gnn_concat else 1
             elif self.gnn_type == 'fagcn':                                       # 05:102-105
                 if in_dim != out_dim:
                     raise ValueError("FAGCN requires a constant hidden dimension")
@@ -278,18 +279,19 @@ class GraphMIL(nn.Module):
                 h = spmm(ops.linear(h, layer.lin.weight, None), g, bias=layer.bias)
             elif self.gnn_type == 'gat':           # edge softmax over the CSR rows; attention dropout = site 32 + i
                 h = gat_conv(ops.linear(h, layer.lin.weight, None), layer.att_src, layer.att_dst, layer.bias, g,
-                             layer.heads, 0.2, clk.spec(p_drop, 32 + i, tr))
+                             layer.heads, 0.2, clk.spec(p_drop, 32 + i, tr), concat=self.gnn_concat)
             elif self.gnn_type == 'gatv2':         # edge softmax of att . leaky_relu(x_l[src] + x_r[dst]); dropout site 32 + i
                 h = gatv2_conv(ops.linear(h, layer.lin_l.weight, layer.lin_l.bias),
                                ops.linear(h, layer.lin_r.weight, layer.lin_r.bias), layer.att, layer.bias, g, layer.heads,
-                               0.2, clk.spec(p_drop, 32 + i, tr))
+                               0.2, clk.spec(p_drop, 32 + i, tr), concat=self.gnn_concat)
             elif self.gnn_type == 'transformer':   # scaled dot-product edge softmax + gated skip (beta)
                 agg = transformer_attention(ops.linear(h, layer.lin_query.weight, layer.lin_query.bias),
                                             ops.linear(h, layer.lin_key.weight, layer.lin_key.bias),
                                             ops.linear(h, layer.lin_value.weight, layer.lin_value.bias), g, layer.heads,
-                                            clk.spec(p_drop, 32 + i, tr))
+                                            clk.spec(p_drop, 32 + i, tr), concat=self.gnn_concat)
                 xr = ops.linear(h, layer.lin_skip.weight, layer.lin_skip.bias)
-                # the scalar gate per node is index plumbing on [N, 3*H*F] -> [N, 1]: one fp32 GEMM + torch elementwise
+                # the scalar gate per node is index plumbing on [N, 3*W] -> [N, 1] (W = H*F, or F for the head mean): one
+                # fp32 GEMM + torch elementwise
                 beta = torch.sigmoid(ops.linear(torch.cat([agg, xr, agg - xr], dim=1), layer.lin_beta.weight, None))
                 h = beta * xr + (1.0 - beta) * agg
             elif self.gnn_type == 'fagcn':         # tanh-gated, GCN-normalised aggregation + eps * x0

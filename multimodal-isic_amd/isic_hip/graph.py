@@ -239,10 +239,11 @@ def l2_normalize(x, eps=1e-12):
 
 class GatFn(torch.autograd.Function):
     """PyG GATConv message passing on a 'gcn'-mode GraphBatch (self loops re-added): per-destination
-    edge softmax of leaky_relu(<x', att_src>[src] + <x', att_dst>[dst]) and the weighted neighbour sum."""
+    edge softmax of leaky_relu(<x', att_src>[src] + <x', att_dst>[dst]) and the weighted neighbour sum.
+    ``concat=False``: the mean over heads, out [N,F] and bias [F], formed inside the kernels (``isic_gat_fwd_mean``)."""
 
     @staticmethod
-    def forward(ctx, xp, att_src, att_dst, bias, graph, heads, slope, drop):
+    def forward(ctx, xp, att_src, att_dst, bias, graph, heads, slope, drop, concat=True):
         from .ops import NO_DROP
         _chk(xp, att_src, att_dst, bias)
         xp = _f32c(xp)
@@ -256,10 +257,10 @@ class GatFn(torch.autograd.Function):
         call("isic_gat_scores", xp, a_s, a_d, al, ar, N, heads, F_)
         nnz = graph.col.numel()
         alpha = torch.empty((nnz, heads), device=dev, dtype=torch.float32)
-        out = torch.empty_like(xp)
-        call("isic_gat_fwd", xp, al, ar, graph.rowptr, graph.col, _f32c(bias) if bias is not None else None, out, alpha, N,
+        out = torch.empty_like(xp) if concat else torch.empty((N, F_), device=dev, dtype=torch.float32)
+        call("isic_gat_fwd" if concat else "isic_gat_fwd_mean", xp, al, ar, graph.rowptr, graph.col, _f32c(bias) if bias is not None else None, out, alpha, N,
              heads, F_, float(slope), drop.threshold, drop.scale, drop.seed, drop.stream)
-        ctx.graph, ctx.cfg = graph, (N, heads, F_, float(slope), drop, bias is not None, att_src.shape)
+        ctx.graph, ctx.cfg = graph, (N, heads, F_, float(slope), drop, bias is not None, att_src.shape, concat)
         ctx.save_for_backward(xp, a_s, a_d, al, ar, alpha)
         return out
 
@@ -267,7 +268,7 @@ class GatFn(torch.autograd.Function):
     def backward(ctx, dout):
         from .ops import gemm
         xp, a_s, a_d, al, ar, alpha = ctx.saved_tensors
-        N, H, F_, slope, drop, has_bias, att_shape = ctx.cfg
+        N, H, F_, slope, drop, has_bias, att_shape, concat = ctx.cfg
         g = ctx.graph
         dout = _f32c(dout)
         dev = xp.device
@@ -275,7 +276,7 @@ class GatFn(torch.autograd.Function):
         dar = torch.empty((N, H), device=dev, dtype=torch.float32)
         dal = torch.empty((N, H), device=dev, dtype=torch.float32)
         dxp = torch.empty_like(xp)
-        call("isic_gat_bwd", dout, xp, alpha, al, ar, a_s, a_d, g.rowptr, g.col, g.rowptr_t, g.col_t, g.perm_t, de, dar,
+        call("isic_gat_bwd" if concat else "isic_gat_bwd_mean", dout, xp, alpha, al, ar, a_s, a_d, g.rowptr, g.col, g.rowptr_t, g.col_t, g.perm_t, de, dar,
              dal, dxp, N, H, F_, slope, drop.threshold, drop.scale, drop.seed, drop.stream)
         # d att_src[h,:] = dal[:,h]^T x'[:,h,:]   (strided views: one small GEMM per head)
         d_as = torch.empty((H, F_), device=dev, dtype=torch.float32)
@@ -285,20 +286,22 @@ class GatFn(torch.autograd.Function):
             gemm(dal[:, h:h + 1], xh, trans_a=True, out=d_as[h:h + 1])
             gemm(dar[:, h:h + 1], xh, trans_a=True, out=d_ad[h:h + 1])
         db = colsum(dout) if has_bias else None
-        return dxp, d_as.reshape(att_shape), d_ad.reshape(att_shape), db, None, None, None, None
+        return dxp, d_as.reshape(att_shape), d_ad.reshape(att_shape), db, None, None, None, None, None
 
 
-def gat_conv(xp, att_src, att_dst, bias, graph, heads, negative_slope=0.2, drop=None):
-    return GatFn.apply(xp, att_src, att_dst, bias, graph, heads, negative_slope, drop)
+def gat_conv(xp, att_src, att_dst, bias, graph, heads, negative_slope=0.2, drop=None, concat=True):
+    """x'[N, H*F] -> [N, H*F], or with ``concat=False`` the mean over heads [N, F] (``bias`` [F])."""
+    return GatFn.apply(xp, att_src, att_dst, bias, graph, heads, negative_slope, drop, bool(concat))
 
 
 class EdgeAttnFn(torch.autograd.Function):
     """Edge-softmax attention aggregation of ``isic_edge_attn_fwd/bwd``.
     mode 0 (GATv2Conv): ks = x_l (also the values), qd = x_r, att[H,F]; 'gcn'-mode GraphBatch (self loops re-added).
-    mode 1 (TransformerConv): ks = key, qd = query, v = value, scale = 1/sqrt(F); 'sum'-mode GraphBatch."""
+    mode 1 (TransformerConv): ks = key, qd = query, v = value, scale = 1/sqrt(F); 'sum'-mode GraphBatch.
+    ``concat=False``: the mean over heads, out [N,F] and bias [F], formed inside the kernels (``isic_edge_attn_fwd_mean``)."""
 
     @staticmethod
-    def forward(ctx, mode, ks, qd, v, att, bias, graph, heads, slope, scale, drop):
+    def forward(ctx, mode, ks, qd, v, att, bias, graph, heads, slope, scale, drop, concat=True):
         from .ops import NO_DROP
         _chk(ks, qd, v, att, bias)
         ks, qd = _f32c(ks), _f32c(qd)
@@ -308,18 +311,18 @@ class EdgeAttnFn(torch.autograd.Function):
         a = _f32c(att).reshape(heads, F_) if att is not None else None
         drop = drop or NO_DROP
         alpha = torch.empty((graph.col.numel(), heads), device=ks.device, dtype=torch.float32)
-        out = torch.empty_like(ks)
-        call("isic_edge_attn_fwd", int(mode), ks, qd, v, a, graph.rowptr, graph.col, _f32c(bias) if bias is not None else None,
+        out = torch.empty_like(ks) if concat else torch.empty((N, F_), device=ks.device, dtype=torch.float32)
+        call("isic_edge_attn_fwd" if concat else "isic_edge_attn_fwd_mean", int(mode), ks, qd, v, a, graph.rowptr, graph.col, _f32c(bias) if bias is not None else None,
              out, alpha, N, heads, F_, float(slope), float(scale), drop.threshold, drop.scale, drop.seed, drop.stream)
         ctx.graph, ctx.cfg = graph, (int(mode), N, heads, F_, float(slope), float(scale), drop, bias is not None,
-                                     att.shape if att is not None else None)
+                                     att.shape if att is not None else None, concat)
         ctx.save_for_backward(ks, qd, v, a, alpha)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         ks, qd, v, a, alpha = ctx.saved_tensors
-        mode, N, H, F_, slope, scale, drop, has_bias, att_shape = ctx.cfg
+        mode, N, H, F_, slope, scale, drop, has_bias, att_shape, concat = ctx.cfg
         g = ctx.graph
         dout = _f32c(dout)
         dev = ks.device
@@ -327,19 +330,22 @@ class EdgeAttnFn(torch.autograd.Function):
         dqd, dks = torch.empty_like(qd), torch.empty_like(ks)
         dv = torch.empty_like(v) if mode == 1 else None
         datt = torch.zeros((H, F_), device=dev, dtype=torch.float32) if mode == 0 else None
-        call("isic_edge_attn_bwd", mode, dout, ks, qd, v, a, alpha, g.rowptr, g.col, g.rowptr_t, g.col_t, g.perm_t, de, dqd,
+        call("isic_edge_attn_bwd" if concat else "isic_edge_attn_bwd_mean", mode, dout, ks, qd, v, a, alpha, g.rowptr, g.col, g.rowptr_t, g.col_t, g.perm_t, de, dqd,
              dks, dv, datt, N, H, F_, slope, scale, drop.threshold, drop.scale, drop.seed, drop.stream)
         db = colsum(dout) if has_bias else None
-        return (None, dks, dqd, dv, datt.reshape(att_shape) if datt is not None else None, db, None, None, None, None, None)
+        return (None, dks, dqd, dv, datt.reshape(att_shape) if datt is not None else None, db, None, None, None, None, None,
+                None)
 
 
-def gatv2_conv(xl, xr, att, bias, graph, heads, negative_slope=0.2, drop=None):
-    return EdgeAttnFn.apply(0, xl, xr, None, att, bias, graph, heads, negative_slope, 1.0, drop)
+def gatv2_conv(xl, xr, att, bias, graph, heads, negative_slope=0.2, drop=None, concat=True):
+    """x_l, x_r [N, H*F] -> [N, H*F], or with ``concat=False`` the mean over heads [N, F] (``bias`` [F])."""
+    return EdgeAttnFn.apply(0, xl, xr, None, att, bias, graph, heads, negative_slope, 1.0, drop, bool(concat))
 
 
-def transformer_attention(q, k, v, graph, heads, drop=None):
+def transformer_attention(q, k, v, graph, heads, drop=None, concat=True):
+    """q, k, v [N, H*F] -> the attention aggregate [N, H*F], or with ``concat=False`` its mean over heads [N, F]."""
     F_ = q.shape[1] // heads
-    return EdgeAttnFn.apply(1, k, q, v, None, None, graph, heads, 0.0, 1.0 / (F_ ** 0.5), drop)
+    return EdgeAttnFn.apply(1, k, q, v, None, None, graph, heads, 0.0, 1.0 / (F_ ** 0.5), drop, bool(concat))
 
 
 class FaFn(torch.autograd.Function):
