@@ -44,12 +44,21 @@ int isic_test_conv2d_wgrad_variant_bf16(const uint16_t* x, const uint16_t* dy, f
                                         size_t workspace_bytes, int variant, void* stream);
 
 /* isic_gemm_f32_ws (same arguments) with the kernel pinned: variant 0 = shipped choice, 1 = always the 64 x 64 x 16
- * register-staged kernel (split-K through fp32 atomics), 2 = the persistent 256 x 128 x 32 kernel or
+ * register-staged kernel (split-K: with a workspace the per-split partials are parked there and added in a fixed order,
+ * without one they meet through fp32 atomics), 2 = the persistent 256 x 128 x 32 kernel or
  * ISIC_ERR_UNSUPPORTED when the shape is not for it, 3 = the register-fed A^T B split-K kernel (small output, long
  * reduction) or ISIC_ERR_UNSUPPORTED, 4 = the row-panel kernel (long M, K <= 128) or ISIC_ERR_UNSUPPORTED.  A/B timing (tools/gemm_bench.py) and tests only. */
 int isic_test_gemm_f32_variant(int variant, int transA, int transB, int M, int N, int K, const float* A, int lda,
                                const float* B, int ldb, float* C, int ldc, const float* bias, int act, float beta,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* The fixed-order slab reducers on their own (csrc/slab_sum.inc states the orders): out[i] = beta * out[i] + the sum over
+ * s of partial[s][i] for a contiguous [slabs][n] stack, through the device functions (and, forms 0 .. 3, the kernels) the
+ * product's split reductions use.  form 0 = 16 lanes and an xor tree, 1 = 4 lanes and an xor tree, 2 = f32x4 with one
+ * accumulator joined through LDS, 3 = f32x4 with two accumulators, 4 = scalars with four accumulators.  Forms 2 and 3 need
+ * n % 4 == 0 and 16-byte aligned pointers; beta is 0 or 1 (one exact add; the product passes nothing else here).
+ * Anything else returns ISIC_ERR_BAD_ARG. */
+int isic_test_slab_reduce_f32(int form, const float* partial, int slabs, int64_t n, float* out, float beta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "slab_sum.inc"
 #include "mfma_tile.h"
 #include "pool_grad.h"
 
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(StemArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int co = i * 16 + fg * 4 + r;
-        // the block's OWN partial (workspace [grid][64*7*7*3]); stem_wgrad_reduce_kernel adds them in block order:
+        // the block's OWN partial (workspace [grid][64*7*7*3]); isic_slab_reduce_launch adds them in a fixed order:
         // deterministic, where fp32 atomics added the blocks in arrival order
         a.dw[(size_t)blockIdx.x * STEM_DW_ELEMS + ((co * 7 + kh) * 7 + kw) * 3 + c] = acc[i][j][r];
       }
@@ -439,25 +440,11 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int co = i * 16 + fg * 4 + r;
-        // the block's OWN partial (workspace [grid][64*7*7*3]); stem_wgrad_reduce_kernel adds them in block order:
+        // the block's OWN partial (workspace [grid][64*7*7*3]); isic_slab_reduce_launch adds them in a fixed order:
         // deterministic, where fp32 atomics added the blocks in arrival order
         a.dw[(size_t)blockIdx.x * STEM_DW_ELEMS + ((co * 7 + kh) * 7 + kw) * 3 + c] = acc[i][j][r];
       }
     }
-}
-
-// dw[e] += sum over the blocks' partials, in block order: 16 lanes per element (lane g takes blocks g, g + 16, ...) joined
-// by a fixed xor tree
-__global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw,
-                                                                 int nparts) {
-  const int g = threadIdx.x & 15;
-  const int e = blockIdx.x * 16 + (threadIdx.x >> 4);
-  float v = 0.f;
-  if (e < STEM_DW_ELEMS)
-    for (int s = g; s < nparts; s += 16) v += partial[(size_t)s * STEM_DW_ELEMS + e];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-  if (e < STEM_DW_ELEMS && g == 0) dw[e] += v;
 }
 
 // fp32 [64][7][7][3] (channels_last memory of the OIHW parameter) -> bf16 [64][7][8][4], zero padded
@@ -518,8 +505,8 @@ int isic_conv_stem_wgrad_bf16(const uint16_t* in_nhwc4, const uint16_t* dy, floa
   if (rc != ISIC_OK) return rc;
   const int grid = a.total_tiles < STEM_WGRAD_BLOCKS ? a.total_tiles : STEM_WGRAD_BLOCKS;
   hipLaunchKernelGGL(conv_stem_wgrad_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
-  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3(ceil_div(STEM_DW_ELEMS, 16)), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<const float*>(workspace), dw, grid);
+  isic_slab_reduce_launch(ISIC_SLAB_XOR16, reinterpret_cast<const float*>(workspace), grid, STEM_DW_ELEMS, dw, 1.f,
+                          as_stream(stream));                       // dw += the blocks' partials (slab_sum.inc, order A)
   return isic_launch_status();
 }
 
@@ -545,8 +532,8 @@ int isic_conv_stem_wgrad_bn_pooled_bf16(const uint16_t* in_nhwc4, const uint16_t
   b.Hp = Hp; b.Wp = Wp;
   const int grid = a.total_tiles < STEM_WGRAD_BLOCKS ? a.total_tiles : STEM_WGRAD_BLOCKS;
   hipLaunchKernelGGL(conv_stem_wgrad_bn_kernel, dim3(grid), dim3(256), 0, as_stream(stream), b);
-  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3(ceil_div(STEM_DW_ELEMS, 16)), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<const float*>(workspace), dw, grid);
+  isic_slab_reduce_launch(ISIC_SLAB_XOR16, reinterpret_cast<const float*>(workspace), grid, STEM_DW_ELEMS, dw, 1.f,
+                          as_stream(stream));                       // dw += the blocks' partials (slab_sum.inc, order A)
   return isic_launch_status();
 }
 

@@ -23,10 +23,11 @@
 //                   the 128-pixel K-tile four ways.
 // The pixel range is additionally split over blockIdx.y; a block's partial tile is transposed through
 // LDS (and, with KSPLIT, summed over its four waves there) and written as whole 256-byte rows into ITS OWN slice of
-// the workspace ([split][Cout][Kh][Kw][Cin]); wgrad_reduce_kernel then adds the slices to the caller's gradient in
+// the workspace ([split][Cout][Kh][Kw][Cin]); the 16- or 4-lane reducer of slab_reduce.hip then adds the slices to the caller's gradient in
 // split order.  DETERMINISTIC (round 3): the fp32 row atomics this replaces added the splits in arrival order, so two
 // identical steps gave different last bits in 6 of ResNet-18's 20 weight gradients.
 #include "common.h"
+#include "slab_sum.inc"
 #include "mfma_tile.h"
 
 namespace {
@@ -225,21 +226,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
   }
 }
 
-// dw[e] += sum over the splits of partial[s][e], in split order.  G lanes per element share the splits (lane g takes
-// s = g, g + G, ...) and meet in a fixed xor tree: the order never depends on timing.
-template <int G>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw,
-                                                            int splits, size_t elems) {
-  const int g = threadIdx.x % G;
-  const size_t e = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
-  float v = 0.f;
-  if (e < elems)
-    for (int s = g; s < splits; s += G) v += partial[(size_t)s * elems + e];
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-  if (e < elems && g == 0) dw[e] += v;
-}
-
 struct WgradPlan {
   bool big;
   int tiles, splits, ktiles, ktiles_per_split;
@@ -422,12 +408,8 @@ int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int 
   dim3 grid(p.tiles, p.splits);
   if (p.big) hipLaunchKernelGGL((conv_wgrad_kernel<false>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_wgrad_kernel<true>), grid, dim3(256), 0, s, a);
-  if (p.splits > 32)
-    hipLaunchKernelGGL((wgrad_reduce_kernel<16>), dim3((unsigned)ceil_div64((int64_t)p.elems, 16)), dim3(256), 0, s, partial, dw,
-                       p.splits, p.elems);
-  else
-    hipLaunchKernelGGL((wgrad_reduce_kernel<4>), dim3((unsigned)ceil_div64((int64_t)p.elems, 64)), dim3(256), 0, s, partial, dw,
-                       p.splits, p.elems);
+  // dw += the splits' slices in a fixed order (slab_sum.inc, order A): 16 lanes per element, 4 where the splits are few
+  isic_slab_reduce_launch(p.splits > 32 ? ISIC_SLAB_XOR16 : ISIC_SLAB_XOR4, partial, p.splits, (int64_t)p.elems, dw, 1.f, s);
   return isic_launch_status();
 }
 

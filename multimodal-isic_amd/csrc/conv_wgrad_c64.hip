@@ -19,6 +19,7 @@
 // does not exist yet, the staging waves form it from the incoming gradient and the convolution output (see BNBWD below).
 
 #include "common.h"
+#include "slab_sum.inc"
 #include "mfma_tile.h"
 #include "pool_grad.h"
 
@@ -384,31 +385,6 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(typename WC64Mode<MODE>:
       *reinterpret_cast<f32x4*>(part + ((size_t)(half * 32 + c2 * 16 + fi) * 9 + t) * 64 + wave * 16 + fg * 4) = acc[t][c2];
 }
 
-// dw[e] += sum over the blocks' partials, in a fixed order: thread (q, grp) of a block sums partials grp, grp+16, ...
-// of four consecutive elements (16-byte loads); the 16 group sums are combined through LDS in group order.
-__global__ __launch_bounds__(256) void wgrad_c64_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw,
-                                                                int nblocks) {
-  __shared__ f32x4 red[16][16];
-  const int q = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const size_t e4 = (size_t)blockIdx.x * 16 + q;                   // float4 index into the gradient
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-  int b = grp;
-  for (; b + 16 < nblocks; b += 32) {
-    s0 += reinterpret_cast<const f32x4*>(partial + (size_t)b * DW_ELEMS)[e4];
-    s1 += reinterpret_cast<const f32x4*>(partial + (size_t)(b + 16) * DW_ELEMS)[e4];
-  }
-  if (b < nblocks) s0 += reinterpret_cast<const f32x4*>(partial + (size_t)b * DW_ELEMS)[e4];
-  red[grp][q] = s0 + s1;
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    f32x4 t = red[0][q];
-#pragma unroll
-    for (int g = 1; g < 16; ++g) t += red[g][q];
-    f32x4* out = reinterpret_cast<f32x4*>(dw) + e4;
-    *out = *out + t;
-  }
-}
-
 int wc64_blocks(int N, int H, int W, int* tiles_per_block) {
   const int cus = isic_cu_count();
   const int64_t total = (int64_t)N * ceil_div(H, WT_H) * ceil_div(W, WT_W);
@@ -441,7 +417,7 @@ int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int 
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   hipLaunchKernelGGL(wgrad_c64_kernel<0>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
-  hipLaunchKernelGGL(wgrad_c64_reduce_kernel, dim3(DW_ELEMS / 64), dim3(256), 0, stream, a.partial, dw, grid);
+  isic_slab_reduce_launch(ISIC_SLAB_LDS16_V2, a.partial, grid, DW_ELEMS, dw, 1.f, stream);   // dw += (slab_sum.inc, order B)
   return ISIC_OK;
 }
 
@@ -470,6 +446,6 @@ int isic_wgrad_c64_bnbwd_launch(const uint16_t* x, const uint16_t* g, const uint
     return ISIC_ERR_LAUNCH;
   if (m) hipLaunchKernelGGL(wgrad_c64_kernel<3>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
   else hipLaunchKernelGGL(wgrad_c64_kernel<2>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
-  hipLaunchKernelGGL(wgrad_c64_reduce_kernel, dim3(DW_ELEMS / 64), dim3(256), 0, stream, a.partial, dw, grid);
+  isic_slab_reduce_launch(ISIC_SLAB_LDS16_V2, a.partial, grid, DW_ELEMS, dw, 1.f, stream);   // dw += (slab_sum.inc, order B)
   return ISIC_OK;
 }

@@ -25,6 +25,7 @@
 // The reference has no convolution kernel of its own (un-vendored encoder, save_latent.py:42-60); ResNet-18 layer table:
 // SURVEY.md 8d.
 #include "common.h"
+#include "slab_sum.inc"
 #include "mfma_tile.h"
 
 namespace {
@@ -216,31 +217,6 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
       *reinterpret_cast<f32x4*>(part + ((size_t)(hh * 64 + c2 * 16 + fi) * 9 + t) * 64 + c * 16 + fg * 4) = acc[t][c2];
 }
 
-// dw[128 co_slice + co][tap][64 ci_slice + ci] += sum over the pair's blocks (fixed order): thread (q, grp) sums blocks
-// grp, grp+16, ... of four consecutive elements, the 16 group sums are combined through LDS in group order
-__global__ __launch_bounds__(256) void wgrad_s2_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw,
-                                                               int blocks_per_pair, int co_slices, int Cin) {
-  __shared__ f32x4 red[16][16];
-  const int q = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const size_t e4 = (size_t)blockIdx.x * 16 + q;                   // float4 index into [pairs][128][9][64]
-  const int pair = (int)(e4 / (SLICE_ELEMS / 4));
-  const size_t l4 = e4 - (size_t)pair * (SLICE_ELEMS / 4);         // ... inside the pair: (co * 9 + tap) * 16 + ci / 4
-  const float* base = partial + (size_t)pair * blocks_per_pair * SLICE_ELEMS;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
-  for (int b = grp; b < blocks_per_pair; b += 16) s0 += reinterpret_cast<const f32x4*>(base + (size_t)b * SLICE_ELEMS)[l4];
-  red[grp][q] = s0;
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    f32x4 t = red[0][q];
-#pragma unroll
-    for (int g = 1; g < 16; ++g) t += red[g][q];
-    const int ci_slice = pair / co_slices, co_slice = pair - ci_slice * co_slices;
-    const int row = (int)(l4 >> 4), ci4 = (int)(l4 & 15);           // row = co * 9 + tap
-    f32x4* out = reinterpret_cast<f32x4*>(dw + ((size_t)co_slice * 128 * 9 + row) * Cin + ci_slice * 64) + ci4;
-    *out = *out + t;
-  }
-}
-
 struct WS2Plan { int Ho, Wo, pack, slot_shift, Wv, tiles_y, tiles_x, total_tiles, tiles_per_block, blocks_per_pair, pairs; };
 
 bool ws2_plan(int N, int Hi, int Wi, int Cin, int Cout, WS2Plan& p) {
@@ -289,7 +265,7 @@ int isic_wgrad_s2_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   hipLaunchKernelGGL(wgrad_s2_kernel, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
-  hipLaunchKernelGGL(wgrad_s2_reduce_kernel, dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
+  hipLaunchKernelGGL((wgrad_pair_reduce_kernel<128, 64>), dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
                      p.blocks_per_pair, a.co_slices, Cin);
   return ISIC_OK;
 }

@@ -9,6 +9,7 @@
 // fixed order and multiplies by `scale`: no float atomics, so the backward is bit-reproducible.
 
 #include "common.h"
+#include "slab_sum.inc"
 
 namespace {
 
@@ -24,43 +25,23 @@ int64_t ct_grid(int64_t work, int64_t per_block, int64_t cap) {
 
 // ---------------------------------------------------------------- slab reducer
 // slab[S][n]: i < n_split -> out_a[i], else out_b[i - n_split] (skipped when out_b is NULL); (+)= scale * sum over the S
-// slabs.  A block covers 16 outputs with 16 threads each: thread p sums the slabs p, p + 16, ... into four accumulators
-// (slab z into accumulator (z / 16) % 4), the four are added pairwise and the 16 threads' partials in index order in LDS:
-// a fixed order, and 16 x 4 loads in flight per output instead of a chain of S dependent ones (512 slabs of the LayerNorm
-// backward took 112 us per call that way).
-constexpr int SR_COLS = 16, SR_PARTS = 16;
+// slabs, in the fixed order B of slab_sum.inc on scalars with four accumulators: a block covers 16 outputs with 16 threads
+// each, 16 x 4 loads in flight per output instead of a chain of S dependent ones (512 slabs of the LayerNorm backward took
+// 112 us per call that way).
 
 __global__ __launch_bounds__(256) void ct_slab_reduce_kernel(const float* __restrict__ slab, int S, int64_t n,
                                                              int64_t n_split, float* out_a, float* out_b, float scale,
                                                              int accumulate) {
-  __shared__ float part[SR_PARTS][SR_COLS + 1];
-  const int c = threadIdx.x % SR_COLS, p = threadIdx.x / SR_COLS;
-  const int64_t i = (int64_t)blockIdx.x * SR_COLS + c;
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  if (i < n) {
-    int z = p, k = 0;
-    for (; z + 3 * SR_PARTS < S; z += 4 * SR_PARTS) {
-      a[0] += slab[(int64_t)z * n + i];
-      a[1] += slab[(int64_t)(z + SR_PARTS) * n + i];
-      a[2] += slab[(int64_t)(z + 2 * SR_PARTS) * n + i];
-      a[3] += slab[(int64_t)(z + 3 * SR_PARTS) * n + i];
-    }
-    for (; z < S; z += SR_PARTS, ++k) a[k] += slab[(int64_t)z * n + i];
-  }
-  part[p][c] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  if (p != 0 || i >= n) return;
+  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
+  const float s = isic_slab_sum_lds16<4>(slab, (size_t)i, S, (size_t)n, i < n);
+  if (threadIdx.x >= 16 || i >= n) return;
   float* out = i < n_split ? out_a + i : (out_b ? out_b + (i - n_split) : nullptr);
-  if (!out) return;
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < SR_PARTS; ++q) s += part[q][c];
-  *out = accumulate ? fmaf(scale, s, *out) : scale * s;
+  if (out) *out = accumulate ? fmaf(scale, s, *out) : scale * s;
 }
 
 int ct_slab_reduce(const float* slab, int S, int64_t n, int64_t n_split, float* a, float* b, float scale, int accumulate,
                    hipStream_t st) {
-  hipLaunchKernelGGL(ct_slab_reduce_kernel, dim3((unsigned)((n + SR_COLS - 1) / SR_COLS)), dim3(SR_COLS * SR_PARTS), 0, st,
+  hipLaunchKernelGGL(ct_slab_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st,
                      slab, S, n, n_split, a, b, scale, accumulate);
   return isic_launch_status();
 }

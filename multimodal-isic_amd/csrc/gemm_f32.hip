@@ -11,6 +11,7 @@
 // and for B alike (any permutation of k is a valid summation order as long as
 // both operands use it).
 #include "common.h"
+#include "slab_sum.inc"
 #include "../../include/isic_hip_test.h"
 
 // persistent LDS-DMA kernel for the large products (gemm_f32p.hip); ISIC_ERR_UNSUPPORTED = "not for this shape"
@@ -46,7 +47,7 @@ struct GemmArgs {
   int transA, transB, act, vecA, vecB;
   float beta;
   int ksplit, klen;     // blockIdx.z handles k in [z*klen, (z+1)*klen): partial sums are atomically added to a pre-scaled C
-  float* partial;       // ... or, with a workspace, stored as [ksplit][M][N] and added in split order by gemm_split_reduce_kernel
+  float* partial;       // ... or, with a workspace, stored as [ksplit][M][N] and added in a fixed order (isic_gemm_split_reduce_launch, slab_reduce.hip)
 };
 
 // Load 4 consecutive elements (along the contiguous dim) of a row-major matrix
@@ -156,50 +157,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
     }
 }
 
-// C = beta * C + sum over the splits in a FIXED order (split-K happens without bias / activation only): 16 lanes per
-// element (lane g adds splits g, g + 16, ...) joined by a fixed xor tree -- up to ~200 splits of a 128 x 128 output would
-// otherwise be 200 dependent loads per thread
-__global__ __launch_bounds__(256) void gemm_split_reduce_kernel(const float* __restrict__ partial, int splits,
-                                                                 float* __restrict__ C, int M, int N, int ldc, float beta) {
-  const int64_t n = (int64_t)M * N;
-  const int g = threadIdx.x & 15;
-  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  float s = 0.f;
-  if (i < n)
-    for (int z = g; z < splits; z += 16) s += partial[(size_t)z * n + i];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (i < n && g == 0) {
-    float* p = C + (i / N) * ldc + (i % N);
-    *p = beta != 0.f ? beta * (*p) + s : s;
-  }
-}
-
-// ... four consecutive elements per thread (N % 4 == 0, 16-byte aligned rows): 16 float4 columns x 16 split groups per block, a
-// thread adds splits g, g + 16, ... with every load independent (16 in flight at 256 splits), the groups are joined through
-// LDS in group order.  The 16-lane form above moves a 256 x 64 KB stack of partial tiles in 9.4 us; this one in half.
-__global__ __launch_bounds__(256) void gemm_split_reduce4_kernel(const float* __restrict__ partial, int splits,
-                                                                  float* __restrict__ C, int M, int N, int ldc, float beta) {
-  __shared__ f32x4 red[16][16];
-  const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int64_t n4 = (int64_t)M * N / 4, e4 = (int64_t)blockIdx.x * 16 + q;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (e4 < n4) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(partial) + e4;
-    for (int z = g; z < splits; z += 16) s += p[(size_t)z * n4];
-  }
-  red[g][q] = s;
-  __syncthreads();
-  if (threadIdx.x < 16 && e4 < n4) {
-    f32x4 t = red[0][q];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += red[k][q];
-    const int64_t i = e4 * 4;
-    f32x4* out = reinterpret_cast<f32x4*>(C + (i / N) * ldc + (i % N));
-    *out = beta != 0.f ? beta * (*out) + t : t;
-  }
-}
-
 // C[M,N] *= beta (0: zero fill) ahead of a split-K accumulation
 __global__ void gemm_scale_kernel(float* __restrict__ C, int M, int N, int ldc, float beta) {
   const int64_t n = (int64_t)M * N;
@@ -213,8 +170,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
                                                       float* __restrict__ out, float beta, int rows_per_block,
                                                       float* __restrict__ partial) {
   // one block per 64 columns x row chunk; 4 waves stride the rows; deterministic tree over waves.  With more than
-  // one row chunk (gridDim.y > 1) the chunk sums are parked in `partial` ([gridDim.y][N], added in chunk order by
-  // colsum_reduce_kernel) or, without a workspace, atomically added to the pre-scaled output.
+  // one row chunk (gridDim.y > 1) the chunk sums are parked in `partial` ([gridDim.y][N], added in a fixed order by
+  // the 16-lane reducer of slab_reduce.hip) or, without a workspace, atomically added to the pre-scaled output.
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = blockIdx.x * 64 + lane;
@@ -264,8 +221,8 @@ __global__ __launch_bounds__(1024) void colsum_small_kernel(const float* __restr
 // thread; LDS tree over the row lanes, one atomic per column and block into the pre-scaled output.  FEW, FAT blocks:
 // same-address atomics retire at ~3 ns each per cache line (measured: 392 blocks x 128 columns took 41 us, all of it
 // atomics), so the grid is ~96 blocks of 16 waves, not one block per 128 rows.
-// With `partial` (workspace [gridDim.y][N]) a block stores its chunk sums there and colsum_reduce_kernel adds the chunks in
-// order: bit-reproducible.  Without a workspace the chunks meet through fp32 atomics in arrival order.
+// With `partial` (workspace [gridDim.y][N]) a block stores its chunk sums there and the 16-lane reducer of slab_reduce.hip adds the
+// chunks in a fixed order: bit-reproducible.  Without a workspace the chunks meet through fp32 atomics in arrival order.
 template <int VGB>
 __global__ __launch_bounds__(1024) void colsum4_kernel(const float* __restrict__ X, int M, int N, int ldx,
                                                        float* __restrict__ out, int rows_per_block,
@@ -301,20 +258,6 @@ __global__ __launch_bounds__(1024) void colsum4_kernel(const float* __restrict__
       for (int e = 0; e < 4; ++e) atomicAdd(out + col + e, t[e]);
     }
   }
-}
-
-// out[n] = beta * out[n] + sum over the chunks in a fixed order: 16 lanes per column (lane g adds chunks g, g + 16, ...)
-// joined by a fixed xor tree (one thread per column walked ~96 dependent loads: 19 us for 128 columns)
-__global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restrict__ partial, int chunks, int N,
-                                                             float* __restrict__ out, float beta) {
-  const int g = threadIdx.x & 15;
-  const int n = blockIdx.x * 16 + (threadIdx.x >> 4);
-  float s = 0.f;
-  if (n < N)
-    for (int c = g; c < chunks; c += 16) s += partial[(size_t)c * N + n];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (n < N && g == 0) out[n] = beta != 0.f ? beta * out[n] + s : s;
 }
 
 __global__ void tanh_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ t, float* __restrict__ dx,
@@ -407,17 +350,6 @@ inline int grid_for(int64_t n, int block) {
 }
 
 }  // namespace
-
-void isic_gemm_split_reduce_launch(const float* partial, int splits, float* C, int M, int N, int ldc, float beta,
-                                   hipStream_t stream) {
-  if (N % 4 == 0 && ldc % 4 == 0 && ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(C)) & 15) == 0) {
-    hipLaunchKernelGGL(gemm_split_reduce4_kernel, dim3((unsigned)ceil_div64((int64_t)M * N / 4, 16)), dim3(256), 0, stream,
-                       partial, splits, C, M, N, ldc, beta);
-    return;
-  }
-  hipLaunchKernelGGL(gemm_split_reduce_kernel, dim3((unsigned)ceil_div64((int64_t)M * N, 16)), dim3(256), 0, stream, partial,
-                     splits, C, M, N, ldc, beta);
-}
 
 extern "C" {
 
@@ -590,8 +522,7 @@ int isic_colsum_f32_ws(const float* X, int M, int N, int ldx, float* out, float 
     else if (vgb == 32) hipLaunchKernelGGL(colsum4_kernel<32>, grid, dim3(1024), 0, as_stream(stream), X, M, N, ldx, out, rpb, partial);
     else hipLaunchKernelGGL(colsum4_kernel<16>, grid, dim3(1024), 0, as_stream(stream), X, M, N, ldx, out, rpb, partial);
     if (partial)
-      hipLaunchKernelGGL(colsum_reduce_kernel, dim3(ceil_div(N, 16)), dim3(256), 0, as_stream(stream), partial, chunks4, N, out,
-                         beta);
+      isic_slab_reduce_launch(ISIC_SLAB_XOR16, partial, chunks4, N, out, beta, as_stream(stream));   // scalar also where N % 4 == 0
     return isic_launch_status();
   }
   // few column blocks x many rows (bias gradients over all the nodes of a batch): split the rows over blockIdx.y
@@ -609,8 +540,7 @@ int isic_colsum_f32_ws(const float* X, int M, int N, int ldx, float* out, float 
   hipLaunchKernelGGL(colsum_kernel, dim3(colblocks, chunks), dim3(256), 0, as_stream(stream), X, M, N, ldx, out, beta,
                      rows_per_block, partial);
   if (partial)
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3(ceil_div(N, 16)), dim3(256), 0, as_stream(stream), partial, chunks, N, out,
-                       beta);
+    isic_slab_reduce_launch(ISIC_SLAB_XOR16, partial, chunks, N, out, beta, as_stream(stream));
   return isic_launch_status();
 }
 

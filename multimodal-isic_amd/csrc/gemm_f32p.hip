@@ -26,6 +26,7 @@
 // Shapes the DMA path cannot take (a dimension that is not a multiple of 4 floats, unaligned pointers) and small products
 // stay on gemm_f32.hip's kernel: isic_gemm_f32_ws decides.
 #include "common.h"
+#include "slab_sum.inc"
 #include "mfma_tile.h"
 
 namespace {
@@ -292,25 +293,16 @@ __global__ __launch_bounds__(1024) void gemm_f32p_kernel(G32Args a) {
   }   // MFMA waves
 }
 
-// C = act(sum over the splits, in a FIXED order, + bias) + beta * C.  partial: [splits][M][N].  Eight lanes per group of 4
-// columns: lane g adds splits g, g + 8, ... (16-byte loads), a fixed xor tree joins them -- one thread per element group
-// walked up to ~200 dependent loads (29 us for a 128 x 768 output and 85 splits).
+// C = act(sum over the splits, in a FIXED order, + bias) + beta * C.  partial: [splits][M][N].  slab_sum.inc, order A on
+// f32x4 with eight lanes per group of 4 columns (16-byte loads) -- one thread per element group walked up to ~200
+// dependent loads (29 us for a 128 x 768 output and 85 splits).
 __global__ __launch_bounds__(256) void gemm_f32p_reduce_kernel(G32Args a) {
   const int nv = a.N >> 2;
-  const int g = threadIdx.x & 7;
-  const int64_t idx = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 3);
+  const int64_t idx = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 3);          // f32x4 index into a slab: m * nv + n / 4
   const bool live = idx < (int64_t)a.M * nv;
   const int m = live ? (int)(idx / nv) : 0, n = live ? (int)(idx - (int64_t)m * nv) * 4 : 0;
-  const size_t stride = (size_t)a.M * a.N;
-  const float* p = a.partial + (size_t)m * a.N + n;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (live)
-    for (int z = g; z < a.splits; z += 8) s += *reinterpret_cast<const f32x4*>(p + (size_t)z * stride);
-#pragma unroll
-  for (int o = 4; o > 0; o >>= 1)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] += __shfl_xor(s[e], o, 8);
-  if (!live || g != 0) return;
+  const f32x4 s = isic_slab_sum_xor<8>(reinterpret_cast<const f32x4*>(a.partial), (size_t)idx, a.splits, (size_t)a.M * nv, live);
+  if (!live || (threadIdx.x & 7) != 0) return;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float v = g32_act(s[e] + (a.bias ? a.bias[n + e] : 0.f), a.act);

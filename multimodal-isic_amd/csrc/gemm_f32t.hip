@@ -11,12 +11,12 @@
 //     per wave;
 //   * a block is a 128 x 128 output tile x a slab of K: 2 x 2 wave tiles x 2 K-groups (the two groups walk alternate
 //     k-steps, their sums are joined through LDS at the end); P k-steps of loads are in flight per wave (registers);
-//   * all 256 CUs get a slab; the slabs' partial tiles go to the caller's workspace and are added in slab order by
-//     gemm_split_reduce_kernel (gemm_f32.hip): no atomics, bit-reproducible.
+//   * all 256 CUs get a slab; the slabs' partial tiles go to the caller's workspace and are added in a fixed order by
+//     isic_gemm_split_reduce_launch (slab_reduce.hip): no atomics, bit-reproducible.
 // Replaces, for these shapes, the 64 x 64 x 16 kernel's split-K (196 splits of 256 k, k-strided operands transposed through
 // scalar LDS stores): 85 us -> see profiles/r03_gemm_bench.txt.  Reference: the autograd backward of the nn.Linear /
 // GCNConv weights in 05_train_gnns.py:66,82,126-139.
-#include "common.h"
+#include "slab_sum.inc"
 
 namespace {
 
@@ -134,10 +134,6 @@ bool tn_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, cons
 }
 
 }  // namespace
-
-// gemm_f32.hip
-void isic_gemm_split_reduce_launch(const float* partial, int splits, float* C, int M, int N, int ldc, float beta,
-                                   hipStream_t stream);
 
 size_t isic_gemm_f32t_workspace_bytes(int transA, int transB, int M, int N, int K) {
   TnPlan p;

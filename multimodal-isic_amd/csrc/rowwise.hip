@@ -7,6 +7,7 @@
 // 01_train_mil_teacher.py:143,244 / 05_train_gnns.py:344 and
 // torch.optim.AdamW/Adam (01:217-224, 05:332-333).
 #include "common.h"
+#include "slab_sum.inc"
 
 namespace {
 
@@ -103,20 +104,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
   }
 }
 
-// dgamma[n] += sum over the blocks' partial rows (and dbeta likewise), in block order: 16 lanes per column, fixed xor tree
-// (dxsum != NULL: a third row per block, the column sums of dx -- the bias gradient of the layer below)
+// dgamma[n] += sum over the blocks' partial rows (and dbeta likewise) in a fixed order: slab_sum.inc, order A with 16 lanes
+// per column (dxsum != NULL: a third row per block, the column sums of dx -- the bias gradient of the layer below)
 __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restrict__ partial, int nblocks, int N,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                              float* __restrict__ dxsum) {
-  const int g = threadIdx.x & 15;
   const int nv = dxsum ? 3 : 2;
   const int n = blockIdx.x * 16 + (threadIdx.x >> 4);        // 0 .. nv*N-1: dgamma columns, then dbeta columns (, then dx sums)
-  float s = 0.f;
-  if (n < nv * N)
-    for (int b = g; b < nblocks; b += 16) s += partial[(size_t)b * nv * N + n];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (n < nv * N && g == 0) {
+  const float s = isic_slab_sum_xor<16>(partial, (size_t)n, nblocks, (size_t)nv * N, n < nv * N);
+  if (n < nv * N && (threadIdx.x & 15) == 0) {
     if (n < N) dgamma[n] += s; else if (n < 2 * N) dbeta[n - N] += s; else dxsum[n - 2 * N] += s;
   }
 }

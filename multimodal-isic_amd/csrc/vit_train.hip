@@ -13,7 +13,9 @@
 namespace {
 
 // ------------------------------------------------------------------ slab reducer
-// out[i] = (accumulate ? out[i] : 0) + scale * sum_{z < S} ws[z][i], z in index order
+// out[i] = (accumulate ? out[i] : 0) + scale * sum_{z < S} ws[z][i], z in index order: one thread per element, i.e. order
+// A of slab_sum.inc with G = 1 and no tree.  It keeps its own text: it issues four loads ahead of four dependent adds, a
+// different instruction stream from the one-load-per-add walk of isic_slab_sum_xor, and the adds are the same either way.
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ ws, int S, int64_t n, float* out,
                                                           float scale, int accumulate) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
