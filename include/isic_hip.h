@@ -625,7 +625,10 @@ int isic_gemm_f16_stats(const uint16_t* A, const uint16_t* W, const float* bias,
                         float* row_stats, int M, int N, int K, int act, int residual_rows, void* stream);
 int isic_gemm_f16_ln(const uint16_t* X, const uint16_t* Wg, const float* bias_b, const float* ln_c, const float* ln_stats,
                      int ln_parts, uint16_t* C, int M, int N, int K, int act, float eps, void* stream);
-/* (mean, rstd) of every row of x[M][N] (fp16, N in {128, 256, 384, 512}) with isic_layernorm_f16's arithmetic. */
+/* (mean, rstd) of every row of x[M][N] (fp16, N in {128, 256, 384, 512}): isic_layernorm_f16's kernel with another way
+ * out (csrc/ln_rows.inc: one source text, the same sums in the same order, mean = sum * (1 / N)).  NOT its bits: the
+ * compiler contracts multiply-adds per kernel, so these statistics may differ in the last bit from the ones
+ * isic_layernorm_f16 normalises with; tests/test_ln_rows_gpu.py pins the bits of each. */
 int isic_row_stats_f16(const uint16_t* x, float* stats, int64_t M, int N, float eps, void* stream);
 /* images NCHW fp32 -> rows[N*(H/P)*(W/P)][C*P*P] fp16: the im2col of the P x P / stride P patch projection
  * (Conv2d weight [D][C][P][P] flattened is the Linear weight).  P % 8 == 0, H % P == W % P == 0. */

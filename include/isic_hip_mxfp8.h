@@ -24,8 +24,11 @@ extern "C" {
 /* Rows x[M][K] (fp16 bit patterns if x_is_f32 == 0, fp32 if 1) -> (q, s): the weights (from the fp32 masters, once per
  * weight version) and the attention output before attn.proj.  K % 32 == 0, else UNSUPPORTED. */
 int isic_mxfp8_quantize(const void* x, int x_is_f32, uint8_t* q, uint8_t* s, int64_t M, int K, void* stream);
-/* LayerNorm over the N = 384 fp16 values of a row (isic_layernorm_f16's arithmetic, affine, eps) quantised to MXFP8
- * straight from the fp32 normalised values (no fp16 rounding between).  N != 384: UNSUPPORTED. */
+/* LayerNorm over the N = 384 fp16 values of a row (affine, eps) quantised to MXFP8 straight from the fp32 normalised
+ * values (no fp16 rounding between): isic_layernorm_f16's kernel with another way out (csrc/ln_rows.inc: one source text,
+ * the same sums in the same order, mean = sum * (1 / N)).  The compiler contracts multiply-adds per kernel, so the fp32
+ * values quantised here may differ in the last bit from the ones isic_layernorm_f16 writes;
+ * tests/test_ln_rows_gpu.py pins the bits of each.  N != 384: UNSUPPORTED. */
 int isic_layernorm_mxfp8_f16(const uint16_t* x, const float* gamma, const float* beta, uint8_t* q, uint8_t* s, int64_t M,
                              int N, float eps, void* stream);
 /* C = act((A_q . A_s)[M,K] (W_q . W_s)[N,K]^T + bias) (+ residual), fp32 accumulation on the block-scaled MFMA.  bias,

@@ -5,7 +5,7 @@
 // every kernel may see and that bench.py therefore stamps its PMC traffic profile with.)
 #pragma once
 #include "common.h"
-#include "mx_quant.inc"
+#include "ln_rows.inc"       // ln_row_center; brings mx_quant.inc
 
 namespace {
 
@@ -112,18 +112,12 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
     const size_t pix0 = (size_t)n * H * W + (size_t)h0 * W + ow;
 #pragma unroll
     for (int r = 0; r < DW_TH; ++r) {
-      float am = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(acc[r][j]));
-      am = fmaxf(am, __shfl_xor(am, 1));
-      am = fmaxf(am, __shfl_xor(am, 2));
-      const bool zero = !(am > 0.f);
-      const int e = zero ? 0 : mx_exponent(am);
-      const u32x2 o = mx_pack8(acc[r], zero ? 0.f : mx_inv_scale(e), zero);
+      unsigned char scale;
+      const u32x2 o = mx_block8(acc[r], scale);
       if (h0 + r < H) {
         const size_t pix = pix0 + (size_t)r * W;
         *reinterpret_cast<u32x2*>(mq + pix * C + cb) = o;
-        if ((g & 3) == 0) ms[pix * (C >> 5) + (cb >> 5)] = (unsigned char)(zero ? 0 : e + 127);
+        if ((g & 3) == 0) ms[pix * (C >> 5) + (cb >> 5)] = scale;
       }
     }
     return;
@@ -141,7 +135,8 @@ __global__ __launch_bounds__(256) void dwconv5x5_f16_kernel(const unsigned short
 
 // ---------------------------------------------------------------- LayerNorm of (x + a + b), optional GELU
 // One wave per row, CPL 16-byte pieces per lane (N / 8 <= 64 CPL); four rows per block.  Two-pass statistics in fp32 on
-// the values held in registers (the arithmetic of layernorm_f16_kernel).
+// the values held in registers: ln_row_center (csrc/ln_rows.inc), the text the ViT-width layernorm_f16_kernel runs too, here
+// with the mean as a true division (LN_MEAN_DIV, explained there).
 // MX (include/isic_hip_convmae_mxfp8.h): no addends, and the fp32 values y32 would receive are quantised to MXFP8 instead
 // -- lanes 4 k .. 4 k + 3 hold the 32-element block lane / 4 + 16 i of the row, and N % 64 == 0 switches those four lanes
 // on or off together; mq[M][N] takes the element bytes, ms[M][N / 32] the scales.
@@ -159,45 +154,8 @@ __global__ __launch_bounds__(256) void layernorm_add_f16_kernel(const unsigned s
   const int pieces = N >> 3;
   const float invn = 1.f / (float)N;
   for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
-    float f[CPL][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int q = lane + 64 * i;
-      const bool on = q < pieces;
-      const size_t off = (size_t)row * N + (size_t)(on ? q : 0) * 8;
-      f16_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
-      if (a) {
-        float t[8];
-        f16_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[i][j] += t[j];
-      }
-      if (b) {
-        float t[8];
-        f16_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[i][j] += t[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += on ? f[i][j] : 0.f;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    // a true division, not s * invn: the compiler fuses "f - s * invn" into one FMA with the product unrounded, and where
-    // 1 / N is inexact (N = 768: 2 * 768 * fl(1 / 768) = 2 + 2^-24) a constant row no longer cancels to 0 -- times
-    // rstd = 1 / sqrt(eps) that is 6e-5 in x^.  N c / N is exact for every row of equal values c.
-    const float mean = s / (float)N;
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const bool on = lane + 64 * i < pieces;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { f[i][j] -= mean; v += on ? f[i][j] * f[i][j] : 0.f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const float rstd = rsqrtf(v * invn + eps);
+    float f[CPL][8], mean, rstd;
+    ln_row_center<64, CPL, LN_MEAN_DIV>(x, a, b, (size_t)row * N, lane, pieces, N, invn, eps, f, mean, rstd);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
       const int q = lane + 64 * i;
@@ -215,17 +173,11 @@ __global__ __launch_bounds__(256) void layernorm_add_f16_kernel(const unsigned s
       }
       const size_t off = (size_t)row * N + col;
       if (MX) {                                                        // every lane reaches the shuffles
-        float am = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(o8[j]));
-        am = fmaxf(am, __shfl_xor(am, 1));
-        am = fmaxf(am, __shfl_xor(am, 2));
-        const bool zero = !(am > 0.f);
-        const int e = zero ? 0 : mx_exponent(am);
-        const u32x2 o = mx_pack8(o8, zero ? 0.f : mx_inv_scale(e), zero);
+        unsigned char scale;
+        const u32x2 o = mx_block8(o8, scale);
         if (q < pieces) {
           *reinterpret_cast<u32x2*>(mq + off) = o;
-          if ((lane & 3) == 0) ms[(size_t)row * (N >> 5) + (q >> 2)] = (unsigned char)(zero ? 0 : e + 127);
+          if ((lane & 3) == 0) ms[(size_t)row * (N >> 5) + (q >> 2)] = scale;
         }
         continue;
       }

@@ -26,17 +26,11 @@ __global__ __launch_bounds__(256) void patch_rows_mx_kernel(const unsigned short
   const unsigned short* src = x + (((size_t)n * H + (size_t)(py * P + kh)) * W + (size_t)px * P) * C + rem;
   float f[8];
   f16_unpack8(*reinterpret_cast<const u32x4*>(src), f);
-  float am = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(f[j]));
-  am = fmaxf(am, __shfl_xor(am, 1));
-  am = fmaxf(am, __shfl_xor(am, 2));
-  const bool zero = !(am > 0.f);
-  const int e = zero ? 0 : mx_exponent(am);
-  const u32x2 o = mx_pack8(f, zero ? 0.f : mx_inv_scale(e), zero);
+  unsigned char scale;
+  const u32x2 o = mx_block8(f, scale);
   if (live) {
     *reinterpret_cast<u32x2*>(q + i * 8) = o;
-    if ((gid & 3) == 0) s[i >> 2] = (unsigned char)(zero ? 0 : e + 127);
+    if ((gid & 3) == 0) s[i >> 2] = scale;
   }
 }
 

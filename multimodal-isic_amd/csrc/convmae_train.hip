@@ -9,6 +9,7 @@
 // fixed order and multiplies by `scale`: no float atomics, so the backward is bit-reproducible.
 
 #include "common.h"
+#include "ln_rows.inc"
 #include "slab_sum.inc"
 
 namespace {
@@ -179,8 +180,10 @@ __global__ __launch_bounds__(256) void dwconv5x5_wgrad_f16_kernel(const unsigned
 }
 
 // ---------------------------------------------------------------- LayerNorm of (x + a + b) (+ GELU): backward
-// One wave per row with the forward's layout (lane l holds the 16-byte pieces l + 64 i, i < CPL), so the recomputed
-// (mean, rstd) are the forward's own arithmetic.  Rows are split over a fixed grid of blocks in contiguous chunks; a lane
+// One wave per row with the forward's layout (lane l holds the 16-byte pieces l + 64 i, i < CPL) and the forward's text
+// for the statistics (ln_row_center, csrc/ln_rows.inc: the same sums in the same order, the mean a true division).  The
+// compiler contracts multiply-adds per kernel, so the recomputed (mean, rstd) may differ from the forward's in the last
+// bit; tests/test_ln_rows_gpu.py pins both.  Rows are split over a fixed grid of blocks in contiguous chunks; a lane
 // keeps its columns' partial (sum dy x^, sum dy) over its wave's rows, the four waves are added in LDS in index order and
 // each block writes one slab [2][N].
 constexpr int LA_BLOCKS = 512;
@@ -223,43 +226,9 @@ __global__ __launch_bounds__(256) void layernorm_add_bwd_f16_kernel(const void* 
   }
   const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = min(M, r0 + chunk);
   for (int64_t row = r0 + wave; row < r1; row += 4) {
-    // ---- the forward's statistics (layernorm_add_f16_kernel, convmae.hip)
-    float f[CPL][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int q = lane + 64 * i;
-      const bool on = q < pieces;
-      const size_t off = (size_t)row * N + (size_t)(on ? q : 0) * 8;
-      f16_unpack8(*reinterpret_cast<const u32x4*>(x + off), f[i]);
-      if (a) {
-        float t[8];
-        f16_unpack8(*reinterpret_cast<const u32x4*>(a + off), t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[i][j] += t[j];
-      }
-      if (b) {
-        float t[8];
-        f16_unpack8(*reinterpret_cast<const u32x4*>(b + off), t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[i][j] += t[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += on ? f[i][j] : 0.f;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)N;                 // the forward's: a division (convmae.hip, layernorm_add_f16_kernel)
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const bool on = lane + 64 * i < pieces;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { f[i][j] -= mean; v += on ? f[i][j] * f[i][j] : 0.f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const float rstd = rsqrtf(v * invn + eps);
+    // ---- the forward's statistics: the same text and mean rule as layernorm_add_f16_kernel (ln_row_center)
+    float f[CPL][8], mean, rstd;
+    ln_row_center<64, CPL, LN_MEAN_DIV>(x, a, b, (size_t)row * N, lane, pieces, N, invn, eps, f, mean, rstd);
     // ---- backward: f becomes x^, d the (GELU-differentiated) incoming gradient
     float d[CPL][8];
     float s1 = 0.f, s2 = 0.f;

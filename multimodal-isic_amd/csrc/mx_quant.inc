@@ -44,6 +44,20 @@ __device__ __forceinline__ u32x2 mx_pack8(const float (&f)[8], float inv, bool z
   return o;
 }
 
+// One lane's 8 values of a 32-element block that four consecutive lanes hold (lanes 4 k .. 4 k + 3; all four must reach
+// the shuffles): amax over the block, its exponent, the lane's element bytes and the block's scale byte.
+__device__ __forceinline__ u32x2 mx_block8(const float (&f)[8], unsigned char& scale) {
+  float am = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(f[j]));
+  am = fmaxf(am, __shfl_xor(am, 1));
+  am = fmaxf(am, __shfl_xor(am, 2));
+  const bool zero = !(am > 0.f);
+  const int e = zero ? 0 : mx_exponent(am);
+  scale = (unsigned char)(zero ? 0 : e + 127);
+  return mx_pack8(f, zero ? 0.f : mx_inv_scale(e), zero);
+}
+
 // the same 8 conversions on v_cvt_pk_fp8_f32 (gfx950: OCP e4m3fn, round to nearest even in the normal range; |v * inv|
 // <= 448, so its saturation behaviour never matters) with the e4m3 subnormal range (|t| < 2^-6) redone by the rule's
 // integer form: the converter's handling of that range has not been checked bit for bit against the rule.  The GELU +

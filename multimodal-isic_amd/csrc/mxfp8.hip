@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "mx_quant.inc"
+#include "ln_rows.inc"       // layernorm_f16_kernel<64, 48, LN_OUT_MX>: the row LayerNorm of isic_layernorm_mxfp8_f16
 
 namespace {
 
@@ -50,69 +51,11 @@ __global__ __launch_bounds__(256) void mx_quantize_kernel(const void* __restrict
       f[2 * j + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
     }
   }
-  float am = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(f[j]));
-  am = fmaxf(am, __shfl_xor(am, 1));
-  am = fmaxf(am, __shfl_xor(am, 2));
-  const bool zero = !(am > 0.f);
-  const int e = zero ? 0 : mx_exponent(am);
-  const u32x2 o = mx_pack8(f, zero ? 0.f : mx_inv_scale(e), zero);
+  unsigned char scale;
+  const u32x2 o = mx_block8(f, scale);
   if (live) {
     *reinterpret_cast<u32x2*>(q + piece * 8) = o;
-    if ((gid & 3) == 0) s[blk] = (unsigned char)(zero ? 0 : e + 127);
-  }
-}
-
-// ---------------------------------------------------------------- LayerNorm -> MXFP8
-// layernorm_f16_kernel's arithmetic for D = 384 (LPR 64, 48 active lanes of 8 values, the same sums in the same order),
-// quantised from the fp32 normalised values: lanes 4b .. 4b + 3 hold block b of the row.
-__global__ __launch_bounds__(256) void layernorm_mx_kernel(const unsigned short* __restrict__ x, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, unsigned char* __restrict__ q,
-                                                           unsigned char* __restrict__ s, int64_t M, float eps) {
-  constexpr int LPR = 64, ACT = 48, N = 8 * ACT;
-  const int lane = threadIdx.x % LPR, rl = threadIdx.x / LPR, rls = 256 / LPR;
-  const bool act = lane < ACT;
-  const int col = (act ? lane : 0) * 8;
-  float g[8], b[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { g[j] = gamma[col + j]; b[j] = beta[col + j]; }
-  for (int64_t row = (int64_t)blockIdx.x * rls + rl; row < M; row += (int64_t)gridDim.x * rls) {
-    float f[8];
-    const u32x4 v = *reinterpret_cast<const u32x4*>(x + row * N + col);
-    {
-      const unsigned w0 = v[0], w1 = v[1], w2 = v[2], w3 = v[3];
-      const unsigned ws[4] = {w0, w1, w2, w3};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f[2 * j] = (float)__builtin_bit_cast(_Float16, (unsigned short)(ws[j] & 0xFFFFu));
-        f[2 * j + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(ws[j] >> 16));
-      }
-    }
-    float sm = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sm += act ? f[j] : 0.f;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) sm += __shfl_xor(sm, o, LPR);
-    const float mean = sm * (1.f / N);
-    float var = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { f[j] -= mean; var += act ? f[j] * f[j] : 0.f; }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) var += __shfl_xor(var, o, LPR);
-    const float rstd = rsqrtf(var * (1.f / N) + eps);
-    float am = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { f[j] = f[j] * rstd * g[j] + b[j]; am = fmaxf(am, fabsf(f[j])); }
-    am = fmaxf(am, __shfl_xor(am, 1, LPR));
-    am = fmaxf(am, __shfl_xor(am, 2, LPR));
-    const bool zero = !(am > 0.f);
-    const int e = zero ? 0 : mx_exponent(am);
-    const u32x2 o = mx_pack8(f, zero ? 0.f : mx_inv_scale(e), zero);
-    if (act) {
-      *reinterpret_cast<u32x2*>(q + row * N + col) = o;
-      if ((lane & 3) == 0) s[row * (N / 32) + (lane >> 2)] = (unsigned char)(zero ? 0 : e + 127);
-    }
+    if ((gid & 3) == 0) s[blk] = scale;
   }
 }
 
@@ -349,7 +292,8 @@ int isic_layernorm_mxfp8_f16(const uint16_t* x, const float* gamma, const float*
   ISIC_CHECK_ARG(x && gamma && beta && q && s);
   int64_t g = (M + 16 - 1) / 16;
   if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(layernorm_mx_kernel, dim3((int)g), dim3(256), 0, as_stream(stream), x, gamma, beta, q, s, M, eps);
+  hipLaunchKernelGGL((layernorm_f16_kernel<64, 48, LN_OUT_MX>), dim3((int)g), dim3(256), 0, as_stream(stream), x, gamma, beta,
+                     q, s, M, eps);
   return isic_launch_status();
 }
 

@@ -7,6 +7,7 @@
 // CPU restatement.
 
 #include "common.h"
+#include "ln_rows.inc"       // layernorm_f16_kernel: the row LayerNorm of isic_layernorm_f16 and isic_row_stats_f16
 
 namespace {
 
@@ -28,78 +29,6 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
     const float f[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     *reinterpret_cast<u32x4*>(out + i * 8) = f16_pack8(f);
-  }
-}
-
-// ---------------------------------------------------------------- LayerNorm, rows of N = 8 * ACT halves
-// LPR lanes per row (a power of two, for the shuffles), the first ACT of them active (N = 384: 48 of 64), 16 bytes per
-// lane; y fp16 and / or y32 fp32 (the encoder's final norm hands fp32 tokens to the MIL head).
-template <int LPR, int ACT>
-__global__ __launch_bounds__(256) void layernorm_f16_kernel(const unsigned short* __restrict__ x,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             unsigned short* __restrict__ y, float* __restrict__ y32,
-                                                             int64_t M, float eps) {
-  constexpr int N = 8 * ACT;
-  const int lane = threadIdx.x % LPR, rl = threadIdx.x / LPR, rls = 256 / LPR;
-  const bool act = lane < ACT;
-  const int col = (act ? lane : 0) * 8;
-  float g[8], b[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { g[j] = gamma[col + j]; b[j] = beta[col + j]; }
-  for (int64_t row = (int64_t)blockIdx.x * rls + rl; row < M; row += (int64_t)gridDim.x * rls) {
-    float f[8];
-    f16_unpack8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += act ? f[j] : 0.f;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mean = s * (1.f / N);
-    float v = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { f[j] -= mean; v += act ? f[j] * f[j] : 0.f; }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
-    const float rstd = rsqrtf(v * (1.f / N) + eps);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = f[j] * rstd * g[j] + b[j];
-    if (act && y) *reinterpret_cast<u32x4*>(y + row * N + col) = f16_pack8(f);
-    if (act && y32) {
-      *reinterpret_cast<f32x4*>(y32 + row * N + col) = (f32x4){f[0], f[1], f[2], f[3]};
-      *reinterpret_cast<f32x4*>(y32 + row * N + col + 4) = (f32x4){f[4], f[5], f[6], f[7]};
-    }
-  }
-}
-
-// ---------------------------------------------------------------- LayerNorm statistics only
-// (mean, rstd) per row with the arithmetic of layernorm_f16_kernel, for a LayerNorm folded into the product that consumes it
-// (isic_gemm_f16_ln): reads x once, writes 8 bytes per row.
-template <int LPR, int ACT>
-__global__ __launch_bounds__(256) void row_stats_f16_kernel(const unsigned short* __restrict__ x, float* __restrict__ stats,
-                                                             int64_t M, float eps) {
-  constexpr int N = 8 * ACT;
-  const int lane = threadIdx.x % LPR, rl = threadIdx.x / LPR, rls = 256 / LPR;
-  const bool act = lane < ACT;
-  const int col = (act ? lane : 0) * 8;
-  for (int64_t row = (int64_t)blockIdx.x * rls + rl; row < M; row += (int64_t)gridDim.x * rls) {
-    float f[8];
-    f16_unpack8(*reinterpret_cast<const u32x4*>(x + row * N + col), f);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += act ? f[j] : 0.f;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mean = s * (1.f / N);
-    float v = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { f[j] -= mean; v += act ? f[j] * f[j] : 0.f; }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
-    if (lane == 0) {
-      stats[row * 2] = mean;
-      stats[row * 2 + 1] = rsqrtf(v * (1.f / N) + eps);
-    }
   }
 }
 
@@ -267,6 +196,26 @@ __global__ __launch_bounds__(AT_WAVES * 64, 2) void attention_f16_kernel(const u
   }
 }
 
+// One dispatch for the two entry points over layernorm_f16_kernel (o0, o1: the mode's outputs, csrc/ln_rows.inc): a block
+// takes 256 / LPR rows per pass, the grid four passes' worth of blocks up to 8192.
+template <LnOut OUT>
+int ln16_launch(const uint16_t* x, const float* gamma, const float* beta, void* o0, void* o1, int64_t M, int N, float eps,
+                       void* stream) {
+  int64_t g;
+#define LAUNCH_LN16(LPR, ACT)                                                                                    \
+  g = (M + (256 / LPR) * 4 - 1) / ((256 / LPR) * 4);                                                             \
+  if (g > 8192) g = 8192;                                                                                        \
+  hipLaunchKernelGGL((layernorm_f16_kernel<LPR, ACT, OUT>), dim3((int)g), dim3(256), 0, as_stream(stream), x, gamma, beta, \
+                     o0, o1, M, eps)
+  if (N == 128) { LAUNCH_LN16(16, 16); }
+  else if (N == 256) { LAUNCH_LN16(32, 32); }
+  else if (N == 384) { LAUNCH_LN16(64, 48); }
+  else if (N == 512) { LAUNCH_LN16(64, 64); }
+  else return ISIC_ERR_UNSUPPORTED;
+#undef LAUNCH_LN16
+  return isic_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -286,37 +235,14 @@ int isic_layernorm_f16(const uint16_t* x, const float* gamma, const float* beta,
   ISIC_CHECK_ARG(M >= 0 && N > 0);
   if (M == 0) return ISIC_OK;
   ISIC_CHECK_ARG(x && gamma && beta && (y || y_f32));
-  int64_t g;
-#define LAUNCH_LN16(LPR, ACT)                                                                                    \
-  g = (M + (256 / LPR) * 4 - 1) / ((256 / LPR) * 4);                                                             \
-  if (g > 8192) g = 8192;                                                                                        \
-  hipLaunchKernelGGL((layernorm_f16_kernel<LPR, ACT>), dim3((int)g), dim3(256), 0, as_stream(stream), x, gamma, beta, \
-                     y, y_f32, M, eps)
-  if (N == 128) { LAUNCH_LN16(16, 16); }
-  else if (N == 256) { LAUNCH_LN16(32, 32); }
-  else if (N == 384) { LAUNCH_LN16(64, 48); }
-  else if (N == 512) { LAUNCH_LN16(64, 64); }
-  else return ISIC_ERR_UNSUPPORTED;
-#undef LAUNCH_LN16
-  return isic_launch_status();
+  return ln16_launch<LN_OUT_Y>(x, gamma, beta, y, y_f32, M, N, eps, stream);
 }
 
 int isic_row_stats_f16(const uint16_t* x, float* stats, int64_t M, int N, float eps, void* stream) {
   ISIC_CHECK_ARG(M >= 0 && N > 0);
   if (M == 0) return ISIC_OK;
   ISIC_CHECK_ARG(x && stats);
-  int64_t g;
-#define LAUNCH_RS16(LPR, ACT)                                                                                    \
-  g = (M + (256 / LPR) * 4 - 1) / ((256 / LPR) * 4);                                                             \
-  if (g > 8192) g = 8192;                                                                                        \
-  hipLaunchKernelGGL((row_stats_f16_kernel<LPR, ACT>), dim3((int)g), dim3(256), 0, as_stream(stream), x, stats, M, eps)
-  if (N == 128) { LAUNCH_RS16(16, 16); }
-  else if (N == 256) { LAUNCH_RS16(32, 32); }
-  else if (N == 384) { LAUNCH_RS16(64, 48); }
-  else if (N == 512) { LAUNCH_RS16(64, 64); }
-  else return ISIC_ERR_UNSUPPORTED;
-#undef LAUNCH_RS16
-  return isic_launch_status();
+  return ln16_launch<LN_OUT_STATS>(x, nullptr, nullptr, nullptr, stats, M, N, eps, stream);
 }
 
 int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tokens, int heads, int head_dim,

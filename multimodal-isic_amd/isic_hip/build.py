@@ -40,7 +40,7 @@ def build(force=False, verbose=True, jobs=None):
     """Compile every ``csrc/*.hip`` and link the shared library.  Returns its path."""
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    # *.inc: kernel templates / device helpers that two translation units share (convmae_kernels.inc, mx_quant.inc)
+    # *.inc: kernel templates / device helpers that translation units share (convmae_kernels.inc, ln_rows.inc, mx_quant.inc, ...)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers += [os.path.join(os.path.dirname(PKG), "include", h)
                 for h in ("isic_hip.h", "isic_hip_mxfp8.h", "isic_hip_vit_train.h", "isic_hip_convmae.h",

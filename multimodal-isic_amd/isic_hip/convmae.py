@@ -54,7 +54,7 @@ csrc/mxfp8.hip), and the launch in front of a product writes its operand as MXFP
                 (patch_embed2), stage 2 with P = 2 once (stage2_output_decode and patch_embed3); decoders -> fp16 s1, s2
     patch_embed2   product -> fp16, ``isic_layernorm_add_f16`` + GELU -> fp16 x;   patch_embed3: product -> fp16, then
                 MX(GELU(LN(.))) (its only reader is patch_embed4);   patch_embed4: + pos_embed (fp16) -> fp16 x
-    blocks3     the ViT's MXFP8 block at D = 768 (isic_hip/vit.py): LN -> MX, qkv -> fp16, ``isic_attention_f16``,
+    blocks3     the ViT's MXFP8 block at D = 768 (``transformer.blocks_forward_mx``): LN -> MX, qkv -> fp16, ``isic_attention_f16``,
                 ``isic_mxfp8_quantize``, proj + residual -> fp16, LN -> MX, fc1 + GELU -> MX, fc2 + residual -> fp16
     output      norm(x + s1 + s2) -> fp32, unchanged
 The LayerNorms are passes of their own (no fold, no row statistics: isic_hip/vit.py says why), so ``fold_layernorm=False``
@@ -91,8 +91,9 @@ import torch
 from torch import nn
 
 from .lib import call
-from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_workspace_bytes, check_grads,
-                          embed, fold_layernorm, linear_ln, linear_res, loss_scale, param_grads)
+from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_forward_mx,
+                          blocks_workspace_bytes, check_grads, embed, fold_layernorm, linear_ln, linear_res, loss_scale,
+                          mx_weights, param_grads)
 
 _F16 = torch.float16
 
@@ -282,17 +283,14 @@ class ConvMAEBaseEncoder(Encoder):
         key = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._wmx is not None and key == self._wmx_key:
             return self._wmx
-        w = {}
-        for name, v in self.state_dict().items():
-            if v.dim() < 2 or name in ("pos_embed", "patch_embed1.proj.weight") or name.endswith(".attn.weight"):
-                continue
-            t = v.detach().float()
-            t = (t.permute(0, 2, 3, 1).reshape(t.shape[0], -1) if t.dim() == 4 else t).contiguous()
-            R, K = t.shape
-            q = torch.empty((R, K), device=device, dtype=torch.uint8)
-            s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
-            call("isic_mxfp8_quantize", t, 1, q, s, R, K)
-            w[name] = (q, s)
+
+        def matrices():
+            for name, v in self.state_dict().items():
+                if v.dim() < 2 or name in ("pos_embed", "patch_embed1.proj.weight") or name.endswith(".attn.weight"):
+                    continue
+                t = v.detach().float()
+                yield name, (t.permute(0, 2, 3, 1).reshape(t.shape[0], -1) if t.dim() == 4 else t)
+        w = mx_weights(matrices(), device)
         self._wmx, self._wmx_key = w, key
         return w
 
@@ -320,9 +318,9 @@ class ConvMAEBaseEncoder(Encoder):
         """The ``precision="mxfp8"`` forward of one chunk (module docstring): every product but the stem's on
         ``isic_gemm_mxfp8``, its operand written as MXFP8 by the launch before it."""
         dev = img.device
-        n, T, heads, r = img.shape[0], self.tokens, self.heads, self.mlp_ratio
+        n, T, r = img.shape[0], self.tokens, self.mlp_ratio
         (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
-        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        M2, M3 = n * g2 * g2, n * g3 * g3
         ceps, eps = self.conv_ln_eps, self.ln_eps
 
         def e16(*shape):
@@ -365,12 +363,7 @@ class ConvMAEBaseEncoder(Encoder):
             return y
 
         # ---- stage 1: the stem stays fp16 (K = 48 padded to 64 is no multiple of 128)
-        rows, t, x = e16(M1, 64), e16(M1, d1), e16(M1, d1)
-        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
-        call("isic_gemm_f16", rows, w["patch_embed1.proj.weight"], w["patch_embed1.proj.bias"], None, t, M1, d1, 64, 0, 0)
-        call("isic_layernorm_add_f16", t, None, None, w["patch_embed1.norm.weight"], w["patch_embed1.norm.bias"], x, None, M1, d1,
-             1, ceps)
-        del rows, t
+        x = self._stem(img, w)
         x = cblocks(x, "blocks1", g1, d1, depth[0])
         s1 = gemm(patch_rows(x, g1, d1, 4), "stage1_output_decode", M3, d3, 16 * d1, out=e16(M3, d3))
         rows = patch_rows(x, g1, d1, 2)
@@ -386,19 +379,28 @@ class ConvMAEBaseEncoder(Encoder):
         h = mx(M3, d3)
         ln_mx(t, "patch_embed3.norm", h, M3, d3, 1, ceps)
         x = gemm(h, "patch_embed4", M3, d3, d3, out=t, res=w["pos_embed"], res_rows=T)
-        if depth[2]:
-            qkv, att, x2, hid = e16(M3, 3 * d3), e16(M3, d3), e16(M3, d3), mx(M3, r * d3)
-        for i in range(depth[2]):
-            b = f"blocks3.{i}"
-            ln_mx(x, b + ".norm1", h, M3, d3, 0, eps)
-            gemm(h, b + ".attn.qkv", M3, 3 * d3, d3, out=qkv)
-            call("isic_attention_f16", qkv, att, n, T, heads, d3 // heads)
-            call("isic_mxfp8_quantize", att, 0, h[0], h[1], M3, d3)
-            gemm(h, b + ".attn.proj", M3, d3, d3, out=x2, res=x)
-            ln_mx(x2, b + ".norm2", h, M3, d3, 0, eps)
-            gemm(h, b + ".mlp.fc1", M3, r * d3, d3, out_mx=hid, act=1)
-            gemm(hid, b + ".mlp.fc2", M3, d3, r * d3, out=x, res=x2)
+        del h
+        x = blocks_forward_mx(w, wmx, x, n, depth[2], self._blocks3_spec(T), self._layernorm_mx)
         call("isic_layernorm_add_f16", x, s1, s2, w["norm.weight"], w["norm.bias"], None, out, n * T, d3, 0, eps)
+
+    @staticmethod
+    def _layernorm_mx(x, gamma, beta, q, s, M, D, eps):
+        """The LayerNorm -> MXFP8 pass of blocks3 (transformer.blocks_forward_mx): no GELU"""
+        call("isic_layernorm_act_mxfp8_f16", x, gamma, beta, q, s, M, D, 0, eps)
+
+    def _stem(self, img, w, save_into=None):
+        """The stem, fp16 in every precision (K = 48 padded to 64 is no multiple of 128): the 4 x 4 patch rows of the
+        image, patch_embed1's product and its LayerNorm + GELU -> x[n * 56 * 56, 256].  ``save_into``: a tape that keeps
+        the product's output as ``t1`` for the backward."""
+        n, d1, M1 = img.shape[0], self.dims[0], img.shape[0] * self.grids[0] ** 2
+        rows, t, x = (torch.empty((M1, c), device=img.device, dtype=_F16) for c in (64, d1, d1))
+        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
+        call("isic_gemm_f16", rows, w["patch_embed1.proj.weight"], w["patch_embed1.proj.bias"], None, t, M1, d1, 64, 0, 0)
+        call("isic_layernorm_add_f16", t, None, None, w["patch_embed1.norm.weight"], w["patch_embed1.norm.bias"], x, None, M1, d1,
+             1, self.conv_ln_eps)
+        if save_into is not None:
+            save_into["t1"] = t
+        return x
 
     def _run_chunk(self, img, w, out, depth):
         n, fold, spec = img.shape[0], self.fold_layernorm, self._blocks3_spec(self.tokens)
@@ -417,7 +419,7 @@ class ConvMAEBaseEncoder(Encoder):
         dev = img.device
         n = img.shape[0]
         (d1, d2, d3), (g1, g2, g3) = self.dims, self.grids
-        M1, M2, M3 = n * g1 * g1, n * g2 * g2, n * g3 * g3
+        M2, M3 = n * g2 * g2, n * g3 * g3
         tape = {}
 
         def e16(*shape):
@@ -438,10 +440,7 @@ class ConvMAEBaseEncoder(Encoder):
             return s
 
         # ---- stage 1: 56 x 56 x 256
-        rows = e16(M1, 64)
-        call("isic_patch_rows_nchw_f32", img, rows, n, self.in_ch, self.img_size, self.img_size, 4, 64)
-        x = patch_embed(rows, "patch_embed1", M1, d1, 64)
-        del rows
+        x = self._stem(img, w, tape if save else None)
         x, blocks1 = self._cblocks(x, w, "blocks1", n, g1, d1, depth[0], fold, save, keep)
         rows = e16(M3, 16 * d1)
         call("isic_patch_rows_nhwc_f16", x, rows, n, g1, g1, d1, 4)

@@ -7,14 +7,21 @@ A block is x2 = x + proj(attention(qkv(LN1(x)))), out = x2 + fc2(GELU(fc1(LN2(x2
 i < total, in the weight dict ``w``; T tokens per image, width D, H heads of 64 (``isic_attention_f16``) or 32
 (``isic_attention_d32_f16``), LayerNorm eps; the MLP width is fc1's.  The stream is fp16 rows [n * T, D].
 
-Forward (``blocks_forward``), layer by layer: ``isic_layernorm_add_f16`` (the ViT-S/16 hands in ``isic_layernorm_f16``, its frozen forward's kernel: the two are
-the same two-pass arithmetic, but the compiler fuses the mean subtraction and the first squares into FMAs in one and not
-in the other, and their outputs differ in the last bit), ``isic_gemm_f16`` (residual in the epilogue; GELU for fc1) and
+Forward (``blocks_forward``), layer by layer: ``isic_layernorm_add_f16`` (the ViT-S/16 hands in ``isic_layernorm_f16``, its
+frozen forward's kernel.  The fp16 row LayerNorm kernels share one source text, csrc/ln_rows.inc: the same sums in the same
+order, with two mean rules -- s * (1 / N) in the ViT-width kernels, s / N in the ``layernorm_add`` family -- and the
+compiler contracts multiply-adds per kernel, so two kernels' statistics may differ in the last bit; DESIGN.md section 4,
+and tests/test_ln_rows_gpu.py pins the bits of each), ``isic_gemm_f16`` (residual in the epilogue; GELU for fc1) and
 the attention.  ``fold``: the pre-norms have no pass of their own (``isic_gemm_f16_ln`` on row statistics from
 ``isic_gemm_f16_stats`` or ``isic_row_stats_f16``; isic_hip/vit.py has the algebra, ``fold_layernorm`` the weights).
 ``save`` (training): fc1 through ``isic_gemm_f16_gelu_pre``, and per block x, LN1(x), qkv, the attention output, x2,
 LN2(x2), fc1's pre-activation and GELU output (fp16) are kept, and no LayerNorm statistics:
 ``isic_layernorm_add_bwd_f16`` recomputes (mean, rstd) from x in fp32.
+
+MXFP8 forward (``blocks_forward_mx``, inference; ``mx_weights`` quantises the matrices): the four products of a block on
+``isic_gemm_mxfp8``, each operand written as MXFP8 by the launch before it -- LN -> MX, qkv (fp16 out), attention,
+``isic_mxfp8_quantize``, proj + residual (fp16 out), LN -> MX, fc1 + GELU -> MX, fc2 + residual (fp16 out); the residual
+stream stays fp16.  isic_hip/vit.py says why the LayerNorm is never folded here.
 
 Backward: on gradients multiplied by a power-of-two loss scale S (``loss_scale``); every reduction into a parameter
 gradient multiplies by s = 1/S in fp32 and accumulates into ``param.grad`` (``Backward``), so gradients are exactly
@@ -142,6 +149,55 @@ def blocks_forward(w, x, st, n, nblk, spec, fold=False, save=False, layernorm=la
             saves.append(dict(x=x, h1=h1, qkv=qkv, att=att, x2=x2, h2=h2, pre=pre, hid=hid))
         x = xo
     return x, saves
+
+
+def mx_weights(named_matrices, device):
+    """{name: (q, s)} of the [R, K] fp32 matrices ``named_matrices`` yields as (name, matrix), quantised on the GPU
+    (``isic_mxfp8_quantize``: q[R, K] e4m3 bytes, s[R, K / 32] scale bytes).  Once per weight version: the caller keeps
+    the key."""
+    out = {}
+    for name, t in named_matrices:
+        t = t.detach().float().contiguous()
+        R, K = t.shape
+        q = torch.empty((R, K), device=device, dtype=torch.uint8)
+        s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
+        call("isic_mxfp8_quantize", t, 1, q, s, R, K)
+        out[name] = (q, s)
+    return out
+
+
+def blocks_forward_mx(w, wmx, x, n, nblk, spec, layernorm_mx):
+    """The first ``nblk`` blocks over the fp16 stream x[n * T, D] with their products on the block-scaled FP8 MFMA (module
+    docstring) -> the output stream.  ``w``: the biases and LayerNorm affines, ``wmx``: ``mx_weights`` of the four
+    matrices of every block.  The stream ping-pongs between x and one second buffer, every block reuses one MX operand /
+    qkv / attention / MX hidden buffer, and x is overwritten.  ``layernorm_mx(x, gamma, beta, q, s, M, D, eps)`` is the
+    LayerNorm -> MXFP8 pass, handed in as ``layernorm`` is for ``blocks_forward``."""
+    dev = x.device
+    T, D, H, eps = spec["T"], spec["D"], spec["H"], spec["eps"]
+    M = n * T
+
+    def mx(cols):
+        return (torch.empty((M, cols), device=dev, dtype=torch.uint8), torch.empty((M, cols // 32), device=dev, dtype=torch.uint8))
+
+    def gemm(a, name, Nout, K, act=0, res=None, out=None, out_mx=(None, None)):
+        wq, ws = wmx[name + ".weight"]
+        call("isic_gemm_mxfp8", a[0], a[1], wq, ws, w[name + ".bias"], res, out, out_mx[0], out_mx[1], M, Nout, K, act, 0)
+
+    for i in range(nblk):
+        b = f"{spec['prefix']}.{i}"
+        Hd = wmx[b + ".mlp.fc1.weight"][0].shape[0]
+        if i == 0:
+            h, hid = mx(D), mx(Hd)
+            qkv, att, x2 = (torch.empty((M, c), device=dev, dtype=_F16) for c in (3 * D, D, D))
+        layernorm_mx(x, w[b + ".norm1.weight"], w[b + ".norm1.bias"], h[0], h[1], M, D, eps)
+        gemm(h, b + ".attn.qkv", 3 * D, D, out=qkv)
+        _attention(qkv, att, n, T, H, D // H)
+        call("isic_mxfp8_quantize", att, 0, h[0], h[1], M, D)
+        gemm(h, b + ".attn.proj", D, D, res=x, out=x2)
+        layernorm_mx(x2, w[b + ".norm2.weight"], w[b + ".norm2.bias"], h[0], h[1], M, D, eps)
+        gemm(h, b + ".mlp.fc1", Hd, D, act=1, out_mx=hid)
+        gemm(hid, b + ".mlp.fc2", D, Hd, res=x2, out=x)
+    return x
 
 
 def blocks_workspace_bytes(w, n, spec):

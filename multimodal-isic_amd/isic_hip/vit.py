@@ -13,12 +13,13 @@ activations are fp16 in HBM ([N*196, 384] rows), arithmetic is fp32 inside the k
 W' = W diag(gamma), c = W' 1, b' = b + W beta:   LN(x) W^T + b = rstd (x W'^T - mean c) + b'   -- the product reads the RAW
 residual stream (`isic_gemm_f16_ln`) and applies the row's (mean, rstd) in its epilogue; the row sums those need come
 out of the epilogue of the product that WROTE the stream (`isic_gemm_f16_stats`: patch projection, attn.proj, mlp.fc2).
-``"stats"`` keeps a statistics-only pass (`isic_row_stats_f16`, LayerNorm's two-pass arithmetic) in place of the epilogue
+``"stats"`` keeps a statistics-only pass (`isic_row_stats_f16`, the LayerNorm kernel's two-pass text) in place of the epilogue
 sums; ``False`` is the layer-by-layer form above.
 
 ``precision="mxfp8"`` (opt-in; the default ``"fp16"`` is the path above, unchanged): the four products of every block run
 on the block-scaled FP8 MFMA (`isic_gemm_mxfp8`, OCP MX E4M3 with one E8M0 scale per 32 elements along K, csrc/mxfp8.hip).
-Per block: LayerNorm quantised straight from fp32 (`isic_layernorm_mxfp8_f16`) -> qkv (fp16 out) -> `isic_attention_f16`
+Per block (``transformer.blocks_forward_mx``): LayerNorm quantised straight from fp32 (`isic_layernorm_mxfp8_f16`) -> qkv
+(fp16 out) -> `isic_attention_f16`
 -> `isic_mxfp8_quantize` -> proj (+ residual, fp16 out) -> LayerNorm -> fc1 + GELU (MXFP8 out: the 1536-wide hidden
 activation crosses HBM as 1 byte + 1/32 scale byte per value) -> fc2 (+ residual, fp16 out).  The patch projection
 (raw pixels, 1.3 % of the FLOPs), the attention and the final LayerNorm stay fp16, and so does the residual stream.  The
@@ -46,8 +47,8 @@ import torch
 from torch import nn
 
 from .lib import call
-from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_workspace_bytes, check_grads,
-                          embed, fold_layernorm, loss_scale, param_grads)
+from .transformer import (Backward, Encoder, EncoderFn, blocks_backward, blocks_forward, blocks_forward_mx,
+                          blocks_workspace_bytes, check_grads, embed, fold_layernorm, loss_scale, mx_weights, param_grads)
 
 _F16 = torch.float16
 
@@ -180,16 +181,8 @@ class ViTSmallEncoder(Encoder):
         key = tuple((self._get(n).data_ptr(), self._get(n)._version) for n in self._names)
         if self._wmx is not None and key == self._wmx_key:
             return self._wmx
-        w = {}
-        for i in range(self.depth):
-            for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
-                n = f"blocks.{i}.{lin}.weight"
-                p = self._get(n).detach().float().contiguous()
-                R, K = p.shape
-                q = torch.empty((R, K), device=device, dtype=torch.uint8)
-                s = torch.empty((R, K // 32), device=device, dtype=torch.uint8)
-                call("isic_mxfp8_quantize", p, 1, q, s, R, K)
-                w[n] = (q, s)
+        names = [f"blocks.{i}.{lin}.weight" for i in range(self.depth) for lin in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
+        w = mx_weights(((n, self._get(n)) for n in names), device)
         self._wmx, self._wmx_key = w, key
         return w
 
@@ -221,33 +214,10 @@ class ViTSmallEncoder(Encoder):
         return self._final_norm(x, w, N)
 
     def _run_tokens_mx(self, images, w, wmx, depth):
-        dev = images.device
-        N, T, D, H = images.shape[0], self.tokens, self.dim, self.heads
-        M = N * T
-        eps = 1e-6
-        u8 = torch.uint8
+        N = images.shape[0]
         x, _, rows = self._patch_stream(images, w, False)
         del rows
-        hq, hs = torch.empty((M, D), device=dev, dtype=u8), torch.empty((M, D // 32), device=dev, dtype=u8)
-        qkv = torch.empty((M, 3 * D), device=dev, dtype=_F16)
-        att = torch.empty((M, D), device=dev, dtype=_F16)
-        midq, mids = torch.empty((M, self.mlp), device=dev, dtype=u8), torch.empty((M, self.mlp // 32), device=dev, dtype=u8)
-        x2 = torch.empty_like(x)
-
-        def gemm(aq, as_, name, res, out, Nout, K, act, outq=None, outs=None):
-            wq, ws = wmx[name + ".weight"]
-            call("isic_gemm_mxfp8", aq, as_, wq, ws, w[name + ".bias"], res, out, outq, outs, M, Nout, K, act, 0)
-
-        for i in range(self.depth if depth is None else depth):
-            b = f"blocks.{i}"
-            call("isic_layernorm_mxfp8_f16", x, w[f"{b}.norm1.weight"], w[f"{b}.norm1.bias"], hq, hs, M, D, eps)
-            gemm(hq, hs, f"{b}.attn.qkv", None, qkv, 3 * D, D, 0)
-            call("isic_attention_f16", qkv, att, N, T, H, D // H)
-            call("isic_mxfp8_quantize", att, 0, hq, hs, M, D)
-            gemm(hq, hs, f"{b}.attn.proj", x, x2, D, D, 0)
-            call("isic_layernorm_mxfp8_f16", x2, w[f"{b}.norm2.weight"], w[f"{b}.norm2.bias"], hq, hs, M, D, eps)
-            gemm(hq, hs, f"{b}.mlp.fc1", None, None, self.mlp, D, 1, midq, mids)
-            gemm(midq, mids, f"{b}.mlp.fc2", x2, x, D, self.mlp, 0)
+        x = blocks_forward_mx(w, wmx, x, N, self.depth if depth is None else depth, self._spec(), self._layernorm_mx)
         return self._final_norm(x, w, N)
 
     def forward_tokens(self, images):
@@ -282,6 +252,11 @@ class ViTSmallEncoder(Encoder):
     def _layernorm(x, gamma, beta, y, M, D, eps):
         """The LayerNorm pass of this encoder's blocks (isic_hip/transformer.py explains why it is handed in)."""
         call("isic_layernorm_f16", x, gamma, beta, y, None, M, D, eps)
+
+    @staticmethod
+    def _layernorm_mx(x, gamma, beta, q, s, M, D, eps):
+        """The LayerNorm -> MXFP8 pass of this encoder's blocks: ``_layernorm``'s kernel with the MXFP8 way out."""
+        call("isic_layernorm_mxfp8_f16", x, gamma, beta, q, s, M, D, eps)
 
     def run_forward_train(self, images):
         """The layer-by-layer forward (bitwise ``run_tokens`` with fold_layernorm=False) that keeps what the backward needs."""
