@@ -666,5 +666,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_convmae_mxfp8.h"
 /* Head-averaged attention (concat=False) of GATConv / GATv2Conv / TransformerConv, the mean formed inside the kernels: four more entry points, same conventions. */
 #include "isic_hip_attn_mean.h"
+/* The shifted Gram matrix of resident latents in fp64 (the device half of the latent PCA): two more entry points, same conventions. */
+#include "isic_hip_pca.h"
 
 #endif /* ISIC_HIP_H */

@@ -19,6 +19,14 @@ What changes:
     identity parameters produces the normalised 224 x 224 images and the nearest-neighbour masks the patch flags are
     computed from.  ``datasets`` must then yield uint8 arrays (``isic_hip.augment.SyntheticDermPixels``).
 
+  * ``device_pca: true`` (opt-in, read only with ``pca: true``) fits and applies the PCA of `:163-185` on the device
+    (``isic_hip.pca.DevicePCA``): the per-batch latents stay resident until the fit is done, every train batch goes through
+    ``partial_fit`` (with ``remove_background`` through the row index of its lesion-flagged patches: the Gram kernel reads
+    through the index; the first batch is gathered once to form the shift, and ``transform`` gathers where the row-indexed
+    GEMM does not serve the shape), and
+    ``patch_latent_pca`` is filled from the transformed batches in the frames' row order.  Without the key ``pca: true``
+    is the reference's sklearn call, unchanged.
+
 ``extract_latents(config, path, remove_background=False, datasets=None)`` keeps the reference's signature and return
 tuple; ``datasets=(train_val_dataset, test_dataset)`` lets a caller hand in any dataset with the ``DermDataset`` dict
 contract (`dataset.py:45-56`) -- the synthetic one below when there are no image files.
@@ -115,7 +123,8 @@ def _device_resized(loader, device):
                "segmentation_path": [it["segmentation_path"] for it in items]}
 
 
-def _extract_from_loader(encoder, loader, device):
+def _extract_from_loader(encoder, loader, device, resident=None):
+    """``resident``: a list that receives (latent [B, T, D], flags [B, T] bool) of every batch, left on the device"""
     pooled_list, raw_list = [], []
     for batch in loader:
         images = batch["image"].to(device)
@@ -129,12 +138,47 @@ def _extract_from_loader(encoder, loader, device):
             "latent_pooled_mean": list(latent.mean(dim=1).cpu().numpy()),               # :63
             "ids_restore": list(ids), "ids_keep": list(ids)}))
         flags = mask_patch_flags(batch["mask"].to(device))
+        if resident is not None:
+            resident.append((latent, flags.reshape(B, -1)))
         raw_list.append(pd.DataFrame({
             "image_path": batch["image_path"], "segmentation_path": batch["segmentation_path"], "target": target,
             "latent": list(latent.cpu().numpy()), "ids_restore": list(ids), "ids_keep": list(ids),
             "lesion_mask_patches": list(flags.cpu().numpy())}))
     cat = lambda l: pd.concat(l, ignore_index=True) if l else pd.DataFrame()
     return cat(pooled_list), cat(raw_list)
+
+
+def _device_pca_columns(resident_train, resident_test, remove, n_train, n_test):
+    """`save_latent.py:163-185` on the device -> the ``patch_latent_pca`` columns of the train and test patch frames (lists
+    of fp32 rows in the row order of ``build_patch_level_df``: image-major, then token order)."""
+    from isic_hip.pca import DevicePCA
+
+    def batches(resident):
+        for latent, flags in resident:
+            x = latent.reshape(-1, latent.shape[-1])
+            rows = torch.nonzero(flags.reshape(-1)).reshape(-1).to(torch.int32) if remove else None
+            yield x, rows
+
+    pca = DevicePCA(n_components=0.90)
+    for x, rows in batches(resident_train):
+        pca.partial_fit(x, rows)
+    if pca.n_samples_seen_ != n_train:
+        raise RuntimeError(f"device_pca: fitted {pca.n_samples_seen_} rows, the train frame has {n_train}")
+    if n_train == 0:
+        if n_test > 0:
+            raise RuntimeError("No train patches to fit PCA. Cannot transform test patches.")
+        return [], []
+    pca.finalize()
+    width = resident_train[0][0].shape[-1]
+    print(f"PCA reduced dimensions from {width} to {pca.n_components_}")
+    cols = []
+    for resident, n in ((resident_train, n_train), (resident_test, n_test)):
+        out = [pca.transform(x, rows).cpu().numpy() for x, rows in batches(resident)]
+        out = np.concatenate(out) if out else np.zeros((0, pca.n_components_), dtype=np.float32)
+        if len(out) != n:
+            raise RuntimeError(f"device_pca: transformed {len(out)} rows, the patch frame has {n}")
+        cols.append(list(out))
+    return cols
 
 
 def extract_latents(config, path, remove_background=False, datasets=None, batch_size=256):
@@ -185,13 +229,19 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
     else:
         print(f"save_latent: checkpoint {ckpt} not found -- encoder keeps its seeded initialisation")
     enc.eval()
-    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device)
-    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device)
+    device_pca = bool(config.get("pca", False)) and bool(config.get("device_pca", False))
+    resident_train, resident_test = ([], []) if device_pca else (None, None)
+    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device, resident_train)
+    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device, resident_test)
     patch_level_train_df, train_count = build_patch_level_df(latent_raw_train, remove=remove_background)
     patch_level_test_df, test_count = build_patch_level_df(latent_raw_test, remove=remove_background)
     print(f"Total lesion-overlapping patches (train_val): {train_count}")
     print(f"Total lesion-overlapping patches (test): {test_count}")
-    if bool(config.get("pca", False)):                                       # :163-180
+    if device_pca:                                                           # :163-185 on the device
+        tr, te = _device_pca_columns(resident_train, resident_test, remove_background, len(patch_level_train_df),
+                                     len(patch_level_test_df))
+        patch_level_train_df["patch_latent_pca"], patch_level_test_df["patch_latent_pca"] = tr, te
+    elif bool(config.get("pca", False)):                                     # :163-180
         from sklearn.decomposition import PCA
         if len(patch_level_train_df) > 0:
             Xtr = np.vstack(patch_level_train_df["patch_latent"].values)
