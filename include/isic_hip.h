@@ -668,5 +668,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_attn_mean.h"
 /* The shifted Gram matrix of resident latents in fp64 (the device half of the latent PCA): two more entry points, same conventions. */
 #include "isic_hip_pca.h"
+/* The integer counts behind the validation metrics (confusion matrix, AUROC pair counts, loss sum) of one validation set: two more entry points, same conventions. */
+#include "isic_hip_metrics.h"
 
 #endif /* ISIC_HIP_H */

@@ -81,12 +81,16 @@ def load_bags(config, args):
     return out[0], out[1]
 
 
-def test_metrics(model, state, bags, labels, device):
+def test_metrics(model, state, bags, labels, device, device_metrics=False):
     """`01:89-118`."""
     if state is not None:
         model.load_state_dict(state)
     if not labels:
         return {k: np.nan for k in ("micro", "macro_p", "macro_r", "macro_f1", "weighted_p", "weighted_r", "weighted_f1")}
+    if device_metrics:
+        m, _ = T.eval_teacher(model, T.BagStore(bags, device), labels, device_metrics=True)
+        return {"micro": m.accuracy, "macro_p": m.macro_precision, "macro_r": m.macro_recall, "macro_f1": m.macro_f1,
+                "weighted_p": m.weighted_precision, "weighted_r": m.weighted_recall, "weighted_f1": m.weighted_f1}
     probs, _ = T.eval_teacher(model, T.BagStore(bags, device), labels)
     y, pred = np.asarray(labels), probs.argmax(axis=1)
     mp, mr, mf, _ = precision_recall_fscore_support(y, pred, average="macro", zero_division=0)
@@ -96,6 +100,8 @@ def test_metrics(model, state, bags, labels, device):
 
 
 def _auc(y, s):
+    if hasattr(s, "per_class_auc"):          # --device-metrics: the ClassMetrics of the validation set
+        return {} if np.isnan(s.auc) else {"val_auc": s.auc}
     try:
         return {"val_auc": roc_auc_score(y, s, multi_class="ovr")}
     except Exception:
@@ -113,6 +119,8 @@ def main():
     parser.add_argument("--folds", type=int, default=SPLITS)
     parser.add_argument("--model-name", default="synthetic.pth")
     parser.add_argument("--out-dir", default="teacher_outputs")
+    parser.add_argument("--device-metrics", action="store_true",
+                        help="score validation and test on the device (isic_hip.metrics) instead of sklearn on the host")
     args, _ = parser.parse_known_args()
     cfg_path = args.config_path if os.path.exists(args.config_path) else os.path.join(os.path.dirname(__file__), args.config_path)
     with open(cfg_path) as f:
@@ -139,9 +147,10 @@ def main():
         patience = config.get("training_plan", {}).get("parameters", {}).get("patience", 8)
         res = T.train_teacher_fold(model, f_tr, y_tr, f_va, y_va, optimizer=bp["optimizer"], lr=float(bp["learning_rate"]),
                                    weight_decay=float(bp["weight_decay"]), epochs=args.epochs, patience=patience,
-                                   bags_per_step=args.bags_per_step, seed=SEED + fold, device=device, metric_fn=_auc)
-        m_bacc = test_metrics(model, res["best_state_bacc"], te_f, te_y, device)
-        m_loss = test_metrics(model, res["best_state_loss"] or res["best_state_bacc"], te_f, te_y, device)
+                                   bags_per_step=args.bags_per_step, seed=SEED + fold, device=device, metric_fn=_auc,
+                                   device_metrics=args.device_metrics)
+        m_bacc = test_metrics(model, res["best_state_bacc"], te_f, te_y, device, args.device_metrics)
+        m_loss = test_metrics(model, res["best_state_loss"] or res["best_state_bacc"], te_f, te_y, device, args.device_metrics)
         if rank == 0:
             print(f"    test (best-bacc state): {m_bacc}\n    test (best-loss state): {m_loss}")
             if res["best_state_bacc"] is not None:

@@ -91,7 +91,7 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
     return T.train_gnn_fold(model, train_records, val_records, test_records, lr=args.learning_rate,
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
                             min_delta=args.min_delta, graphs_per_step=args.graphs_per_step, num_classes=num_classes,
-                            device=device)
+                            device=device, device_metrics=args.device_metrics)
 
 
 def aggregate(rows, prefix):
@@ -143,6 +143,8 @@ def parse_args(argv=None):
     p.add_argument("--results-csv", type=Path, default=Path("gnn_results/common_results.csv"))
     p.add_argument("--job-id", type=str, default="0")
     p.add_argument("--graphs-per-step", type=int, default=1, help="graphs per optimizer step per GPU (1 = reference)")
+    p.add_argument("--device-metrics", action="store_true",
+                   help="score every evaluation on the device (isic_hip.metrics) instead of sklearn on the host")
     return p.parse_args(argv)
 
 

@@ -91,28 +91,63 @@ def _sync_step(opt, sync, world):
     opt.step(grad_scale=1.0 / world)
 
 
+# ----------------------------------------------------------------------------- validation scored on the device
+class _DeviceScores:
+    """The ``device_metrics=True`` side of the evaluations below: every chunk's probabilities and per-sample losses are
+    copied device-to-device into ``[n, C]`` / ``[n]`` buffers allocated once, the labels are on the device once, and ONE
+    ``metrics.class_counts`` call (one launch pair, one read-back, one sync) ends the evaluation -- instead of two ``.cpu()``
+    per chunk and scikit-learn on the host (`01:111-113,266-272`, `05:284-302`)."""
+
+    def __init__(self, labels, device):
+        self.y = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels), device=device)
+        self.y = self.y.to(device=device, dtype=torch.int64)
+        self.scores = self.loss = None
+
+    def put(self, lo, probs, loss):
+        if self.scores is None:
+            n = self.y.shape[0]
+            self.scores = torch.empty((n, probs.shape[1]), device=probs.device, dtype=torch.float32)
+            self.loss = torch.empty((n,), device=probs.device, dtype=torch.float32)
+        self.scores[lo:lo + probs.shape[0]].copy_(probs)
+        self.loss[lo:lo + probs.shape[0]].copy_(loss)
+
+    def finish(self):
+        from .metrics import class_counts
+        return class_counts(self.scores, self.y, self.loss)
+
+
 # ----------------------------------------------------------------------------- MIL teacher
 @torch.no_grad()
-def eval_teacher(model, store, labels, chunk=64):
-    """bag_probs + mean per-bag CE over all bags (`01:247-260`)."""
+def eval_teacher(model, store, labels, chunk=64, device_metrics=False):
+    """bag_probs + mean per-bag CE over all bags (`01:247-260`).  ``device_metrics``: -> (``metrics.ClassMetrics``, loss)
+    from counts formed on the device; the probabilities never leave it."""
     model.eval()
     probs, losses = [], []
     n = len(labels)
+    acc = _DeviceScores(labels, store.device) if device_metrics and n else None
     for lo in range(0, n, chunk):
         idx = list(range(lo, min(n, lo + chunk)))
         x, offs = store.batch(idx)
         out = model(x, offs)
+        if acc is not None:
+            acc.put(lo, out["bag_probs"], ops.CrossEntropyFn.apply(out["bag_logits"], acc.y[lo:lo + len(idx)], 0)[1])
+            continue
         y = torch.as_tensor(np.asarray(labels)[idx], device=x.device)
         losses.append(ops.CrossEntropyFn.apply(out["bag_logits"], y, 0)[1].cpu())
         probs.append(out["bag_probs"].cpu())
+    if acc is not None:
+        cm = acc.finish()
+        return cm, cm.loss
     return torch.cat(probs).numpy(), float(torch.cat(losses).mean()) if losses else float("nan")
 
 
 def train_teacher_fold(model, train_bags, train_labels, val_bags, val_labels, *, optimizer="adamw", lr=2.2e-4,
                        weight_decay=8.6e-4, epochs=200, patience=8, bags_per_step=1, seed=42, device=None, log=print,
-                       metric_fn=None):
+                       metric_fn=None, device_metrics=False):
     """`01_train_mil_teacher.py:203-290` for one fold.  Returns dict(best_state_bacc, best_state_loss,
-    history).  Every rank draws the same sampler stream and takes its slice of each step's bags."""
+    history).  Every rank draws the same sampler stream and takes its slice of each step's bags.
+    ``device_metrics``: the validation is scored on the device (``eval_teacher``); ``metric_fn`` then receives the
+    ``ClassMetrics`` in place of the probabilities."""
     from sklearn.metrics import balanced_accuracy_score
     rank, world = dist_info()
     device = device or next(model.parameters()).device
@@ -141,11 +176,14 @@ def train_teacher_fold(model, train_bags, train_labels, val_bags, val_labels, *,
                 loss = ops.cross_entropy(out["bag_logits"], y) * (len(mine) * world / len(glob))
                 ops.backward(loss)
             _sync_step(opt, sync, world)
-        probs, val_loss = eval_teacher(model, va, val_labels)
+        probs, val_loss = eval_teacher(model, va, val_labels, device_metrics=device_metrics)
         if len(val_labels) == 0:
             break
-        pred = probs.argmax(axis=1)
-        bacc = balanced_accuracy_score(np.asarray(val_labels), pred)
+        if device_metrics:
+            bacc = probs.bacc
+        else:
+            pred = probs.argmax(axis=1)
+            bacc = balanced_accuracy_score(np.asarray(val_labels), pred)
         if bacc > best["bacc"] + 1e-6:
             best["bacc"], best["state_bacc"] = bacc, {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
         if val_loss < best["loss"] - 1e-6:
@@ -206,30 +244,40 @@ class ImageBagStore:
 
 
 @torch.no_grad()
-def eval_milnet(model, store, chunk=64):
+def eval_milnet(model, store, chunk=64, device_metrics=False):
     """Fused-logit class probabilities and mean per-bag CE over all bags, eval mode (running BatchNorm statistics,
-    no dropout) -- the evaluation of `01_train_mil_teacher.py:247-260` for the composed model."""
+    no dropout) -- the evaluation of `01_train_mil_teacher.py:247-260` for the composed model.  ``device_metrics``:
+    -> (``metrics.ClassMetrics``, loss) from counts formed on the device."""
     model.eval()
     probs, losses = [], []
+    acc = _DeviceScores(store.y_dev, store.device) if device_metrics and len(store) else None
     for lo in range(0, len(store), chunk):
         img, rad, y = store.batch(range(lo, min(len(store), lo + chunk)))
         out = model(img, rad)
+        if acc is not None:
+            acc.put(lo, ops.softmax_rows(out["logits"]), ops.CrossEntropyFn.apply(out["logits"], y, 0)[1])
+            continue
         losses.append(ops.CrossEntropyFn.apply(out["logits"], y, 0)[1].cpu())
         probs.append(ops.softmax_rows(out["logits"]).cpu())
+    if acc is not None:
+        cm = acc.finish()
+        return cm, cm.loss
     if not probs:
         return np.zeros((0, 0), np.float32), float("nan")
     return torch.cat(probs).numpy(), float(torch.cat(losses).mean())
 
 
 def train_milnet_fold(model, train_set, val_set, *, optimizer="adamw", lr=2.2e-4, weight_decay=8.6e-4, epochs=200,
-                      patience=8, bags_per_step=8, seed=42, num_classes=7, device=None, log=print):
+                      patience=8, bags_per_step=8, seed=42, num_classes=7, device=None, log=print, device_metrics=False):
     """The 01 loop (`01_train_mil_teacher.py:203-290`) for BASELINE.json configs[1]: ``model.MultiModalMILNet`` (ResNet-18
     patch encoder -> attention-MIL head -> radiomic fusion) trained end to end on bags of image patches.  Class-balanced
     sampler stream (`01:189-193`), ``bags_per_step`` bags per optimizer step and rank (bag-sharded DDP: every rank draws
     the same stream and takes its slice; gradients all-reduced through ``ddp.GradSync`` overlapped with the encoder's
     backward), validation after every epoch -> macro one-vs-rest AUROC / balanced accuracy / loss of the fused logits,
     best states by balanced accuracy and by loss, early stop on the loss (`01:265-290`).
-    ``train_set`` / ``val_set`` = (images[n, K, 3, H, W], radiomics[n, R], labels[n])."""
+    ``train_set`` / ``val_set`` = (images[n, K, 3, H, W], radiomics[n, R], labels[n]).
+    ``device_metrics``: the validation is scored on the device; a history entry then holds the ``ClassMetrics`` under
+    ``"metrics"`` and no ``"probs"``."""
     from sklearn.metrics import balanced_accuracy_score
     rank, world = dist_info()
     device = device or next(model.parameters()).device
@@ -262,18 +310,22 @@ def train_milnet_fold(model, train_set, val_set, *, optimizer="adamw", lr=2.2e-4
                     (loss * (len(mine) * world / len(glob))).backward()
             _sync_step(opt, sync, world)
         ddp.average_buffers(model)               # BatchNorm running statistics are per rank during the epoch
-        probs, val_loss = eval_milnet(model, va)
+        probs, val_loss = eval_milnet(model, va, device_metrics=device_metrics)
         if len(va) == 0:
             break
-        m = gnn_metrics(va.labels, probs, num_classes)
-        bacc = balanced_accuracy_score(va.labels, probs.argmax(axis=1))
+        if device_metrics:
+            m, bacc = {"auc": probs.auc}, probs.bacc
+        else:
+            m = gnn_metrics(va.labels, probs, num_classes)
+            bacc = balanced_accuracy_score(va.labels, probs.argmax(axis=1))
         if bacc > best["bacc"] + 1e-6:
             best["bacc"], best["state_bacc"] = bacc, snapshot()
         if val_loss < best["loss"] - 1e-6:
             best["loss"], best["no_improve"], best["state_loss"] = val_loss, 0, snapshot()
         else:
             best["no_improve"] += 1
-        history.append({"epoch": epoch, "val_auc": m["auc"], "val_bacc": bacc, "val_loss": val_loss, "probs": probs,
+        history.append({"epoch": epoch, "val_auc": m["auc"], "val_bacc": bacc, "val_loss": val_loss,
+                        **({"metrics": probs} if device_metrics else {"probs": probs}),
                         "train_losses": [float(v) for v in torch.stack(step_losses).cpu()] if step_losses else []})
         if rank == 0 and log:
             log(f"    Epoch {epoch:03d}: Val AUROC: {m['auc']:.4f} | Val BAcc: {bacc:.4f} (best: {best['bacc']:.4f})  | "
@@ -430,28 +482,41 @@ def gnn_metrics(labels, scores, num_classes):
 
 
 @torch.no_grad()
-def evaluate_gnn(model, store, num_classes, chunk=32):
+def evaluate_gnn(model, store, num_classes, chunk=32, device_metrics=False):
+    """`05_train_gnns.py:273-302`.  ``device_metrics``: the same keys from counts formed on the device (one read-back per
+    evaluation; the AUROC is NaN when a class has no validation sample, where ``gnn_metrics`` gives sklearn's NaN)."""
     model.eval()
     n = len(store.x)
     if n == 0:
         return {k: float("nan") for k in ("loss", "accuracy", "bacc", "auc", "macro_f1")}
     scores, losses = [], []
+    acc = _DeviceScores(store.y_dev, store.device) if device_metrics else None
     for lo in range(0, n, chunk):
         idx = list(range(lo, min(n, lo + chunk)))
         x, offs, g = store.batch(idx, cache=True)
         probs, _ = model(x, offsets=offs, graph=g)
+        if acc is not None:
+            acc.put(lo, probs, ops.CrossEntropyFn.apply(probs, acc.y[lo:lo + len(idx)], 1)[1])
+            continue
         y = torch.as_tensor(store.y[idx], device=x.device)
         losses.append(ops.CrossEntropyFn.apply(probs, y, 1)[1].cpu())      # CE(log(p + 1e-9)), 05:282
         scores.append(probs.cpu())
+    if acc is not None:
+        if probs.shape[1] != num_classes:
+            raise ValueError(f"evaluate_gnn: the model scores {probs.shape[1]} classes, num_classes is {num_classes}")
+        return acc.finish().as_dict()
     scores = torch.cat(scores).numpy()
     return {"loss": float(torch.cat(losses).mean()), **gnn_metrics(store.y, scores, num_classes)}
 
 
 def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, weight_decay=1e-4, epochs=1,
-                   patience=16, min_delta=1e-6, graphs_per_step=1, num_classes=7, device=None, rng=None):
+                   patience=16, min_delta=1e-6, graphs_per_step=1, num_classes=7, device=None, rng=None,
+                   device_metrics=False, history=None):
     """`05_train_gnns.py:305-358`: AdamW, epoch order = np.random.permutation, best state by validation
     balanced accuracy.  The class weights of `05:328-331` cancel for single-sample CE and
-    batched steps keep the unweighted per-graph mean.  Returns (val_metrics, test_metrics, best_epoch)."""
+    batched steps keep the unweighted per-graph mean.  Returns (val_metrics, test_metrics, best_epoch).
+    ``device_metrics``: every evaluation is scored on the device (``evaluate_gnn``).  ``history``: a list that receives one
+    ``{"epoch", "val_bacc", "val_loss"}`` per epoch."""
     rank, world = dist_info()
     device = device or next(model.parameters()).device
     needs = model.gnn_type != "mlp"
@@ -492,7 +557,9 @@ def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, 
                         loss = ops.cross_entropy_from_probs(probs, y)
                     ops.backward(loss if w == 1.0 else loss * w)
             _sync_step(opt, sync, world)
-        vm = evaluate_gnn(model, va, num_classes)
+        vm = evaluate_gnn(model, va, num_classes, device_metrics=device_metrics)
+        if history is not None:
+            history.append({"epoch": epoch, "val_bacc": vm["bacc"], "val_loss": vm["loss"]})
         if vm["bacc"] > best_bacc + min_delta:
             best_bacc, no_imp, best_epoch = vm["bacc"], 0, epoch
             best_state = copy.deepcopy(model.state_dict())
@@ -502,4 +569,5 @@ def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, 
             break
     if best_state is not None:
         model.load_state_dict(best_state)
-    return evaluate_gnn(model, va, num_classes), evaluate_gnn(model, te, num_classes), best_epoch
+    return (evaluate_gnn(model, va, num_classes, device_metrics=device_metrics),
+            evaluate_gnn(model, te, num_classes, device_metrics=device_metrics), best_epoch)

@@ -149,8 +149,10 @@ def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk
     return DeviceTeacherOutputs(x, torch.cat(probs), torch.cat(att), y, image_ids, kmax=kmax)
 
 
-def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, variant, *, fold=0, seed=42, **fit):
-    """05's fold loop (`05_train_gnns.py:305-358`) fed directly from resident teacher outputs: no pickle, no upload."""
+def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, variant, *, fold=0, seed=42,
+                           device_metrics=False, **fit):
+    """05's fold loop (`05_train_gnns.py:305-358`) fed directly from resident teacher outputs: no pickle, no upload.
+    ``device_metrics``: the fold's evaluations are scored on the device as well (``train.evaluate_gnn``)."""
     from isic_hip import train as T
     recs = [o.graph_records(variant, fold, seed) for o in (outputs_train, outputs_val, outputs_test)]
-    return T.train_gnn_fold(gnn_model, recs[0], recs[1], recs[2], **fit)
+    return T.train_gnn_fold(gnn_model, recs[0], recs[1], recs[2], device_metrics=device_metrics, **fit)
