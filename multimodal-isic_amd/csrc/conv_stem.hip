@@ -289,11 +289,28 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(StemArgs a) {
 // written (3.3 GB at 2048 images) and this kernel read back.  A thread owns the 2x2 pixels (2a+dy, 2b+dx) of one
 // 8-channel group (pool_grad.h): 8 x 16 tile = 4 x 8 such blocks x 8 groups = 256 threads.  The raw loads of the NEXT
 // tile stay in registers while the current one is multiplied; the arithmetic happens when they are committed to LDS.
-// VALU-bound: ~1,650 vector instructions per thread and tile (max-pool routing: 9 compare / select / add per channel;
-// BatchNorm: ~8 per value; addressing) = 6.6 k cycles per tile and SIMD against 1 k of MFMA.  Measured and rejected:
-// a producer / consumer split (4 waves load + form dY with two tiles of operands in flight, 4 waves multiply: 2.7 ms
-// vs 2.15 ms -- one VALU wave per SIMD issues worse than two) and wave-uniform base + per-thread constant offsets with an
-// incremental tile cursor (2.11 ms: the address arithmetic was not the bulk of it).
+//
+// What a tile costs is vector-ALU issue, so the tile loop carries only what forms a value of the result.  Static counts
+// (hipcc -O3, gfx950; profiles/stem_wgrad_valu_bench.txt): 559 vector instructions per thread and tile on the path of a
+// tile whose outputs all exist, against about 1,000 in the loop of the kernel this replaces (1,795 in that whole
+// kernel); 208 VGPRs, two waves per SIMD, no scratch.  Measured at 4096 images: 4.27 -> 3.36 ms per launch, still 1.9x
+// the byte floor (1.75 ms for 10.7 GB), outputs equal element for element.  What is left in the loop is the dY
+// arithmetic: the max-pool routing of 32 values (72 byte compares + 72 selects + 28 packed adds), their bf16 rounding,
+// the ReLU mask (16 packed FMAs, 32 compares, 32 selects), dY = (D + B*y0) + A*dz (32 packed multiplies, 32 packed
+// adds) and its packing.  Removed:
+//   * the patch goes by LDS-DMA into two buffers (no fetch_patch / commit_patch: their division by 40, bounds tests,
+//     64-bit addresses and 8 staging registers);
+//   * tile coordinates are scalar and advance by carries (no division per tile), address bases are scalar, per-thread
+//     offsets are 32-bit and computed once;
+//   * a tile whose outputs all exist takes a path without clamps and `live` / `in` selects;
+//   * the MFMA fragment addresses are two per-tile bases + immediates.
+// The per-thread argmax / gradient loads (each pooling window is fetched by up to four threads) stay as they are.
+// Measured and rejected earlier: a producer / consumer split (4 waves load + form dY with two tiles of operands in
+// flight, 4 waves multiply: 2.7 ms vs 2.15 ms at 2048 images -- one VALU wave per SIMD issues worse than two) and
+// wave-uniform base + per-thread constant offsets with an incremental tile cursor (2.11 ms vs 2.15 ms: the address
+// arithmetic was not the bulk of it).  That variant touched the addressing alone, and with the block-index test still
+// inside the divergent prologue branch its cursor and bases were vector values all the same (see the end of the
+// kernel); the present form also drops the patch staging, the clamps and the validity selects.
 struct StemBnArgs {
   StemArgs s;                       // s.dy unused
   const unsigned short* y0;         // [N,Hout,Wout,64] stem convolution output
@@ -305,29 +322,78 @@ struct StemBnArgs {
   int Hp, Wp;
 };
 
+// The input patch by LDS-DMA: origin (2*oy0 - 3, 2*ox0 - 4) -- one pixel left of the patch the register path stages, so
+// that with an even Win every 16-byte piece (two pixels) is aligned and lies wholly inside or wholly outside the image.
+// A patch row is 20 pieces, the patch 420, lane-linear in LDS: seven wave-instructions of 64 pieces (the last one
+// carries 28 padding pieces into the buffer's tail), two per wave.  Out-of-image pieces read the zero page.
+constexpr int PPIECES = PR * (PROW / 16);
+constexpr int PDMA = (PPIECES + 63) / 64;
+constexpr int PBUF = PDMA * 1024;
+__device__ __attribute__((aligned(256))) unsigned char g_stem_zero_page[256];
+
+struct StemTile { int n, oy0, ox0; };           // block-uniform tile coordinates, advanced without divisions
+
+// max-pool routing of channels 4*HALF .. +3: windows_to_grad4 (pool_grad.h) without its `live` tests -- the caller has
+// set the codes of a missing window to 0xFF, which selects nothing.  Same contributions, same order (window rows, then
+// columns), same bf16 rounding
+template <int HALF>
+__device__ __forceinline__ void stem_route4_interior(const isic_pool::Windows& w, float (&out)[4][4]) {
+  float acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[p][j] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jw = 0; jw < 2; ++jw) {
+      const unsigned lo = w.g[i * 2 + jw][2 * HALF], hi = w.g[i * 2 + jw][2 * HALF + 1];
+      const float g[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xFFFF0000u), __uint_as_float(hi << 16),
+                          __uint_as_float(hi & 0xFFFF0000u)};
+      const unsigned am = w.am[i * 2 + jw][HALF];
+#pragma unroll
+      for (int dy = i; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = jw; dx < 2; ++dx) {
+          const unsigned code = (unsigned)((dy + 1 - 2 * i) * 3 + (dx + 1 - 2 * jw));
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (((am >> (j * 8)) & 0xFFu) == code) acc[dy * 2 + dx][j] += g[j];
+        }
+    }
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[p][j] = bf16_bits_to_f32(f32_to_bf16_bits(acc[p][j]));
+}
+
+// dY = (D + B*y0) + A*dz with every product and sum rounded by itself: no contraction to fused multiply-adds
+__device__ __forceinline__ float stem_dy_unfused(float kA, float kB, float kD, float y0, float dz) {
+#pragma clang fp contract(off)
+  const float t = kD + kB * y0;
+  return t + kA * dz;
+}
+
+// DMA = true needs an even Win and a 16-byte aligned input; DMA = false stages the patch through registers
+// (fetch_patch / commit_patch) and serves every other shape.
+template <bool DMA>
 __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b) {
   const StemArgs& a = b.s;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[PR * PROW + TH * TW * YROW];
+  constexpr int PSZ = DMA ? 2 * PBUF : PR * PROW;        // DMA: two patch buffers, tile t+1 lands while tile t is multiplied
+  constexpr int PSH = DMA ? 8 : 0;                       // DMA: the patch starts one pixel further left
+  __shared__ __attribute__((aligned(16))) unsigned char smem[PSZ + TH * TW * YROW];
   __shared__ __attribute__((aligned(16))) float cst[5][64];     // A, B, D of dY = A*dz + B*y0 + D; sc, sh of the ReLU mask
-  unsigned char* Ps = smem;
-  unsigned char* Ys = smem + PR * PROW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned char* Ys = smem + PSZ;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fg = lane >> 4, fi = lane & 15, fq = fi >> 2, fp = fi & 3;
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
+  // this lane's part of the MFMA fragment addresses (see the tile loop)
+  const unsigned frag_y = (unsigned)((8 * fg + fq) * YROW + 8 * fp);
+  const unsigned frag_p = (unsigned)(2 * (fg >> 1) * PROW + (16 * (fg & 1) + 2 * fq + fp) * 8 + PSH);
   const isic_pool::PoolGeom geom{a.Hout, a.Wout, 64, b.Hp, b.Wp};
 
-  if (tid < 64) {
-    const float inv_rows = 1.f / (float)((int64_t)a.N * a.Hout * a.Wout);
-    // dY = k1*(dz - k2 - xh*k3), xh = (y0 - mu)*rs  ==  A*dz + B*y0 + D  (three constants, two FMAs per element)
-    const float rs = b.rstd[tid], mu = b.mean[tid], k1 = b.gamma[tid] * rs;
-    const float k2 = (float)b.dbeta[tid] * inv_rows, k3 = (float)b.dgamma[tid] * inv_rows;
-    cst[0][tid] = k1; cst[1][tid] = -k1 * k3 * rs; cst[2][tid] = k1 * (k3 * rs * mu - k2);
-    cst[3][tid] = b.scale[tid]; cst[4][tid] = b.shift[tid];
-    if (blockIdx.x == 0 && b.dgamma_f32) {
-      b.dgamma_f32[tid] += (float)b.dgamma[tid];
-      b.dbeta_f32[tid] += (float)b.dbeta[tid];
-    }
-  }
+  const int bid = blockIdx.x;
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -335,35 +401,78 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+  // ---- tile cursor: tile += gridDim.x as (n, oy0, ox0) += (step_n, step_y, step_x) with carries, in scalar registers
+  const int tiles_img = a.tiles_h * a.tiles_w;
+  const int step_n = (int)gridDim.x / tiles_img, step_r = (int)gridDim.x - step_n * tiles_img;
+  const int step_y = (step_r / a.tiles_w) * TH, step_x = (step_r % a.tiles_w) * TW;
+  const int span_y = a.tiles_h * TH, span_x = a.tiles_w * TW;
+  auto advance = [&](StemTile& t) {
+    t.ox0 += step_x;
+    if (t.ox0 >= span_x) { t.ox0 -= span_x; t.oy0 += TH; }
+    t.oy0 += step_y;
+    if (t.oy0 >= span_y) { t.oy0 -= span_y; t.n += 1; }
+    t.n += step_n;
+  };
+  // a tile whose outputs all exist (block-uniform, the usual case) is formed without clamps and validity selects, from
+  // a per-image scalar base and 32-bit per-thread offsets; of its pooling windows only those of the last row / column
+  // can be missing: such a window is loaded from its neighbour's address and its argmax codes are overwritten by 0xFF
+  const bool fits32 = (int64_t)a.Hout * a.Wout < (1 << 24);             // in-image byte offsets (128 B per pixel) fit 31 bits
+  auto interior = [&](const StemTile& t) { return fits32 && t.oy0 + TH <= a.Hout && t.ox0 + TW <= a.Wout; };
+
   // this thread's 2x2 pixel block inside the tile and its channel group
   const int cg = tid & 7, bl = tid >> 3, al = bl >> 3, bw = bl & 7;
-  u32x2 pre[PATCH_PER_THREAD];
+  const unsigned yoff = (unsigned)((2 * al * a.Wout + 2 * bw) * 128 + cg * 16);   // pixel (2al, 2bw) from the tile origin
+  const unsigned goff = (unsigned)((al * b.Wp + bw) * 128 + cg * 16);             // window (al, bw) from the tile's first
+  u32x2 pre[DMA ? 1 : PATCH_PER_THREAD];
   u32x4 xr[4];
   isic_pool::Windows win;
-  auto fetch_dy = [&](int tile) {
-    const int tc = tile < a.total_tiles ? tile : a.total_tiles - 1;       // clamped: always valid addresses
-    const int n = tc / (a.tiles_h * a.tiles_w);
-    const int t2 = tc - n * (a.tiles_h * a.tiles_w);
-    const int oy0 = (t2 / a.tiles_w) * TH, ox0 = (t2 % a.tiles_w) * TW;
-    const int ga = (oy0 >> 1) + al, gb = (ox0 >> 1) + bw;
+  auto fetch_dy = [&](const StemTile& t, auto INT) {
+    if constexpr (decltype(INT)::value) {
+      const unsigned char* yb = reinterpret_cast<const unsigned char*>(b.y0) +
+                                (((int64_t)t.n * a.Hout + t.oy0) * a.Wout + t.ox0) * 128;
+      const int64_t w0 = ((int64_t)t.n * b.Hp + (t.oy0 >> 1)) * b.Wp + (t.ox0 >> 1);
+      const unsigned char* gb = reinterpret_cast<const unsigned char*>(b.gp) + w0 * 128;
+      const unsigned char* ab = b.argmax + w0 * 64;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int hi = min(2 * ga + (p >> 1), a.Hout - 1), wi = min(2 * gb + (p & 1), a.Wout - 1);
-      xr[p] = *reinterpret_cast<const u32x4*>(b.y0 + (((size_t)n * a.Hout + hi) * a.Wout + wi) * 64 + cg * 8);
+      for (int p = 0; p < 4; ++p)
+        xr[p] = *reinterpret_cast<const u32x4*>(yb + (size_t)(p >> 1) * a.Wout * 128 + yoff + (p & 1) * 128);
+      const unsigned drow = ((t.oy0 >> 1) + al + 1 < b.Hp) ? (unsigned)b.Wp * 128u : 0u;
+      const unsigned dcol = ((t.ox0 >> 1) + bw + 1 < b.Wp) ? 128u : 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned o = goff + ((k >> 1) ? drow : 0u) + ((k & 1) ? dcol : 0u);
+        win.am[k] = *reinterpret_cast<const u32x2*>(ab + (o >> 1));
+        win.g[k] = *reinterpret_cast<const u32x4*>(gb + o);
+      }
+    } else {
+      const int ga = (t.oy0 >> 1) + al, gb = (t.ox0 >> 1) + bw;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int hi = min(2 * ga + (p >> 1), a.Hout - 1), wi = min(2 * gb + (p & 1), a.Wout - 1);
+        xr[p] = *reinterpret_cast<const u32x4*>(b.y0 + (((size_t)t.n * a.Hout + hi) * a.Wout + wi) * 64 + cg * 8);
+      }
+      isic_pool::load_windows(win, b.argmax, b.gp, geom, t.n, min(ga, b.Hp - 1), min(gb, b.Wp - 1), cg);
     }
-    isic_pool::load_windows(win, b.argmax, b.gp, geom, n, min(ga, b.Hp - 1), min(gb, b.Wp - 1), cg);
   };
   // raw loads -> dY values of the 2x2 pixels -> LDS rows [pixel][co]
-  auto commit_dy = [&](int tile) {
-    const int n = tile / (a.tiles_h * a.tiles_w);
-    const int t2 = tile - n * (a.tiles_h * a.tiles_w);
-    const int oy0 = (t2 / a.tiles_w) * TH, ox0 = (t2 % a.tiles_w) * TW;
-    const int ga = (oy0 >> 1) + al, gb = (ox0 >> 1) + bw;
-    const bool inside = (oy0 + TH <= a.Hout) && (ox0 + TW <= a.Wout);    // block-uniform: the usual case
+  auto commit_dy = [&](const StemTile& t, auto INT) {
+    constexpr bool I_ = decltype(INT)::value;
+    const int ga = (t.oy0 >> 1) + al, gb = (t.ox0 >> 1) + bw;
+    const bool inside = I_ || ((t.oy0 + TH <= a.Hout) && (t.ox0 + TW <= a.Wout));
+    if constexpr (I_) {
+      const bool row1 = ga + 1 < b.Hp, col1 = gb + 1 < b.Wp;
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        const bool live = ((k >> 1) == 0 || row1) && ((k & 1) == 0 || col1);
+        win.am[k][0] = live ? win.am[k][0] : 0xFFFFFFFFu;
+        win.am[k][1] = live ? win.am[k][1] : 0xFFFFFFFFu;
+      }
+    }
     auto half = [&](auto HC) {
       constexpr int H_ = decltype(HC)::value;
       float g[4][4];
-      isic_pool::windows_to_grad4<H_>(win, geom, ga, gb, g);
+      if constexpr (I_) stem_route4_interior<H_>(win, g);      // (missing windows: codes already 0xFF)
+      else isic_pool::windows_to_grad4<H_>(win, geom, ga, gb, g);
       const int c0 = cg * 8 + H_ * 4;
       const f32x4 kA = *reinterpret_cast<const f32x4*>(&cst[0][c0]), kB = *reinterpret_cast<const f32x4*>(&cst[1][c0]);
       const f32x4 kD = *reinterpret_cast<const f32x4*>(&cst[2][c0]), sc = *reinterpret_cast<const f32x4*>(&cst[3][c0]);
@@ -371,15 +480,16 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int oyl = 2 * al + (p >> 1), oxl = 2 * bw + (p & 1);
-        const bool in = inside || ((oy0 + oyl < a.Hout) && (ox0 + oxl < a.Wout));
+        const bool in = inside || ((t.oy0 + oyl < a.Hout) && (t.ox0 + oxl < a.Wout));
         const unsigned lo = xr[p][2 * H_], hi = xr[p][2 * H_ + 1];
         float xv[4];
         isic_unpack_bf16x4(lo, hi, xv);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float dz = (xv[j] * sc[j] + sh[j] > 0.f) ? g[p][j] : 0.f;
-          o[j] = kA[j] * dz + (kB[j] * xv[j] + kD[j]);
+          // one fused multiply-add in the mask, none in dY = (D + B*y0) + A*dz: the roundings of the two-kernel path
+          const float dz = (fmaf(xv[j], sc[j], sh[j]) > 0.f) ? g[p][j] : 0.f;
+          o[j] = stem_dy_unfused(kA[j], kB[j], kD[j], xv[j], dz);
           if (!inside) o[j] = in ? o[j] : 0.f;
         }
         *reinterpret_cast<u32x2*>(Ys + (oyl * TW + oxl) * YROW + cg * 16 + H_ * 8) = isic_pack_bf16x4(o);
@@ -389,36 +499,98 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
     __builtin_amdgcn_sched_barrier(0);                   // keep the two halves' temporaries from overlapping
     half(std::integral_constant<int, 1>{});
   };
+
+  // ---- patch DMA: this wave's instructions d = wave, wave + 4; piece q = 64 d + lane = patch row q / 20, pixels 2 (q % 20) ..+1
+  int ppr[2], ppc[2];
+  unsigned poff[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int q = (wave + 4 * u) * 64 + lane;
+    ppr[u] = q < PPIECES ? q / (PROW / 16) : -100000;                    // padding piece: never inside the image
+    ppc[u] = 2 * (q % (PROW / 16));
+    poff[u] = q < PPIECES ? (unsigned)((ppr[u] * a.Win + ppc[u]) * 8) : 0u;
+  }
+  const unsigned char* zp = g_stem_zero_page + (lane & 7) * 16;
+  auto issue_patch = [&](const StemTile& t, int buf) {
+    const int hi0 = 2 * t.oy0 - 3, wi0 = 2 * t.ox0 - 4;
+    const unsigned char* org = reinterpret_cast<const unsigned char*>(a.in) +
+                               (((int64_t)t.n * a.Hin + hi0) * a.Win + wi0) * 8;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int d = wave + 4 * u;
+      if (d < PDMA) {                                                    // wave-uniform
+        const bool ok = (unsigned)(hi0 + ppr[u]) < (unsigned)a.Hin && (unsigned)(wi0 + ppc[u]) < (unsigned)a.Win;
+        isic_glds16(ok ? org + poff[u] : zp, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(buf * PBUF + d * 1024)));
+      }
+    }
+  };
+
+  StemTile cur;
+  {
+    const int t0 = bid;                                   // < total_tiles: the grid is never larger
+    const int n = t0 / tiles_img, t2 = t0 - n * tiles_img;
+    cur.n = n; cur.oy0 = (t2 / a.tiles_w) * TH; cur.ox0 = (t2 % a.tiles_w) * TW;
+  }
+  int buf = 0;
+  // (after the scalar set-up above: what is first computed inside this divergent branch and used again behind it
+  //  comes out of the branch's join as a vector value, tile coordinates and address bases included)
+  if (tid < 64) {
+#pragma clang fp contract(off)
+    const float inv_rows = 1.f / (float)((int64_t)a.N * a.Hout * a.Wout);
+    // dY = k1*(dz - k2 - xh*k3), xh = (y0 - mu)*rs  ==  A*dz + B*y0 + D  (three constants); the one fused
+    // multiply-add is written out, nothing else contracts
+    const float rs = b.rstd[tid], mu = b.mean[tid], k1 = b.gamma[tid] * rs;
+    const float k2 = (float)b.dbeta[tid] * inv_rows, k3 = (float)b.dgamma[tid] * inv_rows;
+    cst[0][tid] = k1;
+    cst[1][tid] = (-k1 * k3) * rs;
+    cst[2][tid] = k1 * fmaf(k3 * rs, mu, -k2);
+    cst[3][tid] = b.scale[tid]; cst[4][tid] = b.shift[tid];
+  }
   __syncthreads();                                       // constants visible
-  fetch_patch(pre, a, blockIdx.x, tid);
-  fetch_dy(blockIdx.x);
-  for (int tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
+  if constexpr (DMA) issue_patch(cur, 0);
+  else fetch_patch(pre, a, bid, tid);
+  if (interior(cur)) fetch_dy(cur, std::true_type{});
+  else fetch_dy(cur, std::false_type{});
+  for (int tile = bid; tile < a.total_tiles; tile += gridDim.x) {
+    unsigned char* Ps = smem + (DMA ? buf * PBUF : 0);
     lds_barrier();                                       // previous tile's operands fully consumed
-    commit_patch(Ps, pre, tid);
-    commit_dy(tile);
+    if constexpr (!DMA) commit_patch(Ps, pre, tid);
+    if (interior(cur)) commit_dy(cur, std::true_type{});
+    else commit_dy(cur, std::false_type{});
+    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the patch have landed
     lds_barrier();
-    fetch_patch(pre, a, tile + gridDim.x, tid);
-    fetch_dy(tile + gridDim.x);
+    const bool more = tile + (int)gridDim.x < a.total_tiles;
+    if constexpr (!DMA) fetch_patch(pre, a, tile + gridDim.x, tid);
+    if (more) {                                          // block-uniform
+      advance(cur);
+      if constexpr (DMA) issue_patch(cur, buf ^ 1);      // the other buffer: last read before the two barriers above
+      if (interior(cur)) fetch_dy(cur, std::true_type{});
+      else fetch_dy(cur, std::false_type{});
+    }
+    buf ^= 1;
+    // fragment addresses = one per-tile base + compile-time offsets.  Pixel row k1 = 32 ks + 8 fg + fq (k2 = k1 + 4) and
+    // n-tile nt = wave + 4 j (kernel row kh = (wave >> 1) + 2 j, half = wave & 1): the patch address
+    // (2 (k >> 4) + kh) PROW + (2 (k & 15) + 4 half + fp) 8 splits into the lane's part, the wave's part and
+    // (4 ks + 2 j) PROW (+ 64 for k2).  nt >= 14 (j = 3 of waves 2, 3: kh = 7) would address past the taps: those two
+    // waves read row kh = 6 instead (result discarded at the end)
+    const unsigned char* yb = Ys + frag_y;
+    const unsigned char* pb = Ps + frag_p + ((wave >> 1) * PROW + (wave & 1) * 32);
+    const unsigned char* pb3 = pb - (wave >= 2 ? PROW : 0);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int k1 = ks * 32 + 8 * fg + fq, k2 = k1 + 4;   // the two pixel rows this lane addresses
       bf16x8 af[4], bfr[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(Ys + k1 * YROW + (i * 16 + 4 * fp) * 2));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(Ys + k2 * YROW + (i * 16 + 4 * fp) * 2));
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(yb + ks * 32 * YROW + i * 32));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(yb + (ks * 32 + 4) * YROW + i * 32));
         s16x8_t t; t.lo = lo; t.hi = hi;
         af[i] = __builtin_bit_cast(bf16x8, t);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int nt = wave + 4 * j;
-        const int kh = nt >> 1, half = nt & 1;
-        const int khc = kh > 6 ? 6 : kh;
-        const unsigned char* p1 = Ps + (2 * (k1 >> 4) + khc) * PROW + (2 * (k1 & 15) + half * 4 + fp) * 8;
-        const unsigned char* p2 = Ps + (2 * (k2 >> 4) + khc) * PROW + (2 * (k2 & 15) + half * 4 + fp) * 8;
+        const unsigned char* p1 = (j < 3 ? pb : pb3) + (4 * ks + 2 * j) * PROW;
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)p1);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)p2);
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p1 + 64));
         s16x8_t t; t.lo = lo; t.hi = hi;
         bfr[j] = __builtin_bit_cast(bf16x8, t);
       }
@@ -442,9 +614,16 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
         const int co = i * 16 + fg * 4 + r;
         // the block's OWN partial (workspace [grid][64*7*7*3]); isic_slab_reduce_launch adds them in a fixed order:
         // deterministic, where fp32 atomics added the blocks in arrival order
-        a.dw[(size_t)blockIdx.x * STEM_DW_ELEMS + ((co * 7 + kh) * 7 + kw) * 3 + c] = acc[i][j][r];
+        a.dw[(size_t)bid * STEM_DW_ELEMS + ((co * 7 + kh) * 7 + kw) * 3 + c] = acc[i][j][r];
       }
     }
+  // the fp32 copies of dgamma / dbeta, by block 0.  At the END: a test of the block index inside the divergent branch
+  // at the top lets the compiler merge "block index == 0" with the register at that branch's join, which turns the
+  // block index -- and with it every tile coordinate and address base of the loop -- into vector values
+  if (bid == 0 && tid < 64 && b.dgamma_f32) {
+    b.dgamma_f32[tid] += (float)b.dgamma[tid];
+    b.dbeta_f32[tid] += (float)b.dbeta[tid];
+  }
 }
 
 // fp32 [64][7][7][3] (channels_last memory of the OIHW parameter) -> bf16 [64][7][8][4], zero padded
@@ -531,7 +710,11 @@ int isic_conv_stem_wgrad_bn_pooled_bf16(const uint16_t* in_nhwc4, const uint16_t
   b.shift = shift; b.dgamma = dgamma; b.dbeta = dbeta; b.dgamma_f32 = dgamma_f32; b.dbeta_f32 = dbeta_f32;
   b.Hp = Hp; b.Wp = Wp;
   const int grid = a.total_tiles < STEM_WGRAD_BLOCKS ? a.total_tiles : STEM_WGRAD_BLOCKS;
-  hipLaunchKernelGGL(conv_stem_wgrad_bn_kernel, dim3(grid), dim3(256), 0, as_stream(stream), b);
+  // the patch goes by LDS-DMA where its 16-byte pieces are aligned and never straddle the right border
+  if (Win % 2 == 0 && (reinterpret_cast<uintptr_t>(in_nhwc4) & 15) == 0)
+    hipLaunchKernelGGL(conv_stem_wgrad_bn_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), b);
+  else
+    hipLaunchKernelGGL(conv_stem_wgrad_bn_kernel<false>, dim3(grid), dim3(256), 0, as_stream(stream), b);
   isic_slab_reduce_launch(ISIC_SLAB_XOR16, reinterpret_cast<const float*>(workspace), grid, STEM_DW_ELEMS, dw, 1.f,
                           as_stream(stream));                       // dw += the blocks' partials (slab_sum.inc, order A)
   return isic_launch_status();
