@@ -18,7 +18,7 @@ import pandas as pd
 import torch
 
 from isic_hip.bags import BagOffsets
-from isic_hip.graph import knn_indices
+from isic_hip.graph import knn_indices, random_graphs
 
 NUM_NODES = 196
 GRID_SIDE = 14
@@ -91,8 +91,8 @@ def _knn_edge_index(x, k=8):
 
 def _random_edge_index(num_nodes, r=4, seed=None):
     """Random undirected graph of `03_build_graphs.py:57-78`: per node ``r`` targets from a seeded
-    CPU ``torch.Generator`` permutation, symmetrised, deduplicated in lexicographic order.  Stays on
-    the host: it is defined by torch's CPU random stream."""
+    CPU ``torch.Generator`` permutation, symmetrised, deduplicated in lexicographic order.  The host
+    definition (torch's CPU random stream); ``random_edge_index_batched`` builds the same integers on the device."""
     if num_nodes < 2:
         return torch.empty((2, 0), dtype=torch.long)
     r = int(max(1, min(r, num_nodes - 1)))
@@ -104,6 +104,14 @@ def _random_edge_index(num_nodes, r=4, seed=None):
     picks = picks + (picks >= owner).long()          # candidate list of node i skips i itself
     e = torch.stack([owner.expand(-1, r).reshape(-1), picks.reshape(-1)])
     return torch.unique(torch.cat([e, e.flip(0)], dim=1), dim=1)
+
+
+def random_edge_index_batched(num_nodes, r_values, seeds, device=None):
+    """``_random_edge_index(num_nodes, r, seed)`` for every seed of ``seeds`` and every r of ``r_values`` in ONE launch
+    (``isic_hip.graph.random_graphs``: MT19937 and the Fisher-Yates draws of torch's CPU stream restated on the device, equal
+    to the host build in every integer) -> {r: list of [2, E_g] int64 device tensors}, one per seed."""
+    out = random_graphs([int(s) for s in seeds], int(num_nodes), [int(r) for r in r_values], device=device)
+    return {r: (list(e.unbind(0)) if isinstance(e, torch.Tensor) else e) for r, e in out.items()}
 
 
 def _as_list(value):
@@ -129,12 +137,18 @@ def _build_image_graph_blueprints(row, k_values, r_values, seed):
     }
 
 
-def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values, seed):
-    """All images of one patch-stats frame in ONE k-NN launch (same records as the per-row loop)."""
+def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values, seed, device_random=False):
+    """All images of one patch-stats frame in ONE k-NN launch (same records as the per-row loop).  ``device_random``: the
+    random graphs of all images come from one launch as well (``random_edge_index_batched``) instead of the host builder;
+    the records hold the same numpy arrays either way."""
     xs = [np.asarray(v, dtype=np.float32) for v in teacher_df["patch_embeddings"]]
     offs = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])])
     knn = knn_edge_index_batched(torch.from_numpy(np.concatenate(xs)), offs, [int(k) for k in k_values])
     knn = {k: v.cpu().numpy() for k, v in knn.items()}
+    rand = None
+    if device_random and len(teacher_df):
+        rand = random_edge_index_batched(NUM_NODES, r_values, [seed + fold * 10_000 + row_idx for row_idx in teacher_df.index])
+        rand = {r: [e.cpu().numpy() for e in es] for r, es in rand.items()}
     records = []
     for i, (row_idx, row) in enumerate(teacher_df.iterrows()):
         lo, n = int(offs[i]), int(offs[i + 1] - offs[i])
@@ -147,14 +161,17 @@ def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values,
             "grid4_edge_index": _grid_edge_index(False).numpy(),
             "grid8_edge_index": _grid_edge_index(True).numpy(),
             "knn_edge_indices": per_k,
-            "random_edge_indices": {int(r): _random_edge_index(NUM_NODES, r=int(r), seed=seed + fold * 10_000 + row_idx).numpy()
-                                    for r in r_values},
+            "random_edge_indices": ({int(r): rand[int(r)][i] for r in r_values} if rand is not None else
+                                    {int(r): _random_edge_index(NUM_NODES, r=int(r), seed=seed + fold * 10_000 + row_idx).numpy()
+                                     for r in r_values}),
         })
     return records
 
 
-def process_model_directory(model_dir, output_root, k_values=DEFAULT_K_VALUES, r_values=DEFAULT_R_VALUES, seed=42):
-    """`03_build_graphs.py:117-149`: patch_stats_fold_*_*.pkl -> graph_outputs/<model>/graph_dataset.pkl."""
+def process_model_directory(model_dir, output_root, k_values=DEFAULT_K_VALUES, r_values=DEFAULT_R_VALUES, seed=42,
+                            device_random=False):
+    """`03_build_graphs.py:117-149`: patch_stats_fold_*_*.pkl -> graph_outputs/<model>/graph_dataset.pkl.
+    ``device_random``: see ``build_graph_records``."""
     model_dir, output_root = Path(model_dir), Path(output_root)
     out_dir = output_root / model_dir.name
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -165,7 +182,8 @@ def process_model_directory(model_dir, output_root, k_values=DEFAULT_K_VALUES, r
             frame = pickle.load(f)
         if not isinstance(frame, pd.DataFrame):
             frame = pd.DataFrame(frame)
-        records += build_graph_records(frame, model_dir.name, fold, split, _as_list(k_values), _as_list(r_values), seed)
+        records += build_graph_records(frame, model_dir.name, fold, split, _as_list(k_values), _as_list(r_values), seed,
+                                       device_random=device_random)
     out_path = out_dir / "graph_dataset.pkl"
     with open(out_path, "wb") as f:
         pickle.dump(pd.DataFrame(records), f)

@@ -24,6 +24,65 @@ def knn_indices(x, offsets: BagOffsets, k, return_dist=False):
     return (idx, dist) if return_dist else idx
 
 
+RANDOM_GRAPH_MAX_NODES = 256
+RANDOM_GRAPH_MAX_R_VALUES = 16
+
+
+def random_graph_launch(seeds, n_nodes, r_values, edges, counts):
+    """The bare ``isic_random_graph_i64`` launch on buffers that exist: ``seeds`` int64 [G] on the device, ``edges`` int64
+    (``random_graph_layout`` gives its size), ``counts`` int32 [len(r_values), G].  Nothing is read back."""
+    import ctypes
+    rs = (ctypes.c_int * len(r_values))(*[int(r) for r in r_values])
+    call("isic_random_graph_i64", seeds, int(seeds.numel()), int(n_nodes), ctypes.addressof(rs), len(r_values), edges, counts)
+
+
+def random_graph_layout(G, n_nodes, r_values):
+    """-> ([(first element, cap_j)] per r value in the given order, total elements) of the ``edges`` buffer
+    (include/isic_hip_randgraph.h): block j is [G][2][cap_j], cap_j = min(2 n r_j, n (n - 1)) for r_j clamped to [1, n - 1]."""
+    n, blocks, at = int(n_nodes), [], 0
+    for r in r_values:
+        rc = max(1, min(int(r), n - 1))
+        cap = min(2 * n * rc, n * (n - 1)) if n >= 2 else 0
+        blocks.append((at, cap))
+        at += 2 * int(G) * cap
+    return blocks, at
+
+
+def random_graphs(seeds, n_nodes, r_values, device=None):
+    """The random graphs of `03_build_graphs.py:57-78` for G seeds and a list of r values, built on the device bit for bit
+    as ``build_graphs._random_edge_index(n_nodes, r, seed)`` builds them on the host: ONE launch and ONE read-back (the
+    edge counts).  ``seeds``: Python ints (only the low 32 bits matter, as for torch's CPU generator).  Returns
+    ``{r: edges}``: a ``[G, 2, E]`` int64 tensor when every graph of that r has the same number of edges, else a list of
+    ``[2, E_g]`` tensors -- views of the launch's buffer either way, LOCAL node ids, ascending by (src, dst)."""
+    rs = list(dict.fromkeys(int(r) for r in r_values))
+    n, G = int(n_nodes), len(seeds)
+    if not rs or len(rs) > RANDOM_GRAPH_MAX_R_VALUES:
+        raise IsicHipError(f"random_graphs takes 1..{RANDOM_GRAPH_MAX_R_VALUES} distinct r values, got {len(rs)}", code=-2)
+    if n > RANDOM_GRAPH_MAX_NODES:
+        raise IsicHipError(f"random_graphs supports up to {RANDOM_GRAPH_MAX_NODES} nodes, got {n}", code=-2)
+    if not torch.cuda.is_available():
+        raise IsicHipError("random_graphs needs the MI355X (the host build is build_graphs._random_edge_index)")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    blocks, total = random_graph_layout(G, n, rs)
+    edges = torch.empty((total,), device=dev, dtype=torch.int64)
+    if G == 0 or n < 2:
+        return {r: edges.new_empty((G, 2, 0)) for r in rs}
+    sd = torch.tensor([int(s) & 0xFFFFFFFF for s in seeds], dtype=torch.int64).to(dev)
+    counts = torch.empty((len(rs), G), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        random_graph_launch(sd, n, rs, edges, counts)
+    cnt = counts.cpu().numpy()                                             # the one read-back
+    out = {}
+    for j, (r, (at, cap)) in enumerate(zip(rs, blocks)):
+        block = edges[at:at + 2 * G * cap].view(G, 2, cap)
+        es = cnt[j]
+        if (es == es[0]).all():
+            out[r] = block[:, :, :int(es[0])]
+        else:
+            out[r] = [block[g, :, :int(es[g])] for g in range(G)]
+    return out
+
+
 class GraphBatch:
     """Destination-major CSR (+ its transpose) of a batch of graphs with GCN symmetric
     normalisation and self loops (PyG ``gcn_norm`` semantics, `05_train_gnns.py:82`)."""

@@ -18,22 +18,24 @@ import torch
 
 import build_graphs as bg
 from isic_hip.bags import BagOffsets
-from isic_hip.graph import knn_indices
+from isic_hip.graph import knn_indices, random_graphs
 from isic_hip.lib import IsicHipError
 
 
 class DeviceTeacherOutputs:
     """Teacher outputs of G images of N patches, resident in HBM:
     ``x[G,N,D]``, ``patch_probs[G,N,C]``, ``attention[G,N]``, ``dominant_class[G,N]`` (int32), ``labels[G]``
-    (int64), ``knn[G,N,kmax]`` (local neighbour ids, ascending by distance)."""
+    (int64), ``knn[G,N,kmax]`` (local neighbour ids, ascending by distance).  ``device_random`` (off unless asked for): what
+    the keyword of that name defaults to in ``edge_index`` / ``graph_records`` / ``heterophily_summary`` / ``graph_frame``."""
 
-    def __init__(self, x, patch_probs, attention, labels, image_ids, kmax=16):
+    def __init__(self, x, patch_probs, attention, labels, image_ids, kmax=16, device_random=False):
         if not x.is_cuda:
             raise IsicHipError("the on-device pipeline needs device tensors (no CPU fallback)")
         G, N, D = x.shape
         self.x, self.patch_probs, self.attention = x, patch_probs, attention
         self.labels = labels
         self.image_ids = list(image_ids)
+        self.device_random = bool(device_random)
         self.dominant_class = patch_probs.argmax(dim=2).to(torch.int32)                       # 02:17
         self.kmax = int(max(1, min(kmax, N - 1)))
         offs = BagOffsets.uniform(G, N, x.device)
@@ -51,9 +53,12 @@ class DeviceTeacherOutputs:
         src = torch.arange(N, device=self.x.device).view(1, N, 1).expand(G, N, k)
         return torch.stack([src.reshape(G, -1), self.knn[:, :, :k].reshape(G, -1)], dim=1)
 
-    def edge_index(self, variant, fold=0, seed=42):
+    def edge_index(self, variant, fold=0, seed=42, device_random=None):
         """Edges of a graph variant name of 05 (`05_train_gnns.py:228-239`): knn<k> on the device; grid4 / grid8 are
-        one constant lattice; random<r> is defined by torch's CPU random stream (`03:57-78`) and built on the host."""
+        one constant lattice; random<r> is defined by torch's CPU random stream (`03:57-78`): built on the host and
+        uploaded, or with ``device_random`` (None: the object's own setting, off by default) built on the device from the
+        same stream (``isic_hip.graph.random_graphs``: one launch, the same integers, nothing uploaded; the edge counts are
+        the one read-back)."""
         G, N, _ = self.x.shape
         dev = self.x.device
         if variant.startswith("knn"):
@@ -63,25 +68,30 @@ class DeviceTeacherOutputs:
             return e.unsqueeze(0).expand(G, -1, -1)
         if variant.startswith("random"):
             r = int(variant[6:])
+            if self.device_random if device_random is None else device_random:
+                with torch.cuda.device(dev):
+                    return random_graphs([seed + fold * 10_000 + i for i in range(G)], N, [r], device=dev)[r]
             es = [bg._random_edge_index(N, r=r, seed=seed + fold * 10_000 + i) for i in range(G)]
             if len({int(e.shape[1]) for e in es}) != 1:
                 return [e.to(dev) for e in es]                 # ragged: a list, one tensor per image
             return torch.stack(es).to(dev)
         raise ValueError(f"Unsupported graph variant: {variant}")
 
-    def graph_records(self, variant, fold=0, seed=42):
+    def graph_records(self, variant, fold=0, seed=42, device_random=None):
         """Records for ``train.GraphStore`` / ``train_gnn_fold`` (`05_train_gnns.py:248-270` schema: x, edge_index, y)
-        -- views of the resident tensors, nothing is copied to the host."""
-        ei = self.edge_index(variant, fold, seed)
+        -- views of the resident tensors, nothing is copied to the host.  ``device_random``: see ``edge_index``."""
+        ei = self.edge_index(variant, fold, seed, device_random=device_random)
         y = self.labels.tolist()
         return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i]} for i in range(len(self))]
 
-    def heterophily_summary(self, variant, fold=0, seed=42):
+    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None):
         """Per-image heterophily summaries of a graph variant (`04_measure_heterophily.py:172-181`) from the resident
         tensors: ``measure_heterophily.heterophily_summary_device`` on ``x``, ``patch_probs``, ``dominant_class`` and
-        ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host."""
+        ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host.  ``device_random``: see
+        ``edge_index``."""
         import measure_heterophily as mh
-        return mh.heterophily_summary_device(self.x, self.patch_probs, self.dominant_class, self.edge_index(variant, fold, seed))
+        return mh.heterophily_summary_device(self.x, self.patch_probs, self.dominant_class,
+                                             self.edge_index(variant, fold, seed, device_random=device_random))
 
     # ------------------------------------------------------------------ exports (the reference's pickle schemas)
     def teacher_frame(self):
@@ -100,10 +110,17 @@ class DeviceTeacherOutputs:
                              "patch_probs": list(pp), "dominant_class": list(dom)})
 
     def graph_frame(self, model_name, fold, split, k_values=bg.DEFAULT_K_VALUES, r_values=bg.DEFAULT_R_VALUES, seed=42,
-                    row_offset=0):
-        """`03_build_graphs.py:95-149`: one row per image with grid / k-NN / random edge arrays (numpy)."""
+                    row_offset=0, device_random=None):
+        """`03_build_graphs.py:95-149`: one row per image with grid / k-NN / random edge arrays (numpy).
+        ``device_random``: the random graphs of all images and r values come from one launch instead of the host builder."""
         import pandas as pd
         N = int(self.x.shape[1])
+        rand = None
+        if (self.device_random if device_random is None else device_random) and len(self):
+            with torch.cuda.device(self.x.device):
+                rand = bg.random_edge_index_batched(N, [int(r) for r in r_values],
+                                                    [seed + fold * 10_000 + row_offset + i for i in range(len(self))], device=self.x.device)
+            rand = {r: [e.cpu().numpy() for e in es] for r, es in rand.items()}
         knn = {int(k): self.knn_edge_index(k).cpu().numpy() for k in k_values}
         g4, g8 = bg._grid_edge_index(False).numpy(), bg._grid_edge_index(True).numpy()
         rows = []
@@ -111,8 +128,9 @@ class DeviceTeacherOutputs:
             rows.append({"model_name": model_name, "fold": fold, "split": split, "image_id": self.image_ids[i],
                          "grid4_edge_index": g4, "grid8_edge_index": g8,
                          "knn_edge_indices": {k: v[i] for k, v in knn.items()},
-                         "random_edge_indices": {int(r): bg._random_edge_index(N, r=int(r), seed=seed + fold * 10_000 + row_offset + i).numpy()
-                                                 for r in r_values}})
+                         "random_edge_indices": ({int(r): rand[int(r)][i] for r in r_values} if rand is not None else
+                                                 {int(r): bg._random_edge_index(N, r=int(r), seed=seed + fold * 10_000 + row_offset + i).numpy()
+                                                  for r in r_values})})
         return pd.DataFrame(rows)
 
 
@@ -129,9 +147,10 @@ def with_radiomic_node_features(x, radiomics):
     return torch.cat([x, radiomics.to(x.dtype).unsqueeze(1).expand(G, N, radiomics.shape[1])], dim=2).contiguous()
 
 
-def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk=256, kmax=16):
+def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk=256, kmax=16, device_random=False):
     """`_collect_teacher_outputs` (`01_train_mil_teacher.py:69-87`) with every output left on the device.
-    ``bags``: list of equal-sized [N, D] arrays or one [G, N, D] tensor."""
+    ``bags``: list of equal-sized [N, D] arrays or one [G, N, D] tensor.  ``device_random``: the default of the returned
+    object's ``edge_index`` / ``graph_records`` / ``heterophily_summary`` / ``graph_frame`` keyword of that name."""
     dev = torch.device(device)
     model.eval()
     if isinstance(bags, torch.Tensor):
@@ -146,13 +165,15 @@ def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk
         probs.append(out["patch_probs"].view(hi - lo, N, -1))
         att.append(out["attention"].view(hi - lo, N))
     y = torch.as_tensor(np.asarray(labels, dtype=np.int64), device=dev)
-    return DeviceTeacherOutputs(x, torch.cat(probs), torch.cat(att), y, image_ids, kmax=kmax)
+    return DeviceTeacherOutputs(x, torch.cat(probs), torch.cat(att), y, image_ids, kmax=kmax, device_random=device_random)
 
 
 def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, variant, *, fold=0, seed=42,
-                           device_metrics=False, **fit):
+                           device_metrics=False, device_random=None, **fit):
     """05's fold loop (`05_train_gnns.py:305-358`) fed directly from resident teacher outputs: no pickle, no upload.
-    ``device_metrics``: the fold's evaluations are scored on the device as well (``train.evaluate_gnn``)."""
+    ``device_metrics``: the fold's evaluations are scored on the device as well (``train.evaluate_gnn``).
+    ``device_random``: random<r> variants are built on the device (``DeviceTeacherOutputs.edge_index``); None leaves it to
+    each outputs object's own setting, which is off unless it was asked for."""
     from isic_hip import train as T
-    recs = [o.graph_records(variant, fold, seed) for o in (outputs_train, outputs_val, outputs_test)]
+    recs = [o.graph_records(variant, fold, seed, device_random=device_random) for o in (outputs_train, outputs_val, outputs_test)]
     return T.train_gnn_fold(gnn_model, recs[0], recs[1], recs[2], device_metrics=device_metrics, **fit)
