@@ -26,7 +26,6 @@ constexpr int TH = 8, TW = 16;             // output tile
 constexpr int PR = 2 * TH + 5, PC = 40;    // patch rows (21) / cols (38 used, 40 allocated)
 constexpr int PROW = PC * 8;               // bytes per patch row (4 bf16 per pixel)
 constexpr int WROW = 7 * 64 + 16;          // bytes per co row of the LDS weight image (padded: conflict-free)
-constexpr int CPAD = 72;                   // epilogue row stride (elements)
 constexpr int YROW = 128 + 32;             // bytes per pixel row of the staged dY tile
 constexpr int STEM_DW_ELEMS = 64 * 7 * 7 * 3;   // the weight gradient, [co][kh][kw][c]
 constexpr int STEM_WGRAD_BLOCKS = 512;
@@ -74,43 +73,123 @@ __device__ __forceinline__ void commit_patch(unsigned char* Ps, const u32x2 (&r)
   }
 }
 
-__global__ __launch_bounds__(256) void conv_stem_fwd_kernel(StemArgs a) {
-  // the C tile takes the patch's place once the tile is multiplied (one more barrier per tile): 48 KB of LDS and 156
-  // registers = THREE blocks per CU instead of two (2.96 -> 2.76 ms at 4096 images: a tile is 6.7 KB in and 16 KB out
-  // between three barriers, the kernel waits on those round trips, not on the matrix cores)
-  static_assert(TH * TW * CPAD * 2 >= PR * PROW, "the C tile overlays the patch");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[64 * WROW + TH * TW * CPAD * 2];
+// Forward: register-only epilogue.  The block's LDS weight image holds the 64 packed rows PERMUTED -- MFMA tile j, row m
+// is output channel 32 (j >> 1) + 8 (m >> 2) + 4 (j & 1) + (m & 3) -- so that after the MFMAs (operand roles swapped,
+// D[co][pixel]) lane (fg, fi) holds, of pixel column fi, channels 8 fg .. 8 fg + 7 in tiles 0, 1 and 32 + 8 fg .. + 7 in
+// tiles 2, 3: the 16 bytes at column group fg of both 64-byte halves of the pixel's 128-byte row, which is what
+// isic_pair_rows (common.h) wants.  No C tile in LDS and no barrier after the MFMAs (two per tile, 36 KB of LDS); the
+// packed [64][7][8][4] weights in memory are unchanged.  What the epilogue's round trip through LDS cost was small
+// (2.32 -> 2.23 ms at 4096 images); the larger part of this kernel's time beside its memory traffic was vector-ALU work
+// per tile, so, as in the fused weight gradient, the tile loop keeps only what forms a value of the result (-> 1.91 ms):
+// scalar tile coordinates advanced by carries, per-thread patch coordinates and offsets computed once, a block-uniform
+// path without validity selects and store guards for tiles whose outputs all exist, two values per v_cvt_pk_bf16_f32,
+// the statistics a template parameter instead of a branch per MFMA tile.
+// Measured and left out: a second patch buffer for one barrier per tile (2.233 vs 2.231 ms), two cached
+// 64-byte stores per lane instead of the half-row swap (2.31 vs 2.23 ms), weight fragments held in registers (does not
+// fit 168 VGPRs without scratch).  The persistent grid stays 768 blocks: a block's fp32 partial sums, and with them the
+// last bits of the statistics, depend on which tiles it owns.
+__device__ __forceinline__ int stem_fwd_lds_row(int co) {
+  return (2 * (co >> 5) + ((co >> 2) & 1)) * 16 + 4 * ((co >> 3) & 3) + (co & 3);
+}
+__device__ __forceinline__ int stem_fwd_channel(int j, int fg, int r) { return 32 * (j >> 1) + 8 * fg + 4 * (j & 1) + r; }
+
+// s[e] += r[e], q[e] += r[e] * r[e] for the four rounded values in (lo, hi), the product rounded by itself: the
+// multiply and the add stay separate instructions, as hipcc has always compiled these sums (it prefers packed adds to
+// fused multiply-adds here), so that the statistics do not depend on that choice
+__device__ __forceinline__ void stem_stat4(float* s, float* q, unsigned lo, unsigned hi) {
+#pragma clang fp contract(off)
+  const float r0 = __uint_as_float(lo << 16), r1 = __uint_as_float(lo & 0xFFFF0000u);
+  const float r2 = __uint_as_float(hi << 16), r3 = __uint_as_float(hi & 0xFFFF0000u);
+  s[0] += r0; q[0] += r0 * r0;
+  s[1] += r1; q[1] += r1 * r1;
+  s[2] += r2; q[2] += r2 * r2;
+  s[3] += r3; q[3] += r3 * r3;
+}
+
+struct StemTile { int n, oy0, ox0; };           // block-uniform tile coordinates, advanced without divisions
+
+// STATS: with the fused BatchNorm sums (a.stat_sum / a.stat_sumsq); three blocks per CU (<= 168 VGPRs)
+template <bool STATS>
+__global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(StemArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[64 * WROW + PR * PROW];
   unsigned char* Ws = smem;
   unsigned char* Ps = smem + 64 * WROW;
-  unsigned short* Cs = reinterpret_cast<unsigned short*>(smem + 64 * WROW);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fi = lane & 15, fg = lane >> 4;
 
-  // weights -> LDS once per block: 64 rows x 448 bytes (28 chunks of 16 B)
+  // weights -> LDS once per block: 64 rows x 448 bytes (28 chunks of 16 B), row co at its permuted place
   for (int idx = tid; idx < 64 * 28; idx += 256) {
     const int co = idx / 28, ch = idx - co * 28;
-    *reinterpret_cast<u32x4*>(Ws + co * WROW + ch * 16) = *reinterpret_cast<const u32x4*>(a.w + co * 224 + ch * 8);
+    *reinterpret_cast<u32x4*>(Ws + stem_fwd_lds_row(co) * WROW + ch * 16) =
+        *reinterpret_cast<const u32x4*>(a.w + co * 224 + ch * 8);
   }
 
+  // ---- tile cursor: tile += gridDim.x as (n, oy0, ox0) += (step_n, step_y, step_x) with carries, in scalar registers
+  const int tiles_img = a.tiles_h * a.tiles_w;
+  const int step_n = (int)gridDim.x / tiles_img, step_r = (int)gridDim.x - step_n * tiles_img;
+  const int step_y = (step_r / a.tiles_w) * TH, step_x = (step_r % a.tiles_w) * TW;
+  const int span_y = a.tiles_h * TH, span_x = a.tiles_w * TW;
+  auto advance = [&](StemTile& t) {
+    t.ox0 += step_x;
+    if (t.ox0 >= span_x) { t.ox0 -= span_x; t.oy0 += TH; }
+    t.oy0 += step_y;
+    if (t.oy0 >= span_y) { t.oy0 -= span_y; t.n += 1; }
+    t.n += step_n;
+  };
+  // ---- this thread's patch pixels (idx = tid + 256 u): patch coordinates and in-image byte offset, the same for every tile
+  int ppr[PATCH_PER_THREAD], ppc[PATCH_PER_THREAD];
+  unsigned poff[PATCH_PER_THREAD];
+#pragma unroll
+  for (int u = 0; u < PATCH_PER_THREAD; ++u) {
+    const int idx = tid + 256 * u;
+    const bool have = idx < PR * PC;
+    ppr[u] = have ? idx / PC : -(1 << 24);                               // padding: never inside the image
+    ppc[u] = idx % PC;
+    poff[u] = have ? (unsigned)((ppr[u] * a.Win + ppc[u]) * 8) : 0u;
+  }
   u32x2 pre[PATCH_PER_THREAD];
-  fetch_patch(pre, a, blockIdx.x, tid);
+  auto fetch = [&](const StemTile& t, bool live) {
+    const int hi0 = 2 * t.oy0 - 3, wi0 = 2 * t.ox0 - 3;
+    const unsigned char* org = reinterpret_cast<const unsigned char*>(a.in) + (((int64_t)t.n * a.Hin + hi0) * a.Win + wi0) * 8;
+#pragma unroll
+    for (int u = 0; u < PATCH_PER_THREAD; ++u) {
+      u32x2 v = {0u, 0u};
+      if (live && (unsigned)(hi0 + ppr[u]) < (unsigned)a.Hin && (unsigned)(wi0 + ppc[u]) < (unsigned)a.Win)
+        v = *reinterpret_cast<const u32x2*>(org + poff[u]);
+      pre[u] = v;
+    }
+  };
+
+  StemTile cur;
+  {
+    const int bid = blockIdx.x, t2 = bid % tiles_img;
+    cur.n = bid / tiles_img; cur.oy0 = (t2 / a.tiles_w) * TH; cur.ox0 = (t2 % a.tiles_w) * TW;
+  }
+  fetch(cur, true);
   // fused BatchNorm statistics of the ROUNDED outputs, in registers over all tiles of the block: lane (fg, fi) owns
-  // channels 16j + 4fg + r of pixel column fi -- 16 sums + 16 sums of squares (fp32; ~800 values each), reduced over the
-  // 16 lanes of a DPP row and the four waves once, at the end (the LDS read-back loop this replaces cost 0.3 ms per step)
+  // channels stem_fwd_channel(j, fg, r) of pixel column fi -- 16 sums + 16 sums of squares (fp32; ~800 values each),
+  // reduced over the 16 lanes of a DPP row and the four waves once, at the end.  A channel's values are added in the
+  // order they always were (tiles of the block, rows i, then columns by the butterfly, then waves): only the lane and
+  // slot that hold a channel depend on the permutation.
   float st_s[4][4], st_q[4][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { st_s[j][r] = 0.f; st_q[j][r] = 0.f; }
+  const unsigned frag_p = (unsigned)(4 * wave * PROW + (2 * fi + 2 * fg) * 8);
+  const unsigned frag_w = (unsigned)(fi * WROW + fg * 16);
+  const unsigned lane_o = (unsigned)(((fi & ~1) * 64 + 8 * fg + ((fi & 1) ? 32 : 0)) * 2);   // bytes from the tile row's first pixel
+
   for (int tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
-    const int n = tile / (a.tiles_h * a.tiles_w);
-    const int t2 = tile - n * (a.tiles_h * a.tiles_w);
-    const int oy0 = (t2 / a.tiles_w) * TH, ox0 = (t2 % a.tiles_w) * TW;
-    lds_barrier();    // previous tile's patch and C tile fully consumed / weights visible (no wait for its stores)
-    commit_patch(Ps, pre, tid);
+    StemTile nxt = cur;
+    advance(nxt);
+    lds_barrier();                                       // previous tile's patch fully consumed / weights visible
+#pragma unroll
+    for (int u = 0; u < PATCH_PER_THREAD; ++u)
+      if (tid + 256 * u < PR * PC) *reinterpret_cast<u32x2*>(Ps + (tid + 256 * u) * 8) = pre[u];       // PROW = 8 PC
     lds_barrier();                                       // (NOT __syncthreads(): that drains vmcnt, i.e. waits for the previous
                                                          //  tile's output stores to complete their round trip to memory)
-    fetch_patch(pre, a, tile + gridDim.x, tid);          // next tile's loads fly under this tile's MFMAs and stores
+    fetch(nxt, tile + (int)gridDim.x < a.total_tiles);   // next tile's loads fly under this tile's MFMAs and stores
 
     f32x4 acc[2][4];
 #pragma unroll
@@ -121,52 +200,51 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(StemArgs a) {
     for (int kh = 0; kh < 7; ++kh) {
       bf16x8 af[2], bfr[4];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int oyl = wave * 2 + i;
-        af[i] = *reinterpret_cast<const bf16x8*>(Ps + (2 * oyl + kh) * PROW + (2 * fi + 2 * fg) * 8);
-      }
+      for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(Ps + frag_p + (2 * i + kh) * PROW);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bfr[j] = *reinterpret_cast<const bf16x8*>(Ws + (j * 16 + fi) * WROW + kh * 64 + fg * 16);
-      // swapped operand roles, D[co][pixel]: lane (fg, fi) ends with output channels 16j + 4fg + {0..3} of pixel fi
+      for (int j = 0; j < 4; ++j) bfr[j] = *reinterpret_cast<const bf16x8*>(Ws + frag_w + j * 16 * WROW + kh * 64);
+      // swapped operand roles, D[co][pixel]: lane (fg, fi) ends with LDS rows 16j + 4fg + {0..3} of pixel fi
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
     }
-    lds_barrier();                                       // every wave is done with the patch: the C tile overwrites it
-    // epilogue through LDS: pixel index p = oyl*16 + oxl, row-major [p][co]; one packed 8-byte store per MFMA tile
+    // epilogue from registers: pixel (oy, ox0 + fi), 16 bytes at column group fg of each 64-byte half; adjacent lanes
+    // (pixels fi, fi ^ 1) swap one half, so that a store instruction writes whole 128-byte pixel rows.  A tile whose
+    // outputs all exist (block-uniform, the usual case) takes the path without validity selects and store guards.
+    const bool full = cur.oy0 + TH <= a.Hout && cur.ox0 + TW <= a.Wout;
+    unsigned char* otile = reinterpret_cast<unsigned char*>(a.out) +
+                           (((int64_t)cur.n * a.Hout + cur.oy0) * a.Wout + cur.ox0) * 128;
+    auto epilogue = [&](auto full_c) {
+      constexpr bool FULL = decltype(full_c)::value;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i) {
+        const int oyl = wave * 2 + i;
+        const bool in = FULL || ((cur.oy0 + oyl < a.Hout) && (cur.ox0 + fi < a.Wout));
+        u32x4 vv[2];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int p = (wave * 2 + i) * 16 + fi;
-        const u32x2 v = isic_pack_bf16x4(acc[i][j]);
-        *reinterpret_cast<u32x2*>(Cs + p * CPAD + j * 16 + fg * 4) = v;
-        if (a.stat_sum) {
-          const bool in = (oy0 + wave * 2 + i < a.Hout) && (ox0 + fi < a.Wout);
-          const float r0 = in ? __uint_as_float(v[0] << 16) : 0.f, r1 = in ? __uint_as_float(v[0] & 0xFFFF0000u) : 0.f;
-          const float r2 = in ? __uint_as_float(v[1] << 16) : 0.f, r3 = in ? __uint_as_float(v[1] & 0xFFFF0000u) : 0.f;
-          st_s[j][0] += r0; st_q[j][0] += r0 * r0;
-          st_s[j][1] += r1; st_q[j][1] += r1 * r1;
-          st_s[j][2] += r2; st_q[j][2] += r2 * r2;
-          st_s[j][3] += r3; st_q[j][3] += r3 * r3;
+        for (int j = 0; j < 4; ++j) {
+          const unsigned w0 = isic_pack_bf16x2(acc[i][j][0], acc[i][j][1]), w1 = isic_pack_bf16x2(acc[i][j][2], acc[i][j][3]);
+          vv[j >> 1][2 * (j & 1)] = w0;
+          vv[j >> 1][2 * (j & 1) + 1] = w1;
+          if (STATS) stem_stat4(st_s[j], st_q[j], in ? w0 : 0u, in ? w1 : 0u);
         }
+        u32x4 da, db;
+        isic_pair_rows(vv[0], vv[1], fi & 1, da, db);
+        unsigned char* o = otile + (int64_t)oyl * a.Wout * 128 + lane_o;
+        const bool row = FULL || cur.oy0 + oyl < a.Hout;
+        if (row && (FULL || cur.ox0 + (fi & ~1) < a.Wout)) __builtin_nontemporal_store(da, reinterpret_cast<u32x4*>(o));
+        if (row && (FULL || cur.ox0 + (fi | 1) < a.Wout)) __builtin_nontemporal_store(db, reinterpret_cast<u32x4*>(o + 128));
       }
-    lds_barrier();
-    for (int idx = tid; idx < TH * TW * 8; idx += 256) {
-      const int p = idx >> 3, ch = idx & 7;
-      const int oy = oy0 + (p >> 4), ox = ox0 + (p & 15);
-      if (oy < a.Hout && ox < a.Wout)
-        __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(Cs + p * CPAD + ch * 8),
-                                    reinterpret_cast<u32x4*>(a.out + (((size_t)n * a.Hout + oy) * a.Wout + ox) * 64 + ch * 8));
-    }
+    };
+    if (full) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
+    cur = nxt;
   }
-  if (a.stat_sum) {
-    // DPP row sums over the 16 pixel columns, then the four waves meet in LDS (the weight image is dead by now)
+  if (STATS) {
+    // DPP row sums over the 16 pixel columns, then the four waves meet in LDS
     __shared__ float stat_red[2][4][64];
-    lds_barrier();
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -174,7 +252,8 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(StemArgs a) {
         float sv = st_s[j][r], qv = st_q[j][r];
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) { sv += __shfl_xor(sv, o, 16); qv += __shfl_xor(qv, o, 16); }
-        if (fi == 0) { stat_red[0][wave][j * 16 + fg * 4 + r] = sv; stat_red[1][wave][j * 16 + fg * 4 + r] = qv; }
+        const int c = stem_fwd_channel(j, fg, r);
+        if (fi == 0) { stat_red[0][wave][c] = sv; stat_red[1][wave][c] = qv; }
       }
     lds_barrier();
     if (tid < 128) {
@@ -331,7 +410,6 @@ constexpr int PDMA = (PPIECES + 63) / 64;
 constexpr int PBUF = PDMA * 1024;
 __device__ __attribute__((aligned(256))) unsigned char g_stem_zero_page[256];
 
-struct StemTile { int n, oy0, ox0; };           // block-uniform tile coordinates, advanced without divisions
 
 // max-pool routing of channels 4*HALF .. +3: windows_to_grad4 (pool_grad.h) without its `live` tests -- the caller has
 // set the codes of a missing window to 0xFF, which selects nothing.  Same contributions, same order (window rows, then
@@ -667,7 +745,8 @@ int isic_conv_stem_fwd_stats_bf16(const uint16_t* in_nhwc4, const uint16_t* w_st
   int rc = stem_args(a, N, Hin, Win, Hout, Wout);
   if (rc != ISIC_OK) return rc;
   const int grid = a.total_tiles < STEM_FWD_BLOCKS ? a.total_tiles : STEM_FWD_BLOCKS;
-  hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
+  if (stat_sum) hipLaunchKernelGGL(conv_stem_fwd_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), a);
+  else hipLaunchKernelGGL(conv_stem_fwd_kernel<false>, dim3(grid), dim3(256), 0, as_stream(stream), a);
   return isic_launch_status();
 }
 

@@ -7,6 +7,7 @@
 // (BatchNorm2d eps 1e-5, momentum 0.1, biased variance for normalisation, unbiased for the running
 // estimate; MaxPool2d(3, 2, 1) with first-maximum tie breaking; AdaptiveAvgPool2d(1)).
 #include "common.h"
+#include "mfma_tile.h"
 #include "pool_grad.h"
 
 namespace {
@@ -529,6 +530,8 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_apply_kernel(
 // cover -- 7.5 instead of 9 loads per output (the kernel is bound by its L2 reads: neighbouring windows overlap) -- all at
 // clamped, always valid addresses so that the fifteen loads are in flight together (1.51 -> 1.44 ms at 2048 images; capping
 // it at 128 VGPRs for a fourth wave per SIMD spills and runs 2.3 ms).
+// AFFINE = true is 1,717 vector instructions per thread and bound by them; the stem (C = 64) takes
+// bn_relu_maxpool_c64_kernel below, and this form serves the shapes that kernel does not.
 template <bool AFFINE>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const unsigned short* __restrict__ x,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
@@ -625,6 +628,165 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const unsigned short* 
       }
     }
   }
+}
+
+// ---------------------------------------------------------------- fused BatchNorm + ReLU + max-pool, C = 64
+// y = maxpool(relu(x * scale + shift)) with the argmax codes and the raw value at the argmax, every input pixel normalised
+// ONCE.  A block owns TPH x TPW pooled outputs x 64 channels and their (2 TPH + 1) x (2 TPW + 1) input patch:
+//   1. the raw patch goes to LDS by LDS-DMA, lane-linear (piece q = pixel * 8 + channel group at byte 16 q);
+//   2. every piece is normalised (fmaf, ReLU), rounded to bf16 once and written to a second LDS image of the same
+//      layout; a pixel outside the image gets the bit pattern 0x8000 per channel, which no value can have after the ReLU
+//      (v_max_f32 returns +0 for max(-0, +0), so the normalised values are >= +0 and their 16 bits, as an integer, order
+//      as the values do);
+//   3. a thread scans the windows of TWO adjacent outputs x 8 channels (3 x 5 pixels, one ds_read_b128 each): per
+//      window and channel ONE signed max over the keys (value bits << 16) | (8 - tap code).  The largest value wins and
+//      among equal values the smallest tap code, i.e. the first maximum in scan order, which is what `f > best` selected;
+//      a key of an out-of-image pixel is negative and never wins (the window's centre tap always exists).  The value is
+//      the key's high half, the code its low bits, and the raw value at the argmax is read back from the raw patch.
+// One tile per block and as many blocks as tiles: no tensor-striding loop.
+template <int TPH, int TPW>
+struct PoolTile {
+  static constexpr int PRH = 2 * TPH + 1, PCW = 2 * TPW + 1;     // patch rows / columns (pixels)
+  static constexpr int NT = TPH * TPW * 4;                       // threads: TPH * TPW / 2 output pairs x 8 channel groups
+  static constexpr int NW = NT / 64;
+  static constexpr int NPIECE = PRH * PCW * 8;                   // 16-byte pieces of the patch
+  static constexpr int NINS = (NPIECE + 63) / 64;                // LDS-DMA wave instructions (the last one padded)
+  static constexpr int RAWB = NINS * 1024;
+  static_assert(NT % 64 == 0 && TPW % 2 == 0, "whole waves, whole output pairs");
+  static_assert((NINS + NW - 1) / NW <= 32, "one validity bit per piece of a thread");
+};
+
+template <int TPH, int TPW>
+__global__ __launch_bounds__(TPH * TPW * 4) void bn_relu_maxpool_c64_kernel(
+    const unsigned short* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
+    unsigned short* __restrict__ y, unsigned char* __restrict__ argmax, unsigned short* __restrict__ xsel, int H, int W,
+    int Ho, int Wo, int tiles_h, int tiles_w) {
+  using T = PoolTile<TPH, TPW>;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[T::RAWB + T::NPIECE * 16];
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  const unsigned char* raw = smem;
+  unsigned char* nrm = smem + T::RAWB;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x;
+  const int tw = tile % tiles_w, t1 = tile / tiles_w, th = t1 % tiles_h, n = t1 / tiles_h;
+  const int ho0 = th * TPH, wo0 = tw * TPW, hi0 = 2 * ho0 - 1, wi0 = 2 * wo0 - 1;
+
+  // 1. raw patch -> LDS.  Thread tid moves the pieces q = tid + NT u and normalises the same ones afterwards, so it
+  // waits for its own wave's DMA only.  Pixel coordinates advance by carries (one division per thread); a piece outside
+  // the image, or past the patch in the last instruction, is fetched from the nearest pixel inside -- always a valid
+  // address -- and never takes part: its normalised image is the sentinel and no argmax code points at it.
+  constexpr int NU = (T::NINS + T::NW - 1) / T::NW;
+  constexpr int STEP = T::NT / 8, STEP_R = STEP / T::PCW, STEP_C = STEP % T::PCW;
+  const int cg = tid & 7;
+  const unsigned char* img = reinterpret_cast<const unsigned char*>(x) + (int64_t)n * H * W * 128;   // block-uniform
+  unsigned okmask = 0;
+  {
+    int pr = (tid >> 3) / T::PCW, pc = (tid >> 3) - pr * T::PCW;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int hi = hi0 + pr, wi = wi0 + pc;
+      if (pr < T::PRH && (unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W) okmask |= 1u << u;
+      if (wave + T::NW * u < T::NINS) {                              // wave-uniform
+        const int hc = min(max(hi, 0), H - 1), wc = min(max(wi, 0), W - 1);
+        isic_glds16_s(img, (unsigned)((hc * W + wc) * 128 + cg * 16),
+                      __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((wave + T::NW * u) * 1024)));
+      }
+      pr += STEP_R; pc += STEP_C;
+      if (pc >= T::PCW) { pc -= T::PCW; pr += 1; }
+    }
+  }
+  float sc[8], sh[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { sc[j] = scale[cg * 8 + j]; sh[j] = shift[cg * 8 + j]; }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // this wave's pieces have landed
+
+  // 2. normalise once (NT is a multiple of 8: a thread's pieces all belong to channel group cg)
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int q = tid + T::NT * u;
+    if (q < T::NPIECE) {
+      const bool ok = (okmask >> u) & 1u;
+      const u32x4 r = *reinterpret_cast<const u32x4*>(raw + q * 16);
+      u32x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float lo = fmaxf(fmaf(__uint_as_float(r[i] << 16), sc[2 * i], sh[2 * i]), 0.f);
+        const float hi = fmaxf(fmaf(__uint_as_float(r[i] & 0xFFFF0000u), sc[2 * i + 1], sh[2 * i + 1]), 0.f);
+        o[i] = ok ? isic_pack_bf16x2(lo, hi) : 0x80008000u;
+      }
+      *reinterpret_cast<u32x4*>(nrm + q * 16) = o;
+    }
+  }
+  lds_barrier();
+
+  // 3. window scan
+  const int tp = tid >> 3, oh = tp / (TPW / 2), pw = tp - oh * (TPW / 2);   // (cg = tid & 7 as above)
+  const int ho = ho0 + oh, wq = wo0 + 2 * pw;
+  const unsigned base = (unsigned)(((2 * oh) * T::PCW + 4 * pw) * 128 + cg * 16);
+  int best[2][8];
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) best[o][j] = (int)0x80000000u;
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int c5 = 0; c5 < 5; ++c5) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(nrm + base + (kh * T::PCW + c5) * 128);
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+        const int kw = c5 - 2 * o;                       // this pixel's column inside window o
+        if (kw < 0 || kw > 2) continue;
+        const unsigned K = 8u - (unsigned)(kh * 3 + kw);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          best[o][2 * i] = max(best[o][2 * i], (int)((v[i] << 16) | K));
+          best[o][2 * i + 1] = max(best[o][2 * i + 1], (int)((v[i] & 0xFFFF0000u) | K));
+        }
+      }
+    }
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {
+    const int wo = wq + o;
+    if (ho >= Ho || wo >= Wo) continue;
+    const int64_t oi = (((int64_t)n * Ho + ho) * Wo + wo) * 8 + cg;
+    u32x4 yv;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) yv[i] = ((unsigned)best[o][2 * i] >> 16) | ((unsigned)best[o][2 * i + 1] & 0xFFFF0000u);
+    __builtin_nontemporal_store(yv, reinterpret_cast<u32x4*>(y + oi * 8));
+    unsigned code[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) code[j] = 8u - ((unsigned)best[o][j] & 0xFu);
+    if (xsel) {
+      unsigned rv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned kh = (code[j] * 11u) >> 5;        // code / 3 for code <= 8
+        rv[j] = *reinterpret_cast<const unsigned short*>(raw + base + o * 256 + kh * ((T::PCW - 3) * 128) + code[j] * 128 + j * 2);
+      }
+      u32x4 xs;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xs[i] = rv[2 * i] | (rv[2 * i + 1] << 16);
+      __builtin_nontemporal_store(xs, reinterpret_cast<u32x4*>(xsel + oi * 8));
+    }
+    if (argmax) {
+      u32x2 p;
+      p[0] = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
+      p[1] = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
+      __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(argmax + oi * 8));
+    }
+  }
+}
+
+template <int TPH, int TPW>
+bool launch_bn_relu_maxpool_c64(const uint16_t* x, const float* scale, const float* shift, uint16_t* y, uint8_t* argmax,
+                                uint16_t* x_sel, int N, int H, int W, int Ho, int Wo, hipStream_t stream) {
+  const int tiles_h = ceil_div(Ho, TPH), tiles_w = ceil_div(Wo, TPW);
+  const int64_t tiles = (int64_t)N * tiles_h * tiles_w;
+  if (tiles > 0x7FFFFFFFLL || (int64_t)H * W > (1 << 24)) return false;     // in-image byte offsets are 32-bit
+  hipLaunchKernelGGL((bn_relu_maxpool_c64_kernel<TPH, TPW>), dim3((unsigned)tiles), dim3(PoolTile<TPH, TPW>::NT), 0, stream, x,
+                     scale, shift, y, argmax, x_sel, H, W, Ho, Wo, tiles_h, tiles_w);
+  return true;
 }
 
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const unsigned char* __restrict__ argmax,
@@ -953,6 +1115,11 @@ int isic_bn_relu_maxpool3x3s2_fwd_sel_bf16(const uint16_t* x, const float* scale
                                            void* stream) {
   ISIC_CHECK_ARG(x && scale && shift && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0);
   ISIC_CHECK_ARG(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1);
+  // C = 64 (the stem): the tiled kernel that normalises each pixel once.  Other widths, an input that is not 16-byte
+  // aligned (LDS-DMA) or larger than 2^24 pixels keep the per-thread kernel.
+  if (C == 64 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+      launch_bn_relu_maxpool_c64<8, 8>(x, scale, shift, y, argmax, x_sel, N, H, W, Ho, Wo, as_stream(stream)))
+    return isic_launch_status();
   const int64_t nvec = (int64_t)N * Ho * ((Wo + 1) / 2) * (C / 8);           // a thread makes two adjacent outputs
   hipLaunchKernelGGL(maxpool_fwd_kernel<true>, dim3(grid_for(nvec, 256, STREAM_CAP)), dim3(256), 0, as_stream(stream), x, scale,
                      shift, y, argmax, x_sel, N, H, W, C, Ho, Wo);
