@@ -672,5 +672,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_metrics.h"
 /* The random patch graphs (03_build_graphs.py:57-78) of a batch of images and a list of r values, bit for bit the host build: one more entry point, same conventions. */
 #include "isic_hip_randgraph.h"
+/* Per-image statistics of a token grid over its token axis (mean, max, std, median, skewness, kurtosis: the reference's concat_patch_moments) in one launch: one more entry point, same conventions. */
+#include "isic_hip_moments.h"
 
 #endif /* ISIC_HIP_H */

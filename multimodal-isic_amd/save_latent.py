@@ -27,6 +27,11 @@ What changes:
     ``patch_latent_pca`` is filled from the transformed batches in the frames' row order.  Without the key ``pca: true``
     is the reference's sklearn call, unchanged.
 
+  * ``device_moments: true`` (opt-in) takes ``latent_pooled_max`` and ``latent_pooled_mean`` (`:62-63`) from one
+    ``isic_token_moments_f32`` launch per batch (``isic_hip.moments.token_moments``: slices 1 and 0 of its output) instead
+    of two torch reductions.  The max is the same element; the mean may differ from torch's in the last bits (another
+    summation order), hence opt-in.
+
 ``extract_latents(config, path, remove_background=False, datasets=None)`` keeps the reference's signature and return
 tuple; ``datasets=(train_val_dataset, test_dataset)`` lets a caller hand in any dataset with the ``DermDataset`` dict
 contract (`dataset.py:45-56`) -- the synthetic one below when there are no image files.
@@ -123,19 +128,26 @@ def _device_resized(loader, device):
                "segmentation_path": [it["segmentation_path"] for it in items]}
 
 
-def _extract_from_loader(encoder, loader, device, resident=None):
-    """``resident``: a list that receives (latent [B, T, D], flags [B, T] bool) of every batch, left on the device"""
+def _extract_from_loader(encoder, loader, device, resident=None, device_moments=False):
+    """``resident``: a list that receives (latent [B, T, D], flags [B, T] bool) of every batch, left on the device;
+    ``device_moments``: the pooled max and mean come from one ``token_moments`` launch"""
     pooled_list, raw_list = [], []
     for batch in loader:
         images = batch["image"].to(device)
         latent = encoder.run_tokens(images)                                 # [B, 196, 256] fp32, frozen / eval
-        B, T, _ = latent.shape
+        B, T, D = latent.shape
+        if device_moments:
+            from isic_hip.moments import token_moments
+            stats = token_moments(latent)                                   # [B, 6 D]: mean, max, ...
+            pooled_mean, pooled_max = stats[:, :D], stats[:, D:2 * D]
+        else:
+            pooled_max, pooled_mean = latent.max(dim=1).values, latent.mean(dim=1)
         ids = np.tile(np.arange(T, dtype=np.int64), (B, 1))
         target = batch["target"].numpy()
         pooled_list.append(pd.DataFrame({
             "image_path": batch["image_path"], "segmentation_path": batch["segmentation_path"], "target": target,
-            "latent_pooled_max": list(latent.max(dim=1).values.cpu().numpy()),          # :62
-            "latent_pooled_mean": list(latent.mean(dim=1).cpu().numpy()),               # :63
+            "latent_pooled_max": list(pooled_max.cpu().numpy()),                        # :62
+            "latent_pooled_mean": list(pooled_mean.cpu().numpy()),                      # :63
             "ids_restore": list(ids), "ids_keep": list(ids)}))
         flags = mask_patch_flags(batch["mask"].to(device))
         if resident is not None:
@@ -231,8 +243,9 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
     enc.eval()
     device_pca = bool(config.get("pca", False)) and bool(config.get("device_pca", False))
     resident_train, resident_test = ([], []) if device_pca else (None, None)
-    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device, resident_train)
-    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device, resident_test)
+    device_moments = bool(config.get("device_moments", False))
+    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device, resident_train, device_moments)
+    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device, resident_test, device_moments)
     patch_level_train_df, train_count = build_patch_level_df(latent_raw_train, remove=remove_background)
     patch_level_test_df, test_count = build_patch_level_df(latent_raw_test, remove=remove_background)
     print(f"Total lesion-overlapping patches (train_val): {train_count}")

@@ -11,7 +11,14 @@ loads through ``model_path``.
 Config keys (``training_plan.parameters``; the committed config.yml has none of them, so these defaults apply):
 ``masking_ratio`` 0.75, ``eval_masking_ratio`` 0.75, ``norm_pix_loss`` False, ``batch_size`` 64, ``epochs`` 100,
 ``fold`` 0, ``include_lesion_mask`` False (True raises: ``ConvMAEBase`` does not define ``lesion_mask``),
-``device_augment`` False.  ``--synthetic`` trains on ``save_latent.SyntheticDermImages`` (no dataset needed).
+``device_augment`` False, ``latent_moments`` False.  ``--synthetic`` trains on ``save_latent.SyntheticDermImages`` (no
+dataset needed).
+
+``latent_moments: true`` (``--latent-moments``) is the reference's latent-space probe (``train_ae.py:186-194``) without its
+plot: in every epoch with ``epoch % 10 == 0 or epoch == epochs - 1`` each validation batch also runs
+``forward_encoder(images, 0.0)`` and ``utils.concat_patch_moments`` (one HIP launch, ``isic_token_moments_f32``), and the
+validation set's descriptors are written to ``<out_dir>/latent_moments/epoch_<eeee>.npz`` as ``feats`` (fp32
+``[N_val, 6 * 768]``) and ``target`` (int64).
 
 Augmentation.  The reference trains under ``RandomResizedCrop(224, scale=(0.5, 1.0), ratio=(0.75, 1.33))``, horizontal and
 vertical flips and ``RandomRotate90`` (each with probability 0.5), then ``Normalize`` (``train_ae.py:88-100``), and
@@ -25,8 +32,8 @@ launch with identity parameters.  The crop boxes follow RandomResizedCrop's algo
 stream cannot be reproduced, and its fixed-point uint8 resize is not pinned (include/isic_hip_augment.h).  With
 ``--synthetic`` it trains on ``isic_hip.augment.SyntheticDermPixels``.
 
-Not ported: Neptune logging, the latent-space and reconstruction plots, the ISIC2019 CSV merge and
-``concat_patch_moments``; the colour augmentations the reference has commented out.
+Not ported: Neptune logging, the latent-space and reconstruction plots (PCA + UMAP of the descriptors included), the
+ISIC2019 CSV merge; the colour augmentations the reference has commented out.
 """
 from __future__ import annotations
 
@@ -46,10 +53,11 @@ if HERE not in sys.path:
 
 from isic_hip import optim  # noqa: E402
 from isic_hip.convmae_mae import convmae_convvit_base_patch16_dec512d8b  # noqa: E402
+from utils import concat_patch_moments  # noqa: E402
 
 SPLITS = 10
 DEFAULTS = dict(masking_ratio=0.75, eval_masking_ratio=0.75, norm_pix_loss=False, batch_size=64, epochs=100, fold=0,
-                include_lesion_mask=False, device_augment=False)
+                include_lesion_mask=False, device_augment=False, latent_moments=False)
 
 
 def plan(config):
@@ -93,6 +101,15 @@ def device_batches(pool, ids, batch_size, generator=None):
         yield ag.augment(pool, chunk, box, op, want_mask=False)[0]
 
 
+def _label_ids(labels):
+    """the labels as int64 class indices: integers as they are, anything else (the dx strings of the dataframe) by its
+    rank among the sorted distinct values"""
+    arr = np.asarray(labels)
+    if np.issubdtype(arr.dtype, np.integer):
+        return arr.astype(np.int64)
+    return np.unique(arr, return_inverse=True)[1].astype(np.int64)
+
+
 def train(config, dataset, labels, out_dir, checkpoint=None, log=print, device_augment=False):
     """-> (path of the saved best state, [(train_loss, val_loss) per epoch]).  With ``device_augment`` (or the config key
     of that name) ``dataset`` yields uint8 arrays (``isic_hip.augment.uint8_transform`` / ``SyntheticDermPixels``)."""
@@ -112,14 +129,15 @@ def train(config, dataset, labels, out_dir, checkpoint=None, log=print, device_a
         params = torch.Generator().manual_seed(seed)
         n_train, n_val = len(tr), len(va)
         train_batches = lambda: device_batches(pool, [int(tr[i]) for i in sampler], int(p["batch_size"]), params)
-        val_batches = lambda: device_batches(pool, va.tolist(), 64)
+        val_targets = torch.from_numpy(_label_ids(labels)[va])                 # the pool's batches carry no labels
+        val_batches = lambda: zip(device_batches(pool, va.tolist(), 64), val_targets.split(64))
     else:
         train_loader = DataLoader(Subset(dataset, tr.tolist()), batch_size=int(p["batch_size"]),
                                   sampler=balanced_sampler(np.asarray(labels)[tr]))
         val_loader = DataLoader(Subset(dataset, va.tolist()), batch_size=64, shuffle=False)
         n_train, n_val = len(train_loader.dataset), len(val_loader.dataset)
         train_batches = lambda: (batch["image"].to(device) for batch in train_loader)
-        val_batches = lambda: (batch["image"].to(device) for batch in val_loader)
+        val_batches = lambda: ((batch["image"].to(device), batch["target"]) for batch in val_loader)
     model = convmae_convvit_base_patch16_dec512d8b(norm_pix_loss=bool(p["norm_pix_loss"])).to(device)
     if checkpoint:
         sd = torch.load(checkpoint, map_location=device, weights_only=False)
@@ -140,11 +158,22 @@ def train(config, dataset, labels, out_dir, checkpoint=None, log=print, device_a
         train_loss = run / n_train
         model.eval()
         run = 0.0
+        probe = bool(p["latent_moments"]) and (epoch % 10 == 0 or epoch == int(p["epochs"]) - 1)
+        feats, targets = [], []
         with torch.no_grad():
-            for images in val_batches():
+            for images, target in val_batches():
                 loss, _, _ = model(images, mask_ratio=float(p["eval_masking_ratio"]))
                 run += float(loss) * images.shape[0]
+                if probe:                                                     # train_ae.py:186-191
+                    latent, _, _ = model.forward_encoder(images, 0.0)
+                    feats.append(concat_patch_moments(latent).cpu())
+                    targets.append(torch.as_tensor(target).reshape(-1).long().cpu())
         val_loss = run / n_val
+        if probe:
+            moments_dir = os.path.join(out_dir, "latent_moments")
+            os.makedirs(moments_dir, exist_ok=True)
+            np.savez(os.path.join(moments_dir, f"epoch_{epoch:04d}.npz"), feats=torch.cat(feats).numpy(),
+                     target=torch.cat(targets).numpy())
         history.append((train_loss, val_loss))
         log(f"Epoch [{epoch + 1}/{p['epochs']}], Train Loss: {train_loss:.4f}, Val Loss: {val_loss:.4f}")
         if val_loss < best:
@@ -164,6 +193,8 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="train on save_latent.SyntheticDermImages")
     ap.add_argument("--device-augment", action="store_true",
                     help="the reference's training augmentation, on the device from a resident uint8 pool")
+    ap.add_argument("--latent-moments", action="store_true",
+                    help="every tenth epoch write the validation set's concat_patch_moments descriptors to <out-dir>/latent_moments")
     ap.add_argument("--n-images", type=int, default=256, help="synthetic images")
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
@@ -180,6 +211,8 @@ def main(argv=None):
         params["batch_size"] = a.batch_size
     if a.device_augment:
         params["device_augment"] = True
+    if a.latent_moments:
+        params["latent_moments"] = True
     device_augment = bool(params.get("device_augment", False))
     if a.synthetic:
         from isic_hip.augment import SyntheticDermPixels

@@ -1,9 +1,17 @@
-"""Drop-in for the one helper of the reference's ``utils.py`` that the MIL / GNN path
-uses: ``get_args_parser`` (reference `utils.py:151-158`).  The UMAP / reconstruction
-visualisers of that file are reporting code outside the path."""
+"""Drop-in for the helpers of the reference's ``utils.py`` that compute or parse: ``get_args_parser`` (reference
+`utils.py:151-158`), which the MIL / GNN path uses, and ``concat_patch_moments`` (`utils.py:16-31`), the per-image
+descriptor of the MAE path's latent space, here one HIP launch (``isic_hip.moments.token_moments``).  The UMAP /
+reconstruction visualisers of that file are reporting code outside the path."""
 import argparse
 import os
 import typing
+
+
+def concat_patch_moments(latent, eps=1e-6, unbiased=False):
+    """latent [B, T, D] fp32 on the device -> [B, 6 D]: mean, max, std, median, skewness, excess kurtosis over the
+    tokens, the reference's concatenation order.  No backward; no CPU fallback."""
+    from isic_hip.moments import token_moments
+    return token_moments(latent, eps=eps, unbiased=unbiased)
 
 
 def get_args_parser(path: typing.Union[str, bytes, os.PathLike]):
