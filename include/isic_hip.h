@@ -674,5 +674,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_randgraph.h"
 /* Per-image statistics of a token grid over its token axis (mean, max, std, median, skewness, kurtosis: the reference's concat_patch_moments) in one launch: one more entry point, same conventions. */
 #include "isic_hip_moments.h"
+/* GraphMIL beyond 1024 feature columns and four pooling heads (attention pool forward / backward, LayerNorm backward up to 4096 columns): four more entry points, same conventions. */
+#include "isic_hip_wide.h"
 
 #endif /* ISIC_HIP_H */

@@ -366,6 +366,13 @@ __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict_
 
 }  // namespace
 
+// (declared in slab_sum.inc) the block-order sum of [nblocks][2][N] dgamma / dbeta partial rows for the LayerNorm backward
+// kernels of other translation units (wide_rows.hip): the same kernel, so the same order
+void isic_ln_bwd_reduce_launch(const float* partial, int nblocks, int N, float* dgamma, float* dbeta, hipStream_t stream) {
+  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(ceil_div(2 * N, 16)), dim3(256), 0, stream, partial, nblocks, N, dgamma, dbeta,
+                     (float*)nullptr);
+}
+
 extern "C" {
 
 int isic_layernorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,

@@ -113,3 +113,6 @@ void isic_slab_reduce_launch(IsicSlabForm form, const float* partial, int slabs,
 // the pointers allow 16-byte accesses, ISIC_SLAB_XOR16 otherwise
 void isic_gemm_split_reduce_launch(const float* partial, int splits, float* C, int M, int N, int ldc, float beta,
                                    hipStream_t stream);
+// ---- rowwise.hip: dgamma[n] += sum over the blocks of partial[nblocks][2][N] (row 0; row 1: dbeta) (ln_bwd_reduce_kernel:
+// order A, G = 16), for every LayerNorm backward kernel that parks [2][N] partial rows
+void isic_ln_bwd_reduce_launch(const float* partial, int nblocks, int N, float* dgamma, float* dbeta, hipStream_t stream);

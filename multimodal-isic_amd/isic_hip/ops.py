@@ -396,8 +396,12 @@ class AttnPoolFn(torch.autograd.Function):
             BP = torch.empty((B, C), device=dev, dtype=torch.float32)
         else:
             C, W4c, b4c, P, PP, BL, BP = 0, None, None, None, None, None, None
-        call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP,
-             BL, BP)
+        if not teacher and H > 1024:
+            # GraphMIL beyond 1024 columns (gnn_concat=True: hidden x heads up to 4096): one weighted column sum over h
+            call("isic_attn_pool_wide_fwd", h, t, w3c, b3c, offsets, B, H, A, heads, int(max_bag), att, z)
+        else:
+            call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP,
+                 BL, BP)
         ctx.dims = (B, H, A, heads, C, int(max_bag))
         ctx.teacher = teacher
         ctx.params = (W2, b2, w3, b3, W4, b4)          # the callers' tensors: Parameters take their gradients in place
@@ -428,7 +432,8 @@ class AttnPoolFn(torch.autograd.Function):
         tW2, tb2, tw3, tb3 = _acc_target(pW2), _acc_target(pb2), _acc_target(pw3), _acc_target(pb3)
         small_fused = tb2 is not None and tw3 is not None and tb3 is not None
         db2 = dw3 = db3 = None
-        if H <= 128 and A <= 128:
+        wide = not ctx.teacher and (H > 1024 or heads > 4)    # what isic_attn_pool_bwd refuses: att_heads = 8, hidden x heads > 1024
+        if H <= 128 and A <= 128 and not wide:
             # db2 = sum_n d_u, dw3[k, j] = sum_n d_s[n,k] t[n, kA+j], db3 = sum_n d_s: per-bag sums out of the pool kernel
             # (d_u and t are in its registers), then ONE column sum over the bags
             nA = heads * A
@@ -443,8 +448,13 @@ class AttnPoolFn(torch.autograd.Function):
                 sums = colsum(psum)
                 db2, dw3, db3 = sums[:nA], sums[nA:2 * nA].view(heads, A), sums[2 * nA:]
         else:
-            call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0, d_u,
-                 d_s, d_P)
+            if wide:
+                if dz is None:
+                    dz = torch.zeros((B, H), device=dev, dtype=torch.float32)
+                call("isic_attn_pool_wide_bwd", h, t, att, w3c, offsets, B, H, A, heads, max_bag, dz, d_h, 0, d_u, d_s)
+            else:
+                call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
+                     d_u, d_s, d_P)
             # dw3[k, j] = sum_n d_s[n,k] * t[n, k*A + j]
             if small_fused and heads == 1:
                 colsum(d_u, out=tb2.view(-1), beta=1.0)
@@ -516,8 +526,9 @@ class LayerNormFn(torch.autograd.Function):
         fused = tg is not None and tb is not None      # the kernel ACCUMULATES (+=) into dgamma / dbeta
         dg = tg if fused else torch.zeros((N,), device=x2.device, dtype=torch.float32)
         db = tb if fused else torch.zeros((N,), device=x2.device, dtype=torch.float32)
-        ws = _workspace(call("isic_layernorm_bwd_workspace_bytes", N), x2.device)
-        call("isic_layernorm_bwd_ws", dy2, x2, g, b, mean, rstd, dx, dg, db, M, N, relu, drop.threshold, drop.scale,
+        wide = "_wide" if N > 1024 else ""             # beyond 1024 columns: a block per row instead of a wave per row
+        ws = _workspace(call("isic_layernorm_bwd%s_workspace_bytes" % wide, N), x2.device)
+        call("isic_layernorm_bwd%s_ws" % wide, dy2, x2, g, b, mean, rstd, dx, dg, db, M, N, relu, drop.threshold, drop.scale,
              drop.seed, drop.stream, drop.clock, ws, ws.numel() if ws is not None else 0)
         return dx.reshape(ctx.xshape), (None if fused else dg), (None if fused else db), (dy if ctx.has_res else None), None, None, None
 
