@@ -676,5 +676,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_moments.h"
 /* GraphMIL beyond 1024 feature columns and four pooling heads (attention pool forward / backward, LayerNorm backward up to 4096 columns): four more entry points, same conventions. */
 #include "isic_hip_wide.h"
+/* The gate of gated attention pooling (tanh branch x sigmoid branch in front of the pool kernels, forward and backward with its column sums): three more entry points, same conventions. */
+#include "isic_hip_gated.h"
 
 #endif /* ISIC_HIP_H */

@@ -142,7 +142,8 @@ def main():
         for seeder in (torch.manual_seed, np.random.seed, random.seed, torch.cuda.manual_seed_all):   # 01:203-207
             seeder(SEED + fold)
         model = AttentionMIL_teacher(input_dim=f_tr[0].shape[1], hidden_dim=bp["hidden_dim"], att_dim=bp["att_dim"],
-                                     dropout=bp["dropout"], num_classes=len(set(y_tr))).to(device)
+                                     dropout=bp["dropout"], num_classes=len(set(y_tr)),
+                                     gated=bool(bp.get("gated", False))).to(device)   # gated attention: opt-in key
         model.set_dropout_state(SEED + fold, 0)
         patience = config.get("training_plan", {}).get("parameters", {}).get("patience", 8)
         res = T.train_teacher_fold(model, f_tr, y_tr, f_va, y_va, optimizer=bp["optimizer"], lr=float(bp["learning_rate"]),

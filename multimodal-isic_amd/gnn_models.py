@@ -148,7 +148,8 @@ class _GINConvParams(nn.Module):
 class GraphMIL(nn.Module):
     def __init__(self, input_dim=768, gnn_type='gat', gnn_hidden=256, gnn_layers=2, gnn_dropout=0.1, gnn_heads=4,
                  gnn_concat=True, gcnii_alpha=0.1, gcnii_theta=0.5, att_dim=128, att_heads=4, pool_dropout=0.2,
-                 classifier_dim=128, classifier_light=False, num_classes=7, use_residual=True, use_layer_norm=True):
+                 classifier_dim=128, classifier_light=False, num_classes=7, use_residual=True, use_layer_norm=True,
+                 att_gated=False):
         super().__init__()
         self.gnn_type = gnn_type.lower()
         if self.gnn_type not in GNN_TYPES:
@@ -207,6 +208,12 @@ class GraphMIL(nn.Module):
                 nn.Linear(in_dim, classifier_dim), nn.LayerNorm(classifier_dim), nn.ReLU(), nn.Dropout(pool_dropout),
                 nn.Linear(classifier_dim, h2), nn.LayerNorm(h2), nn.ReLU(), nn.Dropout(pool_dropout / 2),
                 nn.Linear(h2, num_classes))
+        # the gate of Ilse et al. (2018) per pooling head, opt-in (the reference has none); registered last, so that the
+        # state_dict of a gated model is the ungated one plus attention_gates.* at the end
+        self.att_gated = bool(att_gated)
+        if self.att_gated:
+            self.attention_gates = nn.ModuleList([
+                nn.Sequential(nn.Linear(in_dim, att_dim), nn.Sigmoid()) for _ in range(att_heads)])
         self.dropout_clock = _DropoutClock()
         self.last_node_embeddings = None
 
@@ -315,8 +322,12 @@ class GraphMIL(nn.Module):
                 if res is not None:
                     h = h + res
         self.last_node_embeddings = h.detach()
-        W2, b2, w3, b3 = ops.head_params(self.attention_layers)      # the heads' parameters as one [heads*A, H] operand
-        z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads)
+        if self.att_gated:                                           # ... and the gates' as the second half of [2*heads*A, H]
+            W2, b2, w3, b3, Wg, bg = ops.gated_head_params(self.attention_layers, self.attention_gates)
+            z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads, Wg=Wg, bg=bg)
+        else:
+            W2, b2, w3, b3 = ops.head_params(self.attention_layers)  # the heads' parameters as one [heads*A, H] operand
+            z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads)
         c = self.classifier
         if (labels is not None and self.classifier_light and tr and not single
                 and ops.graph_head_supported(z.shape[1], c[0].weight.shape[0], c[3].weight.shape[0])):

@@ -364,6 +364,56 @@ def head_params(attention_layers):
     return HeadParamsFn.apply(*ps)
 
 
+class GatedHeadParamsFn(torch.autograd.Function):
+    """``HeadParamsFn`` with a gate per head: (W_0, b_0, w_0, c_0, U_0, d_0, W_1, ...) -> W2, b2, w3, b3, Wg, bg, where
+    Wg [heads*A, H] follows W2 and bg follows b2 in one buffer, so that ``attn_pool`` reads [W2 ; Wg] as the operand of its
+    one GEMM without another copy.  One gather launch forward, the scatter of ``HeadParamsFn`` backward."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        _chk(*params)
+        heads = len(params) // 6
+        A, H = params[0].shape
+        nW, nb = heads * A * H, heads * A
+        flat = torch.empty(2 * nW + 3 * nb + heads, device=params[0].device, dtype=torch.float32)
+        W2, Wg = flat[:nW].view(nb, H), flat[nW:2 * nW].view(nb, H)
+        b2, bg = flat[2 * nW:2 * nW + nb], flat[2 * nW + nb:2 * nW + 2 * nb]
+        w3, b3 = flat[2 * nW + 2 * nb:2 * nW + 3 * nb].view(heads, A), flat[2 * nW + 3 * nb:]
+        dst = []
+        for k in range(heads):
+            s = slice(k * A, (k + 1) * A)
+            dst += [W2[s], b2[s], w3[k], b3[k:k + 1], Wg[s], bg[s]]
+        multi_copy(dst, [_f32c(p.detach()) for p in params])
+        ctx.params, ctx.dims = params, (heads, A, H)
+        return W2, b2, w3, b3, Wg, bg
+
+    @staticmethod
+    def backward(ctx, gW2, gb2, gw3, gb3, gWg, gbg):
+        heads, A, H = ctx.dims
+        gs = []
+        for k in range(heads):
+            s = slice(k * A, (k + 1) * A)
+            gs += [None if gW2 is None else gW2[s], None if gb2 is None else gb2[s],
+                   None if gw3 is None else gw3.reshape(heads, A)[k], None if gb3 is None else gb3.reshape(heads)[k:k + 1],
+                   None if gWg is None else gWg[s], None if gbg is None else gbg[s]]
+        tg = [_acc_target(p) for p in ctx.params]
+        if all(t is not None for t in tg) and all(g is not None and g.is_contiguous() for g in gs):
+            multi_copy(tg, gs, accumulate=True)
+            return (None,) * len(ctx.params)
+        return tuple(None if g is None else g.reshape(p.shape) for g, p in zip(gs, ctx.params))
+
+
+def gated_head_params(attention_layers, attention_gates):
+    """Fused attn_pool operands of the heads Sequential(Linear, Tanh, Linear) and their gates Sequential(Linear, Sigmoid):
+    W2, b2, w3, b3, Wg, bg."""
+    if len(attention_layers) != len(attention_gates):
+        raise ValueError("gated_head_params: one gate per attention head")
+    ps = []
+    for a, g in zip(attention_layers, attention_gates):
+        ps += [a[0].weight, a[0].bias, a[2].weight, a[2].bias, g[0].weight, g[0].bias]
+    return GatedHeadParamsFn.apply(*ps)
+
+
 # --------------------------------------------------------------------------- attention pool
 class AttnPoolFn(torch.autograd.Function):
     """Attention scores + segmented softmax + pooling over ragged bags.
@@ -490,7 +540,147 @@ class AttnPoolFn(torch.autograd.Function):
         return d_h, dW2, db2, dw3, db3, dW4, db4, None, None, None
 
 
-def attn_pool(h, W2, b2, w3, b3, offsets, max_bag, heads=1, W4=None, b4=None):
+def _follows(first, second):
+    """``second`` starts where the dense ``first`` ends, in the same storage (the two halves of a stacked operand)."""
+    return (first.is_contiguous() and second.is_contiguous() and first.dtype == second.dtype == torch.float32
+            and first.untyped_storage().data_ptr() == second.untyped_storage().data_ptr()
+            and second.storage_offset() == first.storage_offset() + first.numel())
+
+
+class GatedAttnPoolFn(torch.autograd.Function):
+    """``AttnPoolFn`` with the gate of Ilse et al. (2018): t = tanh(h W2^T + b2) * sigmoid(h Wg^T + bg); everything after t
+    (scores, softmax per bag, pooling, the teacher's class space, the wide forms) is the ungated path's pool kernels.
+
+    Forward: ONE GEMM over the stacked operand [W2 ; Wg] -> p [T, 2 heads A] (``gated_head_params`` hands the two halves
+    over as neighbouring views and nothing is copied; two separate Parameters are stacked by one ``multi_copy`` launch),
+    ``isic_gate_fwd_f32`` (p -> tv | sg in place, t), the pool forward on t.  Backward: the pool backward for d_h, d_s, d_P
+    (its d_u carries (1 - t^2), wrong under a gate, and is not used), ``isic_gate_bwd_f32`` (d_p = d_v | d_g and the four
+    small parameter gradients in one pass), then the GEMMs d_[W2 ; Wg] = d_p^T h and d_h += d_p [W2 ; Wg]."""
+
+    @staticmethod
+    def forward(ctx, h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets, max_bag, heads):
+        _chk(h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets)
+        ctx.set_materialize_grads(False)
+        h = _f32c(h)
+        T, H = h.shape
+        nA = W2.shape[0]
+        A = nA // heads
+        if Wg.shape != W2.shape or bg.numel() != nA or b2.numel() != nA:
+            raise ValueError(f"attn_pool: the gate operands must have the shapes of W2 {tuple(W2.shape)} and b2")
+        B = offsets.numel() - 1
+        dev = h.device
+        ctx.stacked = _follows(W2, Wg) and _follows(b2, bg)
+        if ctx.stacked:
+            Wcat, bcat = W2.as_strided((2 * nA, H), (H, 1)), b2.reshape(-1).as_strided((2 * nA,), (1,))
+        else:
+            Wcat = torch.empty((2 * nA, H), device=dev, dtype=torch.float32)
+            bcat = torch.empty((2 * nA,), device=dev, dtype=torch.float32)
+            multi_copy([Wcat[:nA], Wcat[nA:], bcat[:nA], bcat[nA:]],
+                       [_f32c(W2.detach()), _f32c(Wg.detach()), _f32c(b2.detach()).reshape(-1), _f32c(bg.detach()).reshape(-1)])
+        a = gemm(h, Wcat, trans_b=True, bias=bcat)                  # pre-activations; isic_gate_fwd_f32 turns them into tv | sg
+        t = torch.empty((T, nA), device=dev, dtype=torch.float32)
+        call("isic_gate_fwd_f32", a, T, heads, A, t)
+        w3c, b3c = _f32c(w3).reshape(heads, A), _f32c(b3).reshape(heads)
+        att = torch.empty((T, heads), device=dev, dtype=torch.float32)
+        z = torch.empty((B, H), device=dev, dtype=torch.float32)
+        teacher = W4 is not None
+        if teacher:
+            C = W4.shape[0]
+            W4c, b4c = _f32c(W4), _f32c(b4)
+            P = torch.empty((T, C), device=dev, dtype=torch.float32)
+            PP = torch.empty((T, C), device=dev, dtype=torch.float32)
+            BL = torch.empty((B, C), device=dev, dtype=torch.float32)
+            BP = torch.empty((B, C), device=dev, dtype=torch.float32)
+        else:
+            C, W4c, b4c, P, PP, BL, BP = 0, None, None, None, None, None, None
+        if not teacher and H > 1024:
+            call("isic_attn_pool_wide_fwd", h, t, w3c, b3c, offsets, B, H, A, heads, int(max_bag), att, z)
+        else:
+            call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP,
+                 BL, BP)
+        ctx.dims = (B, H, A, heads, C, int(max_bag))
+        ctx.teacher = teacher
+        ctx.params = (W2, b2, w3, b3, Wg, bg, W4, b4)
+        ctx.save_for_backward(h, a, t, att, P, Wcat, w3c, W4c, offsets)
+        if teacher:
+            ctx.mark_non_differentiable(att, P, PP, BP)
+            return z, att, P, PP, BL, BP
+        ctx.mark_non_differentiable(att)
+        return z, att
+
+    @staticmethod
+    def backward(ctx, dz, *rest):
+        h, a, t, att, P, Wcat, w3c, W4c, offsets = ctx.saved_tensors
+        B, H, A, heads, C, max_bag = ctx.dims
+        dBL = rest[3] if ctx.teacher else None
+        T, nA = h.shape[0], heads * A
+        dev = h.device
+        dz = _f32c(dz) if dz is not None else None
+        dBL = _f32c(dBL) if dBL is not None else None
+        d_h = torch.empty((T, H), device=dev, dtype=torch.float32)
+        d_s = torch.empty((T, heads), device=dev, dtype=torch.float32)
+        d_P = torch.empty((T, C), device=dev, dtype=torch.float32) if ctx.teacher else None
+        d_p = torch.empty((T, 2 * nA), device=dev, dtype=torch.float32)
+        if not ctx.teacher and (H > 1024 or heads > 4):
+            if dz is None:
+                dz = torch.zeros((B, H), device=dev, dtype=torch.float32)
+            # isic_attn_pool_wide_bwd refuses a NULL d_u (ISIC_ERR_BAD_ARG): d_p serves as the scratch buffer for its ungated
+            # d_u ([T, heads A], the first half of d_p's memory), and isic_gate_bwd_f32 overwrites all of d_p next
+            call("isic_attn_pool_wide_bwd", h, t, att, w3c, offsets, B, H, A, heads, max_bag, dz, d_h, 0, d_p, d_s)
+        else:
+            call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
+                 None, d_s, d_P)                                    # d_u = NULL: the kernel skips that store
+        # d_p = d_v | d_g and, in the same pass, sums = d_b2 | d_bg | d_w3 | d_b3 (fixed-order slabs, no atomics)
+        sums = (torch.empty if T > 0 else torch.zeros)((3 * nA + heads,), device=dev, dtype=torch.float32)
+        ws = _workspace(call("isic_gate_bwd_f32_workspace_bytes", T, heads, A), dev)
+        call("isic_gate_bwd_f32", d_s, w3c, a, T, heads, A, d_p, sums[:2 * nA], sums[2 * nA:3 * nA], sums[3 * nA:], 0.0,
+             ws, ws.numel() if ws is not None else 0)
+        pW2, pb2, pw3, pb3, pWg, pbg, pW4, pb4 = ctx.params
+        small = [sums[:nA], sums[2 * nA:3 * nA], sums[3 * nA:], sums[nA:2 * nA]]          # d_b2, d_w3, d_b3, d_bg
+        targets = [_acc_target(p) for p in (pb2, pw3, pb3, pbg)]
+        if all(g is not None for g in targets):
+            # the four live in different places of the flat gradient buffer: one launch adds all of them in place
+            multi_copy([g.view(-1) for g in targets], small, accumulate=True)
+            db2 = dw3 = db3 = dbg = None
+        else:
+            db2, dw3, db3, dbg = small[0], small[1].view(heads, A), small[2], small[3]
+        if ctx.stacked:
+            dW = gemm(d_p, h, trans_a=True)                          # [2 heads A, H]: both weight gradients in one GEMM
+            dW2, dWg = dW[:nA], dW[nA:]
+        else:
+            # two Parameters: a GEMM over each column half of d_p, into the flat gradient buffer where it is there (the same
+            # GEMM with beta = 1: the same bits as the gradient tensor plus autograd's add)
+            dW2 = dWg = None
+            tW2, tWg = _acc_target(pW2), _acc_target(pWg)
+            if tW2 is not None:
+                gemm(d_p[:, :nA], h, trans_a=True, out=tW2, beta=1.0)
+            else:
+                dW2 = gemm(d_p[:, :nA], h, trans_a=True)
+            if tWg is not None:
+                gemm(d_p[:, nA:], h, trans_a=True, out=tWg, beta=1.0)
+            else:
+                dWg = gemm(d_p[:, nA:], h, trans_a=True)
+        gemm(d_p, Wcat, out=d_h, beta=1.0)                           # d_h += d_v W2 + d_g Wg
+        dW4 = db4 = None
+        if ctx.teacher:
+            tW4, tb4 = _acc_target(pW4), _acc_target(pb4)
+            if tW4 is not None:
+                gemm(d_P, h, trans_a=True, out=tW4, beta=1.0)
+            else:
+                dW4 = gemm(d_P, h, trans_a=True)
+            if tb4 is not None:
+                colsum(d_P, out=tb4, beta=1.0)
+            else:
+                db4 = colsum(d_P)
+        return d_h, dW2, db2, dw3, db3, dWg, dbg, dW4, db4, None, None, None
+
+
+def attn_pool(h, W2, b2, w3, b3, offsets, max_bag, heads=1, W4=None, b4=None, Wg=None, bg=None):
+    """``Wg`` [heads*A, H], ``bg`` [heads*A]: the gate operands of gated attention pooling; None is the ungated pool."""
+    if (Wg is None) != (bg is None):
+        raise ValueError("attn_pool: the gate takes both Wg and bg")
+    if Wg is not None:
+        return GatedAttnPoolFn.apply(h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets, max_bag, heads)
     return AttnPoolFn.apply(h, W2, b2, w3, b3, W4, b4, offsets, max_bag, heads)
 
 

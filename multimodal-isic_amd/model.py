@@ -170,7 +170,8 @@ class MultiModalMILNet(nn.Module):
     """
 
     def __init__(self, hidden_dim=128, att_dim=64, dropout=0.5, radiomics_dim=128, num_classes=7,
-                 fusion_strategy='concat', encoder_layers=LAYERS, aux_weight=1.0, encoder="resnet18", encoder_kwargs=None):
+                 fusion_strategy='concat', encoder_layers=LAYERS, aux_weight=1.0, encoder="resnet18", encoder_kwargs=None,
+                 mil_gated=False):
         super().__init__()
         if fusion_strategy not in ('concat', 'attention'):
             raise ValueError(f"Unknown fusion_strategy: {fusion_strategy}")
@@ -185,7 +186,8 @@ class MultiModalMILNet(nn.Module):
         else:
             # the reference's own encoder (ConvMAEBaseEncoder.forward: the token mean of its latents), 224 x 224 patches
             self.encoder = ConvMAEBaseEncoder(trainable=True, **(encoder_kwargs or {}))
-        self.mil = AttentionMIL_teacher(self.encoder.out_dim, hidden_dim, att_dim, dropout, num_classes)
+        self.mil = AttentionMIL_teacher(self.encoder.out_dim, hidden_dim, att_dim, dropout, num_classes,
+                                        gated=mil_gated)           # the gate of Ilse et al. (2018): opt-in
         self.image_proj = _mlp_ln(hidden_dim, 256, 128, 0.3, 0.2)
         self.radiomics_mlp = _mlp_ln(radiomics_dim, 256, 128, 0.4, 0.3)
         if fusion_strategy == 'attention':

@@ -52,13 +52,26 @@ class _DropoutClock:
 
 
 class _MILBase(nn.Module):
-    def __init__(self, input_dim, hidden_dim, att_dim, dropout):
+    def __init__(self, input_dim, hidden_dim, att_dim, dropout, gated=False):
         super().__init__()
         # parameter containers with the reference's names / default init (utils_g_mil.py:18-27, 49-59)
         self.feature_extractor = nn.Sequential(nn.Linear(input_dim, hidden_dim), nn.ReLU(), nn.Dropout(dropout))
         self.attention = nn.Sequential(nn.Linear(hidden_dim, att_dim), nn.Tanh(), nn.Linear(att_dim, 1))
         self.dropout_p = float(dropout)
         self.dropout_clock = _DropoutClock()
+        self.gated = bool(gated)
+
+    def _register_gate(self):
+        """The gate of Ilse et al. (2018), opt-in (the reference has none): registered by the subclass AFTER its own modules,
+        so that the state_dict of a gated model is the ungated one plus ``attention_gate.0.weight`` / ``.bias`` at the end."""
+        if self.gated:
+            a0 = self.attention[0]
+            self.attention_gate = nn.Sequential(nn.Linear(a0.in_features, a0.out_features), nn.Sigmoid())
+
+    def _gate_operands(self):
+        if not self.gated:
+            return {}
+        return {"Wg": self.attention_gate[0].weight, "bg": self.attention_gate[0].bias}
 
     def set_dropout_state(self, seed, step=0):
         self.dropout_clock.seed, self.dropout_clock.step = int(seed), int(step)
@@ -80,9 +93,10 @@ class AttentionMIL_teacher(_MILBase):
     (``bag_logits[B, C]``, ``attention[sum K]`` ...).
     """
 
-    def __init__(self, input_dim=768, hidden_dim=128, att_dim=64, dropout=0.5, num_classes=7):
-        super().__init__(input_dim, hidden_dim, att_dim, dropout)
+    def __init__(self, input_dim=768, hidden_dim=128, att_dim=64, dropout=0.5, num_classes=7, gated=False):
+        super().__init__(input_dim, hidden_dim, att_dim, dropout, gated)
         self.patch_classifier = nn.Linear(hidden_dim, num_classes)
+        self._register_gate()
 
     def forward(self, x, offsets=None, return_pooled=False):
         single = offsets is None
@@ -91,7 +105,7 @@ class AttentionMIL_teacher(_MILBase):
         a0, a2 = self.attention[0], self.attention[2]
         z, att, P, PP, BL, BP = ops.attn_pool(h, a0.weight, a0.bias, a2.weight, a2.bias, offs.device, offs.max_bag,
                                               heads=1, W4=self.patch_classifier.weight,
-                                              b4=self.patch_classifier.bias)
+                                              b4=self.patch_classifier.bias, **self._gate_operands())
         out = {
             "bag_logits": BL[0] if single else BL,
             "bag_probs": BP[0] if single else BP,
@@ -108,16 +122,18 @@ class AttentionMIL_teacher(_MILBase):
 class AttentionMIL(_MILBase):
     """Reference `utils_g_mil.py:15-36`: feature-space pooling; returns ``(probs, a)``."""
 
-    def __init__(self, input_dim=76, hidden_dim=128, att_dim=64, dropout=0.5, num_classes=7):
-        super().__init__(input_dim, hidden_dim, att_dim, dropout)
+    def __init__(self, input_dim=76, hidden_dim=128, att_dim=64, dropout=0.5, num_classes=7, gated=False):
+        super().__init__(input_dim, hidden_dim, att_dim, dropout, gated)
         self.classifier = nn.Linear(hidden_dim, num_classes)
+        self._register_gate()
 
     def forward(self, x, offsets=None):
         single = offsets is None
         offs = BagOffsets.single(x.shape[0], x.device) if single else as_offsets(offsets, x.device)
         h = self._hidden(x)
         a0, a2 = self.attention[0], self.attention[2]
-        z, att = ops.attn_pool(h, a0.weight, a0.bias, a2.weight, a2.bias, offs.device, offs.max_bag, heads=1)
+        z, att = ops.attn_pool(h, a0.weight, a0.bias, a2.weight, a2.bias, offs.device, offs.max_bag, heads=1,
+                                **self._gate_operands())
         logits = ops.linear(z, self.classifier.weight, self.classifier.bias)
         probs = ops.softmax_rows(logits)
         if single:
