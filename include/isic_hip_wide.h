@@ -5,8 +5,9 @@
  *
  * Conventions as in isic_hip.h: row-major fp32 device tensors, return 0 or a negative ISIC_ERR_* code, arguments are
  * checked before any device work, no allocation, no synchronisation, `stream` last.  The entries of isic_hip.h keep
- * their domains and their refusals; the caller chooses (isic_hip/ops.py: the wide forward for H > 1024, the wide
- * backward for H > 1024 or heads > 4, the wide LayerNorm backward for N > 1024).
+ * their domains and their refusals; the caller chooses (isic_hip/ops.py: _pool_wide() is the one place that picks the
+ * pool entry, forward and backward, for the autograd Function and for torch.ops.isic_hip.attn_pool alike; the wide
+ * LayerNorm backward for N > 1024).
  */
 #ifndef ISIC_HIP_WIDE_H
 #define ISIC_HIP_WIDE_H

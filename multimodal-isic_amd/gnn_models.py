@@ -322,12 +322,10 @@ class GraphMIL(nn.Module):
                 if res is not None:
                     h = h + res
         self.last_node_embeddings = h.detach()
-        if self.att_gated:                                           # ... and the gates' as the second half of [2*heads*A, H]
-            W2, b2, w3, b3, Wg, bg = ops.gated_head_params(self.attention_layers, self.attention_gates)
-            z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads, Wg=Wg, bg=bg)
-        else:
-            W2, b2, w3, b3 = ops.head_params(self.attention_layers)  # the heads' parameters as one [heads*A, H] operand
-            z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads)
+        # the heads' parameters as one [heads*A, H] operand -- and the gates', if any, as the second half of [2*heads*A, H]
+        W2, b2, w3, b3, *gate = ops.head_params(self.attention_layers, self.attention_gates if self.att_gated else None)
+        Wg, bg = gate or (None, None)
+        z, att = ops.attn_pool(h, W2, b2, w3, b3, offs.device, offs.max_bag, heads=self.att_heads, Wg=Wg, bg=bg)
         c = self.classifier
         if (labels is not None and self.classifier_light and tr and not single
                 and ops.graph_head_supported(z.shape[1], c[0].weight.shape[0], c[3].weight.shape[0])):

@@ -6,7 +6,7 @@ import torch
 
 from .bags import BagOffsets
 from .lib import IsicHipError, call
-from .ops import _acc_target, _chk, _f32c, colsum
+from .ops import _acc_target, _chk, _f32c, _grad_colsum, _grad_gemm, colsum
 
 
 def knn_indices(x, offsets: BagOffsets, k, return_dist=False):
@@ -170,11 +170,7 @@ class SpmmFn(torch.autograd.Function):
             dx = torch.empty_like(dy)
             _spmm_launch(g, True, dy, None, dx, ctx.alpha, None, 0.0)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            tgt = _acc_target(ctx.bias_param)
-            if tgt is not None:
-                colsum(dy, out=tgt, beta=1.0)
-            else:
-                db = colsum(dy)
+            db = _grad_colsum(ctx.bias_param, dy)
         if ctx.has_addend and ctx.needs_input_grad[4]:
             da = dy * ctx.addend_scale
         return dx, None, db, None, da, None
@@ -246,20 +242,10 @@ class GcnBlockFn(torch.autograd.Function):
             call("isic_layernorm_bwd_ws", dy2, agg, g_, b_, mean, rstd, d_agg, dg, db_ln, n, F, 1, drop.threshold, drop.scale,
                  drop.seed, drop.stream, drop.clock, ws, ws.numel() if ws is not None else 0)
         if want_db:
-            t = _acc_target(bias)
-            if t is not None:
-                colsum(d_agg, out=t, beta=1.0)
-            else:
-                dbias = colsum(d_agg)
+            dbias = _grad_colsum(bias, d_agg)
         d_lin = torch.empty_like(d_agg)
         _spmm_launch(ctx.graph, True, d_agg, None, d_lin, 1.0, None, 0.0)
-        dW = None
-        if ctx.needs_input_grad[1]:
-            t = _acc_target(weight)
-            if t is not None:
-                gemm(d_lin, h2, trans_a=True, out=t, beta=1.0)
-            else:
-                dW = gemm(d_lin, h2, trans_a=True)
+        dW = _grad_gemm(weight, d_lin, h2) if ctx.needs_input_grad[1] else None
         dh = None
         if ctx.needs_input_grad[0]:
             dh = gemm(d_lin, w, addend=dy2 if ctx.residual else None)      # (A^T d) W + dy: both paths in one epilogue

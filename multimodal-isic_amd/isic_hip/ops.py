@@ -6,6 +6,7 @@ are rejected (no fallback).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 
@@ -93,6 +94,25 @@ def _acc_target(p):
     if g is None or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
         return None
     return g
+
+
+def _grad_gemm(param, a, b):
+    """d param = a^T b: added into ``param``'s ``.grad`` by the GEMM itself (beta = 1) where ``_acc_target`` allows -- autograd
+    then gets None -- else the gradient tensor."""
+    tgt = _acc_target(param)
+    if tgt is None:
+        return gemm(a, b, trans_a=True)
+    gemm(a, b, trans_a=True, out=tgt, beta=1.0)
+    return None
+
+
+def _grad_colsum(param, x):
+    """d param = the column sums of x, accumulated in place or returned like ``_grad_gemm``."""
+    tgt = _acc_target(param)
+    if tgt is None:
+        return colsum(x)
+    colsum(x, out=tgt, beta=1.0)
+    return None
 
 
 # --------------------------------------------------------------------------- raw helpers (no autograd)
@@ -191,17 +211,9 @@ class LinearFn(torch.autograd.Function):
             dx = gemm(g, w).reshape(ctx.xshape)
         wp, bp = ctx.params
         if ctx.needs_input_grad[1]:
-            tgt = _acc_target(wp)
-            if tgt is not None:
-                gemm(g, x2, trans_a=True, out=tgt, beta=1.0)
-            else:
-                dw = gemm(g, x2, trans_a=True)
+            dw = _grad_gemm(wp, g, x2)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            tgt = _acc_target(bp)
-            if tgt is not None:
-                colsum(g, out=tgt, beta=1.0)
-            else:
-                db = colsum(g)
+            db = _grad_colsum(bp, g)
         return dx, dw, db, None, None
 
 
@@ -259,11 +271,7 @@ class LinearRowsFn(torch.autograd.Function):
                     gemm(g, xs[rows[:M].long()], trans_a=True, out=out, beta=beta)
             dw = None if tgt is not None else out
         if bias is not None and ctx.needs_input_grad[4]:
-            tgt = _acc_target(bias)
-            if tgt is not None:
-                colsum(g, out=tgt, beta=1.0)
-            else:
-                db = colsum(g)
+            db = _grad_colsum(bias, g)
         return None, None, None, dw, db
 
 
@@ -323,221 +331,150 @@ def multi_copy(dsts, srcs, accumulate=False):
 class HeadParamsFn(torch.autograd.Function):
     """The per-head attention parameters (`05_train_gnns.py:126-131`: heads x Sequential(Linear(H, A), Tanh, Linear(A, 1)))
     as the fused operands of ``attn_pool``: (W_0, b_0, w_0, c_0, W_1, ...) -> W2[heads*A, H], b2[heads*A], w3[heads, A],
-    b3[heads].  One gather launch forward; backward one scatter launch that adds the slices into the parameters' ``.grad``
-    (under ``fused_grad_accumulation``) -- instead of four concatenations and 4 * heads AccumulateGrad kernels."""
+    b3[heads], laid out W2 | b2 | w3 | b3 in one buffer.  One gather launch forward; backward one scatter launch that adds
+    the slices into the parameters' ``.grad`` (under ``fused_grad_accumulation``) -- instead of four concatenations and
+    4 * heads AccumulateGrad kernels.
+
+    ``gated``: a gate Sequential(Linear(H, A), Sigmoid) per head, (W_0, b_0, w_0, c_0, U_0, d_0, W_1, ...) -> W2, b2, w3, b3,
+    Wg, bg over the layout W2 | Wg | b2 | bg | w3 | b3: Wg [heads*A, H] follows W2 and bg follows b2, so that ``attn_pool``
+    reads [W2 ; Wg] as the operand of its one GEMM without another copy."""
 
     @staticmethod
-    def forward(ctx, *params):
+    def forward(ctx, gated, *params):
         _chk(*params)
-        heads = len(params) // 4
+        g = 2 if gated else 1
+        heads = len(params) // (2 + 2 * g)
         A, H = params[0].shape
         nW, nb = heads * A * H, heads * A
-        flat = torch.empty(nW + 2 * nb + heads, device=params[0].device, dtype=torch.float32)
-        W2, b2 = flat[:nW].view(heads * A, H), flat[nW:nW + nb]
-        w3, b3 = flat[nW + nb:nW + 2 * nb].view(heads, A), flat[nW + 2 * nb:]
-        dst = []
-        for k in range(heads):
-            dst += [W2[k * A:(k + 1) * A], b2[k * A:(k + 1) * A], w3[k], b3[k:k + 1]]
-        multi_copy(dst, [_f32c(p.detach()) for p in params])
-        ctx.params, ctx.dims = params, (heads, A, H)
-        return W2, b2, w3, b3
-
-    @staticmethod
-    def backward(ctx, gW2, gb2, gw3, gb3):
-        heads, A, H = ctx.dims
-        gs = []
-        for k in range(heads):
-            gs += [None if gW2 is None else gW2[k * A:(k + 1) * A], None if gb2 is None else gb2[k * A:(k + 1) * A],
-                   None if gw3 is None else gw3.reshape(heads, A)[k], None if gb3 is None else gb3.reshape(heads)[k:k + 1]]
-        tg = [_acc_target(p) for p in ctx.params]
-        if all(t is not None for t in tg) and all(g is not None and g.is_contiguous() for g in gs):
-            multi_copy(tg, gs, accumulate=True)
-            return (None,) * len(ctx.params)
-        return tuple(None if g is None else g.reshape(p.shape) for g, p in zip(gs, ctx.params))
-
-
-def head_params(attention_layers):
-    """Fused attn_pool operands of a ModuleList of Sequential(Linear, Tanh, Linear) heads."""
-    ps = []
-    for a in attention_layers:
-        ps += [a[0].weight, a[0].bias, a[2].weight, a[2].bias]
-    return HeadParamsFn.apply(*ps)
-
-
-class GatedHeadParamsFn(torch.autograd.Function):
-    """``HeadParamsFn`` with a gate per head: (W_0, b_0, w_0, c_0, U_0, d_0, W_1, ...) -> W2, b2, w3, b3, Wg, bg, where
-    Wg [heads*A, H] follows W2 and bg follows b2 in one buffer, so that ``attn_pool`` reads [W2 ; Wg] as the operand of its
-    one GEMM without another copy.  One gather launch forward, the scatter of ``HeadParamsFn`` backward."""
-
-    @staticmethod
-    def forward(ctx, *params):
-        _chk(*params)
-        heads = len(params) // 6
-        A, H = params[0].shape
-        nW, nb = heads * A * H, heads * A
-        flat = torch.empty(2 * nW + 3 * nb + heads, device=params[0].device, dtype=torch.float32)
-        W2, Wg = flat[:nW].view(nb, H), flat[nW:2 * nW].view(nb, H)
-        b2, bg = flat[2 * nW:2 * nW + nb], flat[2 * nW + nb:2 * nW + 2 * nb]
-        w3, b3 = flat[2 * nW + 2 * nb:2 * nW + 3 * nb].view(heads, A), flat[2 * nW + 3 * nb:]
+        flat = torch.empty(g * nW + (g + 1) * nb + heads, device=params[0].device, dtype=torch.float32)
+        parts = flat.split([nW] * g + [nb] * g + [nb, heads])
+        W, b = [p.view(nb, H) for p in parts[:g]], parts[g:2 * g]
+        w3, b3 = parts[2 * g].view(heads, A), parts[2 * g + 1]
         dst = []
         for k in range(heads):
             s = slice(k * A, (k + 1) * A)
-            dst += [W2[s], b2[s], w3[k], b3[k:k + 1], Wg[s], bg[s]]
+            dst += [W[0][s], b[0][s], w3[k], b3[k:k + 1]] + ([W[1][s], b[1][s]] if gated else [])
         multi_copy(dst, [_f32c(p.detach()) for p in params])
-        ctx.params, ctx.dims = params, (heads, A, H)
-        return W2, b2, w3, b3, Wg, bg
+        ctx.params, ctx.dims = params, (heads, A)
+        return (W[0], b[0], w3, b3) + ((W[1], b[1]) if gated else ())
 
     @staticmethod
-    def backward(ctx, gW2, gb2, gw3, gb3, gWg, gbg):
-        heads, A, H = ctx.dims
+    def backward(ctx, gW2, gb2, gw3, gb3, *gate):
+        heads, A = ctx.dims
+        cut = lambda g, i: None if g is None else g[i]
+        gw3, gb3 = None if gw3 is None else gw3.reshape(heads, A), None if gb3 is None else gb3.reshape(heads)
         gs = []
         for k in range(heads):
             s = slice(k * A, (k + 1) * A)
-            gs += [None if gW2 is None else gW2[s], None if gb2 is None else gb2[s],
-                   None if gw3 is None else gw3.reshape(heads, A)[k], None if gb3 is None else gb3.reshape(heads)[k:k + 1],
-                   None if gWg is None else gWg[s], None if gbg is None else gbg[s]]
+            gs += [cut(gW2, s), cut(gb2, s), cut(gw3, k), cut(gb3, slice(k, k + 1))] + [cut(g, s) for g in gate]
         tg = [_acc_target(p) for p in ctx.params]
         if all(t is not None for t in tg) and all(g is not None and g.is_contiguous() for g in gs):
             multi_copy(tg, gs, accumulate=True)
-            return (None,) * len(ctx.params)
-        return tuple(None if g is None else g.reshape(p.shape) for g, p in zip(gs, ctx.params))
+            return (None,) * (1 + len(ctx.params))
+        return (None,) + tuple(None if g is None else g.reshape(p.shape) for g, p in zip(gs, ctx.params))
 
 
-def gated_head_params(attention_layers, attention_gates):
-    """Fused attn_pool operands of the heads Sequential(Linear, Tanh, Linear) and their gates Sequential(Linear, Sigmoid):
-    W2, b2, w3, b3, Wg, bg."""
-    if len(attention_layers) != len(attention_gates):
-        raise ValueError("gated_head_params: one gate per attention head")
+def head_params(attention_layers, attention_gates=None):
+    """Fused attn_pool operands of a ModuleList of Sequential(Linear, Tanh, Linear) heads: W2, b2, w3, b3 -- and, given their
+    gates Sequential(Linear, Sigmoid), Wg, bg after them."""
+    gates = attention_gates if attention_gates is not None else [None] * len(attention_layers)
+    if len(attention_layers) != len(gates):
+        raise ValueError("head_params: one gate per attention head")
     ps = []
-    for a, g in zip(attention_layers, attention_gates):
-        ps += [a[0].weight, a[0].bias, a[2].weight, a[2].bias, g[0].weight, g[0].bias]
-    return GatedHeadParamsFn.apply(*ps)
+    for a, g in zip(attention_layers, gates):
+        ps += [a[0].weight, a[0].bias, a[2].weight, a[2].bias] + ([g[0].weight, g[0].bias] if g is not None else [])
+    return HeadParamsFn.apply(attention_gates is not None, *ps)
 
 
 # --------------------------------------------------------------------------- attention pool
-class AttnPoolFn(torch.autograd.Function):
-    """Attention scores + segmented softmax + pooling over ragged bags.
+_Pool = collections.namedtuple("_Pool", "h t att P w3c W4c offsets max_bag heads")      # what the pool backward reads
 
-    t = tanh(h W2^T + b2); s = t w3^T + b3 per head; att = softmax over each bag;
-    z = mean_heads sum_n att*h; teacher form (W4 given): patch logits/probs and
-    class-space pooled bag logits/probs.  Differentiable outputs: z, bag_logits.
-    """
 
-    @staticmethod
-    def forward(ctx, h, W2, b2, w3, b3, W4, b4, offsets, max_bag, heads):
-        _chk(h, W2, b2, w3, b3, W4, b4, offsets)
-        ctx.set_materialize_grads(False)
-        h = _f32c(h)
-        T, H = h.shape
-        A = W2.shape[0] // heads
-        B = offsets.numel() - 1
-        dev = h.device
-        t = gemm(h, _f32c(W2), trans_b=True, bias=_f32c(b2), act=ACT_TANH)
-        w3c, b3c = _f32c(w3).reshape(heads, A), _f32c(b3).reshape(heads)
-        att = torch.empty((T, heads), device=dev, dtype=torch.float32)
-        z = torch.empty((B, H), device=dev, dtype=torch.float32)
-        teacher = W4 is not None
-        if teacher:
-            C = W4.shape[0]
-            W4c, b4c = _f32c(W4), _f32c(b4)
-            P = torch.empty((T, C), device=dev, dtype=torch.float32)
-            PP = torch.empty((T, C), device=dev, dtype=torch.float32)
-            BL = torch.empty((B, C), device=dev, dtype=torch.float32)
-            BP = torch.empty((B, C), device=dev, dtype=torch.float32)
-        else:
-            C, W4c, b4c, P, PP, BL, BP = 0, None, None, None, None, None, None
-        if not teacher and H > 1024:
-            # GraphMIL beyond 1024 columns (gnn_concat=True: hidden x heads up to 4096): one weighted column sum over h
-            call("isic_attn_pool_wide_fwd", h, t, w3c, b3c, offsets, B, H, A, heads, int(max_bag), att, z)
-        else:
-            call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP,
-                 BL, BP)
-        ctx.dims = (B, H, A, heads, C, int(max_bag))
-        ctx.teacher = teacher
-        ctx.params = (W2, b2, w3, b3, W4, b4)          # the callers' tensors: Parameters take their gradients in place
-        ctx.save_for_backward(h, t, att, P, _f32c(W2), w3c, W4c, offsets)
-        if teacher:
-            ctx.mark_non_differentiable(att, P, PP, BP)
-            return z, att, P, PP, BL, BP
-        ctx.mark_non_differentiable(att)
-        return z, att
+def _pool_wide(H, heads, teacher, backward):
+    """THE choice of pool entry: ``isic_attn_pool_wide_fwd`` / ``_wide_bwd`` serve exactly what ``isic_attn_pool_fwd`` /
+    ``_bwd`` refuse -- GraphMIL beyond 1024 columns (gnn_concat=True: hidden x heads up to 4096), and in the backward also
+    att_heads = 8.  The wide entries have no teacher form."""
+    return not teacher and (H > 1024 or (backward and heads > 4))
 
-    @staticmethod
-    def backward(ctx, dz, *rest):
-        h, t, att, P, W2, w3c, W4c, offsets = ctx.saved_tensors
-        B, H, A, heads, C, max_bag = ctx.dims
-        dBL = rest[3] if ctx.teacher else None
-        T = h.shape[0]
-        dev = h.device
-        dz = _f32c(dz) if dz is not None else None
-        dBL = _f32c(dBL) if dBL is not None else None
-        d_h = torch.empty((T, H), device=dev, dtype=torch.float32)
-        d_u = torch.empty((T, heads * A), device=dev, dtype=torch.float32)
-        d_s = torch.empty((T, heads), device=dev, dtype=torch.float32)
-        d_P = torch.empty((T, C), device=dev, dtype=torch.float32) if ctx.teacher else None
-        # Parameters whose .grad lives in the flat gradient buffer (optim.FlatParams) are accumulated INTO by the reduction
-        # kernels themselves (GEMM beta = 1, column sums with beta = 1): no gradient tensor, no AccumulateGrad add launch
-        # (six of them per teacher step: 11 % of a 0.63 ms step at 256 bags)
-        pW2, pb2, pw3, pb3, pW4, pb4 = ctx.params
-        tW2, tb2, tw3, tb3 = _acc_target(pW2), _acc_target(pb2), _acc_target(pw3), _acc_target(pb3)
-        small_fused = tb2 is not None and tw3 is not None and tb3 is not None
-        db2 = dw3 = db3 = None
-        wide = not ctx.teacher and (H > 1024 or heads > 4)    # what isic_attn_pool_bwd refuses: att_heads = 8, hidden x heads > 1024
-        if H <= 128 and A <= 128 and not wide:
-            # db2 = sum_n d_u, dw3[k, j] = sum_n d_s[n,k] t[n, kA+j], db3 = sum_n d_s: per-bag sums out of the pool kernel
-            # (d_u and t are in its registers), then ONE column sum over the bags
-            nA = heads * A
-            psum = torch.empty((B, 2 * nA + heads), device=dev, dtype=torch.float32)
-            call("isic_attn_pool_bwd_sums", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
-                 d_u, d_s, d_P, psum)
-            if small_fused:
-                colsum(psum[:, :nA], out=tb2.view(-1), beta=1.0)
-                colsum(psum[:, nA:2 * nA], out=tw3.view(-1), beta=1.0)
-                colsum(psum[:, 2 * nA:], out=tb3.view(-1), beta=1.0)
-            else:
-                sums = colsum(psum)
-                db2, dw3, db3 = sums[:nA], sums[nA:2 * nA].view(heads, A), sums[2 * nA:]
+
+def _pool_forward(h, t, w3c, b3c, W4c, b4c, offsets, max_bag, heads):
+    """Scores, softmax per bag and pooling of t [T, heads*A] over h -> att, z, P, PP, BL, BP (the last four None without the
+    teacher's W4c, b4c)."""
+    (T, H), A, B = h.shape, t.shape[1] // heads, offsets.numel() - 1
+    new = lambda *shape: torch.empty(shape, device=h.device, dtype=torch.float32)
+    att, z = new(T, heads), new(B, H)
+    teacher = W4c is not None
+    C = W4c.shape[0] if teacher else 0
+    P, PP, BL, BP = (new(T, C), new(T, C), new(B, C), new(B, C)) if teacher else (None,) * 4
+    if _pool_wide(H, heads, teacher, backward=False):         # one weighted column sum over h
+        call("isic_attn_pool_wide_fwd", h, t, w3c, b3c, offsets, B, H, A, heads, int(max_bag), att, z)
+    else:
+        call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP, BL, BP)
+    return att, z, P, PP, BL, BP
+
+
+def _pool_backward(pool, dz, dBL, d_u, want_sums):
+    """The pool backward -> d_h (without the path through t), d_s, d_P, psum.  ``d_u`` [T, heads*A] takes the gradient of the
+    ungated pre-activations; None makes the narrow entry skip that store (the wide one refuses None).  ``want_sums``: where
+    the kernel can (d_u and t are in its registers) it also writes the per-bag sums psum [B, 2 heads A + heads] of
+    d_u | d_s t | d_s, whose ONE column sum over the bags is db2 | dw3 | db3; psum is None otherwise."""
+    h, t, att, P, w3c, W4c, offsets, max_bag, heads = pool
+    (T, H), A, B = h.shape, w3c.shape[1], offsets.numel() - 1
+    new = lambda *shape: torch.empty(shape, device=h.device, dtype=torch.float32)
+    teacher = W4c is not None
+    C = W4c.shape[0] if teacher else 0
+    d_h, d_s, d_P, psum = new(T, H), new(T, heads), new(T, C) if teacher else None, None
+    if _pool_wide(H, heads, teacher, backward=True):
+        if dz is None:
+            dz = torch.zeros((B, H), device=h.device, dtype=torch.float32)
+        call("isic_attn_pool_wide_bwd", h, t, att, w3c, offsets, B, H, A, heads, max_bag, dz, d_h, 0, d_u, d_s)
+    elif want_sums and H <= 128 and A <= 128:
+        psum = new(B, 2 * heads * A + heads)
+        call("isic_attn_pool_bwd_sums", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
+             d_u, d_s, d_P, psum)
+    else:
+        call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
+             d_u, d_s, d_P)
+    return d_h, d_s, d_P, psum
+
+
+def _tanh_back(pool, params, dz, dBL):
+    """Backward of t = tanh(h W2^T + b2) and the pool after it -> d_h (still without d_u W2), d_u, d_P, (dW2, db2, dw3, db3)."""
+    h, t, heads = pool.h, pool.t, pool.heads
+    nA = t.shape[1]
+    A = nA // heads
+    d_u = torch.empty((h.shape[0], nA), device=h.device, dtype=torch.float32)
+    d_h, d_s, d_P, psum = _pool_backward(pool, dz, dBL, d_u, want_sums=True)
+    # Parameters whose .grad lives in the flat gradient buffer (optim.FlatParams) are accumulated INTO by the reduction
+    # kernels themselves (GEMM beta = 1, column sums with beta = 1): no gradient tensor, no AccumulateGrad add launch
+    # (six of them per teacher step: 11 % of a 0.63 ms step at 256 bags)
+    pW2, pb2, pw3, pb3 = params
+    tb2, tw3, tb3 = _acc_target(pb2), _acc_target(pw3), _acc_target(pb3)
+    small_fused = tb2 is not None and tw3 is not None and tb3 is not None
+    db2 = dw3 = db3 = None
+    if psum is not None:
+        if small_fused:
+            colsum(psum[:, :nA], out=tb2.view(-1), beta=1.0)
+            colsum(psum[:, nA:2 * nA], out=tw3.view(-1), beta=1.0)
+            colsum(psum[:, 2 * nA:], out=tb3.view(-1), beta=1.0)
         else:
-            if wide:
-                if dz is None:
-                    dz = torch.zeros((B, H), device=dev, dtype=torch.float32)
-                call("isic_attn_pool_wide_bwd", h, t, att, w3c, offsets, B, H, A, heads, max_bag, dz, d_h, 0, d_u, d_s)
-            else:
-                call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
-                     d_u, d_s, d_P)
-            # dw3[k, j] = sum_n d_s[n,k] * t[n, k*A + j]
-            if small_fused and heads == 1:
-                colsum(d_u, out=tb2.view(-1), beta=1.0)
-                gemm(d_s, t, trans_a=True, out=tw3.view(1, A), beta=1.0)
-                colsum(d_s, out=tb3.view(-1), beta=1.0)
-            else:
-                small_fused = False
-                db2 = colsum(d_u)
-                if heads == 1:
-                    dw3 = gemm(d_s, t, trans_a=True)                 # [1, A]
-                else:
-                    full = gemm(d_s, t, trans_a=True)                # [heads, heads*A]
-                    dw3 = torch.stack([full[k, k * A:(k + 1) * A] for k in range(heads)])
-                db3 = colsum(d_s)
-        # weight gradient of the first Linear: a GEMM over the T instances
-        if tW2 is not None:
-            gemm(d_u, h, trans_a=True, out=tW2, beta=1.0)
-            dW2 = None
+            sums = colsum(psum)
+            db2, dw3, db3 = sums[:nA], sums[nA:2 * nA].view(heads, A), sums[2 * nA:]
+    elif small_fused and heads == 1:
+        colsum(d_u, out=tb2.view(-1), beta=1.0)
+        gemm(d_s, t, trans_a=True, out=tw3.view(1, A), beta=1.0)
+        colsum(d_s, out=tb3.view(-1), beta=1.0)
+    else:
+        db2 = colsum(d_u)
+        # dw3[k, j] = sum_n d_s[n,k] * t[n, k*A + j]
+        if heads == 1:
+            dw3 = gemm(d_s, t, trans_a=True)                 # [1, A]
         else:
-            dW2 = gemm(d_u, h, trans_a=True)                 # [heads*A, H]
-        gemm(d_u, W2, out=d_h, beta=1.0)                     # d_h += d_u W2
-        dW4 = db4 = None
-        if ctx.teacher:
-            tW4, tb4 = _acc_target(pW4), _acc_target(pb4)
-            if tW4 is not None:
-                gemm(d_P, h, trans_a=True, out=tW4, beta=1.0)
-            else:
-                dW4 = gemm(d_P, h, trans_a=True)
-            if tb4 is not None:
-                colsum(d_P, out=tb4, beta=1.0)
-            else:
-                db4 = colsum(d_P)
-        return d_h, dW2, db2, dw3, db3, dW4, db4, None, None, None
+            full = gemm(d_s, t, trans_a=True)                # [heads, heads*A]
+            dw3 = torch.stack([full[k, k * A:(k + 1) * A] for k in range(heads)])
+        db3 = colsum(d_s)
+    dW2 = _grad_gemm(pW2, d_u, h)                            # weight gradient of the first Linear: a GEMM over the T instances
+    return d_h, d_u, d_P, (dW2, db2, dw3, db3)
 
 
 def _follows(first, second):
@@ -547,62 +484,94 @@ def _follows(first, second):
             and second.storage_offset() == first.storage_offset() + first.numel())
 
 
-class GatedAttnPoolFn(torch.autograd.Function):
-    """``AttnPoolFn`` with the gate of Ilse et al. (2018): t = tanh(h W2^T + b2) * sigmoid(h Wg^T + bg); everything after t
-    (scores, softmax per bag, pooling, the teacher's class space, the wide forms) is the ungated path's pool kernels.
+def _gated_front(h, W2, b2, Wg, bg, heads):
+    """t = tanh(h W2^T + b2) * sigmoid(h Wg^T + bg) -> t, the gate kernel's tv | sg [T, 2 heads A], the stacked weight
+    [W2 ; Wg], and whether the caller's tensors ARE that stack.  ONE GEMM over the stacked operand (``head_params`` hands
+    the two halves over as neighbouring views and nothing is copied; two separate Parameters are stacked by one
+    ``multi_copy`` launch), then ``isic_gate_fwd_f32`` (pre-activations -> tv | sg in place, t)."""
+    (T, H), nA, dev = h.shape, W2.shape[0], h.device
+    if Wg.shape != W2.shape or bg.numel() != nA or b2.numel() != nA:
+        raise ValueError(f"attn_pool: the gate operands must have the shapes of W2 {tuple(W2.shape)} and b2")
+    stacked = _follows(W2, Wg) and _follows(b2, bg)
+    if stacked:
+        Wcat, bcat = W2.as_strided((2 * nA, H), (H, 1)), b2.reshape(-1).as_strided((2 * nA,), (1,))
+    else:
+        Wcat = torch.empty((2 * nA, H), device=dev, dtype=torch.float32)
+        bcat = torch.empty((2 * nA,), device=dev, dtype=torch.float32)
+        multi_copy([Wcat[:nA], Wcat[nA:], bcat[:nA], bcat[nA:]],
+                   [_f32c(W2.detach()), _f32c(Wg.detach()), _f32c(b2.detach()).reshape(-1), _f32c(bg.detach()).reshape(-1)])
+    a = gemm(h, Wcat, trans_b=True, bias=bcat)                  # pre-activations; isic_gate_fwd_f32 turns them into tv | sg
+    t = torch.empty((T, nA), device=dev, dtype=torch.float32)
+    call("isic_gate_fwd_f32", a, T, heads, nA // heads, t)
+    return t, a, Wcat, stacked
 
-    Forward: ONE GEMM over the stacked operand [W2 ; Wg] -> p [T, 2 heads A] (``gated_head_params`` hands the two halves
-    over as neighbouring views and nothing is copied; two separate Parameters are stacked by one ``multi_copy`` launch),
-    ``isic_gate_fwd_f32`` (p -> tv | sg in place, t), the pool forward on t.  Backward: the pool backward for d_h, d_s, d_P
-    (its d_u carries (1 - t^2), wrong under a gate, and is not used), ``isic_gate_bwd_f32`` (d_p = d_v | d_g and the four
-    small parameter gradients in one pass), then the GEMMs d_[W2 ; Wg] = d_p^T h and d_h += d_p [W2 ; Wg]."""
+
+def _gated_back(pool, params, a, stacked, dz, dBL):
+    """Backward of ``_gated_front`` and the pool after it -> d_h (still without d_p [W2 ; Wg]), d_p = d_v | d_g, d_P,
+    (dW2, db2, dw3, db3, dWg, dbg).  The pool backward gives d_h, d_s, d_P (its d_u carries (1 - t^2), wrong under a gate,
+    and is not used); ``isic_gate_bwd_f32`` gives d_p and the four small parameter gradients in one pass."""
+    h, w3c, heads = pool.h, pool.w3c, pool.heads
+    T, A, dev = h.shape[0], w3c.shape[1], h.device
+    nA = heads * A
+    d_p = torch.empty((T, 2 * nA), device=dev, dtype=torch.float32)
+    # isic_attn_pool_wide_bwd refuses a NULL d_u (ISIC_ERR_BAD_ARG): d_p serves as the scratch buffer for its ungated
+    # d_u ([T, heads A], the first half of d_p's memory), and isic_gate_bwd_f32 overwrites all of d_p next
+    wide = _pool_wide(h.shape[1], heads, pool.W4c is not None, backward=True)
+    d_h, d_s, d_P, _ = _pool_backward(pool, dz, dBL, d_p if wide else None, want_sums=False)
+    # d_p = d_v | d_g and, in the same pass, sums = d_b2 | d_bg | d_w3 | d_b3 (fixed-order slabs, no atomics)
+    sums = (torch.empty if T > 0 else torch.zeros)((3 * nA + heads,), device=dev, dtype=torch.float32)
+    ws = _workspace(call("isic_gate_bwd_f32_workspace_bytes", T, heads, A), dev)
+    call("isic_gate_bwd_f32", d_s, w3c, a, T, heads, A, d_p, sums[:2 * nA], sums[2 * nA:3 * nA], sums[3 * nA:], 0.0,
+         ws, ws.numel() if ws is not None else 0)
+    pW2, pb2, pw3, pb3, pWg, pbg = params
+    small = [sums[:nA], sums[2 * nA:3 * nA], sums[3 * nA:], sums[nA:2 * nA]]          # d_b2, d_w3, d_b3, d_bg
+    targets = [_acc_target(p) for p in (pb2, pw3, pb3, pbg)]
+    if all(g is not None for g in targets):
+        # the four live in different places of the flat gradient buffer: one launch adds all of them in place
+        multi_copy([g.view(-1) for g in targets], small, accumulate=True)
+        db2 = dw3 = db3 = dbg = None
+    else:
+        db2, dw3, db3, dbg = small[0], small[1].view(heads, A), small[2], small[3]
+    if stacked:
+        dW = gemm(d_p, h, trans_a=True)                          # [2 heads A, H]: both weight gradients in one GEMM
+        dW2, dWg = dW[:nA], dW[nA:]
+    else:
+        # two Parameters: a GEMM over each column half of d_p, into the flat gradient buffer where it is there (the same
+        # GEMM with beta = 1: the same bits as the gradient tensor plus autograd's add)
+        dW2, dWg = _grad_gemm(pW2, d_p[:, :nA], h), _grad_gemm(pWg, d_p[:, nA:], h)
+    return d_h, d_p, d_P, (dW2, db2, dw3, db3, dWg, dbg)
+
+
+class AttnPoolFn(torch.autograd.Function):
+    """Attention scores + segmented softmax + pooling over ragged bags.
+
+    t = tanh(h W2^T + b2), times sigmoid(h Wg^T + bg) with the gate of Ilse et al. (2018) (Wg, bg given); s = t w3^T + b3 per
+    head; att = softmax over each bag; z = mean_heads sum_n att*h; teacher form (W4 given): patch logits/probs and
+    class-space pooled bag logits/probs.  Differentiable outputs: z, bag_logits.
+
+    Only the front (h -> t) and its backward differ between the two forms (``_gated_front`` / ``_gated_back``, the tanh
+    GEMM / ``_tanh_back``); everything after t is ``_pool_forward`` / ``_pool_backward``.
+    """
 
     @staticmethod
     def forward(ctx, h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets, max_bag, heads):
         _chk(h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets)
         ctx.set_materialize_grads(False)
         h = _f32c(h)
-        T, H = h.shape
-        nA = W2.shape[0]
-        A = nA // heads
-        if Wg.shape != W2.shape or bg.numel() != nA or b2.numel() != nA:
-            raise ValueError(f"attn_pool: the gate operands must have the shapes of W2 {tuple(W2.shape)} and b2")
-        B = offsets.numel() - 1
-        dev = h.device
-        ctx.stacked = _follows(W2, Wg) and _follows(b2, bg)
-        if ctx.stacked:
-            Wcat, bcat = W2.as_strided((2 * nA, H), (H, 1)), b2.reshape(-1).as_strided((2 * nA,), (1,))
+        A = W2.shape[0] // heads
+        ctx.gated, ctx.teacher = Wg is not None, W4 is not None
+        if ctx.gated:
+            t, a, Wt, ctx.stacked = _gated_front(h, W2, b2, Wg, bg, heads)
         else:
-            Wcat = torch.empty((2 * nA, H), device=dev, dtype=torch.float32)
-            bcat = torch.empty((2 * nA,), device=dev, dtype=torch.float32)
-            multi_copy([Wcat[:nA], Wcat[nA:], bcat[:nA], bcat[nA:]],
-                       [_f32c(W2.detach()), _f32c(Wg.detach()), _f32c(b2.detach()).reshape(-1), _f32c(bg.detach()).reshape(-1)])
-        a = gemm(h, Wcat, trans_b=True, bias=bcat)                  # pre-activations; isic_gate_fwd_f32 turns them into tv | sg
-        t = torch.empty((T, nA), device=dev, dtype=torch.float32)
-        call("isic_gate_fwd_f32", a, T, heads, A, t)
+            Wt, a = _f32c(W2), None
+            t = gemm(h, Wt, trans_b=True, bias=_f32c(b2), act=ACT_TANH)
         w3c, b3c = _f32c(w3).reshape(heads, A), _f32c(b3).reshape(heads)
-        att = torch.empty((T, heads), device=dev, dtype=torch.float32)
-        z = torch.empty((B, H), device=dev, dtype=torch.float32)
-        teacher = W4 is not None
-        if teacher:
-            C = W4.shape[0]
-            W4c, b4c = _f32c(W4), _f32c(b4)
-            P = torch.empty((T, C), device=dev, dtype=torch.float32)
-            PP = torch.empty((T, C), device=dev, dtype=torch.float32)
-            BL = torch.empty((B, C), device=dev, dtype=torch.float32)
-            BP = torch.empty((B, C), device=dev, dtype=torch.float32)
-        else:
-            C, W4c, b4c, P, PP, BL, BP = 0, None, None, None, None, None, None
-        if not teacher and H > 1024:
-            call("isic_attn_pool_wide_fwd", h, t, w3c, b3c, offsets, B, H, A, heads, int(max_bag), att, z)
-        else:
-            call("isic_attn_pool_fwd", h, t, w3c, b3c, W4c, b4c, offsets, B, H, A, heads, C, int(max_bag), att, z, P, PP,
-                 BL, BP)
-        ctx.dims = (B, H, A, heads, C, int(max_bag))
-        ctx.teacher = teacher
-        ctx.params = (W2, b2, w3, b3, Wg, bg, W4, b4)
-        ctx.save_for_backward(h, a, t, att, P, Wcat, w3c, W4c, offsets)
-        if teacher:
+        W4c, b4c = (_f32c(W4), _f32c(b4)) if ctx.teacher else (None, None)
+        att, z, P, PP, BL, BP = _pool_forward(h, t, w3c, b3c, W4c, b4c, offsets, max_bag, heads)
+        ctx.cfg = (int(max_bag), heads)
+        ctx.params = (W2, b2, w3, b3, Wg, bg, W4, b4)   # the callers' tensors: Parameters take their gradients in place
+        ctx.save_for_backward(h, t, att, P, w3c, W4c, offsets, a, Wt)      # Wt: the front GEMM's weight, W2 or [W2 ; Wg]
+        if ctx.teacher:
             ctx.mark_non_differentiable(att, P, PP, BP)
             return z, att, P, PP, BL, BP
         ctx.mark_non_differentiable(att)
@@ -610,68 +579,21 @@ class GatedAttnPoolFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, *rest):
-        h, a, t, att, P, Wcat, w3c, W4c, offsets = ctx.saved_tensors
-        B, H, A, heads, C, max_bag = ctx.dims
+        *saved, a, Wt = ctx.saved_tensors
+        pool = _Pool(*saved, *ctx.cfg)
         dBL = rest[3] if ctx.teacher else None
-        T, nA = h.shape[0], heads * A
-        dev = h.device
         dz = _f32c(dz) if dz is not None else None
         dBL = _f32c(dBL) if dBL is not None else None
-        d_h = torch.empty((T, H), device=dev, dtype=torch.float32)
-        d_s = torch.empty((T, heads), device=dev, dtype=torch.float32)
-        d_P = torch.empty((T, C), device=dev, dtype=torch.float32) if ctx.teacher else None
-        d_p = torch.empty((T, 2 * nA), device=dev, dtype=torch.float32)
-        if not ctx.teacher and (H > 1024 or heads > 4):
-            if dz is None:
-                dz = torch.zeros((B, H), device=dev, dtype=torch.float32)
-            # isic_attn_pool_wide_bwd refuses a NULL d_u (ISIC_ERR_BAD_ARG): d_p serves as the scratch buffer for its ungated
-            # d_u ([T, heads A], the first half of d_p's memory), and isic_gate_bwd_f32 overwrites all of d_p next
-            call("isic_attn_pool_wide_bwd", h, t, att, w3c, offsets, B, H, A, heads, max_bag, dz, d_h, 0, d_p, d_s)
-        else:
-            call("isic_attn_pool_bwd", h, t, att, P, w3c, W4c, offsets, B, H, A, heads, C, max_bag, dBL, dz, d_h, 0,
-                 None, d_s, d_P)                                    # d_u = NULL: the kernel skips that store
-        # d_p = d_v | d_g and, in the same pass, sums = d_b2 | d_bg | d_w3 | d_b3 (fixed-order slabs, no atomics)
-        sums = (torch.empty if T > 0 else torch.zeros)((3 * nA + heads,), device=dev, dtype=torch.float32)
-        ws = _workspace(call("isic_gate_bwd_f32_workspace_bytes", T, heads, A), dev)
-        call("isic_gate_bwd_f32", d_s, w3c, a, T, heads, A, d_p, sums[:2 * nA], sums[2 * nA:3 * nA], sums[3 * nA:], 0.0,
-             ws, ws.numel() if ws is not None else 0)
         pW2, pb2, pw3, pb3, pWg, pbg, pW4, pb4 = ctx.params
-        small = [sums[:nA], sums[2 * nA:3 * nA], sums[3 * nA:], sums[nA:2 * nA]]          # d_b2, d_w3, d_b3, d_bg
-        targets = [_acc_target(p) for p in (pb2, pw3, pb3, pbg)]
-        if all(g is not None for g in targets):
-            # the four live in different places of the flat gradient buffer: one launch adds all of them in place
-            multi_copy([g.view(-1) for g in targets], small, accumulate=True)
-            db2 = dw3 = db3 = dbg = None
+        if ctx.gated:
+            d_h, d_a, d_P, (dW2, db2, dw3, db3, dWg, dbg) = _gated_back(pool, (pW2, pb2, pw3, pb3, pWg, pbg), a, ctx.stacked,
+                                                                      dz, dBL)
         else:
-            db2, dw3, db3, dbg = small[0], small[1].view(heads, A), small[2], small[3]
-        if ctx.stacked:
-            dW = gemm(d_p, h, trans_a=True)                          # [2 heads A, H]: both weight gradients in one GEMM
-            dW2, dWg = dW[:nA], dW[nA:]
-        else:
-            # two Parameters: a GEMM over each column half of d_p, into the flat gradient buffer where it is there (the same
-            # GEMM with beta = 1: the same bits as the gradient tensor plus autograd's add)
-            dW2 = dWg = None
-            tW2, tWg = _acc_target(pW2), _acc_target(pWg)
-            if tW2 is not None:
-                gemm(d_p[:, :nA], h, trans_a=True, out=tW2, beta=1.0)
-            else:
-                dW2 = gemm(d_p[:, :nA], h, trans_a=True)
-            if tWg is not None:
-                gemm(d_p[:, nA:], h, trans_a=True, out=tWg, beta=1.0)
-            else:
-                dWg = gemm(d_p[:, nA:], h, trans_a=True)
-        gemm(d_p, Wcat, out=d_h, beta=1.0)                           # d_h += d_v W2 + d_g Wg
-        dW4 = db4 = None
-        if ctx.teacher:
-            tW4, tb4 = _acc_target(pW4), _acc_target(pb4)
-            if tW4 is not None:
-                gemm(d_P, h, trans_a=True, out=tW4, beta=1.0)
-            else:
-                dW4 = gemm(d_P, h, trans_a=True)
-            if tb4 is not None:
-                colsum(d_P, out=tb4, beta=1.0)
-            else:
-                db4 = colsum(d_P)
+            d_h, d_a, d_P, (dW2, db2, dw3, db3) = _tanh_back(pool, (pW2, pb2, pw3, pb3), dz, dBL)
+            dWg = dbg = None
+        gemm(d_a, Wt, out=d_h, beta=1.0)                     # d_h += d_u W2, or d_v W2 + d_g Wg
+        # the teacher's tail: dW4 = d_P^T h, db4 = the column sums of d_P
+        dW4, db4 = (_grad_gemm(pW4, d_P, pool.h), _grad_colsum(pb4, d_P)) if ctx.teacher else (None, None)
         return d_h, dW2, db2, dw3, db3, dWg, dbg, dW4, db4, None, None, None
 
 
@@ -679,9 +601,7 @@ def attn_pool(h, W2, b2, w3, b3, offsets, max_bag, heads=1, W4=None, b4=None, Wg
     """``Wg`` [heads*A, H], ``bg`` [heads*A]: the gate operands of gated attention pooling; None is the ungated pool."""
     if (Wg is None) != (bg is None):
         raise ValueError("attn_pool: the gate takes both Wg and bg")
-    if Wg is not None:
-        return GatedAttnPoolFn.apply(h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets, max_bag, heads)
-    return AttnPoolFn.apply(h, W2, b2, w3, b3, W4, b4, offsets, max_bag, heads)
+    return AttnPoolFn.apply(h, W2, b2, w3, b3, Wg, bg, W4, b4, offsets, max_bag, heads)
 
 
 # --------------------------------------------------------------------------- LayerNorm (+ReLU +dropout +residual)

@@ -215,16 +215,12 @@ spmm.register_autograd(_spmm_bwd, setup_context=_spmm_setup)
 @custom_op("isic_hip::attn_pool", mutates_args=())
 def attn_pool(h: Tensor, W2: Tensor, b2: Tensor, w3: Tensor, b3: Tensor, offsets: Tensor, max_bag: int,
               heads: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (z[B, H], att[T, heads], t[T, heads*A]); t = tanh(h W2^T + b2) is returned for the backward op."""
+    """-> (z[B, H], att[T, heads], t[T, heads*A]); t = tanh(h W2^T + b2) is returned for the backward op.  The pool entries
+    are chosen where ``ops.attn_pool`` chooses them (``ops._pool_wide``): the same domain, heads up to 8 and H up to 4096."""
     h2 = _c(h)
-    T, H = h2.shape
     A = W2.shape[0] // heads
-    B = offsets.numel() - 1
     t = _o.gemm(h2, _c(W2), trans_b=True, bias=_c(b2), act=_o.ACT_TANH)
-    att = torch.empty((T, heads), device=h2.device, dtype=torch.float32)
-    z = torch.empty((B, H), device=h2.device, dtype=torch.float32)
-    call("isic_attn_pool_fwd", h2, t, _c(w3).reshape(heads, A), _c(b3).reshape(heads), None, None, offsets, B, H, A, heads, 0,
-         int(max_bag), att, z, None, None, None, None)
+    att, z = _o._pool_forward(h2, t, _c(w3).reshape(heads, A), _c(b3).reshape(heads), None, None, offsets, max_bag, heads)[:2]
     return z, att, t
 
 
@@ -238,30 +234,13 @@ def _(h, W2, b2, w3, b3, offsets, max_bag, heads):
 @custom_op("isic_hip::attn_pool_backward", mutates_args=())
 def attn_pool_backward(dz: Tensor, h: Tensor, t: Tensor, att: Tensor, W2: Tensor, w3: Tensor, offsets: Tensor, max_bag: int,
                        heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    h2, W2c = _c(h), _c(W2)
-    T, H = h2.shape
-    A = W2c.shape[0] // heads
-    B = offsets.numel() - 1
-    d_h = torch.empty((T, H), device=h2.device, dtype=torch.float32)
-    d_u = torch.empty((T, heads * A), device=h2.device, dtype=torch.float32)
-    d_s = torch.empty((T, heads), device=h2.device, dtype=torch.float32)
-    if H <= 128 and A <= 128:                                             # as ops.AttnPoolFn: per-bag sums out of the pool kernel
-        nA = heads * A
-        psum = torch.empty((B, 2 * nA + heads), device=h2.device, dtype=torch.float32)
-        call("isic_attn_pool_bwd_sums", h2, t, att, None, _c(w3).reshape(heads, A), None, offsets, B, H, A, heads, 0, int(max_bag),
-             None, _c(dz), d_h, 0, d_u, d_s, None, psum)
-        sums = _o.colsum(psum)
-        db2, dw3, db3 = sums[:nA].clone(), sums[nA:2 * nA].reshape(w3.shape).clone(), sums[2 * nA:].clone()
-    else:
-        call("isic_attn_pool_bwd", h2, t, att, None, _c(w3).reshape(heads, A), None, offsets, B, H, A, heads, 0, int(max_bag), None,
-             _c(dz), d_h, 0, d_u, d_s, None)
-        db2 = _o.colsum(d_u)
-        full = _o.gemm(d_s, t, trans_a=True)                               # [heads, heads*A]
-        dw3 = torch.stack([full[k, k * A:(k + 1) * A] for k in range(heads)]).reshape(w3.shape)
-        db3 = _o.colsum(d_s)
-    dW2 = _o.gemm(d_u, h2, trans_a=True)
+    W2c = _c(W2)
+    pool = _o._Pool(_c(h), t, att, None, _c(w3).reshape(heads, W2c.shape[0] // heads), None, offsets, int(max_bag), heads)
+    # the backward of ops.AttnPoolFn's ungated form; no Parameters handed over: every gradient comes back as a tensor
+    d_h, d_u, _d_P, (dW2, db2, dw3, db3) = _o._tanh_back(pool, (None,) * 4, _c(dz), None)
     _o.gemm(d_u, W2c, out=d_h, beta=1.0)
-    return d_h, dW2, db2, dw3, db3
+    # (db2, dw3, db3 may be slices of one column-sum buffer: an op's outputs must not share memory)
+    return d_h, dW2, db2.clone(), dw3.reshape(w3.shape).clone(), db3.clone()
 
 
 @attn_pool_backward.register_fake

@@ -89,15 +89,16 @@ def test_spmm_op_equals_function():
     _same(g1[1], g0[1], "dbias")
 
 
-@pytest.mark.parametrize("heads", [1, 4])
-def test_attn_pool_op_equals_function(heads):
+@pytest.mark.parametrize("heads,H", [(1, 128), (4, 128), (8, 64), (2, 1028)],      # the last two: the wide pool entries
+                         ids=["1", "4", "heads8-H64", "heads2-H1028"])
+def test_attn_pool_op_equals_function(heads, H):
     from isic_hip import ops
     from isic_hip.bags import BagOffsets
     O = _ops()
     gen = torch.Generator().manual_seed(6)
     sizes = [196, 64, 1, 130, 17]
     offs = BagOffsets.from_lengths(sizes, DEV)
-    T, H, A = offs.total, 128, 32
+    T, A = offs.total, 32
     h = _leaf(T, H, gen=gen)
     W2, b2 = _leaf(heads * A, H, gen=gen, scale=0.1), _leaf(heads * A, gen=gen, scale=0.1)
     w3, b3 = _leaf(heads, A, gen=gen, scale=0.3), _leaf(heads, gen=gen, scale=0.1)
