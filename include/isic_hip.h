@@ -678,5 +678,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_wide.h"
 /* The gate of gated attention pooling (tanh branch x sigmoid branch in front of the pool kernels, forward and backward with its column sums): three more entry points, same conventions. */
 #include "isic_hip_gated.h"
+/* Patch graphs of unequal size: the subgraphs induced by the lesion patches of a record set (count, then a stable compaction) and the one-launch batch assembly out of a ragged CSR store: three more entry points, same conventions. */
+#include "isic_hip_ragged.h"
 
 #endif /* ISIC_HIP_H */

@@ -57,8 +57,43 @@ def _frame(path):
     return obj if isinstance(obj, pd.DataFrame) else pd.DataFrame(obj)
 
 
-def load_fold_records(root, embedding_model, fold, split, variant):
-    """`05:248-270`: graph blueprints joined one-to-one with patch statistics."""
+def load_lesion_flags(paths):
+    """-> {image id: (patch ids [m], flags [m])} from patch-level frames as ``save_latent.extract_latents`` returns them
+    (columns ``image_path`` or ``image_id``, ``patch_id``, ``patch_in_mask``): the patches of one image in patch-id order,
+    the way `01_train_mil_teacher.py` forms its bags.  The image id is the ``image_id`` column, else the file name of
+    ``image_path`` without its extension."""
+    flags = {}
+    for path in paths:
+        df = _frame(path)
+        missing = {"patch_id", "patch_in_mask"} - set(df.columns)
+        if missing or not ({"image_id", "image_path"} & set(df.columns)):
+            raise ValueError(f"{path}: not a patch-level frame (needs image_path or image_id, patch_id, patch_in_mask)")
+        ids = df["image_id"].astype(str) if "image_id" in df.columns else \
+            df["image_path"].map(lambda p: os.path.splitext(os.path.basename(str(p)))[0])
+        for image_id, grp in df.assign(_image=ids.values).groupby("_image", sort=False):
+            grp = grp.sort_values("patch_id")
+            flags[str(image_id)] = (grp["patch_id"].to_numpy(dtype=np.int64), grp["patch_in_mask"].to_numpy() != 0)
+    return flags
+
+
+def _keep_flags(lesion_flags, image_id, n):
+    """The ``keep`` array [n] of one record: the image's flags in patch order when the frame has all n patches, else placed
+    at their patch ids (a frame written with ``remove_background=True`` lists the lesion patches only)."""
+    if image_id not in lesion_flags:
+        raise ValueError(f"No lesion flags for image {image_id}")
+    pid, flag = lesion_flags[image_id]
+    if len(pid) == n:
+        return flag.copy()
+    if len(pid) > n or (len(pid) and (pid.min() < 0 or pid.max() >= n)) or len(np.unique(pid)) != len(pid):
+        raise ValueError(f"Lesion flags of image {image_id} do not fit its {n} patches")
+    keep = np.zeros(n, dtype=bool)
+    keep[pid] = flag
+    return keep
+
+
+def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=None):
+    """`05:248-270`: graph blueprints joined one-to-one with patch statistics.  ``lesion_flags`` (``load_lesion_flags``)
+    attaches ``"keep"`` [n] to every record; an image id without flags is a ``ValueError`` that names it."""
     gpath = Path(root) / "graph_outputs" / embedding_model / "graph_dataset.pkl"
     spath = Path(root) / "patch_stats" / embedding_model / f"patch_stats_fold_{fold}_{split}.pkl"
     if not gpath.exists() or not spath.exists():
@@ -76,6 +111,8 @@ def load_fold_records(root, embedding_model, fold, split, variant):
         if x.ndim != 2 or ei.shape[0] != 2:
             raise ValueError(f"Invalid graph record for image {row['image_id']}")
         records.append({"x": x, "edge_index": ei, "y": int(row["label"]), "image_id": str(row["image_id"])})
+        if lesion_flags is not None:
+            records[-1]["keep"] = _keep_flags(lesion_flags, records[-1]["image_id"], x.shape[0])
     return records
 
 
@@ -91,7 +128,8 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
     return T.train_gnn_fold(model, train_records, val_records, test_records, lr=args.learning_rate,
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
                             min_delta=args.min_delta, graphs_per_step=args.graphs_per_step, num_classes=num_classes,
-                            device=device, device_metrics=args.device_metrics)
+                            device=device, device_metrics=args.device_metrics,
+                            lesion_only=bool(getattr(args, "lesion_flags", None)))
 
 
 def aggregate(rows, prefix):
@@ -147,6 +185,10 @@ def parse_args(argv=None):
     p.add_argument("--graphs-per-step", type=int, default=1, help="graphs per optimizer step per GPU (1 = reference)")
     p.add_argument("--device-metrics", action="store_true",
                    help="score every evaluation on the device (isic_hip.metrics) instead of sklearn on the host")
+    p.add_argument("--lesion-flags", nargs="+", type=Path, default=None, metavar="PATH",
+                   help="patch-level frames (save_latent: patch_id, patch_in_mask per image): train on the subgraph induced by "
+                        "the lesion patches of every graph (give the run a --results-csv directory of its own: the result "
+                        "key does not record the option); not in the reference")
     return p.parse_args(argv)
 
 
@@ -172,6 +214,7 @@ def run_gnn_experiments(args):
         except Exception:
             pass
     results = pd.read_csv(out_path) if out_path.exists() else pd.DataFrame()
+    lesion_flags = load_lesion_flags(args.lesion_flags) if args.lesion_flags else None
     for emb in models:
         if emb not in available:
             raise FileNotFoundError(f"No graph artifacts for embedding model {emb}")
@@ -185,7 +228,7 @@ def run_gnn_experiments(args):
             load_variant = "grid4" if variant == "none" else variant
             vals, tests, epochs, detail = [], [], [], []
             for fold in args.folds:
-                tr, va, te = (load_fold_records(root, emb, fold, s, load_variant) for s in ("train", "val", "test"))
+                tr, va, te = (load_fold_records(root, emb, fold, s, load_variant, lesion_flags) for s in ("train", "val", "test"))
                 n_cls = max(r["y"] for r in tr + va + te) + 1
                 vm, tm, be = train_one_fold(tr, va, te, args, fold, n_cls, tr[0]["x"].shape[1], device)
                 vals.append(vm); tests.append(tm); epochs.append(be)

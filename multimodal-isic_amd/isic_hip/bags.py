@@ -44,6 +44,17 @@ class BagOffsets:
         return o
 
     @classmethod
+    def from_uploaded(cls, host_offsets, device_offsets):
+        """Offsets whose device copy exists already (part of a larger upload): no host -> device copy of their own."""
+        o = cls.__new__(cls)
+        o.host = np.asarray(host_offsets, dtype=np.int64).reshape(-1)
+        o.num_bags = int(o.host.size - 1)
+        o.max_bag = int(np.diff(o.host).max()) if o.host.size > 1 else 0
+        o.total = int(o.host[-1])
+        o.device = device_offsets
+        return o
+
+    @classmethod
     def from_lengths(cls, lengths, device):
         return cls(np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]), device)
 

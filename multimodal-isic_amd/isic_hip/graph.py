@@ -83,6 +83,57 @@ def random_graphs(seeds, n_nodes, r_values, device=None):
     return out
 
 
+def _dev_i64(v, device):
+    if isinstance(v, torch.Tensor):
+        return v.to(device=device, dtype=torch.int64).contiguous()
+    import numpy as np
+    return torch.as_tensor(np.asarray(v, dtype=np.int64)).to(device)
+
+
+def induced_subgraphs(edge_index, edge_offsets, node_offsets, keep, edge_weight=None):
+    """The subgraph induced by the kept nodes of every graph of a record set, in two launches and ONE read-back
+    (include/isic_hip_ragged.h; tests/ragged_graph_ref.py restates it in numpy).  ``edge_index`` int64 [2, E] on the device
+    with LOCAL node ids, graph g owning edges ``edge_offsets[g]:edge_offsets[g+1]`` and nodes ``node_offsets[g]:
+    node_offsets[g+1]`` of ``keep`` ([T], non-zero = kept; a graph without a kept node keeps every node).  Returns
+    ``(edge_index', edge_offsets', node_offsets', rows)`` -- device int64 tensors, compact LOCAL ids, edge order and node
+    order preserved, ``rows`` [T'] the old LOCAL id of every kept node -- and the compacted ``edge_weight'`` as a fifth
+    element when ``edge_weight`` is given.  An edge endpoint outside its graph is a ``ValueError`` raised before anything
+    is written."""
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index must be [2, E]")
+    if not edge_index.is_cuda:
+        raise IsicHipError("induced_subgraphs needs device tensors (no CPU fallback)")
+    dev = edge_index.device
+    ei = edge_index.to(torch.int64).contiguous()
+    eoff, noff = _dev_i64(edge_offsets, dev), _dev_i64(node_offsets, dev)
+    kp = keep if isinstance(keep, torch.Tensor) else torch.as_tensor(keep)
+    kp = (kp != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    G, T, E = int(noff.numel()) - 1, int(kp.numel()), int(ei.shape[1])
+    if G < 0 or eoff.numel() != G + 1:
+        raise ValueError("edge_offsets and node_offsets must both have G + 1 entries")
+    ew = _f32c(edge_weight) if edge_weight is not None else None
+    if ew is not None and ew.numel() != E:
+        raise ValueError("edge_weight must have one entry per edge")
+    new_id = torch.empty(T, device=dev, dtype=torch.int32)
+    counts = torch.zeros((2, G + 1), device=dev, dtype=torch.int64)        # row 0: kept nodes, row 1: kept edges; [G] stays 0
+    bad = torch.zeros(G, device=dev, dtype=torch.int32)                     # (uint32 on the device side)
+    call("isic_induced_subgraph_count", noff, eoff, ei[0], ei[1], kp, G, T, E, new_id, counts[0], counts[1], bad)
+    # exclusive prefix sums with the totals appended: [0, c0, c0 + c1, ...]
+    offs = torch.cumsum(counts, dim=1).roll(1, dims=1)
+    offs[:, 0] = 0
+    head = torch.cat([offs[:, -1], (bad != 0).sum().view(1)]).cpu().tolist()          # the one read-back: T', E', bad graphs
+    t_out, e_out, n_bad = int(head[0]), int(head[1]), int(head[2])
+    if n_bad:
+        raise ValueError(f"induced_subgraphs: {n_bad} graph(s) have an edge endpoint outside [0, n) or offsets outside the arrays")
+    ei_out = torch.empty((2, e_out), device=dev, dtype=torch.int64)
+    rows = torch.empty(t_out, device=dev, dtype=torch.int64)
+    ew_out = torch.empty(e_out, device=dev, dtype=torch.float32) if ew is not None else None
+    call("isic_induced_subgraph_write", noff, eoff, ei[0], ei[1], ew, new_id, G, T, E, offs[0], offs[1], t_out, e_out,
+         ei_out[0], ei_out[1], ew_out, rows)
+    out = (ei_out, offs[1].clone(), offs[0].clone(), rows)
+    return out + (ew_out,) if ew is not None else out
+
+
 class GraphBatch:
     """Destination-major CSR (+ its transpose) of a batch of graphs with GCN symmetric
     normalisation and self loops (PyG ``gcn_norm`` semantics, `05_train_gnns.py:82`)."""

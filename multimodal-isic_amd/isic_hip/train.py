@@ -337,13 +337,25 @@ def train_milnet_fold(model, train_set, val_set, *, optimizer="adamw", lr=2.2e-4
 
 
 # ----------------------------------------------------------------------------- patch-graph GNN
+# Whether GraphStore(lesion_only=True) assembles its batches out of a ragged stack when the caller does not say
+# (DESIGN.md §4 "Lesion-only patch graphs": the measurement behind the value).
+RAGGED_STACK_DEFAULT_LESION_ONLY = True
+
+
 class GraphStore:
     """Graph records resident in HBM with their normalised CSR built once (graphs are static across
     epochs; the reference re-uploads x and edge_index every step, `05:340-343`)."""
 
-    def __init__(self, records, device, needs_graph=True, mode="gcn"):
+    def __init__(self, records, device, needs_graph=True, mode="gcn", lesion_only=False, ragged_stack=None):
         """``mode``: aggregation of the CSR the model's layers need (``gnn_models._GRAPH_MODE``: 'gcn' =
-        self loops + symmetric normalisation, 'sum' = GINConv, 'mean' = SAGEConv)."""
+        self loops + symmetric normalisation, 'sum' = GINConv, 'mean' = SAGEConv).
+        ``lesion_only``: every record carries ``"keep"`` (bool [n], the lesion flag of each patch) and the store holds the
+        subgraph induced by the kept patches of every record (``graph.induced_subgraphs``: one call over the whole record
+        set, ``x`` gathered once; a record without a kept patch keeps all of them).
+        ``ragged_stack``: graphs of unequal size are assembled per step by ONE launch out of one CSR built over the whole
+        record set (``isic_csr_batch_assemble_ragged``) instead of being rebuilt from concatenated edge lists.  ``None`` =
+        ``RAGGED_STACK_DEFAULT_LESION_ONLY`` for a lesion-only store and off otherwise; with ``True`` an equal-size store
+        assembles through the ragged entry too."""
         if mode not in GraphBatch.MODES:
             raise ValueError(f"unknown graph mode '{mode}'")
         self.device, self.records, self.mode = device, records, mode
@@ -357,6 +369,11 @@ class GraphStore:
         self.ei = [dev_tensor(r["edge_index"], torch.int64, np.int64)
                    if needs_graph and r.get("edge_index") is not None else None for r in records]
         self.needs_graph = needs_graph
+        self.lesion_only = bool(lesion_only)
+        self._ragged, self._xcat = None, None
+        if self.lesion_only:
+            self._restrict_to_lesion(dev_tensor)
+        self._want_ragged = (self.lesion_only and RAGGED_STACK_DEFAULT_LESION_ONLY) if ragged_stack is None else bool(ragged_stack)
         # equal-sized graphs (the reference's case): one [G, n, D] tensor, a step's batch is ONE index_select
         self.y_dev = torch.as_tensor(self.y, device=device)
         self._xstack = torch.stack(self.x) if self.x and len({tuple(t.shape) for t in self.x}) == 1 else None
@@ -364,6 +381,95 @@ class GraphStore:
         self._chunks = {}          # evaluation chunks (sequential index ranges) repeat every epoch: cached whole
         self._stack = None
         self._build_stack()
+        if self._want_ragged:
+            self._build_ragged()
+
+    def _restrict_to_lesion(self, dev_tensor):
+        """Replace every record's graph by the subgraph its ``keep`` flags induce: the edge lists of all records go through
+        ``induced_subgraphs`` in one call, the node features are gathered by its ``rows`` once.  ``self.x`` / ``self.ei``
+        become views of the two results, so every path of the store (single graph, slow path, stacks) sees induced records."""
+        from .graph import induced_subgraphs
+        dev = self.device
+        ns = [int(t.shape[0]) for t in self.x]
+        keeps = []
+        for i, (r, n) in enumerate(zip(self.records, ns)):
+            if r.get("keep") is None:
+                raise ValueError(f"GraphStore(lesion_only=True): record {i} has no 'keep' flags")
+            k = np.asarray(r["keep"].cpu() if isinstance(r["keep"], torch.Tensor) else r["keep"]).reshape(-1) != 0
+            if k.size != n:
+                raise ValueError(f"GraphStore(lesion_only=True): record {i} has {n} nodes but {k.size} 'keep' flags")
+            keeps.append(k)
+        if not self.x:
+            return
+        es = [int(e.shape[1]) if e is not None else 0 for e in self.ei]
+        noff = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        eoff = np.concatenate([[0], np.cumsum(es)]).astype(np.int64)
+        have = [e for e in self.ei if e is not None]
+        ei = torch.cat(have, dim=1) if have else torch.empty((2, 0), device=dev, dtype=torch.int64)
+        keep = torch.as_tensor(np.concatenate(keeps).astype(np.uint8)).to(dev)
+        ei2, eoff2, noff2, rows = induced_subgraphs(ei, eoff, noff, keep)
+        sizes = torch.stack([noff2, eoff2]).cpu().numpy()                    # per-graph sizes of the induced records
+        n2, e2 = np.diff(sizes[0]).tolist(), np.diff(sizes[1]).tolist()
+        start = torch.as_tensor(noff[:-1], device=dev).repeat_interleave(torch.as_tensor(n2, device=dev))
+        xcat = self._xcat = torch.cat(self.x)[rows + start]
+        self.rows = list(torch.split(rows, n2))                              # old local id of every kept node, per record
+        self.x = list(torch.split(xcat, n2))
+        parts = torch.split(ei2, e2, dim=1)
+        self.ei = [p if e is not None else None for p, e in zip(parts, self.ei)]
+
+    def _build_ragged(self):
+        """One ``GraphBatch`` over the whole record set, graphs of any size: graph g owns rows ``node_off[g]:node_off[g+1]``
+        and -- rows being stored in order, in both orientations -- slots ``nnz_off[g]:nnz_off[g+1]``, ``nnz_off[g] =
+        rowptr[node_off[g]]``.  The CSR keeps its GLOBAL ids; a step's batch is cut out and rebased by one launch.  The
+        per-graph sizes are read back once, here; a step computes its prefix sums from them on the host."""
+        if not self.needs_graph or not self.x or any(e is None for e in self.ei):
+            return
+        dev, G = self.device, len(self.x)
+        ns = np.asarray([int(t.shape[0]) for t in self.x], dtype=np.int64)
+        es = np.asarray([int(e.shape[1]) for e in self.ei], dtype=np.int64)
+        noff_h = np.concatenate([[0], np.cumsum(ns)])
+        if noff_h[-1] + es.sum() >= 2 ** 31 - 16 or ns.min() < 1:
+            return
+        noff = torch.as_tensor(noff_h, device=dev)
+        ei = torch.cat([e + int(o) for e, o in zip(self.ei, noff_h[:-1])], dim=1)
+        full = GraphBatch(ei, int(noff_h[-1]), mode=self.mode)
+        nnz_off = full.rowptr[noff].to(torch.int64)
+        if not bool((full.rowptr_t[noff].to(torch.int64) == nnz_off).all()):
+            return                             # the two orientations do not share their segments: no ragged stack
+        same = self._xstack is not None
+        self._ragged = {"G": G, "graph": full, "node_off": noff, "nnz_off": nnz_off, "n": ns, "edges": es,
+                        "nnz": np.diff(nnz_off.cpu().numpy()),
+                        "x": self._xstack.view(-1, self._xstack.shape[-1]) if same else
+                             (self._xcat if self._xcat is not None else torch.cat(self.x))}
+
+    def _ragged_graph(self, key, want_rows):
+        """The batch of the graphs ``key`` (host indices, repeats allowed) out of the ragged stack: ``sel`` and the batch's two
+        prefix arrays go up in one copy, one launch writes the seven CSR arrays and the row index.
+        -> (offsets, GraphBatch, rows int32 padded for ``ops.linear_rows`` or None)"""
+        rg = self._ragged
+        sel = np.asarray(key, dtype=np.int64)
+        if sel.size and (sel.min() < 0 or sel.max() >= rg["G"]):
+            raise IndexError("GraphStore.batch: graph index out of range")
+        B = int(sel.size)
+        up = np.empty(3 * B + 2, dtype=np.int64)                              # sel | node_base [B+1] | nnz_base [B+1]
+        up[:B] = sel
+        up[B] = up[2 * B + 1] = 0
+        np.cumsum(rg["n"][sel], out=up[B + 1:2 * B + 1])
+        np.cumsum(rg["nnz"][sel], out=up[2 * B + 2:])
+        tn, tz = int(up[2 * B]), int(up[3 * B + 1])
+        i32, dev = torch.int32, self.device
+        d = torch.from_numpy(up).to(dev)
+        full = rg["graph"]
+        parts = {"rowptr": torch.empty(tn + 1, device=dev, dtype=i32), "rowptr_t": torch.empty(tn + 1, device=dev, dtype=i32),
+                 "col": torch.empty(tz, device=dev, dtype=i32), "col_t": torch.empty(tz, device=dev, dtype=i32),
+                 "val": torch.empty(tz, device=dev, dtype=torch.float32), "val_t": torch.empty(tz, device=dev, dtype=torch.float32),
+                 "perm_t": torch.empty(tz, device=dev, dtype=i32)}
+        rows = torch.empty((tn + 7) // 8 * 8 + 8, device=dev, dtype=i32) if want_rows else None
+        call("isic_csr_batch_assemble_ragged", d[:B], d[B:2 * B + 1], d[2 * B + 1:], B, rg["G"], tn, tz, rg["node_off"],
+             rg["nnz_off"], full.rowptr, full.rowptr_t, full.col, full.col_t, full.val, full.val_t, full.perm_t,
+             parts["rowptr"], parts["rowptr_t"], parts["col"], parts["col_t"], parts["val"], parts["val_t"], parts["perm_t"], rows)
+        offs = BagOffsets.from_uploaded(up[B:2 * B + 1], d[B:2 * B + 1])
+        return offs, GraphBatch.from_parts(tn, int(rg["edges"][sel].sum()), self.mode, parts), rows
 
     def _build_stack(self):
         """Graphs are static across epochs, so their normalised CSR is built ONCE: one ``GraphBatch`` launch over
@@ -422,8 +528,12 @@ class GraphStore:
     def batch_rows(self, idx):
         """The batch WITHOUT gathering its node features: (x_store[G*n, D], rows int32, n_rows, offsets, GraphBatch) with
         batch node row i = x_store[rows[i]] -- for ``GraphMIL(x_store, x_rows=(rows, n_rows), ...)``, whose input projection
-        reads through the index (``ops.linear_rows``).  Equal-sized graphs with a stacked CSR and a device index only;
-        ``None`` otherwise (use ``batch``)."""
+        reads through the index (``ops.linear_rows``).  Equal-sized graphs with a stacked CSR and a device index, or a
+        ragged stack (graphs of any size, host or device index; x_store[sum n_g, D]); ``None`` otherwise (use ``batch``)."""
+        if self._ragged is not None:           # graphs of any size: the feature store is the concatenation of all records' x
+            key = idx.tolist() if isinstance(idx, torch.Tensor) else [int(i) for i in idx]      # (a host list costs no read-back)
+            offs, graph, rows = self._ragged_graph(key, True)
+            return self._ragged["x"], rows, offs.total, offs, graph
         if not (isinstance(idx, torch.Tensor) and idx.is_cuda) or self._xstack is None or self._stack is None or not self.needs_graph:
             return None
         sel = idx.to(torch.int64)
@@ -446,7 +556,12 @@ class GraphStore:
                 self._single[i] = GraphBatch(self.ei[i], n, mode=self.mode)
             return self.x[i], BagOffsets.single(n, self.device), self._single.get(i)
         uniform = self._xstack is not None and (not self.needs_graph or self._stack is not None)
-        if uniform:
+        if self._ragged is not None:
+            if on_dev:
+                key = tuple(int(i) for i in idx.tolist())
+            offs, graph, rows = self._ragged_graph(key, True)
+            x = self._ragged["x"].index_select(0, rows[:offs.total])
+        elif uniform:
             sel = idx.to(torch.int64) if on_dev else torch.as_tensor(key, device=self.device)
             n, D = int(self._xstack.shape[1]), int(self._xstack.shape[2])
             x = self._xstack[sel].reshape(-1, D)
@@ -484,7 +599,9 @@ def gnn_metrics(labels, scores, num_classes):
 @torch.no_grad()
 def evaluate_gnn(model, store, num_classes, chunk=32, device_metrics=False):
     """`05_train_gnns.py:273-302`.  ``device_metrics``: the same keys from counts formed on the device (one read-back per
-    evaluation; the AUROC is NaN when a class has no validation sample, where ``gnn_metrics`` gives sklearn's NaN)."""
+    evaluation; the AUROC is NaN when a class has no validation sample, where ``gnn_metrics`` gives sklearn's NaN).
+    ``store`` decides what is scored: a ``GraphStore(lesion_only=True)`` evaluates the induced graphs, through its ragged stack
+    when it has one."""
     model.eval()
     n = len(store.x)
     if n == 0:
@@ -511,17 +628,22 @@ def evaluate_gnn(model, store, num_classes, chunk=32, device_metrics=False):
 
 def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, weight_decay=1e-4, epochs=1,
                    patience=16, min_delta=1e-6, graphs_per_step=1, num_classes=7, device=None, rng=None,
-                   device_metrics=False, history=None):
+                   device_metrics=False, history=None, lesion_only=False, ragged_stack=None):
     """`05_train_gnns.py:305-358`: AdamW, epoch order = np.random.permutation, best state by validation
     balanced accuracy.  The class weights of `05:328-331` cancel for single-sample CE and
     batched steps keep the unweighted per-graph mean.  Returns (val_metrics, test_metrics, best_epoch).
     ``device_metrics``: every evaluation is scored on the device (``evaluate_gnn``).  ``history``: a list that receives one
-    ``{"epoch", "val_bacc", "val_loss"}`` per epoch."""
+    ``{"epoch", "val_bacc", "val_loss"}`` per epoch.
+    ``lesion_only`` / ``ragged_stack``: as ``GraphStore`` takes them, for all three record sets (every record carries
+    ``"keep"``).  A ragged batch changes its shapes from step to step, so a captured step (``graphs.CapturedStep``) is not offered
+    for it: ragged steps run eagerly."""
     rank, world = dist_info()
     device = device or next(model.parameters()).device
     needs = model.gnn_type != "mlp"
     mode = model.graph_mode or "gcn"
-    tr, va, te = (GraphStore(r, device, needs, mode=mode) for r in (train_records, val_records, test_records))
+    tr, va, te = (GraphStore(r, device, needs, mode=mode, lesion_only=lesion_only, ragged_stack=ragged_stack)
+                  for r in (train_records, val_records, test_records))
+    ragged = tr._ragged is not None            # its steps index the store with the host list: the batch's sizes are host facts
     opt = optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
     ddp.broadcast_parameters(opt.flat.data)
     sync = ddp.GradSync(opt.flat.grad, world_size=world)
@@ -540,12 +662,12 @@ def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, 
             sync.reset()
             if mine:
                 mine_dev = order_dev[s + lo:s + hi]
-                br = tr.batch_rows(mine_dev) if len(mine) > 1 and hasattr(model, "classifier_light") else None
-                if br is not None:                           # equal-sized graphs: no gather, the projection reads through the index
+                br = tr.batch_rows(mine if ragged else mine_dev) if len(mine) > 1 and hasattr(model, "classifier_light") else None
+                if br is not None:                           # stacked graphs: no gather, the projection reads through the index
                     x, rows, n_rows, offs, g = br
                     xr = (rows, n_rows)
                 else:
-                    x, offs, g = tr.batch(mine_dev if len(mine) > 1 else mine)
+                    x, offs, g = tr.batch(mine_dev if len(mine) > 1 and not ragged else mine)
                     xr = None
                 with ops.fused_grad_accumulation():          # zero_grad -> backward -> step: gradients go straight into the flat buffer
                     y = tr.y_dev[mine_dev]
