@@ -680,5 +680,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_gated.h"
 /* Patch graphs of unequal size: the subgraphs induced by the lesion patches of a record set (count, then a stable compaction) and the one-launch batch assembly out of a ragged CSR store: three more entry points, same conventions. */
 #include "isic_hip_ragged.h"
+/* The heterophily stage on patch graphs of unequal size (edge measures with a lattice position per node, per-graph class bookkeeping, self-loop compaction, lambda_2 with a node count per graph): four more entry points, same conventions. */
+#include "isic_hip_hetero_ragged.h"
 
 #endif /* ISIC_HIP_H */

@@ -6,6 +6,9 @@ the MI355X (``measure_heterophily.py``): each chunk of images is summarised on t
 is one CSV.
 
     python 04_measure_heterophily.py --graph-outputs-root graph_outputs --patch-stats-root patch_stats --out-csv h.csv
+
+``--lesion-flags PATH...`` (the patch-level frames ``05_train_gnns.py --lesion-flags`` takes) measures the subgraph that every
+image's lesion flags induce -- the graphs the GNNs are then trained on -- and adds a ``num_nodes`` column after ``num_edges``.
 """
 import argparse
 import os
@@ -16,9 +19,12 @@ import pandas as pd
 import torch
 
 import measure_heterophily as mh
+from lesion_flags import _keep_flags, load_lesion_flags
 
 
-def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0"):
+def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0", lesion_flags=None):
+    """``lesion_flags`` (``lesion_flags.load_lesion_flags``): summarise the induced subgraphs
+    (``heterophily_summary_lesion_only``); an image id without flags is a ``ValueError`` that names it."""
     rows = []
     for model in sorted(os.listdir(graph_root)):
         gpath = os.path.join(graph_root, model, "graph_dataset.pkl")
@@ -44,7 +50,12 @@ def build_master_summary(graph_root, patch_root, images_per_launch=64, device="c
                     dom = torch.as_tensor(np.stack([np.asarray(r["dominant_class"], dtype=np.int32) for r in recs])).to(dev)
                     eis = [torch.as_tensor(np.asarray(mh.edge_index_from_variant(r, variant), dtype=np.int64)).to(dev)
                            for r in recs]
-                    summary = mh.heterophily_summary_device(x, pp, dom, eis)      # one copy to the host per chunk
+                    if lesion_flags is not None:
+                        keep = torch.as_tensor(np.stack([_keep_flags(lesion_flags, str(r["image_id"]), int(x.shape[1]))
+                                                         for r in recs])).to(dev)
+                        summary = mh.heterophily_summary_lesion_only(x, pp, dom, eis, keep)
+                    else:
+                        summary = mh.heterophily_summary_device(x, pp, dom, eis)      # one copy to the host per chunk
                     kind = "grid" if variant.startswith("grid") else ("knn" if variant.startswith("knn") else "random")
                     metas = [{"model_name": r.get("model_name", model), "fold": int(fold), "split": split,
                               "image_id": r["image_id"], "label": r.get("label"), "graph_variant": variant,
@@ -62,8 +73,11 @@ def main():
     ap.add_argument("--out-csv", default="heterophily_summary.csv")
     ap.add_argument("--images-per-launch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--lesion-flags", nargs="+", default=None, metavar="PATH",
+                    help="patch-level frames with patch_in_mask: measure the subgraph the lesion patches induce")
     a = ap.parse_args()
-    df = build_master_summary(a.graph_outputs_root, a.patch_stats_root, a.images_per_launch, a.device)
+    flags = load_lesion_flags(a.lesion_flags) if a.lesion_flags else None
+    df = build_master_summary(a.graph_outputs_root, a.patch_stats_root, a.images_per_launch, a.device, lesion_flags=flags)
     df.drop(columns=["H_compat_matrix"]).to_csv(a.out_csv, index=False)
     print(f"wrote {len(df)} rows ({df['graph_variant'].nunique() if len(df) else 0} graph variants) to {a.out_csv}")
 

@@ -8,7 +8,6 @@ launch, and one-process-per-GPU data parallelism under ``torch.distributed.run``
 import argparse
 import copy
 import os
-import pickle
 import random
 import sys
 from pathlib import Path
@@ -21,6 +20,7 @@ import torch
 
 from gnn_models import GNN_TYPES, GraphMIL  # noqa: F401  (GraphMIL re-exported like the reference module)
 from isic_hip import train as T
+from lesion_flags import _frame, _keep_flags, load_lesion_flags  # noqa: F401  (shared with 04_measure_heterophily.py)
 
 DEFAULT_NEIGHBORS = tuple(range(1, 9)) + (12, 16)
 RESULT_KEY = ["embedding_model", "graph_variant", "graph_model", "seed", "hidden_dim", "num_layers", "dropout",
@@ -49,46 +49,6 @@ def edge_index_for_variant(row, variant):
         if variant.startswith(prefix):
             return np.asarray(row[col][int(variant[len(prefix):])], dtype=np.int64)
     raise ValueError(f"Unknown graph variant: {variant}")
-
-
-def _frame(path):
-    with Path(path).open("rb") as fh:
-        obj = pickle.load(fh)
-    return obj if isinstance(obj, pd.DataFrame) else pd.DataFrame(obj)
-
-
-def load_lesion_flags(paths):
-    """-> {image id: (patch ids [m], flags [m])} from patch-level frames as ``save_latent.extract_latents`` returns them
-    (columns ``image_path`` or ``image_id``, ``patch_id``, ``patch_in_mask``): the patches of one image in patch-id order,
-    the way `01_train_mil_teacher.py` forms its bags.  The image id is the ``image_id`` column, else the file name of
-    ``image_path`` without its extension."""
-    flags = {}
-    for path in paths:
-        df = _frame(path)
-        missing = {"patch_id", "patch_in_mask"} - set(df.columns)
-        if missing or not ({"image_id", "image_path"} & set(df.columns)):
-            raise ValueError(f"{path}: not a patch-level frame (needs image_path or image_id, patch_id, patch_in_mask)")
-        ids = df["image_id"].astype(str) if "image_id" in df.columns else \
-            df["image_path"].map(lambda p: os.path.splitext(os.path.basename(str(p)))[0])
-        for image_id, grp in df.assign(_image=ids.values).groupby("_image", sort=False):
-            grp = grp.sort_values("patch_id")
-            flags[str(image_id)] = (grp["patch_id"].to_numpy(dtype=np.int64), grp["patch_in_mask"].to_numpy() != 0)
-    return flags
-
-
-def _keep_flags(lesion_flags, image_id, n):
-    """The ``keep`` array [n] of one record: the image's flags in patch order when the frame has all n patches, else placed
-    at their patch ids (a frame written with ``remove_background=True`` lists the lesion patches only)."""
-    if image_id not in lesion_flags:
-        raise ValueError(f"No lesion flags for image {image_id}")
-    pid, flag = lesion_flags[image_id]
-    if len(pid) == n:
-        return flag.copy()
-    if len(pid) > n or (len(pid) and (pid.min() < 0 or pid.max() >= n)) or len(np.unique(pid)) != len(pid):
-        raise ValueError(f"Lesion flags of image {image_id} do not fit its {n} patches")
-    keep = np.zeros(n, dtype=bool)
-    keep[pid] = flag
-    return keep
 
 
 def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=None):

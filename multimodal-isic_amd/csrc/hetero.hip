@@ -6,8 +6,10 @@
 // HBM-bound row gather: one wave per edge, both embedding rows read with 16-byte loads (D floats each), squared
 // difference reduced across the 64 lanes; the class-probability rows (C <= 64) ride on the first lanes.
 // Self loops are NOT dropped here (the reference strips them, :117-118): the host filters on src != dst so that
-// the surviving values keep the reference's edge order.
+// the surviving values keep the reference's edge order.  The gather itself is edge_gather.inc, shared with the kernel for
+// graphs of unequal size (hetero_ragged.hip).
 #include "common.h"
+#include "edge_gather.inc"
 
 namespace {
 
@@ -21,36 +23,13 @@ __global__ __launch_bounds__(256) void edge_hetero_kernel(const float* __restric
   const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
   for (int64_t e = wave0; e < E; e += nwaves) {
     const int64_t s = src[e], d = dst[e];
-    const float* xs = x + (size_t)s * D;
-    const float* xd = x + (size_t)d * D;
-    float acc = 0.f;
-    if ((D & 3) == 0) {
-      for (int i = lane * 4; i < D; i += 256) {
-        const float4 a = *reinterpret_cast<const float4*>(xs + i);
-        const float4 b = *reinterpret_cast<const float4*>(xd + i);
-        const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-        acc += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-      }
-    } else {
-      for (int i = lane; i < D; i += 64) {
-        const float df = xs[i] - xd[i];
-        acc += df * df;
-      }
-    }
-    float kl = 0.f;
-    for (int c = lane; c < C; c += 64) {
-      const float ps = probs[(size_t)s * C + c], pd = probs[(size_t)d * C + c];
-      kl += ps * logf((ps + eps) / (pd + eps));
-    }
-    acc = wave_sum(acc);
-    kl = wave_sum(kl);
+    float acc, kl;
+    edge_row_sums(x + (size_t)s * D, x + (size_t)d * D, probs + (size_t)s * C, probs + (size_t)d * C, D, C, eps, lane, acc, kl);
     if (lane == 0) {
       h_dir[e] = 0.5f * acc;
       h_kl[e] = kl;
       // lattice coordinates of the node inside ITS graph (04:124-125 uses % 14 and // 14 of the local index)
-      const int ls = (int)(s % nodes_per_graph), ld = (int)(d % nodes_per_graph);
-      const float dx = (float)(ls % grid_w - ld % grid_w), dy = (float)(ls / grid_w - ld / grid_w);
-      h_spatial[e] = sqrtf(dx * dx + dy * dy);
+      h_spatial[e] = lattice_distance((int)(s % nodes_per_graph), (int)(d % nodes_per_graph), grid_w);
       same_class[e] = dominant[s] == dominant[d] ? 1.f : 0.f;
     }
   }

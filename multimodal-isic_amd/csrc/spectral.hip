@@ -18,6 +18,9 @@
 //               ~6 rounds to fp64 resolution on the Gershgorin interval.
 // All sums run in a fixed order: the result is bit-identical from run to run.
 //
+// isic_laplacian_lambda2_ragged_f64 (include/isic_hip_hetero_ragged.h): the same device function per graph, with the node
+// count of every graph taken from node_offsets, LOCAL ids and the LDS sized by a host-known max_nodes.
+//
 // isic_segment_stats_f32: mean / population std / median of values[m][e0:e1) per (measure m, segment g), one workgroup
 // per pair: fp64 sums, bitonic sort of the segment in LDS (fp32 keys, padded with +inf to a power of two).
 #include <float.h>
@@ -55,11 +58,12 @@ __host__ __device__ constexpr size_t lambda2_lds_bytes(int n) {
   return ((size_t)n * (n + 1) / 2 + 2 * (size_t)n + 8) * sizeof(double);
 }
 
-__global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_kernel(const int64_t* __restrict__ src,
-                                                                       const int64_t* __restrict__ dst,
-                                                                       const int64_t* __restrict__ edge_offsets, int n,
-                                                                       double* __restrict__ lambda2) {
-  extern __shared__ double sm[];
+// lambda_2 of the graph with n nodes whose edges are src/dst[e0:e1) with node ids id_base .. id_base + n - 1, by the whole
+// workgroup, into *out; `sm` is the dynamic LDS (lambda2_lds_bytes(n) at least).  e0 <= e1 are valid positions (the callers
+// check the offsets); n <= 1 gives 0.0, an id outside the graph NaN.  Block-uniform call sites only.
+__device__ __forceinline__ void laplacian_lambda2_graph(double* sm, const int64_t* __restrict__ src,
+                                                        const int64_t* __restrict__ dst, int64_t e0, int64_t e1, int n,
+                                                        int64_t id_base, double* __restrict__ out) {
   const int T = n * (n + 1) / 2;
   double* Ap = sm;                       // packed lower triangle
   double* vec0 = sm + T;                 // d^-1/2, then the Householder vector v, then the diagonal d
@@ -68,22 +72,15 @@ __global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_kernel(const int
   int* flag = reinterpret_cast<int*>(scal + 6);   // flag[0] bad input, flag[1] multisection winner
   unsigned int* cnt = reinterpret_cast<unsigned int*>(sm);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t g = blockIdx.x;
 
-  const int64_t e0 = edge_offsets[g], e1 = edge_offsets[g + 1];
-  if (e0 < 0 || e1 < e0 || (e1 > e0 && !(src && dst))) {   // uniform over the block: no edge is read
-    if (tid == 0) lambda2[g] = __builtin_nan("");
-    return;
-  }
   for (int s = tid; s < T; s += SP_THREADS) Ap[s] = 0.0;
   if (tid == 0) flag[0] = 0;
   __syncthreads();
 
   // ---- 1. directed multiplicities
-  const int64_t base = g * (int64_t)n;
   int bad = 0;
   for (int64_t e = e0 + tid; e < e1; e += SP_THREADS) {
-    const int64_t s = src[e] - base, t = dst[e] - base;
+    const int64_t s = src[e] - id_base, t = dst[e] - id_base;
     if (s < 0 || s >= n || t < 0 || t >= n) {
       bad = 1;
       continue;
@@ -95,11 +92,11 @@ __global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_kernel(const int
   if (bad) atomicOr(&flag[0], 1);
   __syncthreads();
   if (flag[0]) {
-    if (tid == 0) lambda2[g] = __builtin_nan("");
+    if (tid == 0) *out = __builtin_nan("");
     return;
   }
-  if (n == 1) {
-    if (tid == 0) lambda2[g] = 0.0;
+  if (n <= 1) {
+    if (tid == 0) *out = 0.0;
     return;
   }
   // counters -> symmetric weight max(c_ij, c_ji) in place (each slot read and written by one lane)
@@ -235,7 +232,38 @@ __global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_kernel(const int
     }
     __syncthreads();
   }
-  if (tid == 0) lambda2[g] = 0.5 * (scal[2] + scal[3]);
+  if (tid == 0) *out = 0.5 * (scal[2] + scal[3]);
+}
+
+__global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_kernel(const int64_t* __restrict__ src,
+                                                                       const int64_t* __restrict__ dst,
+                                                                       const int64_t* __restrict__ edge_offsets, int n,
+                                                                       double* __restrict__ lambda2) {
+  extern __shared__ double sm[];
+  const int64_t g = blockIdx.x;
+  const int64_t e0 = edge_offsets[g], e1 = edge_offsets[g + 1];
+  if (e0 < 0 || e1 < e0 || (e1 > e0 && !(src && dst))) {   // uniform over the block: no edge is read
+    if (threadIdx.x == 0) lambda2[g] = __builtin_nan("");
+    return;
+  }
+  laplacian_lambda2_graph(sm, src, dst, e0, e1, n, g * (int64_t)n, lambda2 + g);
+}
+
+// graphs of unequal size with LOCAL ids (isic_hip_hetero_ragged.h): n_g from node_offsets, LDS sized for max_nodes
+__global__ __launch_bounds__(SP_THREADS) void laplacian_lambda2_ragged_kernel(const int64_t* __restrict__ src,
+                                                                              const int64_t* __restrict__ dst,
+                                                                              const int64_t* __restrict__ edge_offsets,
+                                                                              const int64_t* __restrict__ node_offsets,
+                                                                              int64_t E, int max_nodes,
+                                                                              double* __restrict__ lambda2) {
+  extern __shared__ double sm[];
+  const int64_t g = blockIdx.x;
+  const int64_t e0 = edge_offsets[g], e1 = edge_offsets[g + 1], n = node_offsets[g + 1] - node_offsets[g];
+  if (e0 < 0 || e1 < e0 || e1 > E || n < 0 || n > max_nodes) {   // uniform over the block: no edge is read
+    if (threadIdx.x == 0) lambda2[g] = __builtin_nan("");
+    return;
+  }
+  laplacian_lambda2_graph(sm, src, dst, e0, e1, (int)n, 0, lambda2 + g);
 }
 
 // ------------------------------------------------------------------------------------------- segment statistics
@@ -322,6 +350,26 @@ int isic_laplacian_lambda2_f64(const int64_t* src, const int64_t* dst, const int
     return ISIC_ERR_LAUNCH;
   hipLaunchKernelGGL(laplacian_lambda2_kernel, dim3((unsigned)G), dim3(SP_THREADS), lambda2_lds_bytes(nodes),
                      as_stream(stream), src, dst, edge_offsets, nodes, lambda2);
+  return isic_launch_status();
+}
+
+int isic_laplacian_lambda2_ragged_f64(const int64_t* src, const int64_t* dst, const int64_t* edge_offsets,
+                                      const int64_t* node_offsets, int G, int64_t E, int max_nodes, double* lambda2,
+                                      void* stream) {
+  ISIC_CHECK_ARG(G >= 0 && E >= 0 && max_nodes >= 0);
+  if (G == 0) return ISIC_OK;
+  ISIC_CHECK_ARG(edge_offsets && node_offsets && lambda2);
+  ISIC_CHECK_ARG(E == 0 || (src && dst));
+  if (max_nodes > ISIC_SPECTRAL_MAX_NODES || E >= 0x80000000LL) return ISIC_ERR_UNSUPPORTED;
+  static IsicPerDeviceOnce once;
+  if (isic_once_per_device(once, [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(laplacian_lambda2_ragged_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lambda2_lds_bytes(ISIC_SPECTRAL_MAX_NODES));
+      }) != hipSuccess)
+    return ISIC_ERR_LAUNCH;
+  hipLaunchKernelGGL(laplacian_lambda2_ragged_kernel, dim3((unsigned)G), dim3(SP_THREADS), lambda2_lds_bytes(max_nodes),
+                     as_stream(stream), src, dst, edge_offsets, node_offsets, E, max_nodes, lambda2);
   return isic_launch_status();
 }
 

@@ -1,7 +1,8 @@
 """Device launches of the heterophily stage's spectral and summary kernels (``csrc/spectral.hip``):
 
 * ``laplacian_lambda2`` -- lambda_2 of the symmetrised normalised Laplacian per graph (``isic_laplacian_lambda2_f64``,
-  04_measure_heterophily.py:149-159), one workgroup per graph, fp64;
+  04_measure_heterophily.py:149-159), one workgroup per graph, fp64; ``laplacian_lambda2_ragged`` is the same device code
+  for graphs of unequal size with local ids (``isic_laplacian_lambda2_ragged_f64``);
 * ``segment_stats`` -- mean / population std / median of contiguous segments (``isic_segment_stats_f32``,
   04_measure_heterophily.py:172-181), fp64 results.
 
@@ -31,6 +32,24 @@ def laplacian_lambda2(src, dst, edge_offsets, n_graphs, nodes):
     out = torch.empty(int(n_graphs), device=edge_offsets.device, dtype=torch.float64)
     call("isic_laplacian_lambda2_f64", src.contiguous().to(torch.int64), dst.contiguous().to(torch.int64),
          edge_offsets.contiguous().to(torch.int64), int(n_graphs), int(nodes), out)
+    return out
+
+
+def laplacian_lambda2_ragged(src, dst, edge_offsets, node_offsets, max_nodes):
+    """Graphs of unequal size (``isic_laplacian_lambda2_ragged_f64``): src/dst[E] int64 LOCAL node ids, edge_offsets and
+    node_offsets [G+1] int64 -> lambda_2 [G] fp64.  ``max_nodes`` is a host-known bound on the node counts; a graph above it,
+    with an id outside it or with offsets outside the arrays gets NaN, a graph of at most one node 0.0.
+    max_nodes > MAX_NODES raises (code UNSUPPORTED)."""
+    _dev(src, dst, edge_offsets, node_offsets)
+    G = int(node_offsets.numel()) - 1
+    if G < 0 or edge_offsets.numel() != G + 1:
+        raise IsicHipError("edge_offsets and node_offsets must both have G + 1 entries")
+    if src.numel() != dst.numel():
+        raise IsicHipError("src and dst differ in length")
+    out = torch.empty(G, device=edge_offsets.device, dtype=torch.float64)
+    call("isic_laplacian_lambda2_ragged_f64", src.contiguous().to(torch.int64), dst.contiguous().to(torch.int64),
+         edge_offsets.contiguous().to(torch.int64), node_offsets.contiguous().to(torch.int64), G, int(src.numel()),
+         int(max_nodes), out)
     return out
 
 

@@ -10,6 +10,11 @@ one HIP launch per batch (``isic_laplacian_lambda2_f64``: a workgroup per graph,
 multisection in LDS), with a dense ``torch.linalg.eigvalsh`` only for graphs above 196 nodes, which the kernel does
 not take.  ``heterophily_summary_device`` gives the per-image summaries of `:172-181` as device tensors
 (``isic_segment_stats_f32``).  The reference's plotting / aggregation code (`:229-589`) is out of scope.
+
+Graphs of unequal size -- the subgraphs that lesion flags induce (``heterophily_summary_lesion_only``,
+``compute_edge_heterophily_batch(keep=...)``) or any ragged record set (``heterophily_summary_ragged``) -- go through the
+entries of ``include/isic_hip_hetero_ragged.h``: local node ids, a lattice position per node, the class bookkeeping and the
+self-loop compaction inside HIP kernels, up to 196 nodes per graph.  The equal-size path above is unchanged.
 """
 from __future__ import annotations
 
@@ -125,12 +130,158 @@ def _device_measures(x, p, dom, ei, counts, n_img, N):
             "H_adj": h_adj, "expected": expected, "H_compat_matrix": compat, "lambda_2": lam2}
 
 
-def compute_edge_heterophily_batch(embeddings, patch_probs, dominant_class, edge_indices, device="cuda:0"):
-    """A batch of images of equal node count: lists of ``patch_embeddings[N,D]``, ``patch_probs[N,C]``,
-    ``dominant_class[N]`` and per-image ``edge_index[2,E_i]`` (local ids).  Returns one dict per image with the
-    reference's keys (`04:163-170`)."""
+def _ragged_measures(x, probs, dominant, edge_index, edge_offsets, node_offsets, patch_pos, max_nodes, grid_w=GRID_W, eps=EPS):
+    """The device part of the ragged path (include/isic_hip_hetero_ragged.h), four launches and a cumsum, nothing read back:
+    x[T,D], probs[T,C] fp32, dominant[T], edge_index[2,E] LOCAL ids, edge_offsets / node_offsets [G+1], patch_pos[T] or None.
+    Returns ``values`` [3,E] fp32 -- H_kl, H_dirichlet, H_spatial of the edges with src != dst, graph g's at columns
+    ``kept_offsets[g]:kept_offsets[g+1]`` in their input order --, ``kept_offsets`` [G+1], and per graph ``num_edges``,
+    ``H_adj``, ``expected``, ``H_compat_matrix``, ``lambda_2`` and ``bad`` (non-zero: invalid input, NaN results)."""
+    for t in (x, probs, dominant, edge_index, edge_offsets, node_offsets) + (() if patch_pos is None else (patch_pos,)):
+        if not t.is_cuda:
+            raise IsicHipError("the ragged heterophily path takes device tensors (no CPU fallback)")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index must be [2, E]")
+    dev = x.device
+    x = x.contiguous().float()
+    probs = probs.contiguous().float()
+    dom = dominant.contiguous().to(torch.int32)
+    ei = edge_index.contiguous().to(torch.int64)
+    eoff, noff = edge_offsets.contiguous().to(torch.int64), node_offsets.contiguous().to(torch.int64)
+    pos = None if patch_pos is None else patch_pos.contiguous().to(torch.int32)
+    T, D, C, E, G = int(x.shape[0]), int(x.shape[1]), int(probs.shape[1]), int(ei.shape[1]), int(noff.numel()) - 1
+    if G < 0 or eoff.numel() != G + 1:
+        raise ValueError("edge_offsets and node_offsets must both have G + 1 entries")
+    if probs.shape[0] != T or dom.numel() != T or (pos is not None and pos.numel() != T):
+        raise ValueError("x, probs, dominant and patch_pos must have one row per node")
+    # first: the launch that refuses graphs above spectral.MAX_NODES
+    lam2 = spectral.laplacian_lambda2_ragged(ei[0], ei[1], eoff, noff, max_nodes)
+    per_edge = torch.empty((4, E), device=dev, dtype=torch.float32)
+    call("isic_edge_heterophily_ragged_f32", x, probs, dom, pos, ei[0], ei[1], eoff, noff, None, G, T, E, D, C, int(grid_w),
+         float(eps), per_edge[0], per_edge[1], per_edge[2], per_edge[3])
+    kept_offsets = torch.zeros(G + 1, device=dev, dtype=torch.int64)
+    h_adj = torch.empty(G, device=dev, dtype=torch.float64)
+    expected = torch.empty(G, device=dev, dtype=torch.float64)
+    compat = torch.empty((G, C, C), device=dev, dtype=torch.float64)
+    bad = torch.zeros(G, device=dev, dtype=torch.int32)                      # (uint32 on the device side)
+    num_edges = torch.empty(G, device=dev, dtype=torch.int64)
+    call("isic_graph_homophily_ragged", dom, ei[0], ei[1], eoff, noff, G, T, E, C, num_edges, h_adj, expected, compat, bad)
+    torch.cumsum(num_edges, 0, out=kept_offsets[1:])
+    values = torch.zeros((3, E), device=dev, dtype=torch.float32)
+    call("isic_edge_values_compact_ragged_f32", per_edge, ei[0], ei[1], eoff, kept_offsets, G, 3, E, values)
+    return {"values": values, "kept_offsets": kept_offsets, "num_edges": num_edges, "H_adj": h_adj, "expected": expected,
+            "H_compat_matrix": compat, "lambda_2": lam2, "bad": bad}
+
+
+def heterophily_summary_ragged(x, probs, dominant, edge_index, edge_offsets, node_offsets, patch_pos=None, max_nodes=None):
+    """``heterophily_summary_device`` for graphs of unequal size, described as ``graph.induced_subgraphs`` returns them:
+    ``x[T,D]``, ``probs[T,C]``, ``dominant[T]``, ``edge_index[2,E]`` with LOCAL node ids, ``edge_offsets`` and
+    ``node_offsets`` ``[G+1]`` int64 -- device tensors.  ``patch_pos[T]`` is every node's position on the 14-wide lattice
+    (the ``rows`` of an induced subgraph; None: the local id).  ``max_nodes`` is a host-known bound on the node counts; left
+    out, it is read back from ``node_offsets`` (the only copy to the host).  Graphs above ``spectral.MAX_NODES`` nodes raise
+    ``IsicHipError`` with code -2.  Returns the dict of ``heterophily_summary_device`` plus ``num_nodes`` [G] int64; a graph
+    with an endpoint or class out of range or offsets outside the arrays gets NaN and ``num_edges`` 0."""
+    noff = node_offsets.to(torch.int64)
+    num_nodes = noff[1:] - noff[:-1]
+    if max_nodes is None:
+        max_nodes = int(num_nodes.max()) if num_nodes.numel() else 0
+    rm = _ragged_measures(x, probs, dominant, edge_index, edge_offsets, node_offsets, patch_pos, int(max_nodes))
+    E = int(rm["values"].shape[1])
+    # a segment above the kernel's limit gets NaN from the kernel itself, so E is bound enough
+    mean, std, median = spectral.segment_stats(rm["values"], rm["kept_offsets"], min(E, spectral.MAX_SEGMENT))
+    out = {"num_edges": rm["num_edges"], "num_nodes": num_nodes}
+    for i, m in enumerate(MEASURES[:3]):
+        out[f"{m}_mean"], out[f"{m}_std"], out[f"{m}_median"] = mean[i], std[i], median[i]
+    for m in ("H_adj", "lambda_2"):                                   # one value per image: std 0, median = mean
+        v = rm[m]
+        out[f"{m}_mean"], out[f"{m}_std"], out[f"{m}_median"] = v, torch.zeros_like(v), v.clone()
+    out["H_compat_matrix"] = rm["H_compat_matrix"]
+    return out
+
+
+def _concat_local_edges(edge_index, G, dev):
+    """``[G,2,E]`` or a list of ``[2,E_i]`` (local ids, device tensors) -> (edge_index [2, sum E_i], edge_offsets [G+1])."""
+    if isinstance(edge_index, torch.Tensor):
+        if not edge_index.is_cuda or edge_index.dim() != 3 or edge_index.shape[0] != G:
+            raise IsicHipError("edge_index: a device tensor [G, 2, E] or one device tensor [2, E_i] per image")
+        E = int(edge_index.shape[2])
+        return (edge_index.to(torch.int64).permute(1, 0, 2).reshape(2, G * E),
+                torch.arange(G + 1, device=dev, dtype=torch.int64) * E)
+    if len(edge_index) != G or not all(e.is_cuda for e in edge_index):
+        raise IsicHipError("edge_index: one device tensor [2, E_i] per image")
+    counts = [int(e.shape[1]) for e in edge_index]
+    ei = torch.cat([e.to(torch.int64) for e in edge_index], dim=1) if G else torch.zeros((2, 0), device=dev, dtype=torch.int64)
+    return ei, torch.as_tensor([0] + list(np.cumsum(counts)), dtype=torch.int64).to(dev)
+
+
+def _induce(x, probs, dominant, ei, eoff, noff, keep):
+    """Flat node tensors ``[T, .]`` of a record set and its lesion flags ``keep[T]`` -> the arguments of the ragged path for
+    the induced graphs: ``graph.induced_subgraphs``, then ONE gather of the three node tensors by ``rows``."""
+    from isic_hip.graph import induced_subgraphs
+    ei2, eoff2, noff2, rows = induced_subgraphs(ei, eoff, noff, keep)
+    G = int(noff.numel()) - 1
+    gid = torch.repeat_interleave(torch.arange(G, device=rows.device), noff2[1:] - noff2[:-1], output_size=int(rows.numel()))
+    idx = noff[gid] + rows
+    return x[idx], probs[idx], dominant[idx], ei2, eoff2, noff2, rows
+
+
+def heterophily_summary_lesion_only(x, probs, dominant, edge_index, keep):
+    """``heterophily_summary_device`` of the subgraphs that the lesion flags induce: ``x[G,N,D]``, ``probs[G,N,C]``,
+    ``dominant[G,N]``, ``edge_index`` ``[G,2,E]`` or a list of ``[2,E_i]`` (local ids), ``keep[G,N]`` (non-zero = lesion
+    patch; an image without a set flag keeps every node, as ``graph.induced_subgraphs`` defines) -- device tensors.  The
+    kept patches keep their place on the lattice (H_spatial); everything else is measured on the induced graph.  Returns
+    ``heterophily_summary_ragged``'s dict (``num_nodes``: the kept patches of every image)."""
+    for t in (x, probs, dominant, keep):
+        if not t.is_cuda:
+            raise IsicHipError("heterophily_summary_lesion_only takes device tensors (no CPU fallback)")
+    G, N, D = (int(s) for s in x.shape)
+    if tuple(keep.shape) != (G, N):
+        raise ValueError("keep must be [G, N]")
+    if N > spectral.MAX_NODES:
+        raise IsicHipError(f"the ragged heterophily path takes graphs of at most {spectral.MAX_NODES} nodes", code=-2)
+    dev = x.device
+    ei, eoff = _concat_local_edges(edge_index, G, dev)
+    noff = torch.arange(G + 1, device=dev, dtype=torch.int64) * N
+    xs, ps, ds, ei2, eoff2, noff2, rows = _induce(x.reshape(G * N, D), probs.reshape(G * N, -1), dominant.reshape(G * N), ei,
+                                                  eoff, noff, keep.reshape(G * N))
+    return heterophily_summary_ragged(xs, ps, ds, ei2, eoff2, noff2, patch_pos=rows, max_nodes=N)
+
+
+def _edge_heterophily_batch_ragged(embeddings, patch_probs, dominant_class, edge_indices, keep, dev):
+    """``compute_edge_heterophily_batch`` through the ragged path: images of any node count, optionally induced by ``keep``."""
+    n_img = len(embeddings)
+    embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
+    ns = [int(e.shape[0]) for e in embs]
+    if ns and max(ns) > spectral.MAX_NODES:
+        raise IsicHipError(f"the ragged heterophily path takes graphs of at most {spectral.MAX_NODES} nodes", code=-2)
+    cat = lambda arrs, dt: torch.as_tensor(np.concatenate([np.asarray(a, dtype=dt) for a in arrs])).to(dev)   # noqa: E731
+    x, p, dom = cat(embs, np.float32), cat(patch_probs, np.float32), cat(dominant_class, np.int32)
+    eis = [np.asarray(e, dtype=np.int64).reshape(2, -1) for e in edge_indices]
+    ei = torch.as_tensor(np.concatenate(eis, axis=1)).to(dev)
+    eoff = torch.as_tensor(np.concatenate([[0], np.cumsum([e.shape[1] for e in eis])]).astype(np.int64)).to(dev)
+    noff = torch.as_tensor(np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)).to(dev)
+    pos = None
+    if keep is not None:
+        if len(keep) != n_img or any(len(k) != n for k, n in zip(keep, ns)):
+            raise ValueError("keep: one flag per node of every image")
+        x, p, dom, ei, eoff, noff, pos = _induce(x, p, dom, ei, eoff, noff, cat(keep, np.bool_))
+    rm = _ragged_measures(x, p, dom, ei, eoff, noff, pos, max(ns) if ns else 0)
+    vals, bounds = rm["values"].cpu().numpy(), rm["kept_offsets"].cpu().numpy()
+    h_adj, compat, lam = rm["H_adj"].cpu().numpy(), rm["H_compat_matrix"].cpu().numpy(), rm["lambda_2"].cpu().numpy()
+    return [{"H_kl": vals[0, a:b], "H_dirichlet": vals[1, a:b], "H_spatial": vals[2, a:b], "H_adj": float(h_adj[i]),
+             "lambda_2": np.array([float(lam[i])]), "H_compat_matrix": compat[i]}
+            for i, (a, b) in enumerate(zip(bounds[:-1].tolist(), bounds[1:].tolist()))]
+
+
+def compute_edge_heterophily_batch(embeddings, patch_probs, dominant_class, edge_indices, device="cuda:0", keep=None):
+    """A batch of images: lists of ``patch_embeddings[N,D]``, ``patch_probs[N,C]``, ``dominant_class[N]`` and per-image
+    ``edge_index[2,E_i]`` (local ids).  Returns one dict per image with the reference's keys (`04:163-170`).  With ``keep``
+    (one flag array [N_i] per image: the lesion patches) the measures are those of the induced subgraphs, the surviving
+    edges in the reference's order; that and images of unequal node count go through the ragged path (at most 196 nodes
+    per image)."""
     dev = torch.device(device)
     n_img = len(embeddings)
+    if keep is not None or len({int(np.asarray(e).shape[0]) for e in embeddings}) > 1:
+        return _edge_heterophily_batch_ragged(embeddings, patch_probs, dominant_class, edge_indices, keep, dev)
     N = int(np.asarray(embeddings[0]).shape[0])
     C = int(np.asarray(patch_probs[0]).shape[1])
     x = torch.as_tensor(np.stack([np.asarray(e, dtype=np.float32) for e in embeddings])).to(dev).view(n_img * N, -1)
@@ -206,18 +357,22 @@ SUMMARY_STATS = ["num_edges"] + [f"{m}_{s}" for m in MEASURES for s in ("mean", 
 
 def summary_records(summary, metas):
     """A ``heterophily_summary_device`` result -> one dict per image in ``summarize_image``'s layout (the meta keys,
-    ``num_edges``, the statistics, ``H_compat_matrix``), from a single copy to the host."""
+    ``num_edges``, the statistics, ``H_compat_matrix``), from a single copy to the host.  A result of the ragged path
+    (``heterophily_summary_ragged`` / ``_lesion_only``) gives the same records with ``num_nodes`` after ``num_edges``."""
     compat = summary["H_compat_matrix"]
     G, C = int(compat.shape[0]), int(compat.shape[-1])
-    host = torch.cat([torch.stack([summary[k].to(torch.float64) for k in SUMMARY_STATS], dim=1), compat.reshape(G, C * C)],
-                     dim=1).cpu().numpy()
+    cols = [summary[k].to(torch.float64) for k in SUMMARY_STATS] + \
+        ([summary["num_nodes"].to(torch.float64)] if "num_nodes" in summary else [])
+    host = torch.cat([torch.stack(cols, dim=1), compat.reshape(G, C * C)], dim=1).cpu().numpy()
     rows = []
     for i, meta in enumerate(metas):
         out = dict(meta)
         out["num_edges"] = int(host[i, 0])
+        if "num_nodes" in summary:
+            out["num_nodes"] = int(host[i, len(SUMMARY_STATS)])
         for j, k in enumerate(SUMMARY_STATS[1:], start=1):
             out[k] = float(host[i, j])
-        out["H_compat_matrix"] = host[i, len(SUMMARY_STATS):].reshape(C, C)
+        out["H_compat_matrix"] = host[i, len(cols):].reshape(C, C)
         rows.append(out)
     return rows
 

@@ -84,14 +84,18 @@ class DeviceTeacherOutputs:
         y = self.labels.tolist()
         return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i]} for i in range(len(self))]
 
-    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None):
+    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None, keep=None):
         """Per-image heterophily summaries of a graph variant (`04_measure_heterophily.py:172-181`) from the resident
         tensors: ``measure_heterophily.heterophily_summary_device`` on ``x``, ``patch_probs``, ``dominant_class`` and
         ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host.  ``device_random``: see
-        ``edge_index``."""
+        ``edge_index``.  ``keep[G,N]`` (device, non-zero = lesion patch): the summaries of the subgraphs the flags induce
+        (``measure_heterophily.heterophily_summary_lesion_only``: ``num_nodes`` is added, the induced sizes are the one
+        read-back)."""
         import measure_heterophily as mh
-        return mh.heterophily_summary_device(self.x, self.patch_probs, self.dominant_class,
-                                             self.edge_index(variant, fold, seed, device_random=device_random))
+        ei = self.edge_index(variant, fold, seed, device_random=device_random)
+        if keep is not None:
+            return mh.heterophily_summary_lesion_only(self.x, self.patch_probs, self.dominant_class, ei, keep)
+        return mh.heterophily_summary_device(self.x, self.patch_probs, self.dominant_class, ei)
 
     # ------------------------------------------------------------------ exports (the reference's pickle schemas)
     def teacher_frame(self):
