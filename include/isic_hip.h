@@ -682,5 +682,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_ragged.h"
 /* The heterophily stage on patch graphs of unequal size (edge measures with a lattice position per node, per-graph class bookkeeping, self-loop compaction, lambda_2 with a node count per graph): four more entry points, same conventions. */
 #include "isic_hip_hetero_ragged.h"
+/* k-NN graphs among patch sets of unequal size (the lesion patches of a frame): a Gram kernel sized by each graph and the edge lists of several k values with the per-image clamp in one launch: two more entry points, same conventions. */
+#include "isic_hip_knn_ragged.h"
 
 #endif /* ISIC_HIP_H */

@@ -9,6 +9,8 @@ is one CSV.
 
 ``--lesion-flags PATH...`` (the patch-level frames ``05_train_gnns.py --lesion-flags`` takes) measures the subgraph that every
 image's lesion flags induce -- the graphs the GNNs are then trained on -- and adds a ``num_nodes`` column after ``num_edges``.
+``--lesion-knn`` (with ``--lesion-flags``): a ``knn<k>`` variant is measured on the k-NN graph rebuilt AMONG the lesion patches
+of every image, k clamped per image as the reference clamps it on a lesion-only frame; other variants keep the induced subgraph.
 """
 import argparse
 import os
@@ -22,9 +24,12 @@ import measure_heterophily as mh
 from lesion_flags import _keep_flags, load_lesion_flags
 
 
-def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0", lesion_flags=None):
+def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0", lesion_flags=None, lesion_knn=False):
     """``lesion_flags`` (``lesion_flags.load_lesion_flags``): summarise the induced subgraphs
-    (``heterophily_summary_lesion_only``); an image id without flags is a ``ValueError`` that names it."""
+    (``heterophily_summary_lesion_only``); an image id without flags is a ``ValueError`` that names it.
+    ``lesion_knn``: knn<k> variants are rebuilt among the lesion patches (``heterophily_summary_lesion_knn``)."""
+    if lesion_knn and lesion_flags is None:
+        raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs lesion_flags")
     rows = []
     for model in sorted(os.listdir(graph_root)):
         gpath = os.path.join(graph_root, model, "graph_dataset.pkl")
@@ -53,7 +58,10 @@ def build_master_summary(graph_root, patch_root, images_per_launch=64, device="c
                     if lesion_flags is not None:
                         keep = torch.as_tensor(np.stack([_keep_flags(lesion_flags, str(r["image_id"]), int(x.shape[1]))
                                                          for r in recs])).to(dev)
-                        summary = mh.heterophily_summary_lesion_only(x, pp, dom, eis, keep)
+                        if lesion_knn and variant.startswith("knn"):
+                            summary = mh.heterophily_summary_lesion_knn(x, pp, dom, keep, int(variant[3:]))
+                        else:
+                            summary = mh.heterophily_summary_lesion_only(x, pp, dom, eis, keep)
                     else:
                         summary = mh.heterophily_summary_device(x, pp, dom, eis)      # one copy to the host per chunk
                     kind = "grid" if variant.startswith("grid") else ("knn" if variant.startswith("knn") else "random")
@@ -75,9 +83,15 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--lesion-flags", nargs="+", default=None, metavar="PATH",
                     help="patch-level frames with patch_in_mask: measure the subgraph the lesion patches induce")
+    ap.add_argument("--lesion-knn", action="store_true",
+                    help="with --lesion-flags: measure knn<k> variants on the k-NN graph rebuilt among the lesion patches "
+                         "(k clamped per image) instead of the induced subgraph")
     a = ap.parse_args()
+    if a.lesion_knn and not a.lesion_flags:
+        ap.error("--lesion-knn needs --lesion-flags")
     flags = load_lesion_flags(a.lesion_flags) if a.lesion_flags else None
-    df = build_master_summary(a.graph_outputs_root, a.patch_stats_root, a.images_per_launch, a.device, lesion_flags=flags)
+    df = build_master_summary(a.graph_outputs_root, a.patch_stats_root, a.images_per_launch, a.device, lesion_flags=flags,
+                              lesion_knn=a.lesion_knn)
     df.drop(columns=["H_compat_matrix"]).to_csv(a.out_csv, index=False)
     print(f"wrote {len(df)} rows ({df['graph_variant'].nunique() if len(df) else 0} graph variants) to {a.out_csv}")
 

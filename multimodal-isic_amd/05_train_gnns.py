@@ -76,8 +76,16 @@ def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=
     return records
 
 
-def train_one_fold(train_records, val_records, test_records, args, fold, num_classes, input_dim, device):
-    """`05:305-358` (model configuration of the reference call site, `05:310-326`)."""
+def lesion_knn_k(args, variant):
+    """k of ``GraphStore(lesion_knn=k)`` for this variant: set by ``--lesion-knn`` for ``knn<k>`` variants only."""
+    if getattr(args, "lesion_knn", False) and variant is not None and variant.startswith("knn"):
+        return int(variant[3:])
+    return None
+
+
+def train_one_fold(train_records, val_records, test_records, args, fold, num_classes, input_dim, device, variant=None):
+    """`05:305-358` (model configuration of the reference call site, `05:310-326`).  ``variant``: the graph variant of the
+    records, which ``--lesion-knn`` needs (``lesion_knn_k``)."""
     set_seed(args.seed + fold)
     model = GraphMIL(input_dim=input_dim, gnn_type=args.gnn if isinstance(args.gnn, str) else args.gnn[0],
                      gnn_hidden=args.hidden_dim, gnn_layers=args.num_layers, gnn_dropout=args.dropout,
@@ -89,7 +97,7 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
                             min_delta=args.min_delta, graphs_per_step=args.graphs_per_step, num_classes=num_classes,
                             device=device, device_metrics=args.device_metrics,
-                            lesion_only=bool(getattr(args, "lesion_flags", None)))
+                            lesion_only=bool(getattr(args, "lesion_flags", None)), lesion_knn=lesion_knn_k(args, variant))
 
 
 def aggregate(rows, prefix):
@@ -149,7 +157,14 @@ def parse_args(argv=None):
                    help="patch-level frames (save_latent: patch_id, patch_in_mask per image): train on the subgraph induced by "
                         "the lesion patches of every graph (give the run a --results-csv directory of its own: the result "
                         "key does not record the option); not in the reference")
-    return p.parse_args(argv)
+    p.add_argument("--lesion-knn", action="store_true",
+                   help="with --lesion-flags: for knn<k> variants rebuild the k-NN graph AMONG the lesion patches of every image "
+                        "(k clamped per image, as the reference builds it on a lesion-only frame) instead of inducing the "
+                        "stored graph; other variants keep the induced subgraph")
+    args = p.parse_args(argv)
+    if args.lesion_knn and not args.lesion_flags:
+        p.error("--lesion-knn needs --lesion-flags")
+    return args
 
 
 def run_gnn_experiments(args):
@@ -190,7 +205,7 @@ def run_gnn_experiments(args):
             for fold in args.folds:
                 tr, va, te = (load_fold_records(root, emb, fold, s, load_variant, lesion_flags) for s in ("train", "val", "test"))
                 n_cls = max(r["y"] for r in tr + va + te) + 1
-                vm, tm, be = train_one_fold(tr, va, te, args, fold, n_cls, tr[0]["x"].shape[1], device)
+                vm, tm, be = train_one_fold(tr, va, te, args, fold, n_cls, tr[0]["x"].shape[1], device, variant=load_variant)
                 vals.append(vm); tests.append(tm); epochs.append(be)
                 detail.append({"embedding_model": emb, "graph_variant": variant, "graph_model": args.gnn, "fold": fold,
                                "seed": args.seed, "hidden_dim": args.hidden_dim, "num_layers": args.num_layers,

@@ -18,7 +18,7 @@ import pandas as pd
 import torch
 
 from isic_hip.bags import BagOffsets
-from isic_hip.graph import knn_indices, random_graphs
+from isic_hip.graph import knn_edges_ragged, knn_indices, knn_indices_ragged, random_graphs
 
 NUM_NODES = 196
 GRID_SIDE = 14
@@ -75,6 +75,21 @@ def knn_edge_index_batched(x, offsets, k_values):
         src = (src_all if offs.num_bags > 1 else src_all)[:, None].expand(-1, kk)
         out[k] = torch.stack([src.reshape(-1), dst.reshape(-1)], dim=0).long()
     return out
+
+
+def knn_edge_index_ragged(x, offsets, k_values):
+    """x[sum N, D] (device or host) + ragged graph offsets -> {k: (edge_index[2, E_k], edge_offsets[G+1])} with LOCAL node
+    ids: every graph gets the reference's OWN clamp k_g = max(1, min(k, n_g - 1)) and a graph of fewer than 2 nodes no edge
+    (`03_build_graphs.py:42-45` on a frame that holds only the lesion patches of each image), where
+    ``knn_edge_index_batched`` clamps by the smallest graph of the batch.  One top-k launch for the largest k that any
+    graph can use and one launch for all edge lists (``isic_hip.graph.knn_indices_ragged`` / ``knn_edges_ragged``);
+    ``edge_index`` stays on the device, ``edge_offsets`` is a host array."""
+    dev = x.device if x.is_cuda else _device()
+    offs = offsets if isinstance(offsets, BagOffsets) else BagOffsets(offsets, dev)
+    ks = [int(k) for k in k_values]
+    kmax = max(1, min(max(ks), offs.max_bag - 1)) if ks else 1
+    nn = knn_indices_ragged(x.to(dev, torch.float32), offs, kmax)           # [T, kmax] local ids, -1 past n_g - 1
+    return knn_edges_ragged(nn, offs, ks)
 
 
 def _knn_edge_index(x, k=8):
@@ -137,14 +152,29 @@ def _build_image_graph_blueprints(row, k_values, r_values, seed):
     }
 
 
-def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values, seed, device_random=False):
+def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values, seed, device_random=False,
+                        per_graph_k=False):
     """All images of one patch-stats frame in ONE k-NN launch (same records as the per-row loop).  ``device_random``: the
     random graphs of all images come from one launch as well (``random_edge_index_batched``) instead of the host builder;
-    the records hold the same numpy arrays either way."""
+    the records hold the same numpy arrays either way.  ``per_graph_k``: the images may differ in their number of patches
+    (a lesion-only frame) and each gets the reference's own clamp of k by ITS patch count, an image of fewer than 2
+    patches ``[2, 0]`` arrays (``knn_edge_index_ragged``); without it k is clamped by the smallest image of the frame and
+    an image of fewer than 2 patches is a ``ValueError``."""
     xs = [np.asarray(v, dtype=np.float32) for v in teacher_df["patch_embeddings"]]
     offs = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])])
-    knn = knn_edge_index_batched(torch.from_numpy(np.concatenate(xs)), offs, [int(k) for k in k_values])
-    knn = {k: v.cpu().numpy() for k, v in knn.items()}
+    knn_off = None
+    if per_graph_k:
+        if xs:
+            d = xs[0].shape[1] if xs[0].ndim == 2 else 0
+            xcat = np.concatenate([a.reshape(-1, d) for a in xs])
+            rag = knn_edge_index_ragged(torch.from_numpy(xcat), offs, [int(k) for k in k_values])
+        else:
+            rag = {int(k): (torch.empty((2, 0), dtype=torch.long), np.zeros(1, dtype=np.int64)) for k in k_values}
+        knn = {k: e.cpu().numpy() for k, (e, _) in rag.items()}
+        knn_off = {k: o for k, (_, o) in rag.items()}
+    else:
+        knn = knn_edge_index_batched(torch.from_numpy(np.concatenate(xs)), offs, [int(k) for k in k_values])
+        knn = {k: v.cpu().numpy() for k, v in knn.items()}
     rand = None
     if device_random and len(teacher_df):
         rand = random_edge_index_batched(NUM_NODES, r_values, [seed + fold * 10_000 + row_idx for row_idx in teacher_df.index])
@@ -154,6 +184,10 @@ def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values,
         lo, n = int(offs[i]), int(offs[i + 1] - offs[i])
         per_k = {}
         for k in k_values:
+            if knn_off is not None:                        # sliced by the returned edge offsets, LOCAL ids already
+                eo = knn_off[int(k)]
+                per_k[int(k)] = knn[int(k)][:, int(eo[i]):int(eo[i + 1])]
+                continue
             kk = knn[int(k)].shape[1] // int(offs[-1])
             per_k[int(k)] = knn[int(k)][:, lo * kk:(lo + n) * kk] - (lo if len(xs) > 1 else 0)
         records.append({
@@ -169,9 +203,9 @@ def build_graph_records(teacher_df, model_name, fold, split, k_values, r_values,
 
 
 def process_model_directory(model_dir, output_root, k_values=DEFAULT_K_VALUES, r_values=DEFAULT_R_VALUES, seed=42,
-                            device_random=False):
+                            device_random=False, per_graph_k=False):
     """`03_build_graphs.py:117-149`: patch_stats_fold_*_*.pkl -> graph_outputs/<model>/graph_dataset.pkl.
-    ``device_random``: see ``build_graph_records``."""
+    ``device_random``, ``per_graph_k``: see ``build_graph_records``."""
     model_dir, output_root = Path(model_dir), Path(output_root)
     out_dir = output_root / model_dir.name
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -183,7 +217,7 @@ def process_model_directory(model_dir, output_root, k_values=DEFAULT_K_VALUES, r
         if not isinstance(frame, pd.DataFrame):
             frame = pd.DataFrame(frame)
         records += build_graph_records(frame, model_dir.name, fold, split, _as_list(k_values), _as_list(r_values), seed,
-                                       device_random=device_random)
+                                       device_random=device_random, per_graph_k=per_graph_k)
     out_path = out_dir / "graph_dataset.pkl"
     with open(out_path, "wb") as f:
         pickle.dump(pd.DataFrame(records), f)

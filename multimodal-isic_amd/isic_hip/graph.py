@@ -24,6 +24,111 @@ def knn_indices(x, offsets: BagOffsets, k, return_dist=False):
     return (idx, dist) if return_dist else idx
 
 
+KNN_RAGGED_MAX_NODES = 208
+KNN_RAGGED_MAX_K = 16
+KNN_RAGGED_MAX_GRAPHS = 1 << 22                 # one workgroup per graph
+KNN_EDGES_MAX_K_VALUES = 16
+# Whether knn_indices_ragged goes through isic_knn_graph_ragged where that entry supports the batch, and up to which mean
+# number of 16 x 16 tiles per graph (ceil(n / 16)^2; 169 for the reference's 196 nodes): decided by the measurement of
+# tools/knn_ragged_bench.py (profiles/knn_ragged_bench.txt, DESIGN.md "k-NN graphs among the lesion patches") -- the sized
+# kernel wins on lesion-size batches (17 tiles) and up to 128 nodes (64 tiles) and is 2 % behind at 196 nodes (169).
+KNN_RAGGED_USE_SIZED_KERNEL = True
+KNN_RAGGED_MAX_MEAN_TILES = 64.0
+
+
+def knn_ragged_supported(D, k, max_nodes):
+    """What ``isic_knn_graph_ragged`` takes (include/isic_hip_knn_ragged.h)."""
+    return D % 32 == 0 and D >= 32 and 1 <= k <= KNN_RAGGED_MAX_K and max_nodes <= KNN_RAGGED_MAX_NODES
+
+
+def knn_indices_ragged(x, offsets: BagOffsets, k, return_dist=False):
+    """``knn_indices`` for graphs of unequal size (the lesion patches of every image): LOCAL ids [T, k], -1 (distance +inf)
+    where a graph has fewer than k other nodes; graphs of 0 or 1 node are legal.  Through ``isic_knn_graph_ragged`` -- the
+    Gram kernel sized by each graph, bit-equal to ``knn_indices`` -- where that entry supports the batch (D % 32 == 0,
+    k <= 16, up to 2^22 graphs of up to 208 nodes) and the graphs are small enough for it to be the faster one (on average at most
+    ``KNN_RAGGED_MAX_MEAN_TILES`` tiles of 16 x 16 nodes), else through ``knn_indices``."""
+    _chk(x)
+    x = _f32c(x)
+    T, D = x.shape
+    if T != offsets.total:
+        raise ValueError(f"x has {T} rows but offsets cover {offsets.total}")
+    import numpy as np
+    n = np.diff(offsets.host)
+    tiles = float((((n + 15) // 16) ** 2).mean()) if n.size else 0.0
+    if not (KNN_RAGGED_USE_SIZED_KERNEL and tiles <= KNN_RAGGED_MAX_MEAN_TILES and offsets.num_bags <= KNN_RAGGED_MAX_GRAPHS
+            and knn_ragged_supported(D, int(k), offsets.max_bag)):
+        return knn_indices(x, offsets, k, return_dist=return_dist)
+    idx = torch.empty((T, k), device=x.device, dtype=torch.int64)
+    dist = torch.empty((T, k), device=x.device, dtype=torch.float32) if return_dist else None
+    call("isic_knn_graph_ragged", x, offsets.device, offsets.num_bags, D, int(k), offsets.max_bag, T, idx, dist)
+    return (idx, dist) if return_dist else idx
+
+
+def knn_edge_counts(sizes, k_values):
+    """-> int64 [K, G]: edges of graph g in the k-NN list of k_values[q], n_g * kk with the reference's per-image clamp
+    kk = 0 if n_g < 2 else max(1, min(k, n_g - 1)) (`03_build_graphs.py:42-45`).  Host only."""
+    import numpy as np
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    ks = np.asarray([int(k) for k in k_values], dtype=np.int64).reshape(-1, 1)
+    kk = np.where(n[None, :] < 2, 0, np.maximum(1, np.minimum(ks, n[None, :] - 1)))
+    return n[None, :] * kk
+
+
+def knn_edge_offsets(sizes, k_values):
+    """-> {k: int64 [G+1]} the edge offsets of every k-NN list over graphs of ``sizes`` nodes (exclusive prefix sums of
+    ``knn_edge_counts`` with the total appended).  Host only (numpy): the sizes are analytic, nothing is counted on the device."""
+    import numpy as np
+    cnt = knn_edge_counts(sizes, k_values)
+    return {int(k): np.concatenate([[0], np.cumsum(cnt[q])]).astype(np.int64) for q, k in enumerate(k_values)}
+
+
+def knn_edges_ragged(nn, offsets: BagOffsets, k_values, global_ids=False, check=True):
+    """The k-NN edge lists of every k of ``k_values`` (1..16 distinct values) out of ONE neighbour table ``nn`` [T, kmax]
+    (``knn_indices_ragged``), each graph with its own clamp kk = max(1, min(k, n_g - 1)) and no edge at all for a graph of
+    fewer than 2 nodes (`03_build_graphs.py:42-53`): one launch (``isic_knn_edges_ragged``).
+    -> ``{k: (edge_index [2, E_k], edge_offsets [G+1])}``: int64 views of ONE flat device buffer, source-major with the
+    neighbours ascending by distance, LOCAL ids (``global_ids``: plus the graph's first row); ``edge_offsets`` is a host
+    numpy array (``knn_edge_offsets``: the sizes are analytic, nothing is counted on the device).
+    A k whose clamp exceeds ``nn``'s width in some graph is an ``IsicHipError`` (BAD_ARG) raised before the launch; with
+    ``check`` the kernel's count of neighbour ids outside their graph (stored as -1) is read back (4 bytes) and a non-zero
+    count is a ``ValueError``."""
+    import ctypes
+
+    import numpy as np
+    ks = list(dict.fromkeys(int(k) for k in k_values))
+    if not ks or len(ks) > KNN_EDGES_MAX_K_VALUES or min(ks) < 1:
+        raise IsicHipError(f"knn_edges_ragged takes 1..{KNN_EDGES_MAX_K_VALUES} distinct k values >= 1, got {ks}", code=-1)
+    if nn.dim() != 2 or nn.dtype != torch.int64 or not nn.is_cuda:
+        raise IsicHipError("knn_edges_ragged needs a device int64 [T, kmax] neighbour table (no CPU fallback)")
+    nn = nn.contiguous()
+    T, kmax = int(nn.shape[0]), int(nn.shape[1])
+    if T != offsets.total:
+        raise ValueError(f"nn has {T} rows but offsets cover {offsets.total}")
+    G = offsets.num_bags
+    sizes = np.diff(offsets.host)
+    cnt = knn_edge_counts(sizes, ks)                                        # [K, G]
+    if G and int((cnt // np.maximum(sizes, 1)[None, :]).max()) > kmax:
+        raise IsicHipError(f"isic_knn_edges_ragged failed: ISIC_ERR_BAD_ARG (a graph's clamped k exceeds the {kmax} "
+                           f"neighbours per node of nn)", code=-1)
+    base = np.zeros((len(ks), G + 1), dtype=np.int64)                       # absolute positions in the one flat output
+    np.cumsum(cnt, axis=1, out=base[:, 1:])
+    starts = np.concatenate([[0], np.cumsum(base[:, -1])])
+    base += starts[:-1, None]
+    total = int(starts[-1])
+    flat = torch.empty((2, total), device=nn.device, dtype=torch.int64)
+    bad = torch.zeros(1, device=nn.device, dtype=torch.int32)               # (uint32 on the device side)
+    if total and G:
+        kv = (ctypes.c_int32 * len(ks))(*ks)
+        call("isic_knn_edges_ragged", nn, kmax, offsets.device, G, T, ctypes.addressof(kv), len(ks),
+             torch.from_numpy(base).to(nn.device), total, 1 if global_ids else 0, flat[0], flat[1], bad)
+        if check:
+            n_bad = int(bad.item()) & 0xFFFFFFFF
+            if n_bad:
+                raise ValueError(f"knn_edges_ragged: {n_bad} neighbour id(s) outside their graph (stored as -1) or "
+                                 "segments that do not fit their graph")
+    return {k: (flat[:, int(starts[q]):int(starts[q + 1])], base[q] - starts[q]) for q, k in enumerate(ks)}
+
+
 RANDOM_GRAPH_MAX_NODES = 256
 RANDOM_GRAPH_MAX_R_VALUES = 16
 

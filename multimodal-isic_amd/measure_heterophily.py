@@ -246,6 +246,41 @@ def heterophily_summary_lesion_only(x, probs, dominant, edge_index, keep):
     return heterophily_summary_ragged(xs, ps, ds, ei2, eoff2, noff2, patch_pos=rows, max_nodes=N)
 
 
+def heterophily_summary_lesion_knn(x, probs, dominant, keep, k):
+    """``heterophily_summary_lesion_only`` on the k-NN graph built AMONG the lesion patches of every image instead of the
+    subgraph they induce in a k-NN graph over all patches (which loses every edge to a background patch): ``x[G,N,D]``,
+    ``probs[G,N,C]``, ``dominant[G,N]`` device tensors, ``keep[G,N]`` (non-zero = lesion patch, host or device; an image
+    without a set flag keeps every node).  The kept rows are gathered once, their neighbours come from one top-k launch
+    and the edge list from one more (``isic_hip.graph.knn_indices_ragged`` / ``knn_edges_ragged``: every image with the
+    reference's own clamp max(1, min(k, n - 1)), `03_build_graphs.py:42-45`, no edge below 2 kept patches); the kept
+    patches keep their place on the lattice.  Returns ``heterophily_summary_ragged``'s dict: ``num_edges`` is n * k_clamped
+    per image.  The flags are read on the host (the sizes of the launches follow from them)."""
+    from isic_hip.bags import BagOffsets
+    from isic_hip.graph import knn_edges_ragged, knn_indices_ragged
+    for t in (x, probs, dominant):
+        if not t.is_cuda:
+            raise IsicHipError("heterophily_summary_lesion_knn takes device tensors (no CPU fallback)")
+    G, N, D = (int(s) for s in x.shape)
+    kh = np.asarray(keep.cpu() if isinstance(keep, torch.Tensor) else keep).reshape(-1) != 0
+    if kh.size != G * N:
+        raise ValueError("keep must be [G, N]")
+    if N > spectral.MAX_NODES:
+        raise IsicHipError(f"the ragged heterophily path takes graphs of at most {spectral.MAX_NODES} nodes", code=-2)
+    kh = kh.reshape(G, N).copy()
+    kh[~kh.any(axis=1)] = True
+    dev = x.device
+    flat = np.flatnonzero(kh.reshape(-1)).astype(np.int64)
+    idx = torch.as_tensor(flat).to(dev)
+    rows = torch.as_tensor(flat % max(N, 1)).to(dev)
+    offs = BagOffsets.from_lengths(kh.sum(axis=1), dev)
+    xs = x.reshape(G * N, D)[idx].float().contiguous()
+    k = int(k)
+    nn = knn_indices_ragged(xs, offs, max(1, min(k, offs.max_bag - 1)))
+    ei, eoff = knn_edges_ragged(nn, offs, [k])[k]
+    return heterophily_summary_ragged(xs, probs.reshape(G * N, -1)[idx], dominant.reshape(G * N)[idx], ei.contiguous(),
+                                      torch.as_tensor(eoff).to(dev), offs.device, patch_pos=rows, max_nodes=N)
+
+
 def _edge_heterophily_batch_ragged(embeddings, patch_probs, dominant_class, edge_indices, keep, dev):
     """``compute_edge_heterophily_batch`` through the ragged path: images of any node count, optionally induced by ``keep``."""
     n_img = len(embeddings)

@@ -84,14 +84,19 @@ class DeviceTeacherOutputs:
         y = self.labels.tolist()
         return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i]} for i in range(len(self))]
 
-    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None, keep=None):
+    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None, keep=None, lesion_knn=False):
         """Per-image heterophily summaries of a graph variant (`04_measure_heterophily.py:172-181`) from the resident
         tensors: ``measure_heterophily.heterophily_summary_device`` on ``x``, ``patch_probs``, ``dominant_class`` and
         ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host.  ``device_random``: see
         ``edge_index``.  ``keep[G,N]`` (device, non-zero = lesion patch): the summaries of the subgraphs the flags induce
         (``measure_heterophily.heterophily_summary_lesion_only``: ``num_nodes`` is added, the induced sizes are the one
-        read-back)."""
+        read-back).  ``lesion_knn`` (needs ``keep``; knn<k> variants only, the others keep the induced subgraph): the k-NN
+        graph is rebuilt AMONG the kept patches of every image (``heterophily_summary_lesion_knn``)."""
         import measure_heterophily as mh
+        if lesion_knn and keep is None:
+            raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs keep")
+        if lesion_knn and variant.startswith("knn"):
+            return mh.heterophily_summary_lesion_knn(self.x, self.patch_probs, self.dominant_class, keep, int(variant[3:]))
         ei = self.edge_index(variant, fold, seed, device_random=device_random)
         if keep is not None:
             return mh.heterophily_summary_lesion_only(self.x, self.patch_probs, self.dominant_class, ei, keep)
@@ -173,11 +178,27 @@ def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk
 
 
 def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, variant, *, fold=0, seed=42,
-                           device_metrics=False, device_random=None, **fit):
+                           device_metrics=False, device_random=None, keep=None, lesion_knn=False, **fit):
     """05's fold loop (`05_train_gnns.py:305-358`) fed directly from resident teacher outputs: no pickle, no upload.
     ``device_metrics``: the fold's evaluations are scored on the device as well (``train.evaluate_gnn``).
     ``device_random``: random<r> variants are built on the device (``DeviceTeacherOutputs.edge_index``); None leaves it to
-    each outputs object's own setting, which is off unless it was asked for."""
+    each outputs object's own setting, which is off unless it was asked for.
+    ``keep``: three ``[G, N]`` flag arrays (non-zero = lesion patch), one per outputs object: the fold trains on lesion-only
+    graphs (``train.GraphStore(lesion_only=True)``).  ``lesion_knn`` (needs ``keep``): a knn<k> variant is rebuilt as the
+    k-NN graph AMONG the kept patches (``GraphStore(lesion_knn=k)``); other variants keep the induced subgraph."""
     from isic_hip import train as T
+    if lesion_knn and keep is None:
+        raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs keep")
     recs = [o.graph_records(variant, fold, seed, device_random=device_random) for o in (outputs_train, outputs_val, outputs_test)]
+    if keep is not None:
+        if len(keep) != 3:
+            raise ValueError("keep: one [G, N] flag array per outputs object (train, val, test)")
+        for rs, kp in zip(recs, keep):
+            if len(kp) != len(rs):
+                raise ValueError("keep: one row of flags per image")
+            for r, k in zip(rs, kp):
+                r["keep"] = k
+        fit = dict(fit, lesion_only=True)
+        if lesion_knn and variant.startswith("knn"):
+            fit["lesion_knn"] = int(variant[3:])
     return T.train_gnn_fold(gnn_model, recs[0], recs[1], recs[2], device_metrics=device_metrics, **fit)
