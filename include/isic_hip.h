@@ -684,5 +684,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_hetero_ragged.h"
 /* k-NN graphs among patch sets of unequal size (the lesion patches of a frame): a Gram kernel sized by each graph and the edge lists of several k values with the per-image clamp in one launch: two more entry points, same conventions. */
 #include "isic_hip_knn_ragged.h"
+/* The random patch graphs for graphs of unequal size (the lesion patches of a frame), a node count, clamp and seed per graph, bit-equal to the host build: count then write, two more entry points, same conventions. */
+#include "isic_hip_randgraph_ragged.h"
 
 #endif /* ISIC_HIP_H */

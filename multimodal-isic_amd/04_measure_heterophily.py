@@ -11,6 +11,9 @@ is one CSV.
 image's lesion flags induce -- the graphs the GNNs are then trained on -- and adds a ``num_nodes`` column after ``num_edges``.
 ``--lesion-knn`` (with ``--lesion-flags``): a ``knn<k>`` variant is measured on the k-NN graph rebuilt AMONG the lesion patches
 of every image, k clamped per image as the reference clamps it on a lesion-only frame; other variants keep the induced subgraph.
+``--lesion-random`` (with ``--lesion-flags``): a ``random<r>`` variant is measured on the reference's random graph rebuilt AMONG
+the lesion patches of every image (r clamped per image; the image's seed is ``--graph-seed`` + fold * 10000 + its row in the
+fold's patch-statistics frame, `03_build_graphs.py:136`); other variants keep the induced subgraph.
 """
 import argparse
 import os
@@ -24,12 +27,17 @@ import measure_heterophily as mh
 from lesion_flags import _keep_flags, load_lesion_flags
 
 
-def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0", lesion_flags=None, lesion_knn=False):
+def build_master_summary(graph_root, patch_root, images_per_launch=64, device="cuda:0", lesion_flags=None, lesion_knn=False,
+                         lesion_random=False, graph_seed=42):
     """``lesion_flags`` (``lesion_flags.load_lesion_flags``): summarise the induced subgraphs
     (``heterophily_summary_lesion_only``); an image id without flags is a ``ValueError`` that names it.
-    ``lesion_knn``: knn<k> variants are rebuilt among the lesion patches (``heterophily_summary_lesion_knn``)."""
+    ``lesion_knn``: knn<k> variants are rebuilt among the lesion patches (``heterophily_summary_lesion_knn``).
+    ``lesion_random``: random<r> variants are rebuilt among the lesion patches (``heterophily_summary_lesion_random``), an
+    image seeded with ``graph_seed`` + fold * 10000 + its index label in the patch-statistics frame (`03_build_graphs.py:136`)."""
     if lesion_knn and lesion_flags is None:
         raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs lesion_flags")
+    if lesion_random and lesion_flags is None:
+        raise ValueError("lesion_random rebuilds the random graph among the lesion patches: it needs lesion_flags")
     rows = []
     for model in sorted(os.listdir(graph_root)):
         gpath = os.path.join(graph_root, model, "graph_dataset.pkl")
@@ -39,6 +47,7 @@ def build_master_summary(graph_root, patch_root, images_per_launch=64, device="c
         for (fold, split), grp in gdf.groupby(["fold", "split"]):
             ppath = os.path.join(patch_root, model, f"patch_stats_fold_{int(fold)}_{split}.pkl")
             pdf = pd.DataFrame(pickle.load(open(ppath, "rb")))
+            row_idx = dict(zip(pdf["image_id"], pdf.index))
             merged = grp.merge(pdf, on="image_id", how="inner", suffixes=("", "_patch"))        # 04:80-85
             if merged.empty:
                 continue
@@ -60,6 +69,9 @@ def build_master_summary(graph_root, patch_root, images_per_launch=64, device="c
                                                          for r in recs])).to(dev)
                         if lesion_knn and variant.startswith("knn"):
                             summary = mh.heterophily_summary_lesion_knn(x, pp, dom, keep, int(variant[3:]))
+                        elif lesion_random and variant.startswith("random"):
+                            seeds = [int(graph_seed) + int(fold) * 10_000 + int(row_idx[r["image_id"]]) for r in recs]
+                            summary = mh.heterophily_summary_lesion_random(x, pp, dom, keep, int(variant[6:]), seeds)
                         else:
                             summary = mh.heterophily_summary_lesion_only(x, pp, dom, eis, keep)
                     else:
@@ -86,12 +98,19 @@ def main():
     ap.add_argument("--lesion-knn", action="store_true",
                     help="with --lesion-flags: measure knn<k> variants on the k-NN graph rebuilt among the lesion patches "
                          "(k clamped per image) instead of the induced subgraph")
+    ap.add_argument("--lesion-random", action="store_true",
+                    help="with --lesion-flags: measure random<r> variants on the reference's random graph rebuilt among the "
+                         "lesion patches (r clamped per image) instead of the induced subgraph")
+    ap.add_argument("--graph-seed", type=int, default=42,
+                    help="the --seed 03_build_graphs.py was run with (--lesion-random seeds an image as it did)")
     a = ap.parse_args()
     if a.lesion_knn and not a.lesion_flags:
         ap.error("--lesion-knn needs --lesion-flags")
+    if a.lesion_random and not a.lesion_flags:
+        ap.error("--lesion-random needs --lesion-flags")
     flags = load_lesion_flags(a.lesion_flags) if a.lesion_flags else None
     df = build_master_summary(a.graph_outputs_root, a.patch_stats_root, a.images_per_launch, a.device, lesion_flags=flags,
-                              lesion_knn=a.lesion_knn)
+                              lesion_knn=a.lesion_knn, lesion_random=a.lesion_random, graph_seed=a.graph_seed)
     df.drop(columns=["H_compat_matrix"]).to_csv(a.out_csv, index=False)
     print(f"wrote {len(df)} rows ({df['graph_variant'].nunique() if len(df) else 0} graph variants) to {a.out_csv}")
 

@@ -51,9 +51,12 @@ def edge_index_for_variant(row, variant):
     raise ValueError(f"Unknown graph variant: {variant}")
 
 
-def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=None):
+def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=None, graph_seed=42):
     """`05:248-270`: graph blueprints joined one-to-one with patch statistics.  ``lesion_flags`` (``load_lesion_flags``)
-    attaches ``"keep"`` [n] to every record; an image id without flags is a ``ValueError`` that names it."""
+    attaches ``"keep"`` [n] to every record; an image id without flags is a ``ValueError`` that names it.
+    Every record also carries ``"graph_seed"``, the seed `03_build_graphs.py:136` gave the image's random graphs:
+    ``graph_seed + fold * 10000 + row_idx`` with ``row_idx`` the image's index label in this patch-statistics frame (left
+    out where that label is no integer)."""
     gpath = Path(root) / "graph_outputs" / embedding_model / "graph_dataset.pkl"
     spath = Path(root) / "patch_stats" / embedding_model / f"patch_stats_fold_{fold}_{split}.pkl"
     if not gpath.exists() or not spath.exists():
@@ -61,6 +64,7 @@ def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=
     graphs = _frame(gpath)
     graphs = graphs[(graphs["fold"] == fold) & (graphs["split"] == split)]
     stats = _frame(spath)[["image_id", "label", "patch_embeddings"]]
+    row_idx = {str(i): lab for i, lab in zip(stats["image_id"], stats.index) if isinstance(lab, (int, np.integer))}
     merged = graphs.merge(stats, on="image_id", how="inner", validate="one_to_one")
     if len(merged) != len(graphs):
         raise ValueError(f"{embedding_model}, fold {fold}, {split}: graph rows without patch statistics")
@@ -71,6 +75,8 @@ def load_fold_records(root, embedding_model, fold, split, variant, lesion_flags=
         if x.ndim != 2 or ei.shape[0] != 2:
             raise ValueError(f"Invalid graph record for image {row['image_id']}")
         records.append({"x": x, "edge_index": ei, "y": int(row["label"]), "image_id": str(row["image_id"])})
+        if records[-1]["image_id"] in row_idx:
+            records[-1]["graph_seed"] = int(graph_seed) + int(fold) * 10_000 + int(row_idx[records[-1]["image_id"]])
         if lesion_flags is not None:
             records[-1]["keep"] = _keep_flags(lesion_flags, records[-1]["image_id"], x.shape[0])
     return records
@@ -83,9 +89,16 @@ def lesion_knn_k(args, variant):
     return None
 
 
+def lesion_random_r(args, variant):
+    """r of ``GraphStore(lesion_random=r)`` for this variant: set by ``--lesion-random`` for ``random<r>`` variants only."""
+    if getattr(args, "lesion_random", False) and variant is not None and variant.startswith("random"):
+        return int(variant[6:])
+    return None
+
+
 def train_one_fold(train_records, val_records, test_records, args, fold, num_classes, input_dim, device, variant=None):
     """`05:305-358` (model configuration of the reference call site, `05:310-326`).  ``variant``: the graph variant of the
-    records, which ``--lesion-knn`` needs (``lesion_knn_k``)."""
+    records, which ``--lesion-knn`` and ``--lesion-random`` need (``lesion_knn_k``, ``lesion_random_r``)."""
     set_seed(args.seed + fold)
     model = GraphMIL(input_dim=input_dim, gnn_type=args.gnn if isinstance(args.gnn, str) else args.gnn[0],
                      gnn_hidden=args.hidden_dim, gnn_layers=args.num_layers, gnn_dropout=args.dropout,
@@ -97,7 +110,8 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
                             min_delta=args.min_delta, graphs_per_step=args.graphs_per_step, num_classes=num_classes,
                             device=device, device_metrics=args.device_metrics,
-                            lesion_only=bool(getattr(args, "lesion_flags", None)), lesion_knn=lesion_knn_k(args, variant))
+                            lesion_only=bool(getattr(args, "lesion_flags", None)), lesion_knn=lesion_knn_k(args, variant),
+                            lesion_random=lesion_random_r(args, variant))
 
 
 def aggregate(rows, prefix):
@@ -161,9 +175,19 @@ def parse_args(argv=None):
                    help="with --lesion-flags: for knn<k> variants rebuild the k-NN graph AMONG the lesion patches of every image "
                         "(k clamped per image, as the reference builds it on a lesion-only frame) instead of inducing the "
                         "stored graph; other variants keep the induced subgraph")
+    p.add_argument("--lesion-random", action="store_true",
+                   help="with --lesion-flags: for random<r> variants rebuild the reference's random graph AMONG the lesion "
+                        "patches of every image (r clamped per image, seeded as 03_build_graphs.py seeds the image) instead "
+                        "of inducing the stored graph, which keeps only a fraction of the edges; other variants keep the "
+                        "induced subgraph")
+    p.add_argument("--graph-seed", type=int, default=42,
+                   help="the --seed 03_build_graphs.py was run with: an image's random graph is seeded with "
+                        "graph-seed + fold * 10000 + its row in the fold's patch-statistics frame (--lesion-random)")
     args = p.parse_args(argv)
     if args.lesion_knn and not args.lesion_flags:
         p.error("--lesion-knn needs --lesion-flags")
+    if args.lesion_random and not args.lesion_flags:
+        p.error("--lesion-random needs --lesion-flags")
     return args
 
 
@@ -203,7 +227,8 @@ def run_gnn_experiments(args):
             load_variant = "grid4" if variant == "none" else variant
             vals, tests, epochs, detail = [], [], [], []
             for fold in args.folds:
-                tr, va, te = (load_fold_records(root, emb, fold, s, load_variant, lesion_flags) for s in ("train", "val", "test"))
+                tr, va, te = (load_fold_records(root, emb, fold, s, load_variant, lesion_flags, graph_seed=args.graph_seed)
+                              for s in ("train", "val", "test"))
                 n_cls = max(r["y"] for r in tr + va + te) + 1
                 vm, tm, be = train_one_fold(tr, va, te, args, fold, n_cls, tr[0]["x"].shape[1], device, variant=load_variant)
                 vals.append(vm); tests.append(tm); epochs.append(be)

@@ -188,6 +188,96 @@ def random_graphs(seeds, n_nodes, r_values, device=None):
     return out
 
 
+RANDOM_RAGGED_MAX_NODES = 256
+RANDOM_RAGGED_MAX_R_VALUES = 16
+# The packing of isic_random_graph_ragged_count / _write (include/isic_hip_randgraph_ragged.h): graphs of up to this many
+# nodes take a wave each, four to a workgroup, with wave-level synchronisation only; larger graphs take a 256-lane
+# workgroup each, in a second launch that is made only when the batch's largest graph exceeds it.  Measured by
+# tools/rand_graph_ragged_bench.py (profiles/rand_graph_ragged_bench.txt, DESIGN.md "Random graphs among the lesion patches").
+RANDOM_RAGGED_PACK_NODES = 64
+RANDOM_RAGGED_GRAPHS_PER_WORKGROUP = 4
+
+
+def random_edge_caps(sizes, r_values):
+    """-> int64 [n_r, G]: the analytic upper bound on the edges of a random graph of ``sizes[g]`` nodes for ``r_values[j]``,
+    min(2 n r_c, n (n - 1)) with the reference's per-graph clamp r_c = max(1, min(r, n - 1)) (`03_build_graphs.py:61`) and 0
+    below 2 nodes.  Host only (numpy): for planning buffers; the exact counts need the draws (``random_graphs_ragged``)."""
+    import numpy as np
+    n = np.asarray(sizes, dtype=np.int64).reshape(1, -1)
+    r = np.asarray([int(v) for v in r_values], dtype=np.int64).reshape(-1, 1)
+    rc = np.maximum(1, np.minimum(r, n - 1))
+    return np.where(n < 2, 0, np.minimum(2 * n * rc, n * (n - 1))).astype(np.int64)
+
+
+def random_ragged_count_launch(seeds_dev, offsets: BagOffsets, r_values):
+    """The bare ``isic_random_graph_ragged_count`` launch and the prefix sums the write needs, all on the device, nothing
+    read back: -> (head int64 [n_r G + 1]: the counts [n_r, G] row-major and, in the low half of the last element, the
+    kernels' uint32 count of bad graphs; bad: that count as a view; edge_off int64 [n_r, G + 1]: absolute positions in the
+    one flat output, row j closing with row j + 1's start)."""
+    import ctypes
+    G, n_r = offsets.num_bags, len(r_values)
+    dev = seeds_dev.device
+    rv = (ctypes.c_int * n_r)(*[max(-1, min(int(r), 1 << 30)) for r in r_values])
+    head = torch.zeros(n_r * G + 1, device=dev, dtype=torch.int64)
+    counts, bad = head[:-1].view(n_r, G), head[-1:].view(torch.int32)
+    call("isic_random_graph_ragged_count", seeds_dev, offsets.device, G, offsets.max_bag, ctypes.addressof(rv), n_r, counts, bad)
+    ends = torch.cumsum(counts.reshape(-1), 0).view(n_r, G)
+    edge_off = torch.empty((n_r, G + 1), device=dev, dtype=torch.int64)
+    edge_off[:, 1:] = ends
+    edge_off[0, 0] = 0
+    edge_off[1:, 0] = ends[:-1, -1]
+    return head, bad, edge_off
+
+
+def random_ragged_write_launch(seeds_dev, offsets: BagOffsets, r_values, edge_off, flat, bad, global_ids=False):
+    """The bare ``isic_random_graph_ragged_write`` launch into ``flat`` int64 [2, total]; nothing is read back."""
+    import ctypes
+    n_r, total = len(r_values), int(flat.shape[1])
+    rv = (ctypes.c_int * n_r)(*[max(-1, min(int(r), 1 << 30)) for r in r_values])
+    call("isic_random_graph_ragged_write", seeds_dev, offsets.device, offsets.num_bags, offsets.max_bag, ctypes.addressof(rv), n_r,
+         edge_off, total, 1 if global_ids else 0, flat[0] if total else None, flat[1] if total else None, bad)
+
+
+def random_graphs_ragged(seeds, offsets: BagOffsets, r_values, global_ids=False):
+    """``random_graphs`` for graphs of unequal size (the lesion patches of every image): graph g has ``offsets``' g-th node
+    count n_g and the seed ``seeds[g]`` (Python ints; the low 32 bits matter), and is, bit for bit,
+    ``build_graphs._random_edge_index(n_g, r, seeds[g])`` -- r clamped to [1, n_g - 1] by the graph's OWN node count, no
+    edge below 2 nodes.  -> ``{r: (edge_index [2, E_r], edge_offsets [G+1])}``: int64 views of ONE flat device buffer,
+    ascending by (src, dst) inside each graph, LOCAL ids (``global_ids``: plus the graph's first row); ``edge_offsets`` is a
+    host numpy array.  Two launches (``isic_random_graph_ragged_count`` / ``_write``) and ONE read-back, of the counts and
+    the kernels' count of bad graphs; a non-zero one is a ``ValueError``.  Duplicate r values are collapsed."""
+    import numpy as np
+    rs = list(dict.fromkeys(int(r) for r in r_values))
+    G = offsets.num_bags
+    if not rs or len(rs) > RANDOM_RAGGED_MAX_R_VALUES:
+        raise IsicHipError(f"random_graphs_ragged takes 1..{RANDOM_RAGGED_MAX_R_VALUES} distinct r values, got {len(rs)}", code=-2)
+    if len(seeds) != G:
+        raise ValueError(f"{len(seeds)} seeds for {G} graphs")
+    if offsets.max_bag > RANDOM_RAGGED_MAX_NODES:
+        raise IsicHipError(f"random_graphs_ragged supports up to {RANDOM_RAGGED_MAX_NODES} nodes per graph, got {offsets.max_bag}",
+                           code=-2)
+    if not offsets.device.is_cuda:
+        raise IsicHipError("random_graphs_ragged needs the MI355X (the host build is build_graphs._random_edge_index)")
+    dev = offsets.device.device
+    if G == 0:
+        flat = torch.empty((2, 0), device=dev, dtype=torch.int64)
+        return {r: (flat, np.zeros(1, dtype=np.int64)) for r in rs}
+    sd = torch.tensor([int(s) & 0xFFFFFFFF for s in seeds], dtype=torch.int64).to(dev)
+    with torch.cuda.device(dev):
+        head, bad, edge_off = random_ragged_count_launch(sd, offsets, rs)
+        host = head.cpu().numpy()                                           # the one read-back
+        n_bad = int(host[-1]) & 0xFFFFFFFF
+        if n_bad:
+            raise ValueError(f"random_graphs_ragged: {n_bad} graph(s) whose node offsets decrease, leave the node range or "
+                             f"span more than {offsets.max_bag} nodes")
+        cnt = host[:-1].reshape(len(rs), G)
+        flat = torch.empty((2, int(cnt.sum())), device=dev, dtype=torch.int64)
+        random_ragged_write_launch(sd, offsets, rs, edge_off, flat, bad, global_ids)
+    ends = np.concatenate([[0], np.cumsum(cnt.sum(axis=1))])
+    return {r: (flat[:, int(ends[j]):int(ends[j + 1])], np.concatenate([[0], np.cumsum(cnt[j])]).astype(np.int64))
+            for j, r in enumerate(rs)}
+
+
 def _dev_i64(v, device):
     if isinstance(v, torch.Tensor):
         return v.to(device=device, dtype=torch.int64).contiguous()

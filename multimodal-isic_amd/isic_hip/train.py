@@ -346,7 +346,8 @@ class GraphStore:
     """Graph records resident in HBM with their normalised CSR built once (graphs are static across
     epochs; the reference re-uploads x and edge_index every step, `05:340-343`)."""
 
-    def __init__(self, records, device, needs_graph=True, mode="gcn", lesion_only=False, ragged_stack=None, lesion_knn=None):
+    def __init__(self, records, device, needs_graph=True, mode="gcn", lesion_only=False, ragged_stack=None, lesion_knn=None,
+                 lesion_random=None):
         """``mode``: aggregation of the CSR the model's layers need (``gnn_models._GRAPH_MODE``: 'gcn' =
         self loops + symmetric normalisation, 'sum' = GINConv, 'mean' = SAGEConv).
         ``lesion_only``: every record carries ``"keep"`` (bool [n], the lesion flag of each patch) and the store holds the
@@ -360,7 +361,14 @@ class GraphStore:
         (k = ``lesion_knn``) built AMONG the kept patches of every record, as the reference builds it on a lesion-only frame
         (`03_build_graphs.py:37-54`: k clamped by the record's own number of kept patches, no edge below 2 of them) -- the
         induced subgraph of a k-NN graph over all patches loses every edge to a background patch.  One top-k launch and one
-        edge-list launch over the whole record set (``graph.knn_indices_ragged`` / ``knn_edges_ragged``)."""
+        edge-list launch over the whole record set (``graph.knn_indices_ragged`` / ``knn_edges_ragged``).
+        ``lesion_random``: with ``lesion_only`` (and not together with ``lesion_knn``), the records' own ``edge_index`` is
+        ignored and the store holds the reference's random graph (r = ``lesion_random``) built AMONG the kept patches of
+        every record, ``_random_edge_index(kept patches, r, record["graph_seed"])`` bit for bit (`03_build_graphs.py:57-78`:
+        r clamped by the record's own number of kept patches, no edge below 2 of them) -- of the random graph over all
+        patches the induced subgraph keeps a neighbour with probability (kept - 1) / (all - 1) only, so it is no control of
+        the same density.  Every record carries ``"graph_seed"`` (int) next to ``"keep"``; two launches over the whole
+        record set (``graph.random_graphs_ragged``)."""
         if mode not in GraphBatch.MODES:
             raise ValueError(f"unknown graph mode '{mode}'")
         if lesion_knn is not None and not lesion_only:
@@ -368,6 +376,13 @@ class GraphStore:
         if lesion_knn is not None and int(lesion_knn) < 1:
             raise ValueError("GraphStore(lesion_knn=k): k must be >= 1")
         self.lesion_knn = int(lesion_knn) if lesion_knn is not None else None
+        if lesion_random is not None and not lesion_only:
+            raise ValueError("GraphStore(lesion_random=r) rebuilds the random graph among the lesion patches: it needs lesion_only=True")
+        if lesion_random is not None and lesion_knn is not None:
+            raise ValueError("GraphStore: lesion_random and lesion_knn exclude each other (one graph per record)")
+        if lesion_random is not None and int(lesion_random) < 1:
+            raise ValueError("GraphStore(lesion_random=r): r must be >= 1")
+        self.lesion_random = int(lesion_random) if lesion_random is not None else None
         self.device, self.records, self.mode = device, records, mode
         def dev_tensor(v, dtype, np_dtype):      # records hold numpy arrays (05:248-270) or tensors already in HBM
             if isinstance(v, torch.Tensor):
@@ -377,12 +392,15 @@ class GraphStore:
         self.x = [dev_tensor(r["x"], torch.float32, np.float32) for r in records]
         self.y = np.asarray([int(r["y"]) for r in records])
         self.ei = [dev_tensor(r["edge_index"], torch.int64, np.int64)
-                   if needs_graph and self.lesion_knn is None and r.get("edge_index") is not None else None for r in records]
+                   if needs_graph and self.lesion_knn is None and self.lesion_random is None and r.get("edge_index") is not None
+                   else None for r in records]
         self.needs_graph = needs_graph
         self.lesion_only = bool(lesion_only)
         self._ragged, self._xcat = None, None
         if self.lesion_only and self.lesion_knn is not None:
             self._rebuild_knn_among_lesion()
+        elif self.lesion_only and self.lesion_random is not None:
+            self._rebuild_random_among_lesion()
         elif self.lesion_only:
             self._restrict_to_lesion(dev_tensor)
         self._want_ragged = (self.lesion_only and RAGGED_STACK_DEFAULT_LESION_ONLY) if ragged_stack is None else bool(ragged_stack)
@@ -408,18 +426,16 @@ class GraphStore:
             keeps.append(k)
         return keeps
 
-    def _rebuild_knn_among_lesion(self):
-        """Replace every record's graph by the k-NN graph among its kept patches (a record without a kept patch keeps
-        all): ``x`` is gathered by ``keep`` once, the neighbours of all records come from one top-k launch over the kept
-        rows and the edge lists from one more.  ``self.x`` / ``self.ei`` / ``self.rows`` are filled as
-        ``_restrict_to_lesion`` fills them, so every path of the store sees the rebuilt records."""
+    def _gather_kept(self):
+        """``x`` gathered by ``keep`` once (a record without a kept patch keeps all): fills ``self.x`` / ``self.rows`` /
+        ``self._xcat`` as ``_restrict_to_lesion`` fills them and returns (xcat, offsets of the kept patches), or None for
+        an empty record set."""
         from .bags import BagOffsets
-        from .graph import knn_edges_ragged, knn_indices_ragged
         dev = self.device
         ns = [int(t.shape[0]) for t in self.x]
         keeps = [k if k.any() else np.ones_like(k) for k in self._keep_flags(ns)]
         if not self.x:
-            return
+            return None
         noff = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
         local = [np.flatnonzero(k) for k in keeps]                            # old local id of every kept node, per record
         n2 = [int(r.size) for r in local]
@@ -428,13 +444,42 @@ class GraphStore:
         xcat = self._xcat = torch.cat(self.x)[pick]
         self.rows = list(torch.split(rows, n2))
         self.x = list(torch.split(xcat, n2))
-        if not self.needs_graph:
+        return xcat, BagOffsets.from_lengths(n2, dev)
+
+    def _rebuild_knn_among_lesion(self):
+        """Replace every record's graph by the k-NN graph among its kept patches (a record without a kept patch keeps
+        all): ``x`` is gathered by ``keep`` once, the neighbours of all records come from one top-k launch over the kept
+        rows and the edge lists from one more.  ``self.x`` / ``self.ei`` / ``self.rows`` are filled as
+        ``_restrict_to_lesion`` fills them, so every path of the store sees the rebuilt records."""
+        from .graph import knn_edges_ragged, knn_indices_ragged
+        kept = self._gather_kept()
+        if kept is None or not self.needs_graph:
             return
-        offs = BagOffsets.from_lengths(n2, dev)
+        xcat, offs = kept
+        n2 = np.diff(offs.host)
         k = self.lesion_knn
         nn = knn_indices_ragged(xcat, offs, max(1, min(k, offs.max_bag - 1)))
         ei2, eoff = knn_edges_ragged(nn, offs, [k])[k]
         self.ei = [ei2[:, int(eoff[g]):int(eoff[g + 1])] for g in range(len(n2))]
+
+    def _rebuild_random_among_lesion(self):
+        """Replace every record's graph by the reference's random graph among its kept patches, seeded by the record's
+        ``"graph_seed"`` (a record without a kept patch keeps all): ``x`` is gathered by ``keep`` once and the edge lists
+        of all records come from ``graph.random_graphs_ragged``.  ``self.x`` / ``self.ei`` / ``self.rows`` are filled as
+        ``_rebuild_knn_among_lesion`` fills them, so every path of the store sees the rebuilt records."""
+        from .graph import random_graphs_ragged
+        seeds = []
+        for i, r in enumerate(self.records):
+            if r.get("graph_seed") is None:
+                raise ValueError(f"GraphStore(lesion_random=r): record {i} has no 'graph_seed'")
+            seeds.append(int(r["graph_seed"]))
+        kept = self._gather_kept()
+        if kept is None or not self.needs_graph:
+            return
+        _, offs = kept
+        r = self.lesion_random
+        ei2, eoff = random_graphs_ragged(seeds, offs, [r])[r]
+        self.ei = [ei2[:, int(eoff[g]):int(eoff[g + 1])] for g in range(offs.num_bags)]
 
     def _restrict_to_lesion(self, dev_tensor):
         """Replace every record's graph by the subgraph its ``keep`` flags induce: the edge lists of all records go through
@@ -673,7 +718,8 @@ def evaluate_gnn(model, store, num_classes, chunk=32, device_metrics=False):
 
 def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, weight_decay=1e-4, epochs=1,
                    patience=16, min_delta=1e-6, graphs_per_step=1, num_classes=7, device=None, rng=None,
-                   device_metrics=False, history=None, lesion_only=False, ragged_stack=None, lesion_knn=None):
+                   device_metrics=False, history=None, lesion_only=False, ragged_stack=None, lesion_knn=None,
+                   lesion_random=None):
     """`05_train_gnns.py:305-358`: AdamW, epoch order = np.random.permutation, best state by validation
     balanced accuracy.  The class weights of `05:328-331` cancel for single-sample CE and
     batched steps keep the unweighted per-graph mean.  Returns (val_metrics, test_metrics, best_epoch).
@@ -681,14 +727,15 @@ def train_gnn_fold(model, train_records, val_records, test_records, *, lr=1e-4, 
     ``{"epoch", "val_bacc", "val_loss"}`` per epoch.
     ``lesion_only`` / ``ragged_stack``: as ``GraphStore`` takes them, for all three record sets (every record carries
     ``"keep"``; ``lesion_knn=k`` rebuilds the k-NN graph among the kept patches instead of inducing the records' graphs and
-    needs ``lesion_only``).  A ragged batch changes its shapes from step to step, so a captured step (``graphs.CapturedStep``) is not offered
+    needs ``lesion_only``; ``lesion_random=r`` rebuilds the reference's random graph among them from every record's
+    ``"graph_seed"``, needs ``lesion_only`` and excludes ``lesion_knn``).  A ragged batch changes its shapes from step to step, so a captured step (``graphs.CapturedStep``) is not offered
     for it: ragged steps run eagerly."""
     rank, world = dist_info()
     device = device or next(model.parameters()).device
     needs = model.gnn_type != "mlp"
     mode = model.graph_mode or "gcn"
     tr, va, te = (GraphStore(r, device, needs, mode=mode, lesion_only=lesion_only, ragged_stack=ragged_stack,
-                             lesion_knn=lesion_knn)
+                             lesion_knn=lesion_knn, lesion_random=lesion_random)
                   for r in (train_records, val_records, test_records))
     ragged = tr._ragged is not None            # its steps index the store with the host list: the batch's sizes are host facts
     opt = optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)

@@ -255,11 +255,40 @@ def heterophily_summary_lesion_knn(x, probs, dominant, keep, k):
     reference's own clamp max(1, min(k, n - 1)), `03_build_graphs.py:42-45`, no edge below 2 kept patches); the kept
     patches keep their place on the lattice.  Returns ``heterophily_summary_ragged``'s dict: ``num_edges`` is n * k_clamped
     per image.  The flags are read on the host (the sizes of the launches follow from them)."""
-    from isic_hip.bags import BagOffsets
     from isic_hip.graph import knn_edges_ragged, knn_indices_ragged
+    xs, ps, ds, rows, offs, N = _gather_kept_patches(x, probs, dominant, keep, "heterophily_summary_lesion_knn")
+    k = int(k)
+    nn = knn_indices_ragged(xs, offs, max(1, min(k, offs.max_bag - 1)))
+    ei, eoff = knn_edges_ragged(nn, offs, [k])[k]
+    return heterophily_summary_ragged(xs, ps, ds, ei.contiguous(), torch.as_tensor(eoff).to(x.device), offs.device,
+                                      patch_pos=rows, max_nodes=N)
+
+
+def heterophily_summary_lesion_random(x, probs, dominant, keep, r, seeds):
+    """The twin of ``heterophily_summary_lesion_knn`` for a ``random<r>`` variant: the reference's random graph built AMONG
+    the lesion patches of every image, ``_random_edge_index(kept patches, r, seeds[g])`` bit for bit
+    (`03_build_graphs.py:57-78`: r clamped by the image's own number of kept patches, no edge below 2 of them), instead of
+    the subgraph they induce in the random graph over all patches (which keeps a neighbour with probability
+    (kept - 1) / (all - 1) only).  ``seeds``: one Python int per image (`03:136`).  The kept rows are gathered once and
+    the edge lists come from ``isic_hip.graph.random_graphs_ragged``; the kept patches keep their place on the lattice.
+    Returns ``heterophily_summary_ragged``'s dict.  The flags are read on the host."""
+    from isic_hip.graph import random_graphs_ragged
+    xs, ps, ds, rows, offs, N = _gather_kept_patches(x, probs, dominant, keep, "heterophily_summary_lesion_random")
+    if len(seeds) != offs.num_bags:
+        raise ValueError("seeds: one per image")
+    r = int(r)
+    ei, eoff = random_graphs_ragged([int(s) for s in seeds], offs, [r])[r]
+    return heterophily_summary_ragged(xs, ps, ds, ei.contiguous(), torch.as_tensor(eoff).to(x.device), offs.device,
+                                      patch_pos=rows, max_nodes=N)
+
+
+def _gather_kept_patches(x, probs, dominant, keep, who):
+    """``x[G,N,D]``, ``probs[G,N,C]``, ``dominant[G,N]`` restricted to the rows ``keep[G,N]`` flags (an image without a set
+    flag keeps every node) -> (x', probs', dominant', lattice position of every kept row, their BagOffsets, N)."""
+    from isic_hip.bags import BagOffsets
     for t in (x, probs, dominant):
         if not t.is_cuda:
-            raise IsicHipError("heterophily_summary_lesion_knn takes device tensors (no CPU fallback)")
+            raise IsicHipError(f"{who} takes device tensors (no CPU fallback)")
     G, N, D = (int(s) for s in x.shape)
     kh = np.asarray(keep.cpu() if isinstance(keep, torch.Tensor) else keep).reshape(-1) != 0
     if kh.size != G * N:
@@ -274,11 +303,7 @@ def heterophily_summary_lesion_knn(x, probs, dominant, keep, k):
     rows = torch.as_tensor(flat % max(N, 1)).to(dev)
     offs = BagOffsets.from_lengths(kh.sum(axis=1), dev)
     xs = x.reshape(G * N, D)[idx].float().contiguous()
-    k = int(k)
-    nn = knn_indices_ragged(xs, offs, max(1, min(k, offs.max_bag - 1)))
-    ei, eoff = knn_edges_ragged(nn, offs, [k])[k]
-    return heterophily_summary_ragged(xs, probs.reshape(G * N, -1)[idx], dominant.reshape(G * N)[idx], ei.contiguous(),
-                                      torch.as_tensor(eoff).to(dev), offs.device, patch_pos=rows, max_nodes=N)
+    return xs, probs.reshape(G * N, -1)[idx], dominant.reshape(G * N)[idx], rows, offs, N
 
 
 def _edge_heterophily_batch_ragged(embeddings, patch_probs, dominant_class, edge_indices, keep, dev):

@@ -79,22 +79,33 @@ class DeviceTeacherOutputs:
 
     def graph_records(self, variant, fold=0, seed=42, device_random=None):
         """Records for ``train.GraphStore`` / ``train_gnn_fold`` (`05_train_gnns.py:248-270` schema: x, edge_index, y)
-        -- views of the resident tensors, nothing is copied to the host.  ``device_random``: see ``edge_index``."""
-        ei = self.edge_index(variant, fold, seed, device_random=device_random)
+        -- views of the resident tensors, nothing is copied to the host.  ``device_random``: see ``edge_index``.  Every
+        record carries ``"graph_seed"``, the seed ``edge_index`` gives image i's random graphs (seed + fold * 10000 + i);
+        ``variant=None``: records without edges (``edge_index`` None), for a store that builds its own."""
+        ei = self.edge_index(variant, fold, seed, device_random=device_random) if variant is not None else [None] * len(self)
         y = self.labels.tolist()
-        return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i]} for i in range(len(self))]
+        return [{"x": self.x[i], "edge_index": ei[i], "y": int(y[i]), "image_id": self.image_ids[i],
+                 "graph_seed": seed + fold * 10_000 + i} for i in range(len(self))]
 
-    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None, keep=None, lesion_knn=False):
+    def heterophily_summary(self, variant, fold=0, seed=42, device_random=None, keep=None, lesion_knn=False,
+                            lesion_random=False):
         """Per-image heterophily summaries of a graph variant (`04_measure_heterophily.py:172-181`) from the resident
         tensors: ``measure_heterophily.heterophily_summary_device`` on ``x``, ``patch_probs``, ``dominant_class`` and
         ``edge_index(variant)`` -- a dict of device tensors, nothing is copied to the host.  ``device_random``: see
         ``edge_index``.  ``keep[G,N]`` (device, non-zero = lesion patch): the summaries of the subgraphs the flags induce
         (``measure_heterophily.heterophily_summary_lesion_only``: ``num_nodes`` is added, the induced sizes are the one
         read-back).  ``lesion_knn`` (needs ``keep``; knn<k> variants only, the others keep the induced subgraph): the k-NN
-        graph is rebuilt AMONG the kept patches of every image (``heterophily_summary_lesion_knn``)."""
+        graph is rebuilt AMONG the kept patches of every image (``heterophily_summary_lesion_knn``).  ``lesion_random``
+        (needs ``keep``; random<r> variants only): the reference's random graph is rebuilt AMONG the kept patches of every
+        image with the seeds ``edge_index`` uses, seed + fold * 10000 + i (``heterophily_summary_lesion_random``)."""
         import measure_heterophily as mh
         if lesion_knn and keep is None:
             raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs keep")
+        if lesion_random and keep is None:
+            raise ValueError("lesion_random rebuilds the random graph among the lesion patches: it needs keep")
+        if lesion_random and variant.startswith("random"):
+            seeds = [seed + fold * 10_000 + i for i in range(len(self))]
+            return mh.heterophily_summary_lesion_random(self.x, self.patch_probs, self.dominant_class, keep, int(variant[6:]), seeds)
         if lesion_knn and variant.startswith("knn"):
             return mh.heterophily_summary_lesion_knn(self.x, self.patch_probs, self.dominant_class, keep, int(variant[3:]))
         ei = self.edge_index(variant, fold, seed, device_random=device_random)
@@ -178,18 +189,25 @@ def collect_teacher_outputs_device(model, bags, labels, image_ids, device, chunk
 
 
 def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, variant, *, fold=0, seed=42,
-                           device_metrics=False, device_random=None, keep=None, lesion_knn=False, **fit):
+                           device_metrics=False, device_random=None, keep=None, lesion_knn=False, lesion_random=False, **fit):
     """05's fold loop (`05_train_gnns.py:305-358`) fed directly from resident teacher outputs: no pickle, no upload.
     ``device_metrics``: the fold's evaluations are scored on the device as well (``train.evaluate_gnn``).
     ``device_random``: random<r> variants are built on the device (``DeviceTeacherOutputs.edge_index``); None leaves it to
     each outputs object's own setting, which is off unless it was asked for.
     ``keep``: three ``[G, N]`` flag arrays (non-zero = lesion patch), one per outputs object: the fold trains on lesion-only
     graphs (``train.GraphStore(lesion_only=True)``).  ``lesion_knn`` (needs ``keep``): a knn<k> variant is rebuilt as the
-    k-NN graph AMONG the kept patches (``GraphStore(lesion_knn=k)``); other variants keep the induced subgraph."""
+    k-NN graph AMONG the kept patches (``GraphStore(lesion_knn=k)``); other variants keep the induced subgraph.
+    ``lesion_random`` (needs ``keep``): a random<r> variant is rebuilt as the reference's random graph AMONG the kept
+    patches, image i seeded with seed + fold * 10000 + i as ``edge_index`` seeds it (``GraphStore(lesion_random=r)``; the
+    graph over all patches is not built at all); other variants keep the induced subgraph."""
     from isic_hip import train as T
     if lesion_knn and keep is None:
         raise ValueError("lesion_knn rebuilds the k-NN graph among the lesion patches: it needs keep")
-    recs = [o.graph_records(variant, fold, seed, device_random=device_random) for o in (outputs_train, outputs_val, outputs_test)]
+    if lesion_random and keep is None:
+        raise ValueError("lesion_random rebuilds the random graph among the lesion patches: it needs keep")
+    rebuilt_random = bool(lesion_random) and variant.startswith("random")
+    recs = [o.graph_records(None if rebuilt_random else variant, fold, seed, device_random=device_random)
+            for o in (outputs_train, outputs_val, outputs_test)]
     if keep is not None:
         if len(keep) != 3:
             raise ValueError("keep: one [G, N] flag array per outputs object (train, val, test)")
@@ -201,4 +219,6 @@ def train_gnn_from_teacher(gnn_model, outputs_train, outputs_val, outputs_test, 
         fit = dict(fit, lesion_only=True)
         if lesion_knn and variant.startswith("knn"):
             fit["lesion_knn"] = int(variant[3:])
+        if rebuilt_random:
+            fit["lesion_random"] = int(variant[6:])
     return T.train_gnn_fold(gnn_model, recs[0], recs[1], recs[2], device_metrics=device_metrics, **fit)
