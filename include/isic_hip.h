@@ -69,9 +69,11 @@ int isic_gemm_f32_ws(int transA, int transB, int M, int N, int K, const float* A
 /* ... with a row index on an operand: stored row r of A (of B) is read from A[a_rows[r]] (B[b_rows[r]]).  A step's batch of
  * graphs is multiplied straight out of the resident record store -- x[sel] W^T and dY^T x[sel] -- without materialising the
  * gathered node features (05_train_gnns.py:340-343 re-uploads them every step).  The index arrays are read in groups of 8
- * (allocate a multiple of 8 entries).  Supported for the operand that forms the row tiles of the persistent kernel
- * (A of a large product with > 128 output rows; B of a transA product with <= 128 output rows); ISIC_ERR_UNSUPPORTED
- * otherwise -- gather, then isic_gemm_f32_ws.  Both NULL: isic_gemm_f32_ws. */
+ * (allocate a multiple of 8 entries; a pad entry is loaded but never used as a row number).  Supported for the operand that
+ * forms the row tiles of the persistent kernel: A where that kernel keeps the roles (more than 128 output rows, or N <= M),
+ * B where it swaps them (M <= 128 output rows and N > M, in either layout of A and B: the weight gradient dY^T x[sel]);
+ * ISIC_ERR_UNSUPPORTED otherwise, and wherever the persistent kernel does not take the product at all -- gather, then
+ * isic_gemm_f32_ws.  Both NULL: isic_gemm_f32_ws. */
 int isic_gemm_f32_rows_ws(int transA, int transB, int M, int N, int K, const float* A, int lda, const int32_t* a_rows,
                           const float* B, int ldb, const int32_t* b_rows, float* C, int ldc, const float* bias, int act,
                           float beta, void* workspace, size_t workspace_bytes, void* stream);

@@ -8,6 +8,9 @@ import torch
 from oracle import formula
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DEV = "cuda:0"
+NAN = float("nan")
+PAD = 64                                            # NaN floats before and after every guarded output (a multiple of 4)
 
 
 def load_golden(name):
@@ -50,3 +53,34 @@ def assert_close(a, b, rtol=1e-5, atol=1e-6, what=""):
     scale = max(np.abs(b).max(), 1e-30) if b.size else 1.0
     err = np.abs(a - b).max() if b.size else 0.0
     assert err <= atol + rtol * scale, f"{what}: max|diff|={err:.3e} > {atol + rtol * scale:.3e} (scale {scale:.3e})"
+
+
+class Guarded:
+    """an fp32 output of `shape`, NaN pre-filled, with PAD NaN floats before and after it; `offset` floats (0 or 1) move
+    it off 16-byte alignment"""
+
+    def __init__(self, shape, offset=0, init=None):
+        n = int(np.prod(shape))
+        self.buf = torch.full((2 * PAD + n + 4,), NAN, device=DEV, dtype=torch.float32)
+        self.lo = PAD + offset
+        self.n = n
+        self.t = self.buf[self.lo:self.lo + n].view(*shape)
+        if init is not None:
+            self.t.copy_(init)
+
+    def ok(self, finite=True):
+        intact = bool(torch.isnan(self.buf[:self.lo]).all()) and bool(torch.isnan(self.buf[self.lo + self.n:]).all())
+        return intact and (not finite or bool(torch.isfinite(self.t).all()))
+
+    def cpu(self):
+        return self.t.detach().cpu()
+
+
+def stop_after_a_device_error():
+    """the body of the GPU modules' autouse fixture: a device error (not a failed comparison) ends the session -- nothing more
+    is launched on a GPU that has faulted"""
+    import pytest
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:
+        pytest.exit(f"device error, no further GPU work: {e}", returncode=3)

@@ -51,11 +51,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import f32_kernel_ref as R  # noqa: E402
+from helpers import DEV, NAN, Guarded, stop_after_a_device_error  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-NAN = float("nan")
-PAD = 64                                            # NaN floats before and after every guarded output (a multiple of 4)
 F64 = torch.float64
 UNSUPPORTED = -2
 WORST = {}
@@ -87,10 +85,7 @@ def _report():
 def _stop_after_a_device_error():
     """a device error (not a failed comparison) ends the session: nothing more is launched on a GPU that has faulted"""
     yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"device error, no further GPU work: {e}", returncode=3)
+    stop_after_a_device_error()
 
 
 def _note(key, ratios):
@@ -103,27 +98,6 @@ def _check(key, what, ratios):
     print(what, " ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
     _note(key, ratios)
     assert all(v <= 1.0 for v in ratios.values()), (what, ratios)
-
-
-class Guarded:
-    """an fp32 output of `shape`, NaN pre-filled, with PAD NaN floats before and after it; `offset` floats (0 or 1) move
-    it off 16-byte alignment"""
-
-    def __init__(self, shape, offset=0, init=None):
-        n = int(np.prod(shape))
-        self.buf = torch.full((2 * PAD + n + 4,), NAN, device=DEV, dtype=torch.float32)
-        self.lo = PAD + offset
-        self.n = n
-        self.t = self.buf[self.lo:self.lo + n].view(*shape)
-        if init is not None:
-            self.t.copy_(init)
-
-    def ok(self, finite=True):
-        intact = bool(torch.isnan(self.buf[:self.lo]).all()) and bool(torch.isnan(self.buf[self.lo + self.n:]).all())
-        return intact and (not finite or bool(torch.isfinite(self.t).all()))
-
-    def cpu(self):
-        return self.t.detach().cpu()
 
 
 def _place(t, offset=0):
