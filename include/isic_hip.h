@@ -688,5 +688,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_knn_ragged.h"
 /* The random patch graphs for graphs of unequal size (the lesion patches of a frame), a node count, clamp and seed per graph, bit-equal to the host build: count then write, two more entry points, same conventions. */
 #include "isic_hip_randgraph_ragged.h"
+/* The token statistics over a subset of each image's tokens (the lesion patches): flags on the dense grid, or offsets into a compacted store, bit-equal to the dense entry on the kept tokens: two more entry points, same conventions. */
+#include "isic_hip_moments_ragged.h"
 
 #endif /* ISIC_HIP_H */

@@ -32,6 +32,12 @@ What changes:
     of two torch reductions.  The max is the same element; the mean may differ from torch's in the last bits (another
     summation order), hence opt-in.
 
+  * ``lesion_moments: true`` (opt-in) adds two columns to the pooled frames: ``latent_lesion_moments``, the ``[6 D]`` fp32
+    descriptor of ``utils.concat_patch_moments`` over the image's lesion patches only, and ``lesion_patch_count``.  Both come
+    from one ``isic_token_moments_masked_f32`` launch per batch (``token_moments(latent, keep=flags)``) on the flags
+    ``mask_patch_flags`` already makes; an image without a lesion patch carries a NaN row and count 0.  Without the key the
+    frames are unchanged, column for column.
+
 ``extract_latents(config, path, remove_background=False, datasets=None)`` keeps the reference's signature and return
 tuple; ``datasets=(train_val_dataset, test_dataset)`` lets a caller hand in any dataset with the ``DermDataset`` dict
 contract (`dataset.py:45-56`) -- the synthetic one below when there are no image files.
@@ -128,9 +134,10 @@ def _device_resized(loader, device):
                "segmentation_path": [it["segmentation_path"] for it in items]}
 
 
-def _extract_from_loader(encoder, loader, device, resident=None, device_moments=False):
+def _extract_from_loader(encoder, loader, device, resident=None, device_moments=False, lesion_moments=False):
     """``resident``: a list that receives (latent [B, T, D], flags [B, T] bool) of every batch, left on the device;
-    ``device_moments``: the pooled max and mean come from one ``token_moments`` launch"""
+    ``device_moments``: the pooled max and mean come from one ``token_moments`` launch; ``lesion_moments``: the pooled frame
+    gains the descriptor of the lesion patches and their number, from one masked launch"""
     pooled_list, raw_list = [], []
     for batch in loader:
         images = batch["image"].to(device)
@@ -150,6 +157,11 @@ def _extract_from_loader(encoder, loader, device, resident=None, device_moments=
             "latent_pooled_mean": list(pooled_mean.cpu().numpy()),                      # :63
             "ids_restore": list(ids), "ids_keep": list(ids)}))
         flags = mask_patch_flags(batch["mask"].to(device))
+        if lesion_moments:
+            from isic_hip.moments import token_moments
+            lesion, count = token_moments(latent, keep=flags.reshape(B, -1), return_counts=True)
+            pooled_list[-1]["latent_lesion_moments"] = list(lesion.cpu().numpy())
+            pooled_list[-1]["lesion_patch_count"] = count.cpu().numpy().astype(np.int64)
         if resident is not None:
             resident.append((latent, flags.reshape(B, -1)))
         raw_list.append(pd.DataFrame({
@@ -244,8 +256,11 @@ def extract_latents(config, path, remove_background=False, datasets=None, batch_
     device_pca = bool(config.get("pca", False)) and bool(config.get("device_pca", False))
     resident_train, resident_test = ([], []) if device_pca else (None, None)
     device_moments = bool(config.get("device_moments", False))
-    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device, resident_train, device_moments)
-    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device, resident_test, device_moments)
+    lesion_moments = bool(config.get("lesion_moments", False))
+    latent_pooled_train, latent_raw_train = _extract_from_loader(enc, loaders[0], device, resident_train, device_moments,
+                                                                 lesion_moments)
+    latent_pooled_test, latent_raw_test = _extract_from_loader(enc, loaders[1], device, resident_test, device_moments,
+                                                               lesion_moments)
     patch_level_train_df, train_count = build_patch_level_df(latent_raw_train, remove=remove_background)
     patch_level_test_df, test_count = build_patch_level_df(latent_raw_test, remove=remove_background)
     print(f"Total lesion-overlapping patches (train_val): {train_count}")

@@ -7,11 +7,12 @@ import os
 import typing
 
 
-def concat_patch_moments(latent, eps=1e-6, unbiased=False):
+def concat_patch_moments(latent, eps=1e-6, unbiased=False, keep=None):
     """latent [B, T, D] fp32 on the device -> [B, 6 D]: mean, max, std, median, skewness, excess kurtosis over the
-    tokens, the reference's concatenation order.  No backward; no CPU fallback."""
+    tokens, the reference's concatenation order.  ``keep`` [B, T] (non-zero keeps the token) restricts image b to its kept
+    tokens (a NaN row where none is kept).  No backward; no CPU fallback."""
     from isic_hip.moments import token_moments
-    return token_moments(latent, eps=eps, unbiased=unbiased)
+    return token_moments(latent, eps=eps, unbiased=unbiased, keep=keep)
 
 
 def get_args_parser(path: typing.Union[str, bytes, os.PathLike]):
