@@ -690,5 +690,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_randgraph_ragged.h"
 /* The token statistics over a subset of each image's tokens (the lesion patches): flags on the dense grid, or offsets into a compacted store, bit-equal to the dense entry on the kept tokens: two more entry points, same conventions. */
 #include "isic_hip_moments_ragged.h"
+/* The K-hop polynomial graph filter of GPR-GNN / APPNP, graph-resident (all hops of a graph's column slab out of LDS, forward and backward with the coefficient gradient): three more entry points, same conventions. */
+#include "isic_hip_gpr.h"
 
 #endif /* ISIC_HIP_H */

@@ -104,7 +104,8 @@ def train_one_fold(train_records, val_records, test_records, args, fold, num_cla
                      gnn_hidden=args.hidden_dim, gnn_layers=args.num_layers, gnn_dropout=args.dropout,
                      gnn_heads=args.gnn_heads, gnn_concat=args.gnn_concat, att_dim=128, att_heads=4, pool_dropout=0.2,
                      classifier_dim=128, classifier_light=True, num_classes=num_classes, use_residual=True,
-                     use_layer_norm=True, att_gated=getattr(args, "att_gated", False)).to(device)
+                     use_layer_norm=True, att_gated=getattr(args, "att_gated", False), gpr_k=getattr(args, "gpr_k", 10),
+                     gpr_alpha=getattr(args, "gpr_alpha", 0.1)).to(device)
     model.set_dropout_state(args.seed + fold, 0)
     return T.train_gnn_fold(model, train_records, val_records, test_records, lr=args.learning_rate,
                             weight_decay=args.weight_decay, epochs=args.epochs, patience=args.patience,
@@ -152,6 +153,9 @@ def parse_args(argv=None):
                    help="average the attention heads instead of concatenating them (PyG concat=False)")
     p.add_argument("--att-gated", action="store_true",
                    help="gated attention pooling (Ilse et al. 2018): a sigmoid gate per pooling head; not in the reference")
+    p.add_argument("--gpr-k", type=int, default=10, help="hops K of gprgnn / appnp (0..16); not in the reference")
+    p.add_argument("--gpr-alpha", type=float, default=0.1,
+                   help="teleport probability of the PPR coefficients gprgnn starts from and appnp keeps ([0, 1])")
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--patience", type=int, default=16)
     p.add_argument("--min-delta", type=float, default=1e-6)

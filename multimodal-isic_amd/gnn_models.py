@@ -12,7 +12,10 @@ Graph models: ``mlp`` (pure dense, pinned by the reference), ``gcn``, ``gcnii``,
 ``GCN2Conv`` / ``SAGEConv`` / ``GINConv`` / ``GATConv`` semantics restated (``torch_geometric``
 is absent and unpinned in the reference, see oracle/gnn.py), plus ``gatv2`` (GATv2Conv),
 ``transformer`` (TransformerConv(beta=True)) and ``fagcn`` (FAConv) on the edge-attention kernels of
-``edge_attn.hip``.  Two of those cannot run as the reference writes them: its ``gatv2``
+``edge_attn.hip``, and ``gprgnn`` / ``appnp``: the learned polynomial graph filter of GPR-GNN (Chien et al. 2021),
+out = sum_k gamma[k] A^^k lin(x) + bias with ``gamma`` [K+1] a parameter initialised to the PPR coefficients, and its
+fixed-coefficient case, PyG ``APPNP(K, alpha)`` applied to ``lin(x)`` (``gamma`` a buffer) -- ``isic_hip.graph.gpr_prop``.
+Two of those cannot run as the reference writes them: its ``gatv2``
 branch does not widen ``out_dim`` by the head count although ``concat=True`` (`05_train_gnns.py:99-101`),
 so the following LayerNorm rejects the layer's output, and ``fagcn`` is called as
 ``layer(h, edge_index, edge_weight)`` (`:184-185`) whereas the layer takes ``(x, x_0, edge_index)``.
@@ -33,18 +36,19 @@ import math
 import torch
 import torch.nn as nn
 
+from isic_hip import graph as _graph_ops
 from isic_hip import ops
 from isic_hip.bags import BagOffsets, as_offsets
-from isic_hip.graph import (GraphBatch, fa_conv, gat_conv, gatv2_conv, gcn_block, l2_normalize, spmm,
-                            transformer_attention)
+from isic_hip.graph import (GPR_MAX_K, GraphBatch, fa_conv, gat_conv, gatv2_conv, gcn_block, gpr_check, gpr_gamma, gpr_prop,
+                            l2_normalize, spmm, transformer_attention)
 from utils_g_mil import _DropoutClock
 
-GNN_TYPES = ("mlp", "gcn", "gat", "gatv2", "gin", "graphsage", "transformer", "fagcn", "gcnii")
+GNN_TYPES = ("mlp", "gcn", "gat", "gatv2", "gin", "graphsage", "transformer", "fagcn", "gcnii", "gprgnn", "appnp")
 _BUILT = GNN_TYPES
 # CSR the layer aggregates over: 'gcn' = self loops re-added (+ symmetric normalisation where the layer uses it),
 # 'sum' / 'mean' = the edges as given (TransformerConv adds no self loops)
 _GRAPH_MODE = {"gcn": "gcn", "gcnii": "gcn", "graphsage": "mean", "gin": "sum", "gat": "gcn", "gatv2": "gcn",
-               "transformer": "sum", "fagcn": "gcn"}
+               "transformer": "sum", "fagcn": "gcn", "gprgnn": "gcn", "appnp": "gcn"}
 
 
 class _GCNConvParams(nn.Module):
@@ -55,6 +59,20 @@ class _GCNConvParams(nn.Module):
         self.bias = nn.Parameter(torch.zeros(out_dim))
         self.lin = nn.Linear(in_dim, out_dim, bias=False)
         nn.init.xavier_uniform_(self.lin.weight)
+
+
+class _GPRConvParams(_GCNConvParams):
+    """``GPRConv(in, F, K, alpha)``: ``bias`` [F] and ``lin.weight`` [F, in] as ``GCNConv``, plus ``gamma`` [K+1] with the PPR
+    initialisation gamma[k] = alpha (1 - alpha)^k, gamma[K] = (1 - alpha)^K -- an ``nn.Parameter`` (GPR-GNN), or with
+    ``learned=False`` a persistent buffer that is never trained (PyG ``APPNP(K, alpha)`` applied to ``lin(x)``)."""
+
+    def __init__(self, in_dim, out_dim, K, alpha, learned):
+        super().__init__(in_dim, out_dim)
+        g = gpr_gamma(K, alpha)
+        if learned:
+            self.gamma = nn.Parameter(g)
+        else:
+            self.register_buffer("gamma", g, persistent=True)
 
 
 class _GCN2ConvParams(nn.Module):
@@ -149,11 +167,17 @@ class GraphMIL(nn.Module):
     def __init__(self, input_dim=768, gnn_type='gat', gnn_hidden=256, gnn_layers=2, gnn_dropout=0.1, gnn_heads=4,
                  gnn_concat=True, gcnii_alpha=0.1, gcnii_theta=0.5, att_dim=128, att_heads=4, pool_dropout=0.2,
                  classifier_dim=128, classifier_light=False, num_classes=7, use_residual=True, use_layer_norm=True,
-                 att_gated=False):
+                 att_gated=False, gpr_k=10, gpr_alpha=0.1):
         super().__init__()
         self.gnn_type = gnn_type.lower()
         if self.gnn_type not in GNN_TYPES:
             raise ValueError(f"Unsupported gnn_type: {self.gnn_type}")           # 05:113-114
+        if not (isinstance(gpr_k, int) and 0 <= gpr_k <= GPR_MAX_K):
+            raise ValueError(f"gpr_k must be an integer in 0..{GPR_MAX_K}, got {gpr_k!r}")
+        if not 0.0 <= float(gpr_alpha) <= 1.0:                                   # (false for a NaN as well)
+            raise ValueError(f"gpr_alpha must lie in [0, 1], got {gpr_alpha!r}")
+        self.gpr_k, self.gpr_alpha = gpr_k, float(gpr_alpha)
+        self.gpr_resident = None     # True / False pins the path of isic_hip.graph.gpr_prop; None = its measured default
         self.use_residual, self.use_layer_norm = use_residual, use_layer_norm
         self.classifier_light, self.gnn_heads, self.gnn_concat = classifier_light, gnn_heads, gnn_concat
         if (use_residual or self.gnn_type in {"fagcn", "gcnii"}) and input_dim != gnn_hidden:   # 05:65-68
@@ -167,6 +191,8 @@ class GraphMIL(nn.Module):
             out_dim = gnn_hidden
             if self.gnn_type == 'gcn':
                 layer = _GCNConvParams(in_dim, out_dim)
+            elif self.gnn_type in ('gprgnn', 'appnp'):
+                layer = _GPRConvParams(in_dim, out_dim, gpr_k, gpr_alpha, learned=self.gnn_type == 'gprgnn')
             elif self.gnn_type == 'gcnii':
                 if in_dim != out_dim:
                     raise ValueError("GCNII requires a constant hidden dimension across layers")
@@ -248,7 +274,8 @@ class GraphMIL(nn.Module):
             raise ValueError(f"gnn_type '{self.gnn_type}' needs edge_index")
         mode = _GRAPH_MODE[self.gnn_type]
         # 05:184-187 passes edge_weight to gcn / gcnii only
-        return GraphBatch(edge_index, n_nodes, edge_weight if self.gnn_type in ("gcn", "gcnii") else None, mode=mode)
+        return GraphBatch(edge_index, n_nodes, edge_weight if self.gnn_type in ("gcn", "gcnii", "gprgnn", "appnp") else None,
+                          mode=mode)
 
     def forward(self, x, edge_index=None, edge_weight=None, offsets=None, graph=None, labels=None, x_rows=None):
         """x[N, D] (+ edge_index[2, E]) -> (probs[C], attention_weights[N, heads]) as the reference
@@ -272,6 +299,10 @@ class GraphMIL(nn.Module):
             x_in = ops.linear(x, self.input_proj.weight, self.input_proj.bias) if self.input_proj is not None else x
         h, x0 = x_in, x_in
         p_drop = self.gnn_dropout.p
+        # gprgnn / appnp: the path (None = isic_hip.graph.GPR_RESIDENT_DEFAULT) and, for the resident kernel, ONE counter of
+        # refused graphs for all the layers of this forward, read back once at the end (not inside a capture)
+        gpr_res = _graph_ops.GPR_RESIDENT_DEFAULT if self.gpr_resident is None else bool(self.gpr_resident)
+        gpr_bad = None
         for i, layer in enumerate(self.gnn_layers):
             h_prev = h
             if self.gnn_type == 'gcn' and self.use_layer_norm and self.use_residual and layer.lin.weight.shape[0] == h.shape[1]:
@@ -284,6 +315,11 @@ class GraphMIL(nn.Module):
                 h = ops.linear(h, layer[0].weight, layer[0].bias)
             elif self.gnn_type == 'gcn':
                 h = spmm(ops.linear(h, layer.lin.weight, None), g, bias=layer.bias)
+            elif self.gnn_type in ('gprgnn', 'appnp'):     # sum_k gamma[k] A^^k lin(h) + bias
+                if gpr_res and gpr_bad is None:
+                    gpr_bad = torch.zeros(1, device=h.device, dtype=torch.int32)
+                h = gpr_prop(ops.linear(h, layer.lin.weight, None), layer.gamma, g, offs, bias=layer.bias, resident=gpr_res,
+                             bad=gpr_bad)
             elif self.gnn_type == 'gat':           # edge softmax over the CSR rows; attention dropout = site 32 + i
                 h = gat_conv(ops.linear(h, layer.lin.weight, None), layer.att_src, layer.att_dst, layer.bias, g,
                              layer.heads, 0.2, clk.spec(p_drop, 32 + i, tr), concat=self.gnn_concat)
@@ -321,6 +357,8 @@ class GraphMIL(nn.Module):
                 h = ops.relu_dropout(h, clk.spec(p_drop, i, tr))
                 if res is not None:
                     h = h + res
+        if gpr_bad is not None and not torch.cuda.is_current_stream_capturing():
+            gpr_check(gpr_bad)
         self.last_node_embeddings = h.detach()
         # the heads' parameters as one [heads*A, H] operand -- and the gates', if any, as the second half of [2*heads*A, H]
         W2, b2, w3, b3, *gate = ops.head_params(self.attention_layers, self.attention_gates if self.att_gated else None)

@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 
 from .bags import BagOffsets
-from .lib import IsicHipError, call
+from .lib import ERR_UNSUPPORTED, IsicHipError, call
 from .ops import _acc_target, _chk, _f32c, _grad_colsum, _grad_gemm, colsum
 
 
@@ -424,6 +424,131 @@ class SpmmFn(torch.autograd.Function):
 
 def spmm(x, graph, bias=None, alpha=1.0, addend=None, addend_scale=0.0):
     return SpmmFn.apply(x, graph, bias, alpha, addend, addend_scale)
+
+
+GPR_MAX_NODES = 256
+GPR_MAX_K = 16
+GPR_SLAB = 32
+# Which path ``gpr_prop`` takes inside the resident kernel's domain when the caller does not say: decided by the measurement of
+# tools/gpr_bench.py (profiles/gpr_bench.txt, DESIGN.md "GPR-GNN and APPNP: the graph-resident K-hop kernel") under the
+# project's rule -- the resident kernel is the default only if its advantage over the composed path on the WHOLE train step
+# exceeds three times the wider run-to-run range.  Measured at 668 graphs x 196 nodes, F = 128, three layers, K = 10: the
+# GraphMIL[gprgnn] step takes 8.04 ms resident against 10.87 ms composed (appnp: 7.69 against 8.46), ranges below 0.02 ms.
+GPR_RESIDENT_DEFAULT = True
+_GPR_LAST_PATH = None
+
+
+def gpr_last_path():
+    """'resident' or 'composed': the path the last ``gpr_prop`` call took (for tests and the benchmark)."""
+    return _GPR_LAST_PATH
+
+
+def gpr_gamma(K, alpha, dtype=torch.float32):
+    """The PPR coefficients of GPR-GNN / APPNP: gamma[k] = alpha (1 - alpha)^k for k < K, gamma[K] = (1 - alpha)^K."""
+    K, alpha = int(K), float(alpha)
+    g = [alpha * (1.0 - alpha) ** k for k in range(K)] + [(1.0 - alpha) ** K]
+    return torch.tensor(g, dtype=dtype)
+
+
+def gpr_prop_composed(h, gamma, graph, bias=None):
+    """Z = sum_k gamma[k] A^^k h (+ bias) as K calls of ``spmm`` plus torch axpys under ordinary autograd: the fallback
+    outside the resident kernel's domain and the A/B baseline of tools/gpr_bench.py."""
+    K = int(gamma.numel()) - 1
+    p = h
+    z = gamma[0] * p
+    for k in range(1, K + 1):
+        p = spmm(p, graph)
+        z = z + gamma[k] * p
+    return z + bias if bias is not None else z
+
+
+class GprPropFn(torch.autograd.Function):
+    """Z = sum_k gamma[k] A^^k h (+ bias) in one launch (``isic_gpr_prop_f32``); backward on the transposed CSR in one
+    launch plus the fixed-order reduction of the d gamma partials (``isic_gpr_prop_bwd_f32``)."""
+
+    @staticmethod
+    def forward(ctx, h, gamma, graph, offsets, bias, bad):
+        _chk(h, gamma, bias)
+        h2, gm = _f32c(h), _f32c(gamma)
+        n, F = h2.shape
+        if n != graph.n_nodes or n != offsets.total:
+            raise ValueError(f"h has {n} rows, graph has {graph.n_nodes} nodes, offsets cover {offsets.total}")
+        K = int(gm.numel()) - 1
+        z = torch.empty_like(h2)
+        call("isic_gpr_prop_f32", graph.rowptr, graph.col, graph.val, int(graph.col.numel()), offsets.device, offsets.num_bags,
+             offsets.max_bag, n, h2, gm, K, F, _f32c(bias) if bias is not None else None, z, bad)
+        ctx.graph, ctx.offsets, ctx.K, ctx.bad = graph, offsets, K, bad
+        ctx.params = (gamma, bias)              # the Parameters themselves: fused_grad_accumulation adds into their .grad
+        ctx.save_for_backward(h2, gm)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        from .ops import _workspace
+        h2, gm = ctx.saved_tensors
+        gamma, bias = ctx.params
+        g, offs, K = ctx.graph, ctx.offsets, ctx.K
+        dz = _f32c(dz)
+        n, F = dz.shape
+        dh = torch.empty_like(dz) if ctx.needs_input_grad[0] else None
+        dg_out, tg, ws, nbytes = None, None, None, 0
+        if ctx.needs_input_grad[1]:             # appnp: gamma is a buffer, no partials are formed
+            tg = _acc_target(gamma)
+            dg_out = tg if tg is not None else torch.empty((K + 1,), device=dz.device, dtype=torch.float32)
+            nbytes = int(call("isic_gpr_prop_bwd_workspace_bytes", offs.num_bags, K, F))
+            ws = _workspace(nbytes, dz.device)
+        if dh is not None or dg_out is not None:
+            call("isic_gpr_prop_bwd_f32", g.rowptr_t, g.col_t, g.val_t, int(g.col_t.numel()), offs.device, offs.num_bags,
+                 offs.max_bag, n, dz, h2, gm, K, F, dh, dg_out, 1.0 if tg is not None else 0.0, ws, nbytes, ctx.bad)
+        db = _grad_colsum(bias, dz) if bias is not None and ctx.needs_input_grad[4] else None
+        dgamma = None if (dg_out is None or tg is not None) else dg_out.reshape(gamma.shape)
+        return dh, dgamma, None, None, db, None
+
+
+def gpr_prop(h, gamma, graph, offsets=None, bias=None, resident=None, check=True, bad=None):
+    """The K-hop polynomial filter of GPR-GNN / APPNP on a 'gcn'-mode ``GraphBatch``: Z = sum_{k=0..K} gamma[k] A^^k h
+    (+ bias), K = len(gamma) - 1, with gradients for ``h``, ``gamma`` (skipped when it does not require one) and ``bias``.
+
+    ``resident`` picks the path: True = the graph-resident kernel (``isic_gpr_prop_f32``: every hop of a graph's column slab
+    out of LDS, one launch), False = ``gpr_prop_composed``, None = ``GPR_RESIDENT_DEFAULT``.  The resident kernel needs
+    ``offsets`` (``BagOffsets``: graph g owns rows offsets[g]:offsets[g+1], and every edge stays inside its graph) with at
+    most 256 nodes per graph; wherever the entry answers ISIC_ERR_UNSUPPORTED, and without offsets, the composed path runs.
+
+    The kernel counts graphs it refused -- offsets that do not fit, or a column id outside the graph's own node range; such a
+    graph's rows of Z are NOT written: with ``check`` the counter is read back (4 bytes, a synchronisation) and a non-zero
+    count is a ``ValueError``.  ``bad`` (device int32 [1]): the caller's own counter, added to and not read here."""
+    if graph.mode != "gcn":
+        raise ValueError(f"gpr_prop needs a 'gcn'-mode GraphBatch, got '{graph.mode}'")
+    if gamma.dim() != 1 or not 1 <= gamma.numel() <= GPR_MAX_K + 1:
+        raise IsicHipError(f"gpr_prop takes gamma [K + 1] with 0 <= K <= {GPR_MAX_K}, got {tuple(gamma.shape)}", code=-1)
+    global _GPR_LAST_PATH
+    if resident is None:
+        resident = GPR_RESIDENT_DEFAULT
+    _GPR_LAST_PATH = "composed"
+    if not resident or offsets is None:
+        return gpr_prop_composed(h, gamma, graph, bias)
+    own = bad is None
+    if own:
+        bad = torch.zeros(1, device=h.device, dtype=torch.int32)            # (uint32 on the device side)
+    try:
+        z = GprPropFn.apply(h, gamma, graph, offsets, bias, bad)
+    except IsicHipError as e:
+        if e.code != ERR_UNSUPPORTED:
+            raise
+        return gpr_prop_composed(h, gamma, graph, bias)
+    _GPR_LAST_PATH = "resident"
+    if own and check:
+        gpr_check(bad)
+    return z
+
+
+def gpr_check(bad):
+    """Reads a ``gpr_prop`` counter back (a synchronisation) and raises on a non-zero count."""
+    n_bad = int(bad.item()) & 0xFFFFFFFF
+    if n_bad:
+        raise ValueError(f"gpr_prop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
+                         f"{GPR_MAX_NODES} nodes, or that hold a column id outside their own node range; their rows were "
+                         "not written")
 
 
 class GcnBlockFn(torch.autograd.Function):
