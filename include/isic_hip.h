@@ -692,5 +692,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_moments_ragged.h"
 /* The K-hop polynomial graph filter of GPR-GNN / APPNP, graph-resident (all hops of a graph's column slab out of LDS, forward and backward with the coefficient gradient): three more entry points, same conventions. */
 #include "isic_hip_gpr.h"
+/* H2GCN: the exact 2-hop neighbourhood of every graph of a batch built on the device (count, then write behind the caller's scan), and the graph-resident two-operator propagation [A1^ H | A2^ H] with its backward: four more entry points, same conventions. */
+#include "isic_hip_h2.h"
 
 #endif /* ISIC_HIP_H */

@@ -14,7 +14,11 @@ is absent and unpinned in the reference, see oracle/gnn.py), plus ``gatv2`` (GAT
 ``transformer`` (TransformerConv(beta=True)) and ``fagcn`` (FAConv) on the edge-attention kernels of
 ``edge_attn.hip``, and ``gprgnn`` / ``appnp``: the learned polynomial graph filter of GPR-GNN (Chien et al. 2021),
 out = sum_k gamma[k] A^^k lin(x) + bias with ``gamma`` [K+1] a parameter initialised to the PPR coefficients, and its
-fixed-coefficient case, PyG ``APPNP(K, alpha)`` applied to ``lin(x)`` (``gamma`` a buffer) -- ``isic_hip.graph.gpr_prop``.
+fixed-coefficient case, PyG ``APPNP(K, alpha)`` applied to ``lin(x)`` (``gamma`` a buffer) -- ``isic_hip.graph.gpr_prop``,
+and ``h2gcn`` (Zhu et al. 2020): r_0 = the projected input, r_i = the post-layer treatment of [A1^ r_{i-1} | A2^ r_{i-1}] with
+A1^ the symmetrised 1-hop graph without self loops and A2^ the nodes at distance exactly 2 (each D^-1/2 A D^-1/2), the layers
+without parameters, the pooled representation [r_0 | ... | r_L] of (2^(L+1) - 1) x ``gnn_hidden`` columns (at most 4096) --
+``isic_hip.graph.two_hop`` / ``h2_prop``.
 Two of those cannot run as the reference writes them: its ``gatv2``
 branch does not widen ``out_dim`` by the head count although ``concat=True`` (`05_train_gnns.py:99-101`),
 so the following LayerNorm rejects the layer's output, and ``fagcn`` is called as
@@ -40,15 +44,18 @@ from isic_hip import graph as _graph_ops
 from isic_hip import ops
 from isic_hip.bags import BagOffsets, as_offsets
 from isic_hip.graph import (GPR_MAX_K, GraphBatch, fa_conv, gat_conv, gatv2_conv, gcn_block, gpr_check, gpr_gamma, gpr_prop,
-                            l2_normalize, spmm, transformer_attention)
+                            h2_check, h2_prop, l2_normalize, spmm, transformer_attention, two_hop)
 from utils_g_mil import _DropoutClock
 
-GNN_TYPES = ("mlp", "gcn", "gat", "gatv2", "gin", "graphsage", "transformer", "fagcn", "gcnii", "gprgnn", "appnp")
+GNN_TYPES = ("mlp", "gcn", "gat", "gatv2", "gin", "graphsage", "transformer", "fagcn", "gcnii", "gprgnn", "appnp",
+             "h2gcn")
 _BUILT = GNN_TYPES
 # CSR the layer aggregates over: 'gcn' = self loops re-added (+ symmetric normalisation where the layer uses it),
-# 'sum' / 'mean' = the edges as given (TransformerConv adds no self loops)
+# 'sum' / 'mean' = the edges as given (TransformerConv adds no self loops), 'h2' = the 1-hop and exact 2-hop operators of H2GCN
+# (``isic_hip.graph.two_hop``: a ``TwoHopGraph``, built from a 'sum'-mode CSR)
+H2_MAX_WIDTH = 4096          # the widest pool / LayerNorm path (include/isic_hip_wide.h)
 _GRAPH_MODE = {"gcn": "gcn", "gcnii": "gcn", "graphsage": "mean", "gin": "sum", "gat": "gcn", "gatv2": "gcn",
-               "transformer": "sum", "fagcn": "gcn", "gprgnn": "gcn", "appnp": "gcn"}
+               "transformer": "sum", "fagcn": "gcn", "gprgnn": "gcn", "appnp": "gcn", "h2gcn": "h2"}
 
 
 class _GCNConvParams(nn.Module):
@@ -73,6 +80,10 @@ class _GPRConvParams(_GCNConvParams):
             self.gamma = nn.Parameter(g)
         else:
             self.register_buffer("gamma", g, persistent=True)
+
+
+class _H2Layer(nn.Module):
+    """One round of H2GCN (Zhu et al. 2020): r -> [A1^ r | A2^ r], no parameter, no buffer, nothing in the ``state_dict``."""
 
 
 class _GCN2ConvParams(nn.Module):
@@ -178,9 +189,13 @@ class GraphMIL(nn.Module):
             raise ValueError(f"gpr_alpha must lie in [0, 1], got {gpr_alpha!r}")
         self.gpr_k, self.gpr_alpha = gpr_k, float(gpr_alpha)
         self.gpr_resident = None     # True / False pins the path of isic_hip.graph.gpr_prop; None = its measured default
+        self.h2_resident = None      # the same for isic_hip.graph.h2_prop
+        if self.gnn_type == "h2gcn" and ((1 << (gnn_layers + 1)) - 1) * gnn_hidden > H2_MAX_WIDTH:
+            raise ValueError(f"h2gcn concatenates (2^(layers + 1) - 1) x gnn_hidden = {((1 << (gnn_layers + 1)) - 1) * gnn_hidden} "
+                             f"columns, more than the {H2_MAX_WIDTH} the pooling and LayerNorm kernels take")
         self.use_residual, self.use_layer_norm = use_residual, use_layer_norm
         self.classifier_light, self.gnn_heads, self.gnn_concat = classifier_light, gnn_heads, gnn_concat
-        if (use_residual or self.gnn_type in {"fagcn", "gcnii"}) and input_dim != gnn_hidden:   # 05:65-68
+        if (use_residual or self.gnn_type in {"fagcn", "gcnii", "h2gcn"}) and input_dim != gnn_hidden:   # 05:65-68
             self.input_proj = nn.Linear(input_dim, gnn_hidden)
         else:
             self.input_proj = None
@@ -193,6 +208,9 @@ class GraphMIL(nn.Module):
                 layer = _GCNConvParams(in_dim, out_dim)
             elif self.gnn_type in ('gprgnn', 'appnp'):
                 layer = _GPRConvParams(in_dim, out_dim, gpr_k, gpr_alpha, learned=self.gnn_type == 'gprgnn')
+            elif self.gnn_type == 'h2gcn':         # s_i = [A1^ r_{i-1} | A2^ r_{i-1}]: 2^i x gnn_hidden columns
+                layer = _H2Layer()
+                out_dim = 2 * in_dim
             elif self.gnn_type == 'gcnii':
                 if in_dim != out_dim:
                     raise ValueError("GCNII requires a constant hidden dimension across layers")
@@ -221,6 +239,8 @@ class GraphMIL(nn.Module):
                 self.layer_norms.append(nn.LayerNorm(out_dim))
             in_dim = out_dim
         self.gnn_dropout = nn.Dropout(gnn_dropout)
+        if self.gnn_type == 'h2gcn':               # the final representation is [r_0 | r_1 | ... | r_L]
+            in_dim = ((1 << (gnn_layers + 1)) - 1) * gnn_hidden
         self.final_gnn_dim = in_dim
         self.att_heads = att_heads
         self.attention_layers = nn.ModuleList([
@@ -262,7 +282,7 @@ class GraphMIL(nn.Module):
                                                             dtype=torch.float32)
         return torch.add(e, layer.weight1, alpha=layer.beta).t()
 
-    def _graph(self, edge_index, edge_weight, n_nodes, graph):
+    def _graph(self, edge_index, edge_weight, n_nodes, graph, offs=None):
         if self.gnn_type == 'mlp':
             return None
         if graph is not None:
@@ -273,6 +293,8 @@ class GraphMIL(nn.Module):
         if edge_index is None:
             raise ValueError(f"gnn_type '{self.gnn_type}' needs edge_index")
         mode = _GRAPH_MODE[self.gnn_type]
+        if mode == "h2":                           # edge_weight is ignored, as for gat
+            return two_hop(GraphBatch(edge_index, n_nodes, None, mode="sum"), offs)
         # 05:184-187 passes edge_weight to gcn / gcnii only
         return GraphBatch(edge_index, n_nodes, edge_weight if self.gnn_type in ("gcn", "gcnii", "gprgnn", "appnp") else None,
                           mode=mode)
@@ -292,7 +314,7 @@ class GraphMIL(nn.Module):
         n_nodes = x_rows[1] if x_rows is not None else x.shape[0]
         offs = BagOffsets.single(n_nodes, x.device) if single else as_offsets(offsets, x.device)
         clk, tr = self.dropout_clock, self.training
-        g = self._graph(edge_index, edge_weight, n_nodes, graph)
+        g = self._graph(edge_index, edge_weight, n_nodes, graph, offs)
         if x_rows is not None:
             x_in = ops.linear_rows(x, x_rows[0], n_nodes, self.input_proj.weight, self.input_proj.bias)
         else:
@@ -303,6 +325,9 @@ class GraphMIL(nn.Module):
         # refused graphs for all the layers of this forward, read back once at the end (not inside a capture)
         gpr_res = _graph_ops.GPR_RESIDENT_DEFAULT if self.gpr_resident is None else bool(self.gpr_resident)
         gpr_bad = None
+        # h2gcn: the same bookkeeping (one counter per forward), and the representations r_0 .. r_L that are concatenated at the end
+        h2_res = _graph_ops.H2_RESIDENT_DEFAULT if self.h2_resident is None else bool(self.h2_resident)
+        h2_bad, h2_reps = None, [x_in]
         for i, layer in enumerate(self.gnn_layers):
             h_prev = h
             if self.gnn_type == 'gcn' and self.use_layer_norm and self.use_residual and layer.lin.weight.shape[0] == h.shape[1]:
@@ -320,6 +345,10 @@ class GraphMIL(nn.Module):
                     gpr_bad = torch.zeros(1, device=h.device, dtype=torch.int32)
                 h = gpr_prop(ops.linear(h, layer.lin.weight, None), layer.gamma, g, offs, bias=layer.bias, resident=gpr_res,
                              bad=gpr_bad)
+            elif self.gnn_type == 'h2gcn':         # [A1^ h | A2^ h]: ego, 1-hop and 2-hop embeddings stay separate
+                if h2_res and h2_bad is None:
+                    h2_bad = torch.zeros(1, device=h.device, dtype=torch.int32)
+                h = h2_prop(h, g, offs, resident=h2_res, bad=h2_bad)
             elif self.gnn_type == 'gat':           # edge softmax over the CSR rows; attention dropout = site 32 + i
                 h = gat_conv(ops.linear(h, layer.lin.weight, None), layer.att_src, layer.att_dst, layer.bias, g,
                              layer.heads, 0.2, clk.spec(p_drop, 32 + i, tr), concat=self.gnn_concat)
@@ -357,6 +386,12 @@ class GraphMIL(nn.Module):
                 h = ops.relu_dropout(h, clk.spec(p_drop, i, tr))
                 if res is not None:
                     h = h + res
+            if self.gnn_type == 'h2gcn':
+                h2_reps.append(h)
+        if self.gnn_type == 'h2gcn':
+            h = torch.cat(h2_reps, dim=1)
+            if h2_bad is not None and not torch.cuda.is_current_stream_capturing():
+                h2_check(h2_bad)
         if gpr_bad is not None and not torch.cuda.is_current_stream_capturing():
             gpr_check(gpr_bad)
         self.last_node_embeddings = h.detach()

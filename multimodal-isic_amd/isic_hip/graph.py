@@ -361,10 +361,17 @@ class GraphBatch:
              self.rowptr_t, self.col_t, self.val_t, self.perm_t, ws, nbytes)
 
 
+# The mode name of a ``GraphBatch`` whose CSR is symmetric with values of its own (an operator of ``two_hop``): no build
+# produces it (``GraphBatch(..., mode="sym")`` is an error), only ``from_parts`` takes it; its ``_t`` arrays alias the forward
+# ones and ``perm_t`` maps the slot of (i, j) to the slot of (j, i).
+SYM_MODE = "sym"
+
+
 def _graph_from_parts(n_nodes, num_edges, mode, parts):
     """A ``GraphBatch`` over CSR arrays that already exist on the device (no build launch): used by
-    ``train.GraphStore`` to assemble a step's batch out of per-graph pieces built once."""
-    if mode not in GraphBatch.MODES:
+    ``train.GraphStore`` to assemble a step's batch out of per-graph pieces built once.  ``mode``: a build mode, or
+    ``"sym"`` for a symmetric operator that no build produces (``two_hop``)."""
+    if mode not in GraphBatch.MODES and mode != SYM_MODE:
         raise ValueError(f"unknown graph mode '{mode}'")
     g = GraphBatch.__new__(GraphBatch)
     g.n_nodes, g.num_edges, g.mode = int(n_nodes), int(num_edges), mode
@@ -549,6 +556,169 @@ def gpr_check(bad):
         raise ValueError(f"gpr_prop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
                          f"{GPR_MAX_NODES} nodes, or that hold a column id outside their own node range; their rows were "
                          "not written")
+
+
+H2_MAX_NODES = 256
+H2_SLAB = 32
+# Which path ``h2_prop`` takes inside the resident kernel's domain when the caller does not say: decided by the measurement of
+# tools/h2_bench.py (profiles/h2_bench.txt, DESIGN.md "H2GCN: the device 2-hop build and the two-operator propagation") under
+# the project's rule -- the resident kernel is the default only if its advantage over the composed path on the WHOLE train step
+# exceeds three times the wider run-to-run range.  Measured at 668 graphs x 196 nodes, F = 128, two layers: the GraphMIL[h2gcn]
+# step takes 8.06 ms resident against 7.40 ms composed on grid8, 13.25 against 9.26 on knn8 and 13.44 against 9.53 on random8
+# (ranges below 0.13 ms): the resident kernel loses on every variant, also at 117 - 129 entries per 2-hop row, and is opt-in.
+H2_RESIDENT_DEFAULT = False
+_H2_LAST_PATH = None
+
+
+def h2_last_path():
+    """'resident' or 'composed': the path the last ``h2_prop`` call took (for tests and the benchmark)."""
+    return _H2_LAST_PATH
+
+
+class TwoHopGraph:
+    """The two symmetric operators of H2GCN over a batch of graphs (``two_hop``): ``a1`` = A1^, the symmetrised 1-hop graph
+    without self loops, ``a2`` = A2^, the nodes at distance exactly 2, each D^-1/2 A D^-1/2 by its own row counts -- two
+    ``GraphBatch``es of mode ``"sym"`` with GLOBAL ids, columns ascending inside a row.  ``mode`` is ``"h2"``: what
+    ``GraphMIL(gnn_type="h2gcn")`` asks of a prebuilt graph."""
+
+    mode = "h2"
+
+    def __init__(self, a1, a2):
+        if a1.n_nodes != a2.n_nodes:
+            raise ValueError("the two operators must cover the same nodes")
+        self.a1, self.a2, self.n_nodes = a1, a2, a1.n_nodes
+
+
+def _sym_graph(n, rowptr, col, val, perm):
+    return GraphBatch.from_parts(n, int(col.numel()), SYM_MODE, {"rowptr": rowptr, "col": col, "val": val, "rowptr_t": rowptr,
+                                                                "col_t": col, "val_t": val, "perm_t": perm})
+
+
+def two_hop_count_launch(graph, offsets, deg, bad):
+    """The bare ``isic_two_hop_count`` launch: ``deg`` int32 [2, N] (zeroed by the caller), ``bad`` int32 [1]."""
+    call("isic_two_hop_count", graph.rowptr, graph.col, int(graph.col.numel()), offsets.device, offsets.num_bags, offsets.max_bag,
+         graph.n_nodes, deg[0], deg[1], bad)
+
+
+def two_hop_write_launch(graph, offsets, rp, nnz1, nnz2, out1, out2, bad):
+    """The bare ``isic_two_hop_write`` launch: ``rp`` int32 [2, N + 1], ``outp`` = (col, val, perm) of nnzp entries each."""
+    call("isic_two_hop_write", graph.rowptr, graph.col, int(graph.col.numel()), offsets.device, offsets.num_bags, offsets.max_bag,
+         graph.n_nodes, rp[0], rp[1], int(nnz1), int(nnz2), out1[0], out1[1], out1[2], out2[0], out2[1], out2[2], bad)
+
+
+def two_hop(graph, offsets) -> TwoHopGraph:
+    """The 1-hop and the exact 2-hop operator of every graph of a batch (include/isic_hip_h2.h; tests/h2gcn_ref.py restates
+    them): ``graph`` is any ``GraphBatch`` -- only its structure is read: direction, duplicates, self loops and values do not
+    matter -- and ``offsets`` (``BagOffsets``) says which rows each graph owns, at most 256 per graph.  Two launches
+    (``isic_two_hop_count`` / ``_write``), a scan between them and ONE read-back: the two entry totals and the kernels' count of
+    refused graphs, which is a ``ValueError`` when it is not zero."""
+    n = graph.n_nodes
+    if n != offsets.total:
+        raise ValueError(f"graph has {n} nodes, offsets cover {offsets.total}")
+    if offsets.max_bag > H2_MAX_NODES:
+        raise IsicHipError(f"two_hop supports up to {H2_MAX_NODES} nodes per graph, got {offsets.max_bag}", code=ERR_UNSUPPORTED)
+    dev = graph.rowptr.device
+    i32 = torch.int32
+    deg = torch.zeros((2, n), device=dev, dtype=i32)
+    bad = torch.zeros(1, device=dev, dtype=i32)                             # (uint32 on the device side)
+    two_hop_count_launch(graph, offsets, deg, bad)
+    rp = torch.zeros((2, n + 1), device=dev, dtype=torch.int64)
+    rp[:, 1:] = torch.cumsum(deg, dim=1, dtype=torch.int64)
+    head = torch.cat([rp[:, -1], bad.to(torch.int64) & 0xFFFFFFFF]).cpu().tolist()       # the one read-back
+    nnz1, nnz2, n_bad = int(head[0]), int(head[1]), int(head[2])
+    if n_bad:
+        raise ValueError(f"two_hop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
+                         f"{H2_MAX_NODES} nodes, whose row pointers decrease or leave the entry range, or that hold a column id outside "
+                         "their own node range")
+    if max(nnz1, nnz2) >= 2 ** 31 - 1:
+        raise IsicHipError("two_hop: more than 2^31 - 2 entries in one operator", code=ERR_UNSUPPORTED)
+    rp = rp.to(i32)
+    outs = [(torch.empty(z, device=dev, dtype=i32), torch.empty(z, device=dev, dtype=torch.float32),
+             torch.empty(z, device=dev, dtype=i32)) for z in (nnz1, nnz2)]
+    two_hop_write_launch(graph, offsets, rp, nnz1, nnz2, outs[0], outs[1], bad)
+    return TwoHopGraph(_sym_graph(n, rp[0], *outs[0]), _sym_graph(n, rp[1], *outs[1]))
+
+
+def h2_prop_composed(h, g2):
+    """[A1^ h | A2^ h] as two calls of ``spmm`` plus ``torch.cat`` under ordinary autograd: the fallback outside the resident
+    kernel's domain and the A/B baseline of tools/h2_bench.py."""
+    return torch.cat([spmm(h, g2.a1), spmm(h, g2.a2)], dim=1)
+
+
+def _h2_launch(name, g2, offsets, x, ldx, F, out, ldo, bad):
+    a1, a2 = g2.a1, g2.a2
+    call(name, a1.rowptr, a1.col, a1.val, int(a1.col.numel()), a2.rowptr, a2.col, a2.val, int(a2.col.numel()), offsets.device,
+         offsets.num_bags, offsets.max_bag, g2.n_nodes, x, int(ldx), int(F), out, int(ldo), bad)
+
+
+class H2PropFn(torch.autograd.Function):
+    """Z = [A1^ h | A2^ h] in one launch (``isic_h2_prop_f32``); the backward dh = A1^ dz[:, :F] + A2^ dz[:, F:] in one launch
+    on the same CSRs (``isic_h2_prop_bwd_f32``): the operators are symmetric."""
+
+    @staticmethod
+    def forward(ctx, h, g2, offsets, bad):
+        _chk(h)
+        h2 = _f32c(h)
+        n, F = h2.shape
+        if n != g2.n_nodes or n != offsets.total:
+            raise ValueError(f"h has {n} rows, graph has {g2.n_nodes} nodes, offsets cover {offsets.total}")
+        z = torch.empty((n, 2 * F), device=h2.device, dtype=torch.float32)
+        _h2_launch("isic_h2_prop_f32", g2, offsets, h2, F, F, z, 2 * F, bad)
+        ctx.g2, ctx.offsets, ctx.bad = g2, offsets, bad
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dz = _f32c(dz)
+        n, F = dz.shape[0], dz.shape[1] // 2
+        dh = torch.empty((n, F), device=dz.device, dtype=torch.float32)
+        _h2_launch("isic_h2_prop_bwd_f32", ctx.g2, ctx.offsets, dz, 2 * F, F, dh, F, ctx.bad)
+        return dh, None, None, None
+
+
+def h2_prop(h, g2, offsets=None, resident=None, bad=None):
+    """The layer of H2GCN on a ``TwoHopGraph``: Z [N, 2 F] = [A1^ h | A2^ h], with the gradient for ``h``.
+
+    ``resident`` picks the path: True = the graph-resident kernel (``isic_h2_prop_f32``: a graph's column slab staged once in
+    LDS, both operators gathered out of it, one launch), False = ``h2_prop_composed``, None = ``H2_RESIDENT_DEFAULT``.  The
+    resident kernel needs ``offsets`` (``BagOffsets``: graph g owns rows offsets[g]:offsets[g+1]) with at most 256 nodes per
+    graph; wherever the entry answers ISIC_ERR_UNSUPPORTED, and without offsets, the composed path runs.
+
+    The kernel counts graphs it refused (their rows of Z are NOT written): without ``bad`` the counter is read back (4 bytes, a
+    synchronisation) and a non-zero count is a ``ValueError``.  ``bad`` (device int32 [1]): the caller's own counter, added to
+    and not read here (``h2_check``)."""
+    if getattr(g2, "mode", None) != "h2":
+        raise ValueError("h2_prop needs a TwoHopGraph (isic_hip.graph.two_hop)")
+    global _H2_LAST_PATH
+    if resident is None:
+        resident = H2_RESIDENT_DEFAULT
+    _H2_LAST_PATH = "composed"
+    if not resident or offsets is None:
+        return h2_prop_composed(h, g2)
+    own = bad is None
+    if own:
+        bad = torch.zeros(1, device=h.device, dtype=torch.int32)            # (uint32 on the device side)
+    try:
+        z = H2PropFn.apply(h, g2, offsets, bad)
+    except IsicHipError as e:
+        if e.code != ERR_UNSUPPORTED:
+            raise
+        return h2_prop_composed(h, g2)
+    _H2_LAST_PATH = "resident"
+    if own:
+        h2_check(bad)
+    return z
+
+
+def h2_check(bad):
+    """Reads an ``h2_prop`` counter back (a synchronisation) and raises on a non-zero count."""
+    n_bad = int(bad.item()) & 0xFFFFFFFF
+    if n_bad:
+        raise ValueError(f"h2_prop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
+                         f"{H2_MAX_NODES} nodes, or whose operators hold a column id outside the graph's own node range; their "
+                         "rows were not written")
 
 
 class GcnBlockFn(torch.autograd.Function):

@@ -342,6 +342,9 @@ def train_milnet_fold(model, train_set, val_set, *, optimizer="adamw", lr=2.2e-4
 RAGGED_STACK_DEFAULT_LESION_ONLY = True
 
 
+H2_MODE = "h2"                                 # gnn_models._GRAPH_MODE["h2gcn"]: a batch's graph is a graph.TwoHopGraph
+
+
 class GraphStore:
     """Graph records resident in HBM with their normalised CSR built once (graphs are static across
     epochs; the reference re-uploads x and edge_index every step, `05:340-343`)."""
@@ -349,7 +352,12 @@ class GraphStore:
     def __init__(self, records, device, needs_graph=True, mode="gcn", lesion_only=False, ragged_stack=None, lesion_knn=None,
                  lesion_random=None):
         """``mode``: aggregation of the CSR the model's layers need (``gnn_models._GRAPH_MODE``: 'gcn' =
-        self loops + symmetric normalisation, 'sum' = GINConv, 'mean' = SAGEConv).
+        self loops + symmetric normalisation, 'sum' = GINConv, 'mean' = SAGEConv), or 'h2' for H2GCN: every batch's graph is a
+        ``graph.TwoHopGraph`` (the 1-hop and the exact 2-hop operator).  The pair is built ONCE over the whole record set from a
+        'sum'-mode CSR (``graph.two_hop``) and a step is assembled by two ``isic_csr_batch_assemble_ragged`` launches, one per
+        operator -- the 2-hop entry count differs from graph to graph, so the equal-size stack does not apply and the ragged
+        stack is the default; where it cannot be built (a record of more than 256 or of no nodes) a step builds its pair from
+        the concatenated batch.
         ``lesion_only``: every record carries ``"keep"`` (bool [n], the lesion flag of each patch) and the store holds the
         subgraph induced by the kept patches of every record (``graph.induced_subgraphs``: one call over the whole record
         set, ``x`` gathered once; a record without a kept patch keeps all of them).
@@ -369,7 +377,7 @@ class GraphStore:
         patches the induced subgraph keeps a neighbour with probability (kept - 1) / (all - 1) only, so it is no control of
         the same density.  Every record carries ``"graph_seed"`` (int) next to ``"keep"``; two launches over the whole
         record set (``graph.random_graphs_ragged``)."""
-        if mode not in GraphBatch.MODES:
+        if mode not in GraphBatch.MODES and mode != H2_MODE:
             raise ValueError(f"unknown graph mode '{mode}'")
         if lesion_knn is not None and not lesion_only:
             raise ValueError("GraphStore(lesion_knn=k) rebuilds the k-NN graph among the lesion patches: it needs lesion_only=True")
@@ -403,7 +411,8 @@ class GraphStore:
             self._rebuild_random_among_lesion()
         elif self.lesion_only:
             self._restrict_to_lesion(dev_tensor)
-        self._want_ragged = (self.lesion_only and RAGGED_STACK_DEFAULT_LESION_ONLY) if ragged_stack is None else bool(ragged_stack)
+        self._want_ragged = ((self.lesion_only and RAGGED_STACK_DEFAULT_LESION_ONLY) or mode == H2_MODE) if ragged_stack is None \
+            else bool(ragged_stack)
         # equal-sized graphs (the reference's case): one [G, n, D] tensor, a step's batch is ONE index_select
         self.y_dev = torch.as_tensor(self.y, device=device)
         self._xstack = torch.stack(self.x) if self.x and len({tuple(t.shape) for t in self.x}) == 1 else None
@@ -413,6 +422,14 @@ class GraphStore:
         self._build_stack()
         if self._want_ragged:
             self._build_ragged()
+
+    def _make_graph(self, ei, n_nodes, offs):
+        """The graph of one batch from its concatenated edge list: a ``GraphBatch`` of the store's mode, or for 'h2' the
+        ``TwoHopGraph`` of its 'sum'-mode CSR."""
+        if self.mode != H2_MODE:
+            return GraphBatch(ei, n_nodes, mode=self.mode)
+        from .graph import two_hop
+        return two_hop(GraphBatch(ei, n_nodes, mode="sum"), offs)
 
     def _keep_flags(self, ns):
         """The ``keep`` flags of every record as host bool arrays, checked against the records' node counts ``ns``."""
@@ -522,15 +539,28 @@ class GraphStore:
             return
         noff = torch.as_tensor(noff_h, device=dev)
         ei = torch.cat([e + int(o) for e, o in zip(self.ei, noff_h[:-1])], dim=1)
+        def feature_store():                   # the concatenation of all records' x: formed only where a stack is kept
+            if self._xstack is not None:
+                return self._xstack.view(-1, self._xstack.shape[-1])
+            return self._xcat if self._xcat is not None else torch.cat(self.x)
+
+        if self.mode == H2_MODE:
+            # the two operators of the whole record set, built once; an operator is symmetric, so its two orientations share
+            # their segments by construction
+            from .graph import H2_MAX_NODES, two_hop
+            if ns.max() > H2_MAX_NODES:
+                return
+            pair = two_hop(GraphBatch(ei, int(noff_h[-1]), mode="sum"), BagOffsets(noff_h, dev))
+            nnz_off = torch.stack([pair.a1.rowptr[noff], pair.a2.rowptr[noff]]).to(torch.int64)
+            self._ragged = {"G": G, "pair": pair, "node_off": noff, "nnz_off": nnz_off, "n": ns, "edges": es,
+                            "nnz": np.diff(nnz_off.cpu().numpy(), axis=1), "x": feature_store()}
+            return
         full = GraphBatch(ei, int(noff_h[-1]), mode=self.mode)
         nnz_off = full.rowptr[noff].to(torch.int64)
         if not bool((full.rowptr_t[noff].to(torch.int64) == nnz_off).all()):
             return                             # the two orientations do not share their segments: no ragged stack
-        same = self._xstack is not None
         self._ragged = {"G": G, "graph": full, "node_off": noff, "nnz_off": nnz_off, "n": ns, "edges": es,
-                        "nnz": np.diff(nnz_off.cpu().numpy()),
-                        "x": self._xstack.view(-1, self._xstack.shape[-1]) if same else
-                             (self._xcat if self._xcat is not None else torch.cat(self.x))}
+                        "nnz": np.diff(nnz_off.cpu().numpy()), "x": feature_store()}
 
     def _ragged_graph(self, key, want_rows):
         """The batch of the graphs ``key`` (host indices, repeats allowed) out of the ragged stack: ``sel`` and the batch's two
@@ -541,6 +571,8 @@ class GraphStore:
         if sel.size and (sel.min() < 0 or sel.max() >= rg["G"]):
             raise IndexError("GraphStore.batch: graph index out of range")
         B = int(sel.size)
+        if self.mode == H2_MODE:
+            return self._ragged_pair(sel, want_rows)
         up = np.empty(3 * B + 2, dtype=np.int64)                              # sel | node_base [B+1] | nnz_base [B+1]
         up[:B] = sel
         up[B] = up[2 * B + 1] = 0
@@ -561,12 +593,46 @@ class GraphStore:
         offs = BagOffsets.from_uploaded(up[B:2 * B + 1], d[B:2 * B + 1])
         return offs, GraphBatch.from_parts(tn, int(rg["edges"][sel].sum()), self.mode, parts), rows
 
+    def _ragged_pair(self, sel, want_rows):
+        """``_ragged_graph`` for the 'h2' store: ``sel`` and the batch's three prefix arrays (nodes, entries of A1, entries of
+        A2) go up in one copy, and one launch per operator cuts it out of the record set's pair and rebases it.  The store's
+        ``_t`` arrays alias its forward ones (an operator is symmetric); the batch's are written as arrays of their own with
+        the same content, because the entry's outputs may not overlap."""
+        from .graph import SYM_MODE, TwoHopGraph
+        rg = self._ragged
+        B = int(sel.size)
+        up = np.empty(4 * B + 3, dtype=np.int64)                              # sel | node_base | nnz_base of A1 | of A2, [B+1] each
+        up[:B] = sel
+        up[B] = up[2 * B + 1] = up[3 * B + 2] = 0
+        np.cumsum(rg["n"][sel], out=up[B + 1:2 * B + 1])
+        np.cumsum(rg["nnz"][0][sel], out=up[2 * B + 2:3 * B + 2])
+        np.cumsum(rg["nnz"][1][sel], out=up[3 * B + 3:])
+        tn = int(up[2 * B])
+        i32, dev = torch.int32, self.device
+        d = torch.from_numpy(up).to(dev)
+        rows = torch.empty((tn + 7) // 8 * 8 + 8, device=dev, dtype=i32) if want_rows else None
+        ops_out = []
+        for q, full in enumerate((rg["pair"].a1, rg["pair"].a2)):
+            zb = d[(2 + q) * B + 1 + q:(3 + q) * B + 2 + q]
+            tz = int(up[(3 + q) * B + 1 + q])
+            parts = {"rowptr": torch.empty(tn + 1, device=dev, dtype=i32), "rowptr_t": torch.empty(tn + 1, device=dev, dtype=i32),
+                     "col": torch.empty(tz, device=dev, dtype=i32), "col_t": torch.empty(tz, device=dev, dtype=i32),
+                     "val": torch.empty(tz, device=dev, dtype=torch.float32),
+                     "val_t": torch.empty(tz, device=dev, dtype=torch.float32), "perm_t": torch.empty(tz, device=dev, dtype=i32)}
+            call("isic_csr_batch_assemble_ragged", d[:B], d[B:2 * B + 1], zb, B, rg["G"], tn, tz, rg["node_off"], rg["nnz_off"][q],
+                 full.rowptr, full.rowptr_t, full.col, full.col_t, full.val, full.val_t, full.perm_t, parts["rowptr"],
+                 parts["rowptr_t"], parts["col"], parts["col_t"], parts["val"], parts["val_t"], parts["perm_t"],
+                 rows if q == 0 else None)
+            ops_out.append(GraphBatch.from_parts(tn, tz, SYM_MODE, parts))
+        offs = BagOffsets.from_uploaded(up[B:2 * B + 1], d[B:2 * B + 1])
+        return offs, TwoHopGraph(*ops_out), rows
+
     def _build_stack(self):
         """Graphs are static across epochs, so their normalised CSR is built ONCE: one ``GraphBatch`` launch over
         the whole record set.  When every graph has the same node and edge count (the reference's case: 196
         nodes, k-NN / grid edges) the per-graph pieces are kept as [G, ...] stacks with LOCAL ids, and a step's
         batch is six ``index_select``s plus offsets -- no per-step sort / scan / Python loop over graphs."""
-        if not self.needs_graph or not self.x or any(e is None for e in self.ei):
+        if not self.needs_graph or not self.x or any(e is None for e in self.ei) or self.mode == H2_MODE:
             return
         ns = {int(t.shape[0]) for t in self.x}
         es = {int(e.shape[1]) for e in self.ei}
@@ -643,7 +709,7 @@ class GraphStore:
             i = key[0]
             n = int(self.x[i].shape[0])
             if self.needs_graph and i not in self._single:
-                self._single[i] = GraphBatch(self.ei[i], n, mode=self.mode)
+                self._single[i] = self._make_graph(self.ei[i], n, BagOffsets.single(n, self.device))
             return self.x[i], BagOffsets.single(n, self.device), self._single.get(i)
         uniform = self._xstack is not None and (not self.needs_graph or self._stack is not None)
         if self._ragged is not None:
@@ -666,7 +732,7 @@ class GraphStore:
             graph = None
             if self.needs_graph:
                 ei = torch.cat([self.ei[i] + int(o) for i, o in zip(key, offs.host[:-1])], dim=1)
-                graph = GraphBatch(ei, offs.total, mode=self.mode)
+                graph = self._make_graph(ei, offs.total, offs)
         out = (x, offs, graph)
         if cache and key is not None:
             self._chunks[key] = out
