@@ -13,7 +13,16 @@
 //
 //   * block = (128 input channels, 64 output channels, pixel range): 9 x 128 x 64 fp32 = 144 accumulator VGPRs per wave at
 //     eight waves -- the whole register file of the CU (512 threads x 256), so there are no staging waves: every wave
-//     multiplies AND issues its ninth of the tile's 70 LDS-DMA groups between its MFMAs (addresses formed on the fly);
+//     multiplies AND issues nine of the tile's LDS-DMA groups between its MFMA groups.  The slot decides the kind: slots
+//     j = 0..6 bring X group wave + 8 j (54 real, two padding DMAs into a sink), slots 7, 8 dY group wave + 8 (j - 7) --
+//     no branch on the kind in the unrolled loop, and nine DMAs per wave and tile, which is all the tile top's vmcnt(0)
+//     relies on.  An address is (valid ? operand + wave-uniform tile part : zero page) + lane part: the lane part (pixel
+//     in group x pixel pitch + swizzled slot; per slot for packed images) is formed ONCE before the tile loop, the tile
+//     part is scalar arithmetic, validity is a wave-uniform row test and one column compare (packed: one bit of a lane
+//     mask, with a second mask for the batch's last, partly empty pack).  No vector multiply or division is left in the
+//     loop.  wgrad_dma_addr.inc holds this arithmetic for device and host, next to the per-DMA form it replaced;
+//     tests/wgrad_dma_addr_check.cpp compares the two on the host ("Weight-gradient DMA addresses");
+//   * two instances: <false> for W >= 16, <true> for packed images, so each carries only the lane registers it needs;
 //   * per tile 55 KB of X + 16 KB of dY for 144 MFMAs per wave instead of 63.5 KB for 72: 1.8x fewer staged bytes per MAC;
 //   * LDS images as before -- X: 256-byte pixel rows, 32-byte granules XOR-swizzled by (P & 3) | ((row + (col >> 3)) & 1) << 2;
 //     dY: now 128-byte pixel rows, granule G of tile pixel P holds channel block G ^ (((P >> 1) & 1) | ((P >> 3) & 1) << 1):
@@ -23,20 +32,14 @@
 #include "common.h"
 #include "slab_sum.inc"
 #include "mfma_tile.h"
+#include "wgrad_dma_addr.inc"
 
 namespace {
 
-constexpr int T_H = 4, T_W = 32;
-constexpr int XPITCH = 40;
-constexpr int XROWS = T_H + 2;
-constexpr int XB = XROWS * XPITCH * 256;            // 61,440 B
-constexpr int YB = T_H * T_W * 128;                 // 16,384 B: [128 pixels][64 co]
-constexpr int STG = XB + YB;                        // 77,824 B
-constexpr int SCR = 2 * STG;
-constexpr int LDS_ALL = SCR + 1024;                 // 156,672 B
-constexpr int XGROUPS = XROWS * 9, YGROUPS = 16;    // 54 + 16 DMA groups per tile
-constexpr int NDMA = 9;                             // per wave (8 x 9 >= 70)
+using namespace wga::c128;                          // tile, LDS image and DMA-slot constants: wgrad_dma_addr.inc
+constexpr int LDS_ALL = SINK + 1024;                // 156,672 B: two stages of 77,824 B + the sink of padding / dead DMAs
 constexpr int SLICE_ELEMS = 64 * 9 * 128;           // one block's partial gradient
+static_assert(XB == 61440 && YB == 16384 && STG == 77824 && 8 * XSLOTS >= XGROUPS && 8 * (NDMA - XSLOTS) == YGROUPS, "");
 
 struct WC128BArgs {
   const unsigned short* x;      // [N][H][W][Cx]
@@ -49,6 +52,8 @@ struct WC128BArgs {
 
 __device__ __attribute__((aligned(256))) unsigned char g_wc128b_zeros[2048];
 
+// PACKED: two / four small images per tile row (per-slot lane offsets and a validity mask instead of column compares)
+template <bool PACKED>
 __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
@@ -59,71 +64,37 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
   const int t_begin = bs * a.tiles_per_block;
   const int ntl = min(a.total_tiles - t_begin, a.tiles_per_block);       // >= 1 by construction of the grid
 
-  // ---------------------------------------------------------------- staging (every wave: groups d = wave + 8 j)
+  // ---------------------------------------------------------------- staging (every wave: nine slots, wgrad_dma_addr.inc)
   const int tiles_img = a.tiles_y * a.tiles_x;
-  struct Tile { int n, y0, x0; };
-  auto advance = [&](Tile& tl) {
-    tl.x0 += T_W;
-    if (tl.x0 >= a.Wv) {
-      tl.x0 = 0; tl.y0 += T_H;
-      if (tl.y0 >= a.H) { tl.y0 = 0; tl.n += 1; }
-    }
-  };
-  Tile ahead;
+  wga::Tile ahead;
   {
     const int n = t_begin / tiles_img, rem = t_begin - n * tiles_img;
     const int ty = rem / a.tiles_x;
     ahead.n = n; ahead.y0 = ty * T_H; ahead.x0 = (rem - ty * a.tiles_x) * T_W;
   }
-  const int xl_px_ = lane >> 4, xl_slot = lane & 15;             // X: pixel in group, 16-byte slot of the 256-byte row
-  const int yl_px_ = lane >> 3, yl_slot = lane & 7;              // dY: pixel in group, 16-byte slot of the 128-byte row
-  const int xl_px = xl_px_, yl_px = yl_px_;
-  const unsigned xsrc0 = (unsigned)(((((xl_slot >> 1) ^ xl_px) << 1) | (xl_slot & 1)) << 4);          // key bit 2 clear
-  const unsigned xsrc1 = (unsigned)(((((xl_slot >> 1) ^ (xl_px | 4)) << 1) | (xl_slot & 1)) << 4);    // bit 2 set
-  // dY pixel P = 32 r + 8 (g2 & 3) + yl_px: key = ((P >> 1) & 1) | ((P >> 3) & 1) << 1 = ((yl_px >> 1) & 1) | (g2 & 1) << 1
-  const unsigned ysrc0 = (unsigned)(((((yl_slot >> 1) ^ ((yl_px >> 1) & 1)) << 1) | (yl_slot & 1)) << 4);
-  const unsigned ysrc1 = (unsigned)(((((yl_slot >> 1) ^ (((yl_px >> 1) & 1) | 2)) << 1) | (yl_slot & 1)) << 4);
+  // the lane parts of the addresses once; the tile origin and (packed) the validity mask of the tile ahead once per tile
+  const Geom geo = {a.N, a.H, a.W, a.Cx, a.Cy, a.pack, a.slot_shift};
+  const Lane<PACKED> ln = lane_init<PACKED>(geo, wave, lane);
   const unsigned long long zeros = (unsigned long long)g_wc128b_zeros;
-  const int slot_mask = (1 << a.slot_shift) - 1;
-  const int xpix = a.Cx * 2, ypix = a.Cy * 2;                    // bytes per pixel
   const unsigned long long xbase = (unsigned long long)a.x + (unsigned long long)ci_slice * 256;
   const unsigned long long ybase = (unsigned long long)a.dy + (unsigned long long)slice * 128;
-  // one DMA group of tile `tl` into stage `stage` (j = 0..8; wave-uniform group number d = wave + 8 j)
-  auto dma_one = [&](int j, const Tile& tl, int stage, bool live) {
-    const int d = wave + 8 * j;
-    // (the lane's share of an address depends on lane and wave only: hipcc would hoist it out of the tile loop for all nine
-    //  groups at once and SPILL it -- a scratch reload waits vmcnt(0), i.e. for every DMA in flight; hide the invariance)
-    int xl_px = xl_px_, yl_px = yl_px_;
-    asm volatile("" : "+v"(xl_px), "+v"(yl_px));
-    const unsigned sbase = lds0 + (unsigned)stage * STG;
-    const long long porg = ((long long)tl.n * a.pack * a.H + tl.y0) * a.W + tl.x0;     // first pixel of the tile (slot 0)
-    const int imgs_left = a.N - tl.n * a.pack;
-    unsigned long long src;
-    unsigned dst;
-    bool real = live;
-    if (d < XGROUPS) {
-      const int pr = d / 9, g = d - 9 * pr;
-      const int vc = -1 + 4 * g + xl_px;
-      const int k = a.pack == 1 ? 0 : (vc >> a.slot_shift), rc = a.pack == 1 ? vc : (vc & slot_mask);
-      const bool row_ok = (unsigned)(tl.y0 - 1 + pr) < (unsigned)a.H;
-      const bool ok = real && row_ok && (unsigned)(tl.x0 + rc) < (unsigned)a.W && (unsigned)k < (unsigned)imgs_left && k < a.pack;
-      const long long off = (long long)(((k * a.H + (pr - 1)) * a.W + rc)) * xpix;
-      src = (ok ? xbase + (unsigned long long)(porg * xpix + off) : zeros) + (((pr + (g >> 1)) & 1) ? xsrc1 : xsrc0);
-      dst = sbase + (unsigned)((pr * XPITCH + 4 * g) * 256);
-    } else if (d < XGROUPS + YGROUPS) {
-      const int g2 = d - XGROUPS;
-      const int r = g2 >> 2, c = 8 * (g2 & 3) + yl_px;
-      const int k = a.pack == 1 ? 0 : (c >> a.slot_shift), rc = a.pack == 1 ? c : (c & slot_mask);
-      const bool ok = real && tl.y0 + r < a.H && tl.x0 + rc < a.W && k < imgs_left;
-      const long long off = (long long)(((k * a.H + r) * a.W + rc)) * ypix;
-      src = (ok ? ybase + (unsigned long long)(porg * ypix + off) : zeros) + ((g2 & 1) ? ysrc1 : ysrc0);
-      dst = sbase + (unsigned)(XB + g2 * 1024);
-    } else {
-      real = false;
-      src = zeros + (unsigned)(lane * 16);
-      dst = 0;
+  wga::TileOrg org = tile_org(geo, ahead);
+  unsigned vmask = tile_mask<PACKED>(geo, ln, ahead);
+  // slot j of tile `ahead` into stage `stage`: j = 0..6 X group wave + 8 j (two of the 56 are padding), j = 7, 8 dY group
+  // wave + 8 (j - 7); a dead prefetch (!live) and the padding read the zero page into the sink behind the stages
+  auto dma_one = [&](int j, int stage, bool live) {
+    const wga::Dma r = dma<PACKED>(geo, ln, org, vmask, ahead, wave, j, stage, live);
+    const unsigned long long base = r.ok ? (r.op ? ybase : xbase) + (unsigned long long)r.soff : zeros;
+    isic_glds16(reinterpret_cast<const void*>(base + r.loff), lds0 + r.dst);
+  };
+  auto next_tile = [&] {
+    ahead.x0 += T_W;
+    if (ahead.x0 >= a.Wv) {
+      ahead.x0 = 0; ahead.y0 += T_H;
+      if (ahead.y0 >= a.H) { ahead.y0 = 0; ahead.n += 1; }
     }
-    isic_glds16(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
+    org = tile_org(geo, ahead);
+    vmask = tile_mask<PACKED>(geo, ln, ahead);
   };
 
   // ---------------------------------------------------------------- fragments: wave c = input channels 16c .. 16c+16
@@ -154,8 +125,8 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
     for (int c = 0; c < 4; ++c) acc[t][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
-  for (int j = 0; j < NDMA; ++j) dma_one(j, ahead, 0, true);
-  advance(ahead);
+  for (int j = 0; j < NDMA; ++j) dma_one(j, 0, true);
+  next_tile();
 
   for (int kk = 0; kk < ntl; ++kk) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile kk landed (this wave's groups)
@@ -188,7 +159,7 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
         // the tile's nine DMA groups of the NEXT tile go out between the MFMA groups: 12 slots per tile, 9 used
         const int slot = s * 3 + kh;
         // (two per group in groups 0-4, or all nine in front of the first group: 0 .. +3 % slower -- when they go out is not it)
-        if (slot < NDMA) dma_one(slot, ahead, nstage, more);
+        if (slot < NDMA) dma_one(slot, nstage, more);
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(512) void wgrad_c128b_kernel(WC128BArgs a) {
         __builtin_amdgcn_sched_barrier(0);      // a DMA's address arithmetic and the fragment reads stay in their own slot
       }
     }
-    advance(ahead);
+    next_tile();
   }
 
   // this block's partial: lane (fg, fi) holds D[ci = 16c + 4fg + r][co = 64 slice + 16 c2 + fi]
@@ -221,6 +192,8 @@ bool wc128b_plan(int N, int H, int W, int Cin, int Cout, WC128BPlan& p) {
   p.tiles_x = ceil_div(p.Wv, T_W);
   const int64_t total = (int64_t)ceil_div(N, p.pack) * p.tiles_y * p.tiles_x;
   if (total > 0x7FFFFFFFLL || (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) > 0x7FFFFFFFFFLL) return false;
+  // packed: a lane's byte offset from the first image of its pack is held in 32 bits (wgrad_dma_addr.inc)
+  if (p.pack > 1 && (int64_t)(p.pack + 1) * H * W * (Cin > Cout ? Cin : Cout) * 2 > 0x7FFFFFFFLL) return false;
   p.total_tiles = (int)total;
   p.pairs = (Cin / 128) * (Cout / 64);
   const int per_pair = cus >= p.pairs ? cus / p.pairs : 1;
@@ -249,15 +222,18 @@ int isic_wgrad_c128b_launch(const uint16_t* x, const uint16_t* dy, float* dw, in
   a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.total_tiles = p.total_tiles;
   a.tiles_per_block = p.tiles_per_block; a.blocks_per_pair = p.blocks_per_pair;
   a.Cx = Cin; a.Cy = Cout; a.co_slices = Cout / 64; a.pack = p.pack; a.slot_shift = p.slot_shift; a.Wv = p.Wv;
+  const void* kernel = p.pack > 1 ? reinterpret_cast<const void*>(wgrad_c128b_kernel<true>)
+                                  : reinterpret_cast<const void*>(wgrad_c128b_kernel<false>);
   static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device
   if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c128b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_ALL);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c128b_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
+        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c128b_kernel<false>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   void* kargs[] = {&a};
-  if (hipLaunchKernel(reinterpret_cast<const void*>(wgrad_c128b_kernel), dim3(p.pairs * p.blocks_per_pair), dim3(512), kargs,
-                      LDS_ALL, stream) != hipSuccess)
+  if (hipLaunchKernel(kernel, dim3(p.pairs * p.blocks_per_pair), dim3(512), kargs, LDS_ALL, stream) != hipSuccess)
     return ISIC_ERR_LAUNCH;
   hipLaunchKernelGGL((wgrad_pair_reduce_kernel<64, 128>), dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
                      p.blocks_per_pair, a.co_slices, Cin);

@@ -8,7 +8,12 @@
 //
 //   * block = (64 input channels, 128 output channels, pixel range): 9 x 64 x 128 fp32 = 144 accumulator VGPRs per wave at
 //     eight waves (wave = 16 input channels x 64 output channels), as in conv_wgrad_c128b.hip -- no staging waves, every
-//     wave issues its eighth of a tile's 61 LDS-DMA groups between its MFMA groups;
+//     wave issues eight of a tile's LDS-DMA groups between its MFMA groups.  The slot decides the kind: slots j = 0..5
+//     bring X group wave + 8 j (45 real, three padding DMAs into a sink), slots 6, 7 dY group wave + 8 (j - 6).  An
+//     address is (valid ? operand + wave-uniform tile part : zero page) + lane part, the lane part formed once before
+//     the tile loop, the tile part scalar, validity a row test and one column compare (packed: one bit of a lane mask) --
+//     as in conv_wgrad_c128b.hip; wgrad_dma_addr.inc holds the arithmetic for device and host
+//     (tests/wgrad_dma_addr_check.cpp).  Two instances: <false> for output widths >= 16, <true> for packed images;
 //   * tile = 2 x 32 output pixels: 5 input rows x 65 input columns, staged DE-INTERLEAVED -- per patch row an odd-column
 //     plane (40 positions: input columns -1, 1, 3, ...) and an even-column plane (32 positions) -- so that the 32 pixels of
 //     a k-step are CONSECUTIVE positions of one plane for every tap column (kw = 0: odd plane from position 0, kw = 1: even
@@ -27,21 +32,14 @@
 #include "common.h"
 #include "slab_sum.inc"
 #include "mfma_tile.h"
+#include "wgrad_dma_addr.inc"
 
 namespace {
 
-constexpr int T_H = 2, T_W = 32;
-constexpr int XROWS = 2 * T_H + 1;                  // 5 input rows per tile
-constexpr int ODDP = 40, EVENP = 32;                // positions per plane (odd: input column 2 (q - 1) + 1, even: 2 q)
-constexpr int XROWB = (ODDP + EVENP) * 128;         // 9,216 B per patch row
-constexpr int XB = XROWS * XROWB;                   // 46,080 B
-constexpr int YB = T_H * T_W * 256;                 // 16,384 B: [64 pixels][128 co]
-constexpr int STG = XB + YB;                        // 62,464 B
-constexpr int SCR = 2 * STG;
-constexpr int LDS_ALL = SCR + 1024;                 // 125,952 B
-constexpr int XGROUPS = XROWS * 9, YGROUPS = 16;    // 45 + 16 DMA groups (1 KB each) per tile
-constexpr int NDMA = 8;                             // per wave (8 x 8 >= 61)
+using namespace wga::s2;                            // tile, LDS image and DMA-slot constants: wgrad_dma_addr.inc
+constexpr int LDS_ALL = SINK + 1024;                // 125,952 B: two stages of 62,464 B + the sink of padding / dead DMAs
 constexpr int SLICE_ELEMS = 128 * 9 * 64;           // one block's partial gradient
+static_assert(XB == 46080 && YB == 16384 && STG == 62464 && 8 * XSLOTS >= XGROUPS && 8 * (NDMA - XSLOTS) == YGROUPS, "");
 
 struct WS2Args {
   const unsigned short* x;      // [N][Hi][Wi][Cx]
@@ -54,6 +52,8 @@ struct WS2Args {
 
 __device__ __attribute__((aligned(256))) unsigned char g_ws2_zeros[2048];
 
+// PACKED: two / four small images per tile row (per-slot lane offsets and a validity mask instead of column compares)
+template <bool PACKED>
 __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
@@ -64,75 +64,37 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
   const int t_begin = bs * a.tiles_per_block;
   const int ntl = min(a.total_tiles - t_begin, a.tiles_per_block);       // >= 1 by construction of the grid
 
-  // ---------------------------------------------------------------- staging (every wave: groups d = wave + 8 j)
+  // ---------------------------------------------------------------- staging (every wave: eight slots, wgrad_dma_addr.inc)
   const int tiles_img = a.tiles_y * a.tiles_x;
-  struct Tile { int n, y0, x0; };                                         // n: packed image group; (y0, x0): output pixel
-  auto advance = [&](Tile& tl) {
-    tl.x0 += T_W;
-    if (tl.x0 >= a.Wv) {
-      tl.x0 = 0; tl.y0 += T_H;
-      if (tl.y0 >= a.Ho) { tl.y0 = 0; tl.n += 1; }
-    }
-  };
-  Tile ahead;
+  wga::Tile ahead;                                                        // n: packed image group; (y0, x0): output pixel
   {
     const int n = t_begin / tiles_img, rem = t_begin - n * tiles_img;
     const int ty = rem / a.tiles_x;
     ahead.n = n; ahead.y0 = ty * T_H; ahead.x0 = (rem - ty * a.tiles_x) * T_W;
   }
-  const int xl_px_ = lane >> 3, xl_slot = lane & 7;              // X: position in group, 16-byte slot of the 128-byte row
-  const int yl_px_ = lane >> 4, yl_slot = lane & 15;             // dY: pixel in group, 16-byte slot of the 256-byte row
-  // X position q = 8 gp + xl_px: key = ((q >> 1) & 1) | ((q >> 3) & 1) << 1 = ((xl_px >> 1) & 1) | (gp & 1) << 1
-  const unsigned xsrc0 = (unsigned)(((((xl_slot >> 1) ^ ((xl_px_ >> 1) & 1)) << 1) | (xl_slot & 1)) << 4);
-  const unsigned xsrc1 = (unsigned)(((((xl_slot >> 1) ^ (((xl_px_ >> 1) & 1) | 2)) << 1) | (xl_slot & 1)) << 4);
-  // dY pixel P = 4 g2 + yl_px: key = (P & 3) | ((P >> 3) & 1) << 2 = yl_px | ((g2 >> 1) & 1) << 2
-  const unsigned ysrc0 = (unsigned)(((((yl_slot >> 1) ^ yl_px_) << 1) | (yl_slot & 1)) << 4);
-  const unsigned ysrc1 = (unsigned)(((((yl_slot >> 1) ^ (yl_px_ | 4)) << 1) | (yl_slot & 1)) << 4);
+  // the lane parts of the addresses once; the tile origin and (packed) the validity mask of the tile ahead once per tile
+  const Geom geo = {a.N, a.Hi, a.Wi, a.Ho, a.Wo, a.Cx, a.Cy, a.pack, a.slot_shift};
+  const Lane<PACKED> ln = lane_init<PACKED>(geo, wave, lane);
   const unsigned long long zeros = (unsigned long long)g_ws2_zeros;
-  const int slot_mask = (1 << a.slot_shift) - 1;
-  const int xpix = a.Cx * 2, ypix = a.Cy * 2;                    // bytes per pixel
   const unsigned long long xbase = (unsigned long long)a.x + (unsigned long long)ci_slice * 128;
   const unsigned long long ybase = (unsigned long long)a.dy + (unsigned long long)slice * 256;
-  // one DMA group of tile `tl` into stage `stage` (j = 0..7; wave-uniform group number d = wave + 8 j)
-  auto dma_one = [&](int j, const Tile& tl, int stage, bool live) {
-    const int d = wave + 8 * j;
-    // (the lane's share of an address depends on lane and wave only: hipcc would hoist it out of the tile loop for all
-    //  groups at once and SPILL it -- a scratch reload waits vmcnt(0), i.e. for every DMA in flight; hide the invariance)
-    int xl_px = xl_px_, yl_px = yl_px_;
-    asm volatile("" : "+v"(xl_px), "+v"(yl_px));
-    const unsigned sbase = lds0 + (unsigned)stage * STG;
-    const int img0 = tl.n * a.pack;
-    const int imgs_left = a.N - img0;
-    unsigned long long src;
-    unsigned dst;
-    bool real = live;
-    if (d < XGROUPS) {
-      const int pr = d / 9, g = d - 9 * pr;
-      const bool odd = g < 5;
-      const int gp = odd ? g : g - 5;
-      const int vj = tl.x0 + 8 * gp + xl_px - (odd ? 1 : 0);              // virtual output column of this position
-      const int k = a.pack == 1 ? 0 : (vj >> a.slot_shift), rc = a.pack == 1 ? vj : (vj & slot_mask);
-      const int xc = 2 * rc + (odd ? 1 : 0), xr = 2 * tl.y0 - 1 + pr;
-      const bool ok = real && (unsigned)xr < (unsigned)a.Hi && vj >= 0 && (unsigned)xc < (unsigned)a.Wi &&
-                      (unsigned)k < (unsigned)imgs_left && k < a.pack;
-      const long long pix = ((long long)(img0 + k) * a.Hi + xr) * a.Wi + xc;
-      src = (ok ? xbase + (unsigned long long)(pix * xpix) : zeros) + ((gp & 1) ? xsrc1 : xsrc0);
-      dst = sbase + (unsigned)(pr * XROWB + g * 1024);
-    } else if (d < XGROUPS + YGROUPS) {
-      const int g2 = d - XGROUPS;
-      const int r = g2 >> 3, c = 4 * (g2 & 7) + yl_px;
-      const int vj = tl.x0 + c;
-      const int k = a.pack == 1 ? 0 : (vj >> a.slot_shift), rc = a.pack == 1 ? vj : (vj & slot_mask);
-      const bool ok = real && tl.y0 + r < a.Ho && rc < a.Wo && k < imgs_left && k < a.pack;
-      const long long pix = ((long long)(img0 + k) * a.Ho + tl.y0 + r) * a.Wo + rc;
-      src = (ok ? ybase + (unsigned long long)(pix * ypix) : zeros) + (((g2 >> 1) & 1) ? ysrc1 : ysrc0);
-      dst = sbase + (unsigned)(XB + g2 * 1024);
-    } else {
-      real = false;
-      src = zeros + (unsigned)(lane * 16);
-      dst = 0;
+  wga::TileOrg org = tile_org(geo, ahead);
+  unsigned vmask = tile_mask<PACKED>(geo, ln, ahead);
+  // slot j of tile `ahead` into stage `stage`: j = 0..5 X group wave + 8 j (three of the 48 are padding), j = 6, 7 dY group
+  // wave + 8 (j - 6); a dead prefetch (!live) and the padding read the zero page into the sink behind the stages
+  auto dma_one = [&](int j, int stage, bool live) {
+    const wga::Dma r = dma<PACKED>(geo, ln, org, vmask, ahead, wave, j, stage, live);
+    const unsigned long long base = r.ok ? (r.op ? ybase : xbase) + (unsigned long long)r.soff : zeros;
+    isic_glds16(reinterpret_cast<const void*>(base + r.loff), lds0 + r.dst);
+  };
+  auto next_tile = [&] {
+    ahead.x0 += T_W;
+    if (ahead.x0 >= a.Wv) {
+      ahead.x0 = 0; ahead.y0 += T_H;
+      if (ahead.y0 >= a.Ho) { ahead.y0 = 0; ahead.n += 1; }
     }
-    isic_glds16(reinterpret_cast<const void*>(src), real ? dst : lds0 + SCR);
+    org = tile_org(geo, ahead);
+    vmask = tile_mask<PACKED>(geo, ln, ahead);
   };
 
   // ---------------------------------------------------------------- fragments: wave = (ci block c, co half hh)
@@ -163,8 +125,8 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
     for (int c2 = 0; c2 < 4; ++c2) acc[t][c2] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
-  for (int j = 0; j < NDMA; ++j) dma_one(j, ahead, 0, true);
-  advance(ahead);
+  for (int j = 0; j < NDMA; ++j) dma_one(j, 0, true);
+  next_tile();
 
   for (int kk = 0; kk < ntl; ++kk) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile kk landed (this wave's groups)
@@ -193,8 +155,8 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
       const int s = grp / 3, kh = grp - 3 * s;
       if (grp + 1 < 6) read_x(grp + 1);         // the next group's fragments are read under this group's MFMAs
       // the wave's eight DMA groups of the NEXT tile go out between the MFMA groups (two with each of the first two)
-      if (grp < 2) { dma_one(2 * grp, ahead, nstage, more); dma_one(2 * grp + 1, ahead, nstage, more); }
-      else dma_one(grp + 2, ahead, nstage, more);
+      if (grp < 2) { dma_one(2 * grp, nstage, more); dma_one(2 * grp + 1, nstage, more); }
+      else dma_one(grp + 2, nstage, more);
 #pragma unroll
       for (int c2 = 0; c2 < 4; ++c2) {
 #pragma unroll
@@ -205,7 +167,7 @@ __global__ __launch_bounds__(512) void wgrad_s2_kernel(WS2Args a) {
       }
       __builtin_amdgcn_sched_barrier(0);        // a DMA's address arithmetic and the fragment reads stay in their own slot
     }
-    advance(ahead);
+    next_tile();
   }
 
   // this block's partial: lane (fg, fi) holds D[ci = 16 c + 4 fg + r][co = 64 hh + 16 c2 + fi]
@@ -261,10 +223,13 @@ int isic_wgrad_s2_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N
   a.Cx = Cin; a.Cy = Cout; a.co_slices = Cout / 128; a.pack = p.pack; a.slot_shift = p.slot_shift; a.Wv = p.Wv;
   static IsicPerDeviceOnce once;
   if (isic_once_per_device(once, [&] {
-        return hipFuncSetAttribute((const void*)wgrad_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
+        const hipError_t e = hipFuncSetAttribute((const void*)wgrad_s2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
+        return e != hipSuccess ? e
+                               : hipFuncSetAttribute((const void*)wgrad_s2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
       }) != hipSuccess)
     return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(wgrad_s2_kernel, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
+  if (p.pack > 1) hipLaunchKernelGGL(wgrad_s2_kernel<true>, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
+  else hipLaunchKernelGGL(wgrad_s2_kernel<false>, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
   hipLaunchKernelGGL((wgrad_pair_reduce_kernel<128, 64>), dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
                      p.blocks_per_pair, a.co_slices, Cin);
   return ISIC_OK;
