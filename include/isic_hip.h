@@ -694,5 +694,7 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
 #include "isic_hip_gpr.h"
 /* H2GCN: the exact 2-hop neighbourhood of every graph of a batch built on the device (count, then write behind the caller's scan), and the graph-resident two-operator propagation [A1^ H | A2^ H] with its backward: four more entry points, same conventions. */
 #include "isic_hip_h2.h"
+/* Radiomic features of the lesions of a resident uint8 image pool (first-order, GLCM and GLDM of the gray, red, green and blue channel, counted in one pass and formed in fp64 by the same workgroup): one more entry point, same conventions. */
+#include "isic_hip_radiomics.h"
 
 #endif /* ISIC_HIP_H */

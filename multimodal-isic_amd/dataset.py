@@ -16,9 +16,11 @@ ARTIFACT_COLS = ['hair', 'ruler_marks', 'bubbles', 'vignette', 'frame', 'other']
 
 
 class DermDataset(Dataset):
-    def __init__(self, df, radiomics, transform=None, is_train=True, crop_size=450):
+    def __init__(self, df, radiomics, transform=None, is_train=True, crop_size=450, crop=True):
+        """``crop=False`` hands out the decoded image and mask whole, as the reference's radiomic extraction reads them
+        (`RadiomicExtractor.py:29-36`); the default is the lesion-centred square crop of the training path."""
         self.df, self.radiomics = df, radiomics
-        self.transform, self.is_train, self.crop_size = transform, is_train, crop_size
+        self.transform, self.is_train, self.crop_size, self.crop = transform, is_train, crop_size, crop
         self.artifact_cols = list(ARTIFACT_COLS)
 
     def __len__(self):
@@ -45,7 +47,7 @@ class DermDataset(Dataset):
             if m.size != (image.shape[1], image.shape[0]):
                 m = m.resize((image.shape[1], image.shape[0]), Image.NEAREST)
             mask = np.asarray(m)
-        return self._square_crop_on_mask(image, mask)
+        return self._square_crop_on_mask(image, mask) if self.crop else (image, mask)
 
     def __getitem__(self, idx):
         row = self.df.iloc[idx]

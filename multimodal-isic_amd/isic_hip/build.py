@@ -49,7 +49,7 @@ def build(force=False, verbose=True, jobs=None):
                           "isic_hip_metrics.h", "isic_hip_randgraph.h", "isic_hip_moments.h", "isic_hip_wide.h",
                           "isic_hip_gated.h", "isic_hip_ragged.h", "isic_hip_hetero_ragged.h",
                           "isic_hip_knn_ragged.h", "isic_hip_randgraph_ragged.h", "isic_hip_moments_ragged.h",
-                          "isic_hip_gpr.h", "isic_hip_h2.h")]
+                          "isic_hip_gpr.h", "isic_hip_h2.h", "isic_hip_radiomics.h")]
     todo, objs = [], []
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")

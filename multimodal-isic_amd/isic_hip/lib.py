@@ -54,7 +54,7 @@ def extension_header_paths():
     include/isic_hip_attn_mean.h, include/isic_hip_pca.h, include/isic_hip_metrics.h, include/isic_hip_randgraph.h,
     include/isic_hip_moments.h, include/isic_hip_wide.h, include/isic_hip_gated.h, include/isic_hip_ragged.h,
     include/isic_hip_hetero_ragged.h, include/isic_hip_knn_ragged.h, include/isic_hip_randgraph_ragged.h,
-    include/isic_hip_moments_ragged.h, include/isic_hip_gpr.h, include/isic_hip_h2.h)."""
+    include/isic_hip_moments_ragged.h, include/isic_hip_gpr.h, include/isic_hip_h2.h, include/isic_hip_radiomics.h)."""
     inc = os.path.dirname(header_path())
     return [os.path.join(inc, h) for h in ("isic_hip_mxfp8.h", "isic_hip_vit_train.h", "isic_hip_convmae.h",
                                                       "isic_hip_convmae_train.h", "isic_hip_mae.h", "isic_hip_augment.h", "isic_hip_wgrad_bnbwd.h",
@@ -62,7 +62,8 @@ def extension_header_paths():
                                                       "isic_hip_metrics.h", "isic_hip_randgraph.h", "isic_hip_moments.h", "isic_hip_wide.h",
                                                       "isic_hip_gated.h", "isic_hip_ragged.h", "isic_hip_hetero_ragged.h",
                                                       "isic_hip_knn_ragged.h", "isic_hip_randgraph_ragged.h",
-                                                      "isic_hip_moments_ragged.h", "isic_hip_gpr.h", "isic_hip_h2.h")]
+                                                      "isic_hip_moments_ragged.h", "isic_hip_gpr.h", "isic_hip_h2.h",
+                                                      "isic_hip_radiomics.h")]
 
 
 def test_header_path():
