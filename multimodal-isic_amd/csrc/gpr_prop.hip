@@ -15,14 +15,13 @@
 // -- and the two halves of a wave never conflict.  The CSR entries of a row are read from memory by every hop (the same
 // address in all 32 lanes of a half wave: one request, an L1 hit after the validation pass below has read them once).
 //
-//   * Validation before anything is indexed.  The graph's two offsets are compared with N and max_nodes; then the two ends
-//     of its CSR range with nnz; then every row pointer of its rows with that range and every column id of the range with
-//     the graph's own node range.  __syncthreads_or joins the verdict, so the block leaves together: a bad graph adds 1 to
-//     bad[0] (an integer atomic, slab 0 only), zeroes its dgamma partials and writes nothing else.
+//   * Validation before anything is indexed: the node-range and CSR checks of graph_resident.inc, joined by __syncthreads_or.
+//     A bad graph adds 1 to bad[0] (an integer atomic, slab 0 only), zeroes its dgamma partials and writes nothing else.
 //   * dgamma.  After hop k a thread has s = sum_j P_k[r_j][c] h[j]; a wave's s meet in the xor tree of wave_sum, the four wave
 //     sums of hop k are parked in LDS and added in wave order by thread k at the end: partial[block][k].  The blocks' partials
 //     meet in order A of slab_sum.inc (isic_slab_reduce_launch, 16 lanes per element).  No float atomics anywhere.
 #include "slab_sum.inc"
+#include "graph_resident.inc"
 
 #include "../../include/isic_hip_gpr.h"
 
@@ -30,17 +29,11 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int W = ISIC_GPR_SLAB;
-constexpr int ROWS_PER_PASS = BLOCK / W;      // 8 rows of the slab per pass of the block
-constexpr int MAX_LDS_BYTES = 2 * ISIC_GPR_MAX_NODES * W * (int)sizeof(float);
-static_assert(W == 32 && ROWS_PER_PASS == 8 && MAX_LDS_BYTES == 65536, "a half wave per row of the slab");
+constexpr int BLOCK = GR_BLOCK, W = GR_W, ROWS_PER_PASS = GR_ROWS_PER_PASS;
 static_assert(ISIC_GPR_MAX_K + 1 <= BLOCK, "thread k adds the wave sums of hop k");
 
 struct GprArgs {
-  const int32_t* rowptr;
-  const int32_t* col;
-  const float* val;
+  GrCsr csr;
   const int64_t* offsets;
   const float* X;          // forward: H; backward: dZ
   const float* Hd;         // backward: H when dgamma is wanted, else NULL
@@ -49,7 +42,7 @@ struct GprArgs {
   float* out;              // forward: Z; backward: dH or NULL
   float* partial;          // backward: [blocks][K + 1] when dgamma is wanted, else NULL
   uint32_t* bad;
-  int64_t nnz, N;
+  int64_t N;
   int max_nodes, K, F, slabs;
 };
 
@@ -63,27 +56,12 @@ __global__ __launch_bounds__(BLOCK) void gpr_prop_kernel(GprArgs a) {
   const bool want_dg = a.partial != nullptr;      // backward with dgamma; the forward has neither partial nor Hd
   float* prow = want_dg ? a.partial + (int64_t)blockIdx.x * (K + 1) : nullptr;
 
-  // ---- the graph's node range, compared with the sizes passed by value before anything is indexed with it
-  const int64_t lo = a.offsets[g], hi = a.offsets[g + 1];
-  const bool range_ok = lo >= 0 && hi >= lo && hi <= a.N && hi - lo <= (int64_t)a.max_nodes;
-  const int n = range_ok ? (int)(hi - lo) : 0;
-  int flag = range_ok ? 0 : 1;
-  if (range_ok && n > 0) {
-    // ---- its CSR range, its row pointers and its column ids (0 <= lo < hi <= N: rowptr[lo .. hi] exists)
-    const int64_t pb = a.rowptr[lo], pe = a.rowptr[hi];
-    if (pb < 0 || pe < pb || pe > a.nnz) {
-      flag = 1;
-    } else {
-      for (int r = tid; r < n; r += BLOCK) {
-        const int64_t b = a.rowptr[lo + r], e = a.rowptr[lo + r + 1];
-        if (b < pb || e < b || e > pe) flag = 1;
-      }
-      for (int64_t p = pb + tid; p < pe; p += BLOCK) {
-        const int64_t cl = (int64_t)a.col[p] - lo;
-        if (cl < 0 || cl >= n) flag = 1;
-      }
-    }
-  }
+  // ---- the graph's node range, then its CSR range, row pointers and column ids (graph_resident.inc)
+  const GrRange nr = gr_range(a.offsets, g, a.N, a.max_nodes);
+  const int64_t lo = nr.lo;
+  const int n = nr.n;
+  int flag = nr.flag;
+  if (n > 0) flag = gr_csr_flag(a.csr, lo, n);
   flag = __syncthreads_or(flag);
   if (flag || n == 0) {                         // the same verdict in every thread: the block leaves together
     if (flag && slab == 0 && tid == 0) atomicAdd(a.bad, 1u);
@@ -120,8 +98,7 @@ __global__ __launch_bounds__(BLOCK) void gpr_prop_kernel(GprArgs a) {
   }
 
   // ---- the hops
-  const int32_t* rp = a.rowptr + lo;
-  const unsigned ilo = (unsigned)lo;             // every column id is an int32 inside [lo, hi): col - lo is 0 .. n - 1
+  const unsigned ilo = (unsigned)lo;
   for (int k = 1; k <= K; ++k) {
     __syncthreads();
     const float* src = (k & 1) ? buf0 : buf1;
@@ -135,10 +112,7 @@ __global__ __launch_bounds__(BLOCK) void gpr_prop_kernel(GprArgs a) {
       if (r < n) {
         // the row bounds are read again by every hop (an L1 hit): kept across the hops they cost two registers a row, and
         // with them the kernel took 238 registers at RPT = 16 and spilled at 25
-        const int pb = rp[r], pe = rp[r + 1];
-        float acc = 0.f;
-#pragma unroll 4
-        for (int p = pb; p < pe; ++p) acc = fmaf(a.val[p], src[(int)((unsigned)a.col[p] - ilo) * W + c], acc);
+        const float acc = gr_row_sum(a.csr, lo + r, ilo, src, c);
         if (!last) dst[r * W + c] = acc;
         z[j] = fmaf(gk, acc, z[j]);
         if (want_dg) s = fmaf(acc, h[j], s);
@@ -171,15 +145,7 @@ __global__ __launch_bounds__(BLOCK) void gpr_prop_kernel(GprArgs a) {
 template <int RPT>
 int launch_rpt(const GprArgs& a, int64_t blocks, hipStream_t st) {
   static IsicPerDeviceOnce once;                 // one per instantiation; hipFuncSetAttribute is per device
-  const auto kernel = gpr_prop_kernel<RPT>;
-  if (isic_once_per_device(once, [&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   MAX_LDS_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  const size_t lds_bytes = (size_t)2 * a.max_nodes * W * sizeof(float);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(BLOCK), lds_bytes, st, a);
-  return isic_launch_status();
+  return gr_launch(gpr_prop_kernel<RPT>, once, blocks, (size_t)2 * a.max_nodes * W * sizeof(float), st, a);
 }
 
 int launch(const GprArgs& a, int64_t blocks, hipStream_t st) {
@@ -190,15 +156,14 @@ int launch(const GprArgs& a, int64_t blocks, hipStream_t st) {
   return launch_rpt<32>(a, blocks, st);
 }
 
-bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 // the argument checks the two entries share; 1 = go on, else the code to return
-int check_common(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, const int64_t* node_offsets,
-                 int64_t G, int max_nodes, int64_t N, const float* X, const float* gamma, int K, int F, const uint32_t* bad) {
-  ISIC_CHECK_ARG(G >= 0 && N >= 0 && nnz >= 0 && max_nodes >= 0 && F >= 1 && K >= 0 && K <= ISIC_GPR_MAX_K);
-  ISIC_CHECK_ARG((rowptr && node_offsets && gamma && bad && (X || N == 0) && ((col && val) || nnz == 0)) || G == 0);
-  ISIC_CHECK_ARG(aligned_to(node_offsets, 8) && aligned_to(rowptr, 4) && aligned_to(col, 4) && aligned_to(val, 4) &&
-                 aligned_to(X, 4) && aligned_to(gamma, 4) && aligned_to(bad, 4));
+int check_common(const GrCsr& s, const int64_t* node_offsets, int64_t G, int max_nodes, int64_t N, const float* X,
+                 const float* gamma, int K, int F, const uint32_t* bad) {
+  ISIC_CHECK_ARG(G >= 0 && N >= 0 && s.nnz >= 0 && max_nodes >= 0 && F >= 1 && K >= 0 && K <= ISIC_GPR_MAX_K);
+  ISIC_CHECK_ARG((gr_csr_args_ok(s, true) && node_offsets && gamma && bad && (X || N == 0)) || G == 0);
+  // (the alignment of the CSR arrays once more: here it is asked of an empty batch too)
+  ISIC_CHECK_ARG(gr_aligned_to(node_offsets, 8) && gr_aligned_to(s.rowptr, 4) && gr_aligned_to(s.col, 4) &&
+                 gr_aligned_to(s.val, 4) && gr_aligned_to(X, 4) && gr_aligned_to(gamma, 4) && gr_aligned_to(bad, 4));
   if (max_nodes > ISIC_GPR_MAX_NODES) return ISIC_ERR_UNSUPPORTED;
   if (G > (int64_t)INT_MAX / ceil_div(F, W)) return ISIC_ERR_UNSUPPORTED;
   return 1;
@@ -211,13 +176,14 @@ extern "C" {
 int isic_gpr_prop_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, const int64_t* node_offsets,
                       int64_t G, int max_nodes, int64_t N, const float* H, const float* gamma, int K, int F,
                       const float* bias, float* Z, uint32_t* bad, void* stream) {
-  const int rc = check_common(rowptr, col, val, nnz, node_offsets, G, max_nodes, N, H, gamma, K, F, bad);
+  const GrCsr csr = {rowptr, col, val, nnz};
+  const int rc = check_common(csr, node_offsets, G, max_nodes, N, H, gamma, K, F, bad);
   if (rc != 1) return rc;
-  ISIC_CHECK_ARG((Z || G == 0) && aligned_to(Z, 4) && aligned_to(bias, 4));
+  ISIC_CHECK_ARG((Z || G == 0) && gr_aligned_to(Z, 4) && gr_aligned_to(bias, 4));
   if (G == 0) return ISIC_OK;
   GprArgs a = {};
-  a.rowptr = rowptr; a.col = col; a.val = val; a.offsets = node_offsets; a.X = H; a.gamma = gamma; a.bias = bias; a.out = Z;
-  a.bad = bad; a.nnz = nnz; a.N = N; a.max_nodes = max_nodes; a.K = K; a.F = F; a.slabs = ceil_div(F, W);
+  a.csr = csr; a.offsets = node_offsets; a.X = H; a.gamma = gamma; a.bias = bias; a.out = Z;
+  a.bad = bad; a.N = N; a.max_nodes = max_nodes; a.K = K; a.F = F; a.slabs = ceil_div(F, W);
   return launch(a, G * a.slabs, as_stream(stream));
 }
 
@@ -230,10 +196,11 @@ int isic_gpr_prop_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const f
                           const int64_t* node_offsets, int64_t G, int max_nodes, int64_t N, const float* dZ, const float* H,
                           const float* gamma, int K, int F, float* dH, float* dgamma, float beta_gamma, void* workspace,
                           size_t workspace_bytes, uint32_t* bad, void* stream) {
-  const int rc = check_common(rowptr_t, col_t, val_t, nnz, node_offsets, G, max_nodes, N, dZ, gamma, K, F, bad);
+  const GrCsr csr = {rowptr_t, col_t, val_t, nnz};
+  const int rc = check_common(csr, node_offsets, G, max_nodes, N, dZ, gamma, K, F, bad);
   if (rc != 1) return rc;
   ISIC_CHECK_ARG(beta_gamma == 0.f || beta_gamma == 1.f);
-  ISIC_CHECK_ARG(aligned_to(dH, 4) && aligned_to(dgamma, 4) && aligned_to(H, 4));
+  ISIC_CHECK_ARG(gr_aligned_to(dH, 4) && gr_aligned_to(dgamma, 4) && gr_aligned_to(H, 4));
   ISIC_CHECK_ARG(!dgamma || H || N == 0 || G == 0);
   hipStream_t st = as_stream(stream);
   if (G == 0) {
@@ -241,12 +208,12 @@ int isic_gpr_prop_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const f
       return ISIC_ERR_LAUNCH;
     return ISIC_OK;
   }
-  if (dgamma && (!workspace || !aligned_to(workspace, 4) || workspace_bytes < isic_gpr_prop_bwd_workspace_bytes(G, K, F)))
+  if (dgamma && (!workspace || !gr_aligned_to(workspace, 4) || workspace_bytes < isic_gpr_prop_bwd_workspace_bytes(G, K, F)))
     return ISIC_ERR_WORKSPACE;
   if (!dH && !dgamma) return ISIC_OK;
   GprArgs a = {};
-  a.rowptr = rowptr_t; a.col = col_t; a.val = val_t; a.offsets = node_offsets; a.X = dZ; a.Hd = dgamma ? H : nullptr;
-  a.gamma = gamma; a.out = dH; a.partial = dgamma ? reinterpret_cast<float*>(workspace) : nullptr; a.bad = bad; a.nnz = nnz;
+  a.csr = csr; a.offsets = node_offsets; a.X = dZ; a.Hd = dgamma ? H : nullptr;
+  a.gamma = gamma; a.out = dH; a.partial = dgamma ? reinterpret_cast<float*>(workspace) : nullptr; a.bad = bad;
   a.N = N; a.max_nodes = max_nodes; a.K = K; a.F = F; a.slabs = ceil_div(F, W);
   const int64_t blocks = G * a.slabs;
   const int lrc = launch(a, blocks, st);

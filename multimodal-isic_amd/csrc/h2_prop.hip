@@ -11,13 +11,13 @@
 // wave: one request.  Nothing is carried across rows, so there is no register array and no template on the row count: the
 // 2-hop rows hold tens to hundreds of entries and the row loop is the whole kernel.
 //
-//   * Validation before anything is indexed, for BOTH operators: the graph's two offsets against N and max_nodes; the two ends
-//     of its CSR range against nnz; every row pointer of its rows against that range and every column id of the range against
-//     the graph's own node range.  __syncthreads_or joins the verdict, so the block leaves together: a bad graph adds 1 to
-//     bad[0] (an integer atomic, slab 0 only) and writes nothing.
+//   * Validation before anything is indexed: the node-range check and, for BOTH operators, the CSR check of
+//     graph_resident.inc, joined by __syncthreads_or.  A bad graph adds 1 to bad[0] (an integer atomic, slab 0 only) and
+//     writes nothing.
 //   * The backward completes the sum over A1's row, then the sum over A2's row, then adds the two: three roundings more than
 //     the longer dot product, in a fixed order.  No float atomics anywhere.
 #include "common.h"
+#include "graph_resident.inc"
 
 #include "../../include/isic_hip_h2.h"
 
@@ -25,21 +25,10 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int W = ISIC_H2_SLAB;
-constexpr int ROWS_PER_PASS = BLOCK / W;      // 8 rows of the slab per pass of the block
-constexpr int MAX_LDS_BYTES = 2 * ISIC_H2_MAX_NODES * W * (int)sizeof(float);
-static_assert(W == 32 && ROWS_PER_PASS == 8 && MAX_LDS_BYTES == 65536, "a half wave per row of the slab");
-
-struct Csr {
-  const int32_t* rowptr;
-  const int32_t* col;
-  const float* val;
-  int64_t nnz;
-};
+constexpr int BLOCK = GR_BLOCK, W = GR_W, ROWS_PER_PASS = GR_ROWS_PER_PASS;
 
 struct H2Args {
-  Csr op1, op2;
+  GrCsr op1, op2;
   const int64_t* offsets;
   const float* X;          // forward: H (row stride ldx = ldh); backward: dZ (ldx = ldz)
   float* out;              // forward: Z (ldo = ldz); backward: dH (ldo = ldh)
@@ -48,31 +37,6 @@ struct H2Args {
   int max_nodes, F, slabs;
 };
 
-// 1 if the rows [lo, lo + n) of the operator do not fit its arrays or hold a column id outside the graph (this thread's share)
-__device__ __forceinline__ int csr_flag(const Csr& s, int64_t lo, int n, int tid) {
-  const int64_t pb = s.rowptr[lo], pe = s.rowptr[lo + n];
-  if (pb < 0 || pe < pb || pe > s.nnz) return 1;
-  int flag = 0;
-  for (int r = tid; r < n; r += BLOCK) {
-    const int64_t b = s.rowptr[lo + r], e = s.rowptr[lo + r + 1];
-    if (b < pb || e < b || e > pe) flag = 1;
-  }
-  for (int64_t p = pb + tid; p < pe; p += BLOCK) {
-    const int64_t cl = (int64_t)s.col[p] - lo;
-    if (cl < 0 || cl >= n) flag = 1;
-  }
-  return flag;
-}
-
-// sum_p val[p] * src[col[p] - lo][c] over the row's slots, in slot order
-__device__ __forceinline__ float row_sum(const Csr& s, int64_t row, unsigned ilo, const float* src, int c) {
-  const int pb = s.rowptr[row], pe = s.rowptr[row + 1];
-  float acc = 0.f;
-#pragma unroll 4
-  for (int p = pb; p < pe; ++p) acc = fmaf(s.val[p], src[(int)((unsigned)s.col[p] - ilo) * W + c], acc);
-  return acc;
-}
-
 template <bool BWD>
 __global__ __launch_bounds__(BLOCK) void h2_prop_kernel(H2Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];    // forward [n][W]; backward [2][n][W]
@@ -80,13 +44,12 @@ __global__ __launch_bounds__(BLOCK) void h2_prop_kernel(H2Args a) {
   const int64_t g = blockIdx.x / a.slabs;
   const int slab = (int)(blockIdx.x % a.slabs), f0 = slab * W;
 
-  // ---- the graph's node range, compared with the sizes passed by value before anything is indexed with it
-  const int64_t lo = a.offsets[g], hi = a.offsets[g + 1];
-  const bool range_ok = lo >= 0 && hi >= lo && hi <= a.N && hi - lo <= (int64_t)a.max_nodes;
-  const int n = range_ok ? (int)(hi - lo) : 0;
-  int flag = range_ok ? 0 : 1;
-  // ---- both CSR ranges, their row pointers and column ids (0 <= lo < hi <= N: rowptr[lo .. hi] exists)
-  if (range_ok && n > 0) flag = csr_flag(a.op1, lo, n, tid) | csr_flag(a.op2, lo, n, tid);
+  // ---- the graph's node range, then both CSR ranges, their row pointers and column ids (graph_resident.inc)
+  const GrRange nr = gr_range(a.offsets, g, a.N, a.max_nodes);
+  const int64_t lo = nr.lo;
+  const int n = nr.n;
+  int flag = nr.flag;
+  if (n > 0) flag = gr_csr_flag(a.op1, lo, n) | gr_csr_flag(a.op2, lo, n);
   flag = __syncthreads_or(flag);
   if (flag || n == 0) {                         // the same verdict in every thread: the block leaves together
     if (flag && slab == 0 && tid == 0) atomicAdd(a.bad, 1u);
@@ -108,8 +71,8 @@ __global__ __launch_bounds__(BLOCK) void h2_prop_kernel(H2Args a) {
   // ---- gather: every column id is an int32 inside [lo, hi), so col - lo is 0 .. n - 1
   const unsigned ilo = (unsigned)lo;
   for (int r = r0; r < n; r += ROWS_PER_PASS) {
-    const float s1 = row_sum(a.op1, lo + r, ilo, buf1, c);
-    const float s2 = row_sum(a.op2, lo + r, ilo, buf2, c);
+    const float s1 = gr_row_sum(a.op1, lo + r, ilo, buf1, c);
+    const float s2 = gr_row_sum(a.op2, lo + r, ilo, buf2, c);
     if (col_ok) {
       const int64_t at = (lo + r) * a.ldo + f0 + c;
       if (BWD) {
@@ -125,30 +88,17 @@ __global__ __launch_bounds__(BLOCK) void h2_prop_kernel(H2Args a) {
 template <bool BWD>
 int launch(const H2Args& a, int64_t blocks, hipStream_t st) {
   static IsicPerDeviceOnce once;                 // one per instantiation; hipFuncSetAttribute is per device
-  const auto kernel = h2_prop_kernel<BWD>;
-  if (isic_once_per_device(once, [&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   MAX_LDS_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  const size_t lds_bytes = (size_t)(BWD ? 2 : 1) * a.max_nodes * W * sizeof(float);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(BLOCK), lds_bytes, st, a);
-  return isic_launch_status();
-}
-
-bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-bool csr_args_ok(const Csr& s) {
-  return s.rowptr && ((s.col && s.val) || s.nnz == 0) && aligned_to(s.rowptr, 4) && aligned_to(s.col, 4) && aligned_to(s.val, 4);
+  return gr_launch(h2_prop_kernel<BWD>, once, blocks, (size_t)(BWD ? 2 : 1) * a.max_nodes * W * sizeof(float), st, a);
 }
 
 // the argument checks and the launch the two entries share (ldh, ldz as the header names them)
-int run(bool bwd, const Csr& op1, const Csr& op2, const int64_t* node_offsets, int64_t G, int max_nodes, int64_t N,
+int run(bool bwd, const GrCsr& op1, const GrCsr& op2, const int64_t* node_offsets, int64_t G, int max_nodes, int64_t N,
         const float* X, float* out, int64_t ldh, int64_t ldz, int F, uint32_t* bad, void* stream) {
   ISIC_CHECK_ARG(G >= 0 && N >= 0 && op1.nnz >= 0 && op2.nnz >= 0 && max_nodes >= 0 && F >= 1);
   ISIC_CHECK_ARG(ldh >= (int64_t)F && ldz >= 2 * (int64_t)F);
-  ISIC_CHECK_ARG((csr_args_ok(op1) && csr_args_ok(op2) && node_offsets && bad && ((X && out) || N == 0)) || G == 0);
-  ISIC_CHECK_ARG(aligned_to(node_offsets, 8) && aligned_to(X, 4) && aligned_to(out, 4) && aligned_to(bad, 4));
+  ISIC_CHECK_ARG((gr_csr_args_ok(op1, true) && gr_csr_args_ok(op2, true) && node_offsets && bad && ((X && out) || N == 0)) ||
+                 G == 0);
+  ISIC_CHECK_ARG(gr_aligned_to(node_offsets, 8) && gr_aligned_to(X, 4) && gr_aligned_to(out, 4) && gr_aligned_to(bad, 4));
   if (max_nodes > ISIC_H2_MAX_NODES) return ISIC_ERR_UNSUPPORTED;
   if (N > (int64_t)INT_MAX || op1.nnz > (int64_t)INT_MAX || op2.nnz > (int64_t)INT_MAX) return ISIC_ERR_UNSUPPORTED;
   if (G > (int64_t)INT_MAX / ceil_div(F, W)) return ISIC_ERR_UNSUPPORTED;
@@ -168,7 +118,7 @@ int isic_h2_prop_f32(const int32_t* rowptr1, const int32_t* col1, const float* v
                      const int32_t* col2, const float* val2, int64_t nnz2, const int64_t* node_offsets, int64_t G,
                      int max_nodes, int64_t N, const float* H, int64_t ldh, int F, float* Z, int64_t ldz, uint32_t* bad,
                      void* stream) {
-  return run(false, Csr{rowptr1, col1, val1, nnz1}, Csr{rowptr2, col2, val2, nnz2}, node_offsets, G, max_nodes, N, H, Z, ldh,
+  return run(false, GrCsr{rowptr1, col1, val1, nnz1}, GrCsr{rowptr2, col2, val2, nnz2}, node_offsets, G, max_nodes, N, H, Z, ldh,
              ldz, F, bad, stream);
 }
 
@@ -176,7 +126,7 @@ int isic_h2_prop_bwd_f32(const int32_t* rowptr1, const int32_t* col1, const floa
                          const int32_t* col2, const float* val2, int64_t nnz2, const int64_t* node_offsets, int64_t G,
                          int max_nodes, int64_t N, const float* dZ, int64_t ldz, int F, float* dH, int64_t ldh, uint32_t* bad,
                          void* stream) {
-  return run(true, Csr{rowptr1, col1, val1, nnz1}, Csr{rowptr2, col2, val2, nnz2}, node_offsets, G, max_nodes, N, dZ, dH, ldh,
+  return run(true, GrCsr{rowptr1, col1, val1, nnz1}, GrCsr{rowptr2, col2, val2, nnz2}, node_offsets, G, max_nodes, N, dZ, dH, ldh,
              ldz, F, bad, stream);
 }
 

@@ -3,10 +3,9 @@
 //   isic_two_hop_write   col / val / perm of both operators behind the caller's exclusive scans of those degrees
 // Both are the same build: a block of 256 threads takes one graph (n <= 256 nodes), thread i owns node i.
 //
-//   * Validation before anything is indexed, as in gpr_prop.hip: the graph's two offsets against N and max_nodes, the two ends
-//     of its CSR range against nnz, every row pointer of its rows against that range, every column id against the graph's own
-//     node range (the write also: every row pointer of both operators against [0, nnz1] / [0, nnz2]).  __syncthreads_or joins
-//     the verdict: a bad graph adds 1 to bad[0] (an integer atomic) and writes nothing.
+//   * Validation before anything is indexed: the node-range and CSR checks of graph_resident.inc (the write also: every row
+//     pointer of both operators against [0, nnz1] / [0, nnz2]), joined by __syncthreads_or.  A bad graph adds 1 to bad[0] (an
+//     integer atomic) and writes nothing.
 //   * A1 as bit rows in LDS, 8 words a row at a stride of ROW = 9 words (thread i reads words i * 9 + k: 32 lanes on 32 banks;
 //     at a stride of 8 they would meet on four).  Thread i walks CSR row i and sets (i,j) and (j,i) with atomicOr on LDS -- an
 //     integer OR, so the matrix does not depend on the order of the entries or of the threads; self loops are skipped,
@@ -18,6 +17,7 @@
 //     told otherwise; nothing here can contract to an FMA), perm = rowptr[j] + the number of set bits of row j below i.
 //     A slot outside [rowptr[i], rowptr[i+1]) is not stored.
 #include "common.h"
+#include "graph_resident.inc"
 
 #include "../../include/isic_hip_h2.h"
 
@@ -25,14 +25,13 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = GR_BLOCK;
 constexpr int WORDS = ISIC_H2_MAX_NODES / 32;      // 8 words of 32 bits a row
 constexpr int ROW = WORDS + 1;                     // LDS stride of a bit row
 static_assert(ISIC_H2_MAX_NODES == BLOCK && WORDS == 8, "a thread per node, eight words per bit row");
 
 struct TwoHopArgs {
-  const int32_t* rowptr;
-  const int32_t* col;
+  GrCsr csr;                  // the input graph: structure only, val is NULL
   const int64_t* offsets;
   const int32_t* rowptr1;     // write only
   const int32_t* rowptr2;
@@ -45,7 +44,7 @@ struct TwoHopArgs {
   float* val2;
   int32_t* perm2;
   uint32_t* bad;
-  int64_t nnz, nnz1, nnz2, N;
+  int64_t nnz1, nnz2, N;
   int max_nodes;
 };
 
@@ -87,26 +86,13 @@ __global__ __launch_bounds__(BLOCK) void two_hop_kernel(TwoHopArgs a) {
   const int tid = threadIdx.x;
   const int64_t g = blockIdx.x;
 
-  // ---- the graph's node range, compared with the sizes passed by value before anything is indexed with it
-  const int64_t lo = a.offsets[g], hi = a.offsets[g + 1];
-  const bool range_ok = lo >= 0 && hi >= lo && hi <= a.N && hi - lo <= (int64_t)a.max_nodes;
-  const int n = range_ok ? (int)(hi - lo) : 0;
-  int flag = range_ok ? 0 : 1;
-  if (range_ok && n > 0) {
-    // ---- its CSR range, its row pointers and its column ids (0 <= lo < hi <= N: rowptr[lo .. hi] exists)
-    const int64_t pb = a.rowptr[lo], pe = a.rowptr[hi];
-    if (pb < 0 || pe < pb || pe > a.nnz) {
-      flag = 1;
-    } else {
-      for (int r = tid; r < n; r += BLOCK) {
-        const int64_t b = a.rowptr[lo + r], e = a.rowptr[lo + r + 1];
-        if (b < pb || e < b || e > pe) flag = 1;
-      }
-      for (int64_t p = pb + tid; p < pe; p += BLOCK) {
-        const int64_t cl = (int64_t)a.col[p] - lo;
-        if (cl < 0 || cl >= n) flag = 1;
-      }
-    }
+  // ---- the graph's node range, then its CSR range, row pointers and column ids (graph_resident.inc)
+  const GrRange nr = gr_range(a.offsets, g, a.N, a.max_nodes);
+  const int64_t lo = nr.lo;
+  const int n = nr.n;
+  int flag = nr.flag;
+  if (n > 0) {
+    flag = gr_csr_flag(a.csr, lo, n);
     if (WRITE) {                                   // the operators' row pointers of this graph's rows: values inside [0, nnzp]
       for (int r = tid; r <= n; r += BLOCK) {
         const int64_t v1 = a.rowptr1[lo + r], v2 = a.rowptr2[lo + r];
@@ -124,9 +110,9 @@ __global__ __launch_bounds__(BLOCK) void two_hop_kernel(TwoHopArgs a) {
   for (int w = tid; w < n * ROW; w += BLOCK) adj1[w] = 0u;
   __syncthreads();
   if (tid < n) {
-    const int pb = a.rowptr[lo + tid], pe = a.rowptr[lo + tid + 1];
+    const int pb = a.csr.rowptr[lo + tid], pe = a.csr.rowptr[lo + tid + 1];
     for (int p = pb; p < pe; ++p) {
-      const int j = (int)((int64_t)a.col[p] - lo);                 // 0 .. n - 1 (validated)
+      const int j = (int)((int64_t)a.csr.col[p] - lo);                // 0 .. n - 1 (validated)
       if (j != tid) {
         atomicOr(&adj1[tid * ROW + (j >> 5)], 1u << (j & 31));
         atomicOr(&adj1[j * ROW + (tid >> 5)], 1u << (tid & 31));
@@ -187,16 +173,14 @@ __global__ __launch_bounds__(BLOCK) void two_hop_kernel(TwoHopArgs a) {
   }
 }
 
-bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 // the argument checks the two entries share; 1 = go on, else the code to return
-int check_common(const int32_t* rowptr, const int32_t* col, int64_t nnz, const int64_t* node_offsets, int64_t G, int max_nodes,
-                 int64_t N, const uint32_t* bad) {
-  ISIC_CHECK_ARG(G >= 0 && N >= 0 && nnz >= 0 && max_nodes >= 0);
-  ISIC_CHECK_ARG((rowptr && node_offsets && bad && (col || nnz == 0)) || G == 0);
-  ISIC_CHECK_ARG(aligned_to(node_offsets, 8) && aligned_to(rowptr, 4) && aligned_to(col, 4) && aligned_to(bad, 4));
+int check_common(const GrCsr& s, const int64_t* node_offsets, int64_t G, int max_nodes, int64_t N, const uint32_t* bad) {
+  ISIC_CHECK_ARG(G >= 0 && N >= 0 && s.nnz >= 0 && max_nodes >= 0);
+  ISIC_CHECK_ARG((gr_csr_args_ok(s, false) && node_offsets && bad) || G == 0);
+  // (the alignment of the CSR arrays once more: here it is asked of an empty batch too)
+  ISIC_CHECK_ARG(gr_aligned_to(node_offsets, 8) && gr_aligned_to(s.rowptr, 4) && gr_aligned_to(s.col, 4) && gr_aligned_to(bad, 4));
   if (max_nodes > ISIC_H2_MAX_NODES) return ISIC_ERR_UNSUPPORTED;
-  if (G > (int64_t)INT_MAX || N > (int64_t)INT_MAX || nnz > (int64_t)INT_MAX) return ISIC_ERR_UNSUPPORTED;
+  if (G > (int64_t)INT_MAX || N > (int64_t)INT_MAX || s.nnz > (int64_t)INT_MAX) return ISIC_ERR_UNSUPPORTED;
   return 1;
 }
 
@@ -206,13 +190,13 @@ extern "C" {
 
 int isic_two_hop_count(const int32_t* rowptr, const int32_t* col, int64_t nnz, const int64_t* node_offsets, int64_t G,
                        int max_nodes, int64_t N, int32_t* deg1, int32_t* deg2, uint32_t* bad, void* stream) {
-  const int rc = check_common(rowptr, col, nnz, node_offsets, G, max_nodes, N, bad);
+  const GrCsr csr = {rowptr, col, nullptr, nnz};
+  const int rc = check_common(csr, node_offsets, G, max_nodes, N, bad);
   if (rc != 1) return rc;
-  ISIC_CHECK_ARG(((deg1 && deg2) || N == 0 || G == 0) && aligned_to(deg1, 4) && aligned_to(deg2, 4));
+  ISIC_CHECK_ARG(((deg1 && deg2) || N == 0 || G == 0) && gr_aligned_to(deg1, 4) && gr_aligned_to(deg2, 4));
   if (G == 0) return ISIC_OK;
   TwoHopArgs a = {};
-  a.rowptr = rowptr; a.col = col; a.offsets = node_offsets; a.deg1 = deg1; a.deg2 = deg2; a.bad = bad; a.nnz = nnz; a.N = N;
-  a.max_nodes = max_nodes;
+  a.csr = csr; a.offsets = node_offsets; a.deg1 = deg1; a.deg2 = deg2; a.bad = bad; a.N = N; a.max_nodes = max_nodes;
   hipLaunchKernelGGL(two_hop_kernel<false>, dim3((unsigned)G), dim3(BLOCK), 0, as_stream(stream), a);
   return isic_launch_status();
 }
@@ -221,18 +205,19 @@ int isic_two_hop_write(const int32_t* rowptr, const int32_t* col, int64_t nnz, c
                        int max_nodes, int64_t N, const int32_t* rowptr1, const int32_t* rowptr2, int64_t nnz1, int64_t nnz2,
                        int32_t* col1, float* val1, int32_t* perm1, int32_t* col2, float* val2, int32_t* perm2, uint32_t* bad,
                        void* stream) {
-  const int rc = check_common(rowptr, col, nnz, node_offsets, G, max_nodes, N, bad);
+  const GrCsr csr = {rowptr, col, nullptr, nnz};
+  const int rc = check_common(csr, node_offsets, G, max_nodes, N, bad);
   if (rc != 1) return rc;
   ISIC_CHECK_ARG(nnz1 >= 0 && nnz2 >= 0);
   ISIC_CHECK_ARG((rowptr1 && rowptr2 && ((col1 && val1 && perm1) || nnz1 == 0) && ((col2 && val2 && perm2) || nnz2 == 0)) || G == 0);
-  ISIC_CHECK_ARG(aligned_to(rowptr1, 4) && aligned_to(rowptr2, 4) && aligned_to(col1, 4) && aligned_to(val1, 4) &&
-                 aligned_to(perm1, 4) && aligned_to(col2, 4) && aligned_to(val2, 4) && aligned_to(perm2, 4));
+  ISIC_CHECK_ARG(gr_aligned_to(rowptr1, 4) && gr_aligned_to(rowptr2, 4) && gr_aligned_to(col1, 4) && gr_aligned_to(val1, 4) &&
+                 gr_aligned_to(perm1, 4) && gr_aligned_to(col2, 4) && gr_aligned_to(val2, 4) && gr_aligned_to(perm2, 4));
   if (nnz1 > (int64_t)INT_MAX || nnz2 > (int64_t)INT_MAX) return ISIC_ERR_UNSUPPORTED;
   if (G == 0) return ISIC_OK;
   TwoHopArgs a = {};
-  a.rowptr = rowptr; a.col = col; a.offsets = node_offsets; a.rowptr1 = rowptr1; a.rowptr2 = rowptr2; a.col1 = col1;
-  a.val1 = val1; a.perm1 = perm1; a.col2 = col2; a.val2 = val2; a.perm2 = perm2; a.bad = bad; a.nnz = nnz; a.nnz1 = nnz1;
-  a.nnz2 = nnz2; a.N = N; a.max_nodes = max_nodes;
+  a.csr = csr; a.offsets = node_offsets; a.rowptr1 = rowptr1; a.rowptr2 = rowptr2; a.col1 = col1;
+  a.val1 = val1; a.perm1 = perm1; a.col2 = col2; a.val2 = val2; a.perm2 = perm2; a.bad = bad; a.nnz1 = nnz1; a.nnz2 = nnz2;
+  a.N = N; a.max_nodes = max_nodes;
   hipLaunchKernelGGL(two_hop_kernel<true>, dim3((unsigned)G), dim3(BLOCK), 0, as_stream(stream), a);
   return isic_launch_status();
 }

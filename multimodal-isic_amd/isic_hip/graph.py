@@ -442,12 +442,52 @@ GPR_SLAB = 32
 # exceeds three times the wider run-to-run range.  Measured at 668 graphs x 196 nodes, F = 128, three layers, K = 10: the
 # GraphMIL[gprgnn] step takes 8.04 ms resident against 10.87 ms composed (appnp: 7.69 against 8.46), ranges below 0.02 ms.
 GPR_RESIDENT_DEFAULT = True
-_GPR_LAST_PATH = None
+_LAST_PATH = {}                                 # entry name -> 'resident' | 'composed'
+# What follows "NAME: n graph(s) whose node offsets decrease, leave the node range or span more than 256 nodes, " when a
+# graph-resident kernel has counted graphs it refused (256 = GPR_MAX_NODES = H2_MAX_NODES: csrc/graph_resident.inc)
+_REFUSED = {
+    "gpr_prop": "or that hold a column id outside their own node range; their rows were not written",
+    "h2_prop": "or whose operators hold a column id outside the graph's own node range; their rows were not written",
+    "two_hop": "whose row pointers decrease or leave the entry range, or that hold a column id outside their own node range",
+}
+
+
+def _raise_if_refused(name, bad, also=None):
+    """Reads the counter of refused graphs of a graph-resident kernel back -- ONE copy and synchronisation, together with the
+    int64 values ``also`` -- and raises on a non-zero count; returns the values of ``also``."""
+    *rest, n_bad = (bad if also is None else torch.cat([also, bad.to(torch.int64)])).cpu().tolist()
+    n_bad &= 0xFFFFFFFF                                                     # (uint32 on the device side)
+    if n_bad:
+        raise ValueError(f"{name}: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
+                         f"{GPR_MAX_NODES} nodes, {_REFUSED[name]}")
+    return rest
+
+
+def _resident_or_composed(name, resident, offsets, composed, apply, device, bad, check):
+    """The dispatch ``gpr_prop`` and ``h2_prop`` share: ``composed()`` unless ``resident`` (the caller's choice or the entry's
+    ``*_RESIDENT_DEFAULT``) and ``offsets`` are there, and wherever ``apply(bad)`` answers ISIC_ERR_UNSUPPORTED.  Records the
+    path taken; a counter made here is read back if ``check``."""
+    _LAST_PATH[name] = "composed"
+    if not resident or offsets is None:
+        return composed()
+    own = bad is None
+    if own:
+        bad = torch.zeros(1, device=device, dtype=torch.int32)              # (uint32 on the device side)
+    try:
+        z = apply(bad)
+    except IsicHipError as e:
+        if e.code != ERR_UNSUPPORTED:
+            raise
+        return composed()
+    _LAST_PATH[name] = "resident"
+    if own and check:
+        _raise_if_refused(name, bad)
+    return z
 
 
 def gpr_last_path():
     """'resident' or 'composed': the path the last ``gpr_prop`` call took (for tests and the benchmark)."""
-    return _GPR_LAST_PATH
+    return _LAST_PATH.get("gpr_prop")
 
 
 def gpr_gamma(K, alpha, dtype=torch.float32):
@@ -528,34 +568,14 @@ def gpr_prop(h, gamma, graph, offsets=None, bias=None, resident=None, check=True
         raise ValueError(f"gpr_prop needs a 'gcn'-mode GraphBatch, got '{graph.mode}'")
     if gamma.dim() != 1 or not 1 <= gamma.numel() <= GPR_MAX_K + 1:
         raise IsicHipError(f"gpr_prop takes gamma [K + 1] with 0 <= K <= {GPR_MAX_K}, got {tuple(gamma.shape)}", code=-1)
-    global _GPR_LAST_PATH
-    if resident is None:
-        resident = GPR_RESIDENT_DEFAULT
-    _GPR_LAST_PATH = "composed"
-    if not resident or offsets is None:
-        return gpr_prop_composed(h, gamma, graph, bias)
-    own = bad is None
-    if own:
-        bad = torch.zeros(1, device=h.device, dtype=torch.int32)            # (uint32 on the device side)
-    try:
-        z = GprPropFn.apply(h, gamma, graph, offsets, bias, bad)
-    except IsicHipError as e:
-        if e.code != ERR_UNSUPPORTED:
-            raise
-        return gpr_prop_composed(h, gamma, graph, bias)
-    _GPR_LAST_PATH = "resident"
-    if own and check:
-        gpr_check(bad)
-    return z
+    return _resident_or_composed("gpr_prop", GPR_RESIDENT_DEFAULT if resident is None else resident, offsets,
+                                 lambda: gpr_prop_composed(h, gamma, graph, bias),
+                                 lambda b: GprPropFn.apply(h, gamma, graph, offsets, bias, b), h.device, bad, check)
 
 
 def gpr_check(bad):
     """Reads a ``gpr_prop`` counter back (a synchronisation) and raises on a non-zero count."""
-    n_bad = int(bad.item()) & 0xFFFFFFFF
-    if n_bad:
-        raise ValueError(f"gpr_prop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
-                         f"{GPR_MAX_NODES} nodes, or that hold a column id outside their own node range; their rows were "
-                         "not written")
+    _raise_if_refused("gpr_prop", bad)
 
 
 H2_MAX_NODES = 256
@@ -567,12 +587,11 @@ H2_SLAB = 32
 # step takes 8.06 ms resident against 7.40 ms composed on grid8, 13.25 against 9.26 on knn8 and 13.44 against 9.53 on random8
 # (ranges below 0.13 ms): the resident kernel loses on every variant, also at 117 - 129 entries per 2-hop row, and is opt-in.
 H2_RESIDENT_DEFAULT = False
-_H2_LAST_PATH = None
 
 
 def h2_last_path():
     """'resident' or 'composed': the path the last ``h2_prop`` call took (for tests and the benchmark)."""
-    return _H2_LAST_PATH
+    return _LAST_PATH.get("h2_prop")
 
 
 class TwoHopGraph:
@@ -624,12 +643,7 @@ def two_hop(graph, offsets) -> TwoHopGraph:
     two_hop_count_launch(graph, offsets, deg, bad)
     rp = torch.zeros((2, n + 1), device=dev, dtype=torch.int64)
     rp[:, 1:] = torch.cumsum(deg, dim=1, dtype=torch.int64)
-    head = torch.cat([rp[:, -1], bad.to(torch.int64) & 0xFFFFFFFF]).cpu().tolist()       # the one read-back
-    nnz1, nnz2, n_bad = int(head[0]), int(head[1]), int(head[2])
-    if n_bad:
-        raise ValueError(f"two_hop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
-                         f"{H2_MAX_NODES} nodes, whose row pointers decrease or leave the entry range, or that hold a column id outside "
-                         "their own node range")
+    nnz1, nnz2 = _raise_if_refused("two_hop", bad, also=rp[:, -1])          # the one read-back
     if max(nnz1, nnz2) >= 2 ** 31 - 1:
         raise IsicHipError("two_hop: more than 2^31 - 2 entries in one operator", code=ERR_UNSUPPORTED)
     rp = rp.to(i32)
@@ -691,34 +705,14 @@ def h2_prop(h, g2, offsets=None, resident=None, bad=None):
     and not read here (``h2_check``)."""
     if getattr(g2, "mode", None) != "h2":
         raise ValueError("h2_prop needs a TwoHopGraph (isic_hip.graph.two_hop)")
-    global _H2_LAST_PATH
-    if resident is None:
-        resident = H2_RESIDENT_DEFAULT
-    _H2_LAST_PATH = "composed"
-    if not resident or offsets is None:
-        return h2_prop_composed(h, g2)
-    own = bad is None
-    if own:
-        bad = torch.zeros(1, device=h.device, dtype=torch.int32)            # (uint32 on the device side)
-    try:
-        z = H2PropFn.apply(h, g2, offsets, bad)
-    except IsicHipError as e:
-        if e.code != ERR_UNSUPPORTED:
-            raise
-        return h2_prop_composed(h, g2)
-    _H2_LAST_PATH = "resident"
-    if own:
-        h2_check(bad)
-    return z
+    return _resident_or_composed("h2_prop", H2_RESIDENT_DEFAULT if resident is None else resident, offsets,
+                                 lambda: h2_prop_composed(h, g2), lambda b: H2PropFn.apply(h, g2, offsets, b), h.device, bad,
+                                 True)
 
 
 def h2_check(bad):
     """Reads an ``h2_prop`` counter back (a synchronisation) and raises on a non-zero count."""
-    n_bad = int(bad.item()) & 0xFFFFFFFF
-    if n_bad:
-        raise ValueError(f"h2_prop: {n_bad} graph(s) whose node offsets decrease, leave the node range or span more than "
-                         f"{H2_MAX_NODES} nodes, or whose operators hold a column id outside the graph's own node range; their "
-                         "rows were not written")
+    _raise_if_refused("h2_prop", bad)
 
 
 class GcnBlockFn(torch.autograd.Function):

@@ -211,6 +211,56 @@ def test_bad_graphs_are_counted_and_write_nothing():
         gpr_prop(h[:offs2.total].to(DEV), gamma.to(DEV), g2, offs2, resident=True)
 
 
+def test_a_graph_whose_row_pointers_are_wrong_is_counted_and_writes_nothing():
+    """the row-pointer checks of both entries: in the forward a row pointer of graph 1 above its successor, in the backward a
+    row pointer of graph 2 (transposed CSR) beyond nnz.  bad == 1, the graph's rows of Z / dH keep the sentinel, the other
+    graphs' rows are the bits of a clean run, dgamma is finite"""
+    from isic_hip.graph import GraphBatch
+    from isic_hip.lib import call
+    sizes = [10, 12, 7]
+    _, offsets, eis, ews = R.kernel_batch(seed=3, sizes=sizes, k=4)
+    ei, _ = R.batch_edges(offsets, eis, ews)
+    N, F, K = offsets[-1], 36, 3
+    graph = GraphBatch(ei.to(DEV), N)
+    h, dz, bias, gamma = (t.to(DEV) for t in _inputs(N, F, K, seed=9))
+    off_dev = torch.tensor(offsets, device=DEV)
+    nnz, nnz_t = int(graph.col.numel()), int(graph.col_t.numel())
+    nbytes = int(call("isic_gpr_prop_bwd_workspace_bytes", len(sizes), K, F))
+    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+
+    def forward(rowptr):
+        z = torch.full((N, F), SENTINEL, device=DEV)
+        bad = torch.zeros(1, device=DEV, dtype=torch.int32)
+        call("isic_gpr_prop_f32", rowptr, graph.col, graph.val, nnz, off_dev, len(sizes), 256, N, h, gamma, K, F, bias, z, bad)
+        return z, int(bad.item())
+
+    def backward(rowptr_t):
+        dh = torch.full((N, F), SENTINEL, device=DEV)
+        dg = torch.full((K + 1,), SENTINEL, device=DEV)
+        bad = torch.zeros(1, device=DEV, dtype=torch.int32)
+        call("isic_gpr_prop_bwd_f32", rowptr_t, graph.col_t, graph.val_t, nnz_t, off_dev, len(sizes), 256, N, dz, h, gamma, K, F,
+             dh, dg, 0.0, ws, nbytes, bad)
+        return dh, dg, int(bad.item())
+
+    rp, rpt = graph.rowptr.clone(), graph.rowptr_t.clone()
+    rp[offsets[1] + 2] = rp[offsets[1] + 3] + 1
+    rpt[offsets[2] + 3] = nnz_t + 1000
+    good_z, n_bad = forward(graph.rowptr)
+    assert n_bad == 0 and bool((good_z != SENTINEL).all())
+    good_dh, _, n_bad = backward(graph.rowptr_t)
+    assert n_bad == 0 and bool((good_dh != SENTINEL).all())
+    z, n_bad = forward(rp)
+    dh, dg, n_bad_t = backward(rpt)
+    assert n_bad == 1 and n_bad_t == 1
+    assert bool(torch.isfinite(dg).all()) and bool((dg != SENTINEL).all())
+    for out, good, refused in ((z, good_z, 1), (dh, good_dh, 2)):
+        for g, (lo, hi) in enumerate(zip(offsets[:-1], offsets[1:])):
+            if g == refused:
+                assert bool((out[lo:hi] == SENTINEL).all()), g
+            else:
+                assert torch.equal(out[lo:hi], good[lo:hi]), g
+
+
 def test_a_graph_beyond_256_nodes_takes_the_composed_path():
     from isic_hip import graph as G
     from isic_hip.bags import BagOffsets
