@@ -597,16 +597,8 @@ __global__ __launch_bounds__(NTHR_B) void attn_pool_bwd_kernel(PoolBwdArgs a) {
   }
 }
 
-template <typename K>
-int ensure_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return ISIC_ERR_UNSUPPORTED;
-  if (bytes > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bytes) != hipSuccess)
-      return ISIC_ERR_LAUNCH;
-  }
-  return ISIC_OK;
-}
+// the pools size their LDS by the call's shape: anything up to a workgroup's 160 KB runs, more is ISIC_ERR_UNSUPPORTED
+constexpr int POOL_MAX_LDS = 160 * 1024;
 
 }  // namespace
 
@@ -636,22 +628,16 @@ int isic_attn_pool_fwd(const float* h, const float* t, const float* w3, const fl
     if (!W4 && z && H <= 128 && A <= 128 && heads <= MAX_HEADS && !patch_logits && !patch_probs && !bag_logits && !bag_probs) {
       // GraphMIL form: the two-pass kernel
       const size_t lds2 = sizeof(float) * ((size_t)nh * A + (size_t)max_bag * nh + max_bag + 4 * (size_t)H + 2 * MAX_HEADS);
-      rc = ensure_lds(attn_pool_fwd2_kernel, lds2);
-      if (rc != ISIC_OK) return rc;
-      hipLaunchKernelGGL(attn_pool_fwd2_kernel, dim3(B), dim3(NTHR), lds2, as_stream(stream), a);
-      return isic_launch_status();
+      return isic_launch_lds<attn_pool_fwd2_kernel, POOL_MAX_LDS>(dim3(B), dim3(NTHR), lds2, as_stream(stream), a);
     }
-#define LAUNCH_POOL(JH, JA)                                                                         \
-  rc = ensure_lds(attn_pool_fwd_kernel<JH, JA>, lds);                                               \
-  if (rc != ISIC_OK) return rc;                                                                     \
-  hipLaunchKernelGGL((attn_pool_fwd_kernel<JH, JA>), dim3(B), dim3(NTHR), lds, as_stream(stream), a)
+#define LAUNCH_POOL(JH, JA) \
+  rc = isic_launch_lds<attn_pool_fwd_kernel<JH, JA>, POOL_MAX_LDS>(dim3(B), dim3(NTHR), lds, as_stream(stream), a)
     if (H <= 128 && A <= 128) { LAUNCH_POOL(2, 2); }
     else if (H <= 128) { LAUNCH_POOL(2, 0); }
     else if (H <= 256) { LAUNCH_POOL(4, 0); }
     else if (H <= 512) { LAUNCH_POOL(8, 0); }
     else { LAUNCH_POOL(16, 0); }
 #undef LAUNCH_POOL
-    rc = isic_launch_status();
     if (rc != ISIC_OK) return rc;
   }
   return ISIC_OK;
@@ -682,17 +668,9 @@ int isic_attn_pool_bwd_sums(const float* h, const float* t, const float* att, co
   if (param_sums && !(H <= 128 && A <= 128 && d_u)) return ISIC_ERR_UNSUPPORTED;      // the sums are taken by the two-columns-per-lane form
   const size_t lds = sizeof(float) * ((size_t)heads * A + (W4 ? (size_t)C * H : 0) + H + (size_t)max_bag * heads +
                                       NWAVE_B * heads + (param_sums ? (size_t)NWAVE_B * (2 * heads * A + heads) : 0));
-  int rc;
-  if (H <= 128 && A <= 128) {
-    rc = ensure_lds(attn_pool_bwd_kernel<true>, lds);
-    if (rc != ISIC_OK) return rc;
-    hipLaunchKernelGGL(attn_pool_bwd_kernel<true>, dim3(B), dim3(NTHR_B), lds, as_stream(stream), a);
-  } else {
-    rc = ensure_lds(attn_pool_bwd_kernel<false>, lds);
-    if (rc != ISIC_OK) return rc;
-    hipLaunchKernelGGL(attn_pool_bwd_kernel<false>, dim3(B), dim3(NTHR_B), lds, as_stream(stream), a);
-  }
-  return isic_launch_status();
+  if (H <= 128 && A <= 128)
+    return isic_launch_lds<attn_pool_bwd_kernel<true>, POOL_MAX_LDS>(dim3(B), dim3(NTHR_B), lds, as_stream(stream), a);
+  return isic_launch_lds<attn_pool_bwd_kernel<false>, POOL_MAX_LDS>(dim3(B), dim3(NTHR_B), lds, as_stream(stream), a);
 }
 
 }  // extern "C"

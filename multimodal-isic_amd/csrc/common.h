@@ -68,6 +68,22 @@ static inline hipError_t isic_once_per_device(IsicPerDeviceOnce& o, Fn fn) {
   std::call_once(o.flag[d], [&] { o.rc[d] = fn(); });
   return o.rc[d];
 }
+// The one way a kernel with dynamic LDS is launched.  Opts `Kernel` (one flag per instantiation: the static below belongs to
+// this template instance) into MAX_LDS bytes once per device, launches it with this call's `lds` bytes, and returns the launch
+// status.  That status is READ here, which clears it: the caller returns this code and asks isic_launch_status() for nothing
+// this call launched.  lds > MAX_LDS launches nothing.
+template <auto Kernel, int MAX_LDS, class... Args>
+static inline int isic_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static_assert(MAX_LDS > 0 && MAX_LDS <= 160 * 1024, "a gfx950 workgroup has 160 KB of LDS");
+  if (lds > (size_t)MAX_LDS) return ISIC_ERR_UNSUPPORTED;
+  static IsicPerDeviceOnce once;
+  if (isic_once_per_device(once, [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+      }) != hipSuccess)
+    return ISIC_ERR_LAUNCH;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return isic_launch_status();
+}
 static inline int isic_cu_count() {
   static int cus[ISIC_MAX_DEVICES];                        // 0 = not asked yet; the race is benign (same value)
   const int dev = isic_current_device();

@@ -487,14 +487,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64p_kernel(C64PArgs a) {
 
 template <bool STATS, bool ADDEND>
 int launch_c64p(const C64PArgs& a, int grid, hipStream_t stream) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64p_kernel<STATS, ADDEND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  P_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((conv3x3_c64p_kernel<STATS, ADDEND>), dim3(grid), dim3(512), P_LDS, stream, a);
-  return ISIC_OK;
+  return isic_launch_lds<conv3x3_c64p_kernel<STATS, ADDEND>, P_LDS>(dim3(grid), dim3(512), P_LDS, stream, a);
 }
 
 }  // namespace
@@ -526,12 +519,5 @@ int isic_conv3x3_c64_launch(int variant, const uint16_t* in, const uint16_t* w, 
   a.stat_sum = stat_sum; a.stat_sumsq = stat_sumsq; a.stat_slots = stat_slots > 0 ? stat_slots : 1;
   a.N = N; a.H = H; a.W = W;
   a.tiles_y = tiles_y; a.tiles_x = tiles_x;
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(conv3x3_c64_kernel, dim3((unsigned)blocks), dim3(256), LDS_BYTES, stream, a);
-  return ISIC_OK;
+  return isic_launch_lds<conv3x3_c64_kernel, LDS_BYTES>(dim3((unsigned)blocks), dim3(256), LDS_BYTES, stream, a);
 }

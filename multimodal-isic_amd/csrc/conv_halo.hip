@@ -516,14 +516,7 @@ __global__ __launch_bounds__(1024) void conv_halo_kernel(HaloArgs a) {
 
 template <int STATS, bool ADDEND, int KPB>
 int launch_halo(const HaloArgs& a, int grid, int lds, hipStream_t stream) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_kernel<STATS, ADDEND, KPB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((conv_halo_kernel<STATS, ADDEND, KPB>), dim3(grid), dim3(1024), lds, stream, a);
-  return ISIC_OK;
+  return isic_launch_lds<conv_halo_kernel<STATS, ADDEND, KPB>, 160 * 1024>(dim3(grid), dim3(1024), lds, stream, a);
 }
 
 }  // namespace

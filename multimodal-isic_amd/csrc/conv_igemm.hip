@@ -288,23 +288,17 @@ int launch_conv(const ConvArgsN& a, hipStream_t s) {
   constexpr int CBYTES = BM * (BN + 8) * 2 + 2 * MT * 4;
   constexpr int MAIN = NSTAGE * STAGE;
   constexpr int LDS = MAIN > CBYTES ? MAIN : CBYTES;
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, NSTAGE>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   int maxM = 0;
   for (int i = 0; i < a.n; ++i) maxM = a.c[i].M > maxM ? a.c[i].M : maxM;
   dim3 grid(ceil_div(maxM, BM), a.c[0].Cout / BN, a.n);
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NSTAGE>), grid, dim3(2 * MT), LDS, s, a);
-  return ISIC_OK;
+  return isic_launch_lds<conv_igemm_kernel<BM, BN, WM, WN, NSTAGE>, LDS>(grid, dim3(2 * MT), LDS, s, a);
 }
 
 constexpr int kDefaultConvC64 = 2;    // 64 -> 64 3x3 layers: persistent halo kernel (conv_c64.hip)
 
 }  // namespace
 
+// each *_launch below returns the status of its own launch: the caller returns it
 int isic_conv3x3_c64_launch(int variant, const uint16_t* in, const uint16_t* w, uint16_t* out, int N, int H, int W,
                             const uint16_t* addend, const uint8_t* addend_mask, double* stat_sum, double* stat_sumsq,
                             int stat_slots, hipStream_t stream);
@@ -366,16 +360,14 @@ int conv2d_dispatch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N,
   const bool same3x3 = Kh == 3 && Kw == 3 && up == 1 && down == 1 && pad == 1 && Hin == Hout && Win == Wout;
   if (Cin == 64 && Cout == 64 && same3x3 && cv.c64 != 0) {
     ISIC_CHECK_ARG(cv.exp == 0);                           // the ten-thousands digit selects a loop of conv_halo.hip only
-    const int rc = isic_conv3x3_c64_launch(cv.c64, in, w, out, N, Hin, Win, addend, addend_mask, stat_sum, stat_sumsq,
-                                           stat_slots, as_stream(stream));
-    return rc != ISIC_OK ? rc : isic_launch_status();
+    return isic_conv3x3_c64_launch(cv.c64, in, w, out, N, Hin, Win, addend, addend_mask, stat_sum, stat_sumsq, stat_slots,
+                                   as_stream(stream));
   }
   // >= 128-channel 3x3 layers: every input pixel staged once for all nine taps (conv_halo.hip)
   if (same3x3 && cv.halo != 1 && !(stat_sum && addend) && isic_conv_halo_supported(N, Hin, Win, Cin, Cout) &&
       (cv.halo == 2 || Cin >= 128)) {
-    const int rc = isic_conv_halo_launch(in, w, out, N, Hin, Win, Cin, Cout, addend, addend_mask, stat_sum, stat_sumsq,
-                                         stat_slots, nullptr, nullptr, cv.exp, as_stream(stream));
-    return rc != ISIC_OK ? rc : isic_launch_status();
+    return isic_conv_halo_launch(in, w, out, N, Hin, Win, Cin, Cout, addend, addend_mask, stat_sum, stat_sumsq, stat_slots,
+                                 nullptr, nullptr, cv.exp, as_stream(stream));
   }
   if (addend_mask) return ISIC_ERR_UNSUPPORTED;            // only the two pixels-staged-once kernels take a masked addend
   ConvArgs a;
@@ -423,12 +415,10 @@ int conv2d_dispatch(const uint16_t* in, const uint16_t* w, uint16_t* out, int N,
   if (Cout % 64 == 0 && !(stat_sum && addend) && cv.pgemm != 1 &&
       (cv.pgemm == 2 || in2 != nullptr ||
        (Cout % 128 == 0 && (up != 1 || (down != 1 && Kh * Kw > 1) || (Kh == 1 && Kw == 1 && down == 1))))) {
-    const int rc = isic_conv_pgemm_launch(all, s);
-    return rc != ISIC_OK ? rc : isic_launch_status();
+    return isic_conv_pgemm_launch(all, s);
   }
-  const int rc = Cout % 128 != 0 ? launch_conv<256, 64, 4, 1, 2>(all, s)      // 4 MFMA + 4 staging waves, two stages
-                                  : launch_conv<256, 128, 4, 2, 3>(all, s);    // 8 MFMA + 8 staging waves, three stages
-  return rc != ISIC_OK ? rc : isic_launch_status();
+  return Cout % 128 != 0 ? launch_conv<256, 64, 4, 1, 2>(all, s)      // 4 MFMA + 4 staging waves, two stages
+                          : launch_conv<256, 128, 4, 2, 3>(all, s);    // 8 MFMA + 8 staging waves, three stages
 }
 
 }  // namespace
@@ -510,9 +500,8 @@ int isic_conv2d_dgrad_bnbwd_bf16(const uint16_t* in, const uint16_t* w, uint16_t
                                  double* sum_dzy, int stat_slots, void* stream) {
   ISIC_CHECK_ARG(in && w && out && relu_mask && y_raw && sum_dz && sum_dzy && stat_slots > 0);
   if (!isic_conv2d_dgrad_bnbwd_supported(N, Hin, Win, Cin, Hout, Wout, Cout, Kh, Kw, up, down, pad)) return ISIC_ERR_UNSUPPORTED;
-  const int rc = isic_conv_halo_launch(in, w, out, N, Hin, Win, Cin, Cout, addend, nullptr, sum_dz, sum_dzy, stat_slots,
-                                       relu_mask, y_raw, 0, as_stream(stream));
-  return rc != ISIC_OK ? rc : isic_launch_status();
+  return isic_conv_halo_launch(in, w, out, N, Hin, Win, Cin, Cout, addend, nullptr, sum_dz, sum_dzy, stat_slots, relu_mask,
+                               y_raw, 0, as_stream(stream));
 }
 
 }  // extern "C"

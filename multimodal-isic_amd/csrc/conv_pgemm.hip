@@ -293,14 +293,7 @@ __global__ __launch_bounds__(1024) void conv_pgemm_kernel(PGemmArgs pa) {
 
 template <int PN, bool STATS, bool ADDEND>
 int launch_pgemm(const PGemmArgs& pa, dim3 grid, hipStream_t stream) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pgemm_kernel<PN, STATS, ADDEND>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, p_lds(PN));
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((conv_pgemm_kernel<PN, STATS, ADDEND>), grid, dim3(1024), p_lds(PN), stream, pa);
-  return ISIC_OK;
+  return isic_launch_lds<conv_pgemm_kernel<PN, STATS, ADDEND>, p_lds(PN)>(grid, dim3(1024), p_lds(PN), stream, pa);
 }
 
 }  // namespace

@@ -254,6 +254,7 @@ WgradPlan wgrad_plan(int N, int Cin, int Hout, int Wout, int Cout, int Kh, int K
 
 }  // namespace
 
+// The *_launch functions below return the status of everything they launched (kernel and reduce): the caller returns it.
 // all-taps-per-block kernel of the 64 -> 64 3x3 layers (conv_wgrad_c64.hip)
 size_t isic_wgrad_c64_workspace_bytes(int N, int H, int W);
 int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, void* workspace,
@@ -333,9 +334,8 @@ int isic_conv2d_wgrad_bnbwd_bf16(const uint16_t* x, const uint16_t* dz, const ui
   if (!relu_mask && !scale) return ISIC_ERR_UNSUPPORTED;   // no ReLU / mask from the output: the two-launch form
   if (!isic_conv2d_wgrad_bnbwd_supported(N, H, W, 64, 64, 3, 3, 1, 1, relu_mask != nullptr)) return ISIC_ERR_UNSUPPORTED;
   if (workspace_bytes < isic_wgrad_c64_workspace_bytes(N, H, W)) return ISIC_ERR_WORKSPACE;
-  const int rc = isic_wgrad_c64_bnbwd_launch(x, dz, c, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, scale, shift, dc, dw,
-                                             dgamma_f32, dbeta_f32, N, H, W, workspace, as_stream(stream));
-  return rc != ISIC_OK ? rc : isic_launch_status();
+  return isic_wgrad_c64_bnbwd_launch(x, dz, c, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, scale, shift, dc, dw,
+                                     dgamma_f32, dbeta_f32, N, H, W, workspace, as_stream(stream));
 }
 
 int isic_test_conv2d_wgrad_variant_bf16(const uint16_t* x, const uint16_t* dy, float* dw, int N, int Hin, int Win, int Cin,
@@ -366,8 +366,7 @@ int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int 
     const size_t need = isic_wgrad_c64_workspace_bytes(N, Hin, Win);
     if (need != 0) {
       if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
-      const int rc = isic_wgrad_c64_launch(x, dy, dw, N, Hin, Win, workspace, as_stream(stream));
-      return rc != ISIC_OK ? rc : isic_launch_status();
+      return isic_wgrad_c64_launch(x, dy, dw, N, Hin, Win, workspace, as_stream(stream));
     }
   }
   if (Cin % 128 == 0 && Cout % 64 == 0 && Kh == 3 && Kw == 3 && stride == 1 && pad == 1 && Hin == Hout && Win == Wout &&
@@ -375,8 +374,7 @@ int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int 
     const size_t need = isic_wgrad_c128b_workspace_bytes(N, Hin, Win, Cin, Cout);
     if (need != 0) {
       if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
-      const int rc = isic_wgrad_c128b_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, as_stream(stream));
-      return rc != ISIC_OK ? rc : isic_launch_status();
+      return isic_wgrad_c128b_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, as_stream(stream));
     }
   }
   // the input staged once per tile instead of once per tap: 1.42 -> 0.71 ms for 64 -> 128 @ 56x56 and 0.76 -> 0.70 ms for
@@ -387,8 +385,7 @@ int conv2d_wgrad_dispatch(const uint16_t* x, const uint16_t* dy, float* dw, int 
     const size_t need = isic_wgrad_s2_workspace_bytes(N, Hin, Win, Cin, Cout);
     if (need != 0) {
       if (workspace_bytes < need) return ISIC_ERR_WORKSPACE;
-      const int rc = isic_wgrad_s2_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, as_stream(stream));
-      return rc != ISIC_OK ? rc : isic_launch_status();
+      return isic_wgrad_s2_launch(x, dy, dw, N, Hin, Win, Cin, Cout, workspace, as_stream(stream));
     }
   }
   const WgradPlan p = wgrad_plan(N, Cin, Hout, Wout, Cout, Kh, Kw);

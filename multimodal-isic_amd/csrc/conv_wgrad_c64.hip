@@ -410,15 +410,10 @@ int isic_wgrad_c64_launch(const uint16_t* x, const uint16_t* dy, float* dw, int 
   a.tiles_y = ceil_div(H, WT_H); a.tiles_x = ceil_div(W, WT_W);
   a.total_tiles = N * a.tiles_y * a.tiles_x;
   const int grid = wc64_blocks(N, H, W, &a.tiles_per_block);
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_c64_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_TOTAL);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(wgrad_c64_kernel<0>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  const int rc = isic_launch_lds<wgrad_c64_kernel<0>, LDS_TOTAL>(dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  if (rc != ISIC_OK) return rc;
   isic_slab_reduce_launch(ISIC_SLAB_LDS16_V2, a.partial, grid, DW_ELEMS, dw, 1.f, stream);   // dw += (slab_sum.inc, order B)
-  return ISIC_OK;
+  return isic_launch_status();
 }
 
 // called by isic_conv2d_wgrad_bnbwd_bf16: the same launch with dY = BatchNorm backward of (g, c) formed on the way
@@ -436,16 +431,9 @@ int isic_wgrad_c64_bnbwd_launch(const uint16_t* x, const uint16_t* g, const uint
   a.c = c; a.mask = relu_mask; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.scale = scale; a.shift = shift;
   a.dgamma = dgamma; a.dbeta = dbeta; a.dc = dc; a.dgamma_f32 = dgamma_f32; a.dbeta_f32 = dbeta_f32;
   const int grid = wc64_blocks(N, H, W, &a.tiles_per_block);
-  static IsicPerDeviceOnce once[2];
-  const int m = relu_mask ? 1 : 0;
-  if (isic_once_per_device(once[m], [m] {
-        return hipFuncSetAttribute(m ? reinterpret_cast<const void*>(wgrad_c64_kernel<3>)
-                                     : reinterpret_cast<const void*>(wgrad_c64_kernel<2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  if (m) hipLaunchKernelGGL(wgrad_c64_kernel<3>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
-  else hipLaunchKernelGGL(wgrad_c64_kernel<2>, dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  const int rc = relu_mask ? isic_launch_lds<wgrad_c64_kernel<3>, LDS_TOTAL>(dim3(grid), dim3(768), LDS_TOTAL, stream, a)
+                           : isic_launch_lds<wgrad_c64_kernel<2>, LDS_TOTAL>(dim3(grid), dim3(768), LDS_TOTAL, stream, a);
+  if (rc != ISIC_OK) return rc;
   isic_slab_reduce_launch(ISIC_SLAB_LDS16_V2, a.partial, grid, DW_ELEMS, dw, 1.f, stream);   // dw += (slab_sum.inc, order B)
-  return ISIC_OK;
+  return isic_launch_status();
 }

@@ -221,16 +221,11 @@ int isic_wgrad_s2_launch(const uint16_t* x, const uint16_t* dy, float* dw, int N
   a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.total_tiles = p.total_tiles;
   a.tiles_per_block = p.tiles_per_block; a.blocks_per_pair = p.blocks_per_pair;
   a.Cx = Cin; a.Cy = Cout; a.co_slices = Cout / 128; a.pack = p.pack; a.slot_shift = p.slot_shift; a.Wv = p.Wv;
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [&] {
-        const hipError_t e = hipFuncSetAttribute((const void*)wgrad_s2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
-        return e != hipSuccess ? e
-                               : hipFuncSetAttribute((const void*)wgrad_s2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALL);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  if (p.pack > 1) hipLaunchKernelGGL(wgrad_s2_kernel<true>, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
-  else hipLaunchKernelGGL(wgrad_s2_kernel<false>, dim3(p.pairs * p.blocks_per_pair), dim3(512), LDS_ALL, stream, a);
+  const dim3 grid(p.pairs * p.blocks_per_pair);
+  const int rc = p.pack > 1 ? isic_launch_lds<wgrad_s2_kernel<true>, LDS_ALL>(grid, dim3(512), LDS_ALL, stream, a)
+                            : isic_launch_lds<wgrad_s2_kernel<false>, LDS_ALL>(grid, dim3(512), LDS_ALL, stream, a);
+  if (rc != ISIC_OK) return rc;
   hipLaunchKernelGGL((wgrad_pair_reduce_kernel<128, 64>), dim3(p.pairs * (SLICE_ELEMS / 64)), dim3(256), 0, stream, a.partial, dw,
                      p.blocks_per_pair, a.co_slices, Cin);
-  return ISIC_OK;
+  return isic_launch_status();
 }

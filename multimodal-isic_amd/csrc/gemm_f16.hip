@@ -307,14 +307,7 @@ __global__ __launch_bounds__(1024) void gemm_f16_kernel(GemmF16Args a) {
 
 template <int GELU, bool RES, bool LNF = false, bool SOUT = false>
 int launch_g16(const GemmF16Args& a, dim3 grid, hipStream_t stream) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<GELU, RES, LNF, SOUT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((gemm_f16_kernel<GELU, RES, LNF, SOUT>), grid, dim3(1024), G_LDS, stream, a);
-  return isic_launch_status();
+  return isic_launch_lds<gemm_f16_kernel<GELU, RES, LNF, SOUT>, G_LDS>(grid, dim3(1024), G_LDS, stream, a);
 }
 
 // grid + the fields of `a` that depend on it

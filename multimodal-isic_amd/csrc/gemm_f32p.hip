@@ -313,14 +313,7 @@ __global__ __launch_bounds__(256) void gemm_f32p_reduce_kernel(G32Args a) {
 
 template <bool AK, bool BK>
 int launch_g32(const G32Args& a, dim3 grid, hipStream_t stream) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32p_kernel<AK, BK>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL((gemm_f32p_kernel<AK, BK>), grid, dim3(1024), P_LDS, stream, a);
-  return ISIC_OK;
+  return isic_launch_lds<gemm_f32p_kernel<AK, BK>, P_LDS>(grid, dim3(1024), P_LDS, stream, a);
 }
 
 struct G32Plan {
@@ -436,10 +429,8 @@ int isic_gemm_f32p_rows_launch(int transA, int transB, int M, int N, int K, cons
   else if (AK && !BK) rc = launch_g32<true, false>(a, grid, stream);
   else if (!AK && BK) rc = launch_g32<false, true>(a, grid, stream);
   else rc = launch_g32<false, false>(a, grid, stream);
-  if (rc != ISIC_OK) return rc;
-  if (p.splits > 1) {
-    const int64_t items = (int64_t)a.M * (a.N >> 2);
-    hipLaunchKernelGGL(gemm_f32p_reduce_kernel, dim3((unsigned)ceil_div64(items, 32)), dim3(256), 0, stream, a);
-  }
+  if (rc != ISIC_OK || p.splits <= 1) return rc;
+  const int64_t items = (int64_t)a.M * (a.N >> 2);
+  hipLaunchKernelGGL(gemm_f32p_reduce_kernel, dim3((unsigned)ceil_div64(items, 32)), dim3(256), 0, stream, a);
   return isic_launch_status();
 }

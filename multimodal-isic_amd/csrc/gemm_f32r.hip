@@ -204,19 +204,11 @@ bool rp_ok(int transA, int M, int N, int K, int lda, int ldb, int ldc, const voi
 
 template <int KC, bool ADD>
 int rp_launch(const RpArgs& a, hipStream_t stream) {
-  const int lds = RP_SLICE * (KC * 16 + 4) * (int)sizeof(float);
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (lds > 48 * 1024 &&
-      isic_once_per_device(once, [lds] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rowpanel_kernel<KC, ADD>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
+  constexpr int lds = RP_SLICE * (KC * 16 + 4) * (int)sizeof(float);
   const int cus = isic_cu_count();
   int grid = ceil_div(a.panels * (a.N >= RP_SLICE ? 2 : 1), RP_WAVES);
   if (grid > cus) grid = cus;
-  hipLaunchKernelGGL((gemm_rowpanel_kernel<KC, ADD>), dim3(grid), dim3(RP_WAVES * 64), lds, stream, a);
-  return isic_launch_status();
+  return isic_launch_lds<gemm_rowpanel_kernel<KC, ADD>, lds>(dim3(grid), dim3(RP_WAVES * 64), lds, stream, a);
 }
 
 }  // namespace

@@ -144,8 +144,7 @@ __global__ __launch_bounds__(BLOCK) void gpr_prop_kernel(GprArgs a) {
 
 template <int RPT>
 int launch_rpt(const GprArgs& a, int64_t blocks, hipStream_t st) {
-  static IsicPerDeviceOnce once;                 // one per instantiation; hipFuncSetAttribute is per device
-  return gr_launch(gpr_prop_kernel<RPT>, once, blocks, (size_t)2 * a.max_nodes * W * sizeof(float), st, a);
+  return gr_launch<gpr_prop_kernel<RPT>>(blocks, (size_t)2 * a.max_nodes * W * sizeof(float), st, a);
 }
 
 int launch(const GprArgs& a, int64_t blocks, hipStream_t st) {

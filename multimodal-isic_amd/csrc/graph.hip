@@ -484,22 +484,18 @@ int isic_knn_graph(const float* x, const int64_t* offsets, int G, int D, int k, 
   ISIC_CHECK_ARG(x && offsets && nn_idx && workspace_sqnorm);
   // graphs of <= 208 nodes: the whole Gram matrix per workgroup, top-k out of the accumulators (knn_gram.hip)
   if (isic_knn_gram_supported(D, k, max_nodes)) {
-    const int rc = isic_knn_gram_launch(x, offsets, G, D, k, nn_idx, nn_dist, as_stream(stream));
-    return rc != ISIC_OK ? rc : isic_launch_status();
+    return isic_knn_gram_launch(x, offsets, G, D, k, nn_idx, nn_dist, as_stream(stream));
   }
+  constexpr int KNN_MAX_LDS = 150 * 1024;              // ~2400 nodes per graph
   const int npad = ((max_nodes + 63) / 64) * 64;
   const size_t lds = (size_t)16 * npad * sizeof(float);
-  if (lds > 150 * 1024) return ISIC_ERR_UNSUPPORTED;   // > ~2400 nodes per graph
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
+  if (lds > KNN_MAX_LDS) return ISIC_ERR_UNSUPPORTED;  // before anything is launched
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((total_nodes + 3) / 4)), dim3(256), 0, as_stream(stream), x,
                      total_nodes, D, workspace_sqnorm);
   dim3 grid(ceil_div(max_nodes, 16), G);
   ISIC_CHECK_ARG(grid.y <= 65535u);
-  hipLaunchKernelGGL(knn_kernel, grid, dim3(256), lds, as_stream(stream), x, workspace_sqnorm, offsets, D, k, max_nodes,
-                     nn_idx, nn_dist);
-  return isic_launch_status();
+  return isic_launch_lds<knn_kernel, KNN_MAX_LDS>(grid, dim3(256), lds, as_stream(stream), x, workspace_sqnorm, offsets, D, k,
+                                                  max_nodes, nn_idx, nn_dist);
 }
 
 size_t isic_gcn_csr_workspace_bytes(int64_t n_nodes, int64_t E) {

@@ -245,12 +245,6 @@ int isic_graph_head_fwd_bwd(const float* z, const float* W1, const float* b1, co
   const size_t lds = head_lds_bytes(H, D, C);
   if (workspace_bytes < isic_graph_head_workspace_bytes(B, H, D, C) || (reinterpret_cast<uintptr_t>(workspace) & 15))
     return ISIC_ERR_WORKSPACE;
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(graph_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024 - 256);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   HeadArgs a;
   a.z = z; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.labels = labels;
   a.probs = probs; a.loss_ps = loss_per_sample; a.loss_mean = loss_mean; a.dz = dz;
@@ -260,8 +254,7 @@ int isic_graph_head_fwd_bwd(const float* z, const float* W1, const float* b1, co
   a.B = B; a.H = H; a.D = D; a.C = C;
   a.thr = drop_threshold; a.scale = drop_scale; a.seed = seed; a.stream_id = stream_id;
   a.clock = reinterpret_cast<const unsigned long long*>(clock);
-  hipLaunchKernelGGL(graph_head_kernel, dim3(nb), dim3(HT), lds, as_stream(stream), a);
-  return isic_launch_status();
+  return isic_launch_lds<graph_head_kernel, 160 * 1024 - 256>(dim3(nb), dim3(HT), lds, as_stream(stream), a);
 }
 
 int isic_graph_head_param_grads(const void* workspace, int B, int H, int D, int C, const float* grad_scale, float* dW1,

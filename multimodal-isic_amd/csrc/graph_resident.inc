@@ -75,15 +75,8 @@ static inline bool gr_csr_args_ok(const GrCsr& s, bool need_val) {
          gr_aligned_to(s.val, 4);
 }
 
-// Opts the kernel into 64 KB of dynamic LDS once per device (`once`: one per kernel instantiation), then launches it.
-template <class Args>
-static inline int gr_launch(void (*kernel)(Args), IsicPerDeviceOnce& once, int64_t blocks, size_t lds_bytes, hipStream_t st,
-                            const Args& a) {
-  if (isic_once_per_device(once, [&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   GR_MAX_LDS_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(GR_BLOCK), lds_bytes, st, a);
-  return isic_launch_status();
+// One block of GR_BLOCK threads per graph, at most 64 KB of dynamic LDS.
+template <auto Kernel, class Args>
+static inline int gr_launch(int64_t blocks, size_t lds_bytes, hipStream_t st, const Args& a) {
+  return isic_launch_lds<Kernel, GR_MAX_LDS_BYTES>(dim3((unsigned)blocks), dim3(GR_BLOCK), lds_bytes, st, a);
 }

@@ -87,8 +87,7 @@ __global__ __launch_bounds__(BLOCK) void h2_prop_kernel(H2Args a) {
 
 template <bool BWD>
 int launch(const H2Args& a, int64_t blocks, hipStream_t st) {
-  static IsicPerDeviceOnce once;                 // one per instantiation; hipFuncSetAttribute is per device
-  return gr_launch(h2_prop_kernel<BWD>, once, blocks, (size_t)(BWD ? 2 : 1) * a.max_nodes * W * sizeof(float), st, a);
+  return gr_launch<h2_prop_kernel<BWD>>(blocks, (size_t)(BWD ? 2 : 1) * a.max_nodes * W * sizeof(float), st, a);
 }
 
 // the argument checks and the launch the two entries share (ldh, ldz as the header names them)

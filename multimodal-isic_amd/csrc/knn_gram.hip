@@ -215,20 +215,10 @@ int isic_knn_gram_launch(const float* x, const int64_t* offsets, int G, int D, i
                          hipStream_t stream) {
   KnnGramArgs a;
   a.x = x; a.offsets = offsets; a.nn_idx = nn_idx; a.nn_dist = nn_dist; a.G = G; a.D = D; a.k = k;
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_gram_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, KG_LDS);
-        if (e != hipSuccess) return e;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(knn_gram_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, KG_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   const int cus = isic_cu_count();
   // a whole number of graphs per block where possible (2048 graphs on 256 CUs: 8 each)
   const int per = ceil_div(G, cus);
   const int grid = ceil_div(G, per);
-  if (nn_dist) hipLaunchKernelGGL(knn_gram_kernel<true>, dim3(grid), dim3(KG_THREADS), KG_LDS, stream, a);
-  else hipLaunchKernelGGL(knn_gram_kernel<false>, dim3(grid), dim3(KG_THREADS), KG_LDS, stream, a);
-  return ISIC_OK;
+  if (!nn_dist) return isic_launch_lds<knn_gram_kernel<false>, KG_LDS>(dim3(grid), dim3(KG_THREADS), KG_LDS, stream, a);
+  return isic_launch_lds<knn_gram_kernel<true>, KG_LDS>(dim3(grid), dim3(KG_THREADS), KG_LDS, stream, a);
 }

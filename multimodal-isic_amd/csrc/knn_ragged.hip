@@ -215,21 +215,10 @@ template <int NW, int KC>
 int kr_launch(KnnRaggedArgs a, int above, hipStream_t stream) {
   a.above = above;
   constexpr int LDS = KR_STAGES * KC * NW * 16 * 128 + NW * 16 * 4;
-  static_assert(LDS <= 160 * 1024, "a workgroup's LDS");
-  static IsicPerDeviceOnce once;                           // one per instantiation
-  if (isic_once_per_device(once, [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_ragged_kernel<NW, KC, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(knn_ragged_kernel<NW, KC, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   // one workgroup per graph, handed out by the hardware as workgroups retire (graphs differ in work by up to (16 NW / 16)^2
   // and a launch skips the graphs of the other classes, so a fixed share per workgroup leaves a long tail)
-  if (a.nn_dist) hipLaunchKernelGGL((knn_ragged_kernel<NW, KC, true>), dim3(a.G), dim3(NW * 64), LDS, stream, a);
-  else hipLaunchKernelGGL((knn_ragged_kernel<NW, KC, false>), dim3(a.G), dim3(NW * 64), LDS, stream, a);
-  return isic_launch_status();
+  if (!a.nn_dist) return isic_launch_lds<knn_ragged_kernel<NW, KC, false>, LDS>(dim3(a.G), dim3(NW * 64), LDS, stream, a);
+  return isic_launch_lds<knn_ragged_kernel<NW, KC, true>, LDS>(dim3(a.G), dim3(NW * 64), LDS, stream, a);
 }
 
 // ---------------------------------------------------------------------------------------------------- edge lists

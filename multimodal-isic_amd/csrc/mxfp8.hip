@@ -249,15 +249,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(MxGemmArgs a) {
 
 template <int GELU, bool RES, bool MXOUT>
 int launch_mx(const MxGemmArgs& a, hipStream_t stream) {
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_mxfp8_kernel<GELU, RES, MXOUT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, MG_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   const int grid = (a.ntiles_total + 7) / 8 * 8;
-  hipLaunchKernelGGL((gemm_mxfp8_kernel<GELU, RES, MXOUT>), dim3(grid), dim3(256), MG_LDS, stream, a);
-  return isic_launch_status();
+  return isic_launch_lds<gemm_mxfp8_kernel<GELU, RES, MXOUT>, MG_LDS>(dim3(grid), dim3(256), MG_LDS, stream, a);
 }
 
 template <int GELU, bool RES>

@@ -113,14 +113,7 @@ int isic_random_graph_i64(const int64_t* seeds, int G, int n_nodes, const int* r
   a.regens = graph_regens(n, a.swaps);
   a.z_bytes = (unsigned)round4((size_t)n * a.swaps);
   const size_t lds = graph_lds_bytes(n, a.swaps);
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(rand_graph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)MAX_DYN_LDS);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(rand_graph_kernel, dim3((unsigned)G), dim3(BLOCK), lds, st, a);
-  return isic_launch_status();
+  return isic_launch_lds<rand_graph_kernel, (int)MAX_DYN_LDS>(dim3((unsigned)G), dim3(BLOCK), lds, st, a);
 }
 
 }  // extern "C"

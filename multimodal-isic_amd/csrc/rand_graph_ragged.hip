@@ -129,18 +129,12 @@ int launch(RaggedArgs a, hipStream_t st) {
   if (isic_launch_status() != ISIC_OK) return ISIC_ERR_LAUNCH;
   if (a.max_nodes <= PACK_N) return ISIC_OK;
   // larger graphs: a workgroup each
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(rand_graph_ragged_kernel<BLOCK, WRITE>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)graph_lds_bytes(MAX_N, MAX_N - 2));
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   a.n_above = PACK_N;
   a.n_upto = a.max_nodes;
   a.first = 0;
   a.group_words = class_words(a.max_nodes);
-  hipLaunchKernelGGL((rand_graph_ragged_kernel<BLOCK, WRITE>), dim3((unsigned)a.G), dim3(BLOCK), (size_t)a.group_words * 4, st, a);
-  return isic_launch_status();
+  return isic_launch_lds<rand_graph_ragged_kernel<BLOCK, WRITE>, (int)graph_lds_bytes(MAX_N, MAX_N - 2)>(
+      dim3((unsigned)a.G), dim3(BLOCK), (size_t)a.group_words * 4, st, a);
 }
 
 // the r list in ascending order, each value at least 1 and at most MAX_N (a larger one clamps to n - 1 anyway)

@@ -57,6 +57,7 @@ __device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }   // first
 __host__ __device__ constexpr size_t lambda2_lds_bytes(int n) {
   return ((size_t)n * (n + 1) / 2 + 2 * (size_t)n + 8) * sizeof(double);
 }
+constexpr int SP_MAX_LDS = (int)lambda2_lds_bytes(ISIC_SPECTRAL_MAX_NODES);
 
 // lambda_2 of the graph with n nodes whose edges are src/dst[e0:e1) with node ids id_base .. id_base + n - 1, by the whole
 // workgroup, into *out; `sm` is the dynamic LDS (lambda2_lds_bytes(n) at least).  e0 <= e1 are valid positions (the callers
@@ -341,16 +342,8 @@ int isic_laplacian_lambda2_f64(const int64_t* src, const int64_t* dst, const int
   ISIC_CHECK_ARG(G >= 0);
   if (G == 0) return ISIC_OK;
   ISIC_CHECK_ARG(edge_offsets && lambda2);
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(laplacian_lambda2_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lambda2_lds_bytes(ISIC_SPECTRAL_MAX_NODES));
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(laplacian_lambda2_kernel, dim3((unsigned)G), dim3(SP_THREADS), lambda2_lds_bytes(nodes),
-                     as_stream(stream), src, dst, edge_offsets, nodes, lambda2);
-  return isic_launch_status();
+  return isic_launch_lds<laplacian_lambda2_kernel, SP_MAX_LDS>(dim3((unsigned)G), dim3(SP_THREADS), lambda2_lds_bytes(nodes),
+                                                               as_stream(stream), src, dst, edge_offsets, nodes, lambda2);
 }
 
 int isic_laplacian_lambda2_ragged_f64(const int64_t* src, const int64_t* dst, const int64_t* edge_offsets,
@@ -361,16 +354,9 @@ int isic_laplacian_lambda2_ragged_f64(const int64_t* src, const int64_t* dst, co
   ISIC_CHECK_ARG(edge_offsets && node_offsets && lambda2);
   ISIC_CHECK_ARG(E == 0 || (src && dst));
   if (max_nodes > ISIC_SPECTRAL_MAX_NODES || E >= 0x80000000LL) return ISIC_ERR_UNSUPPORTED;
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(laplacian_lambda2_ragged_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lambda2_lds_bytes(ISIC_SPECTRAL_MAX_NODES));
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(laplacian_lambda2_ragged_kernel, dim3((unsigned)G), dim3(SP_THREADS), lambda2_lds_bytes(max_nodes),
-                     as_stream(stream), src, dst, edge_offsets, node_offsets, E, max_nodes, lambda2);
-  return isic_launch_status();
+  return isic_launch_lds<laplacian_lambda2_ragged_kernel, SP_MAX_LDS>(dim3((unsigned)G), dim3(SP_THREADS),
+                                                                      lambda2_lds_bytes(max_nodes), as_stream(stream), src, dst,
+                                                                      edge_offsets, node_offsets, E, max_nodes, lambda2);
 }
 
 int isic_segment_stats_f32(const float* values, const int64_t* edge_offsets, int64_t num_edges, int M, int G,

@@ -47,15 +47,8 @@ int slab_width(int T) { return T <= 256 ? 64 : (T <= 512 ? 32 : 16); }
 
 template <int W>
 int launch_moments(const MomentsArgs& a, int64_t blocks, hipStream_t st) {
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(token_moments_kernel<W>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, MAX_TILE_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   const size_t lds = (size_t)a.T * W * sizeof(float);
-  hipLaunchKernelGGL(token_moments_kernel<W>, dim3((unsigned)blocks), dim3(BLOCK), lds, st, a);
-  return isic_launch_status();
+  return isic_launch_lds<token_moments_kernel<W>, MAX_TILE_BYTES>(dim3((unsigned)blocks), dim3(BLOCK), lds, st, a);
 }
 
 }  // namespace

@@ -121,16 +121,10 @@ __global__ __launch_bounds__(BLOCK) void token_moments_ragged_kernel(SubsetArgs 
   moments_of_tile<W>(tile, n, a.D, d0, a.eps, a.unbiased, orow);
 }
 
-template <class Kernel>
-int launch_subset(Kernel kernel, IsicPerDeviceOnce& once, const SubsetArgs& a, int64_t blocks, int rows, hipStream_t st) {
-  if (isic_once_per_device(once, [&] {      // hipFuncSetAttribute is per device
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   MAX_TILE_BYTES);
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
+template <auto Kernel>
+int launch_subset(const SubsetArgs& a, int64_t blocks, int rows, hipStream_t st) {
   const size_t lds = (size_t)rows * W * sizeof(float);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(BLOCK), lds, st, a);
-  return isic_launch_status();
+  return isic_launch_lds<Kernel, MAX_TILE_BYTES>(dim3((unsigned)blocks), dim3(BLOCK), lds, st, a);
 }
 
 bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
@@ -154,8 +148,7 @@ int isic_token_moments_masked_f32(const float* X, const uint8_t* keep, int64_t B
   a.X = X; a.keep = keep; a.out = out; a.counts = counts; a.ldx = ldx; a.ldo = ldo; a.T = T; a.D = D; a.slabs = slabs;
   a.vec = (ldx % 4 == 0 && aligned_to(X, 16)) ? 1 : 0;
   a.eps = eps; a.unbiased = unbiased;
-  static IsicPerDeviceOnce once;
-  return launch_subset(token_moments_masked_kernel, once, a, B * slabs, T, as_stream(stream));
+  return launch_subset<token_moments_masked_kernel>(a, B * slabs, T, as_stream(stream));
 }
 
 int isic_token_moments_ragged_f32(const float* X, const int64_t* node_offsets, int64_t G, int max_nodes, int64_t total,
@@ -175,8 +168,7 @@ int isic_token_moments_ragged_f32(const float* X, const int64_t* node_offsets, i
   a.D = D; a.slabs = slabs; a.max_nodes = max_nodes;
   a.vec = (ldx % 4 == 0 && aligned_to(X, 16)) ? 1 : 0;
   a.eps = eps; a.unbiased = unbiased;
-  static IsicPerDeviceOnce once;
-  return launch_subset(token_moments_ragged_kernel, once, a, G * slabs, max_nodes, as_stream(stream));
+  return launch_subset<token_moments_ragged_kernel>(a, G * slabs, max_nodes, as_stream(stream));
 }
 
 }  // extern "C"

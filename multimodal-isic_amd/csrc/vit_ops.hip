@@ -251,16 +251,9 @@ int isic_attention_f16(const uint16_t* qkv, uint16_t* out, int n_images, int tok
   if (head_dim != 64 || tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
   if (n_images == 0) return ISIC_OK;
   ISIC_CHECK_ARG(qkv && out);
-  static IsicPerDeviceOnce once;              // hipFuncSetAttribute is per device (one flag set per template instance)
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<64>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, at_lds<64>());
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   const float scale_log2e = 0.125f * 1.4426950408889634f;            // 1 / sqrt(64), base-2 exponent
-  hipLaunchKernelGGL(attention_f16_kernel<64>, dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<64>(), as_stream(stream), qkv,
-                     out, tokens, heads, scale_log2e);
-  return isic_launch_status();
+  return isic_launch_lds<attention_f16_kernel<64>, at_lds<64>()>(dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<64>(),
+                                                                 as_stream(stream), qkv, out, tokens, heads, scale_log2e);
 }
 
 // include/isic_hip_mae.h: the MAE decoder's heads, 32 wide
@@ -269,16 +262,9 @@ int isic_attention_d32_f16(const uint16_t* qkv, uint16_t* out, int n_images, int
   if (tokens > AT_TMAX) return ISIC_ERR_UNSUPPORTED;
   if (n_images == 0) return ISIC_OK;
   ISIC_CHECK_ARG(qkv && out);
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f16_kernel<32>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, at_lds<32>());
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
   const float scale_log2e = 0.17677669529663688f * 1.4426950408889634f;   // 1 / sqrt(32), base-2 exponent
-  hipLaunchKernelGGL(attention_f16_kernel<32>, dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<32>(), as_stream(stream), qkv,
-                     out, tokens, heads, scale_log2e);
-  return isic_launch_status();
+  return isic_launch_lds<attention_f16_kernel<32>, at_lds<32>()>(dim3(n_images * heads), dim3(AT_WAVES * 64), at_lds<32>(),
+                                                                 as_stream(stream), qkv, out, tokens, heads, scale_log2e);
 }
 
 }  // extern "C"

@@ -405,15 +405,8 @@ int isic_attention_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint1
   if (head_dim != 64 || tokens > AB_MAXT) return ISIC_ERR_UNSUPPORTED;
   if (n_images == 0) return ISIC_OK;
   ISIC_CHECK_ARG(qkv && out && dout && dqkv);
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_f16_kernel<64>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, ab_lds<64>());
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(attention_bwd_f16_kernel<64>, dim3(n_images * heads), dim3(AB_THREADS), ab_lds<64>(), as_stream(stream), qkv,
-                     out, dout, dqkv, tokens, heads);
-  return isic_launch_status();
+  return isic_launch_lds<attention_bwd_f16_kernel<64>, ab_lds<64>()>(dim3(n_images * heads), dim3(AB_THREADS), ab_lds<64>(),
+                                                                     as_stream(stream), qkv, out, dout, dqkv, tokens, heads);
 }
 
 // include/isic_hip_mae.h: the MAE decoder's heads, 32 wide
@@ -423,15 +416,8 @@ int isic_attention_d32_bwd_f16(const uint16_t* qkv, const uint16_t* out, const u
   if (tokens > AB_MAXT) return ISIC_ERR_UNSUPPORTED;
   if (n_images == 0) return ISIC_OK;
   ISIC_CHECK_ARG(qkv && out && dout && dqkv);
-  static IsicPerDeviceOnce once;
-  if (isic_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_f16_kernel<32>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, ab_lds<32>());
-      }) != hipSuccess)
-    return ISIC_ERR_LAUNCH;
-  hipLaunchKernelGGL(attention_bwd_f16_kernel<32>, dim3(n_images * heads), dim3(AB_THREADS), ab_lds<32>(), as_stream(stream), qkv,
-                     out, dout, dqkv, tokens, heads);
-  return isic_launch_status();
+  return isic_launch_lds<attention_bwd_f16_kernel<32>, ab_lds<32>()>(dim3(n_images * heads), dim3(AB_THREADS), ab_lds<32>(),
+                                                                     as_stream(stream), qkv, out, dout, dqkv, tokens, heads);
 }
 
 }  // extern "C"

@@ -376,16 +376,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_wide_vec_kernel(
   }
 }
 
-template <typename K>
-int wide_ensure_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return ISIC_ERR_UNSUPPORTED;
-  if (bytes > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bytes) != hipSuccess)
-      return ISIC_ERR_LAUNCH;
-  }
-  return ISIC_OK;
-}
+// the row kernels size their LDS by the call's shape: up to a workgroup's 160 KB runs, more is ISIC_ERR_UNSUPPORTED
+constexpr int WIDE_MAX_LDS = 160 * 1024;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -407,17 +399,11 @@ int isic_attn_pool_wide_fwd(const float* h, const float* t, const float* w3, con
   if (rc != ISIC_OK) return rc;
   const size_t lds1 = sizeof(float) * ((size_t)pad4(heads * A) + pad4(max_bag * heads) + 16);
   const bool vec = A % 4 == 0 && aligned16(t);
-  if (vec) {
-    rc = wide_ensure_lds(pool_wide_att_kernel<true>, lds1);
-    if (rc != ISIC_OK) return rc;
-    hipLaunchKernelGGL(pool_wide_att_kernel<true>, dim3(B), dim3(SC_NTHR), lds1, as_stream(stream), t, w3, b3, offsets, A,
-                       heads, max_bag, att);
-  } else {
-    rc = wide_ensure_lds(pool_wide_att_kernel<false>, lds1);
-    if (rc != ISIC_OK) return rc;
-    hipLaunchKernelGGL(pool_wide_att_kernel<false>, dim3(B), dim3(SC_NTHR), lds1, as_stream(stream), t, w3, b3, offsets, A,
-                       heads, max_bag, att);
-  }
+  rc = vec ? isic_launch_lds<pool_wide_att_kernel<true>, WIDE_MAX_LDS>(dim3(B), dim3(SC_NTHR), lds1, as_stream(stream), t, w3, b3,
+                                                                       offsets, A, heads, max_bag, att)
+           : isic_launch_lds<pool_wide_att_kernel<false>, WIDE_MAX_LDS>(dim3(B), dim3(SC_NTHR), lds1, as_stream(stream), t, w3, b3,
+                                                                        offsets, A, heads, max_bag, att);
+  if (rc != ISIC_OK) return rc;
   const size_t lds2 = sizeof(float) * ((size_t)pad4(max_bag) + ZS_GROUPS * ZS_COLS);
   hipLaunchKernelGGL(pool_wide_sum_kernel, dim3(ceil_div(H, ZS_COLS), B), dim3(ZS_COLS * ZS_GROUPS), lds2, as_stream(stream),
                      h, att, offsets, H, heads, max_bag, z);
@@ -434,16 +420,15 @@ int isic_attn_pool_wide_bwd(const float* h, const float* t, const float* att, co
   if (rc != ISIC_OK) return rc;
   const size_t lds = sizeof(float) * ((size_t)pad4(heads * A) + pad4(H) + pad4(max_bag) + 8);
   const bool vech = H % 4 == 0 && aligned16(h), veca = A % 4 == 0 && aligned16(t) && aligned16(d_u);
-#define LAUNCH_WIDE_BWD(VH, VA)                                                                                          \
-  rc = wide_ensure_lds(pool_wide_bwd_rows_kernel<VH, VA>, lds);                                                          \
-  if (rc != ISIC_OK) return rc;                                                                                          \
-  hipLaunchKernelGGL((pool_wide_bwd_rows_kernel<VH, VA>), dim3(B), dim3(BW_NTHR), lds, as_stream(stream), h, t, att, w3, \
-                     offsets, H, A, heads, max_bag, d_z, d_u, d_s)
+#define LAUNCH_WIDE_BWD(VH, VA)                                                                                            \
+  rc = isic_launch_lds<pool_wide_bwd_rows_kernel<VH, VA>, WIDE_MAX_LDS>(dim3(B), dim3(BW_NTHR), lds, as_stream(stream), h, \
+                                                                        t, att, w3, offsets, H, A, heads, max_bag, d_z, d_u, d_s)
   if (vech && veca) { LAUNCH_WIDE_BWD(true, true); }
   else if (vech) { LAUNCH_WIDE_BWD(true, false); }
   else if (veca) { LAUNCH_WIDE_BWD(false, true); }
   else { LAUNCH_WIDE_BWD(false, false); }
 #undef LAUNCH_WIDE_BWD
+  if (rc != ISIC_OK) return rc;
   hipLaunchKernelGGL(pool_wide_dh_kernel, dim3(ceil_div(H, DH_COLS), B, DH_SPLIT), dim3(DH_COLS), 0, as_stream(stream), att,
                      offsets, H, heads, d_z, d_h, accumulate_dh);
   return isic_launch_status();

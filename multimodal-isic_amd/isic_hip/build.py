@@ -8,6 +8,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from .abi_headers import included_headers
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 CSRC = os.path.join(PKG, "csrc")
@@ -29,6 +31,14 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def header_deps():
+    """What every object file depends on besides its own source: the headers of csrc/ and the C ABI."""
+    # *.inc: kernel templates / device helpers that translation units share (convmae_kernels.inc, ln_rows.inc, mx_quant.inc, ...)
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    abi = os.path.join(os.path.dirname(PKG), "include", "isic_hip.h")
+    return headers + [abi] + included_headers(abi)     # the opt-in headers: the #include lines of isic_hip.h
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -40,16 +50,7 @@ def build(force=False, verbose=True, jobs=None):
     """Compile every ``csrc/*.hip`` and link the shared library.  Returns its path."""
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    # *.inc: kernel templates / device helpers that translation units share (convmae_kernels.inc, ln_rows.inc, mx_quant.inc, ...)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    headers += [os.path.join(os.path.dirname(PKG), "include", h)
-                for h in ("isic_hip.h", "isic_hip_mxfp8.h", "isic_hip_vit_train.h", "isic_hip_convmae.h",
-                          "isic_hip_convmae_train.h", "isic_hip_mae.h", "isic_hip_augment.h", "isic_hip_wgrad_bnbwd.h",
-                          "isic_hip_bn_pair.h", "isic_hip_convmae_mxfp8.h", "isic_hip_attn_mean.h", "isic_hip_pca.h",
-                          "isic_hip_metrics.h", "isic_hip_randgraph.h", "isic_hip_moments.h", "isic_hip_wide.h",
-                          "isic_hip_gated.h", "isic_hip_ragged.h", "isic_hip_hetero_ragged.h",
-                          "isic_hip_knn_ragged.h", "isic_hip_randgraph_ragged.h", "isic_hip_moments_ragged.h",
-                          "isic_hip_gpr.h", "isic_hip_h2.h", "isic_hip_radiomics.h")]
+    headers = header_deps()
     todo, objs = [], []
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")

@@ -12,6 +12,8 @@ import re
 
 import torch
 
+from .abi_headers import included_headers
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libisic_hip.so")
@@ -48,22 +50,9 @@ def header_path():
 
 
 def extension_header_paths():
-    """Headers isic_hip.h includes for opt-in paths beyond the drop-in surface (include/isic_hip_mxfp8.h,
-    include/isic_hip_vit_train.h, include/isic_hip_convmae.h, include/isic_hip_convmae_train.h, include/isic_hip_mae.h, include/isic_hip_augment.h,
-    include/isic_hip_wgrad_bnbwd.h, include/isic_hip_bn_pair.h, include/isic_hip_convmae_mxfp8.h,
-    include/isic_hip_attn_mean.h, include/isic_hip_pca.h, include/isic_hip_metrics.h, include/isic_hip_randgraph.h,
-    include/isic_hip_moments.h, include/isic_hip_wide.h, include/isic_hip_gated.h, include/isic_hip_ragged.h,
-    include/isic_hip_hetero_ragged.h, include/isic_hip_knn_ragged.h, include/isic_hip_randgraph_ragged.h,
-    include/isic_hip_moments_ragged.h, include/isic_hip_gpr.h, include/isic_hip_h2.h, include/isic_hip_radiomics.h)."""
-    inc = os.path.dirname(header_path())
-    return [os.path.join(inc, h) for h in ("isic_hip_mxfp8.h", "isic_hip_vit_train.h", "isic_hip_convmae.h",
-                                                      "isic_hip_convmae_train.h", "isic_hip_mae.h", "isic_hip_augment.h", "isic_hip_wgrad_bnbwd.h",
-                                                      "isic_hip_bn_pair.h", "isic_hip_convmae_mxfp8.h", "isic_hip_attn_mean.h", "isic_hip_pca.h",
-                                                      "isic_hip_metrics.h", "isic_hip_randgraph.h", "isic_hip_moments.h", "isic_hip_wide.h",
-                                                      "isic_hip_gated.h", "isic_hip_ragged.h", "isic_hip_hetero_ragged.h",
-                                                      "isic_hip_knn_ragged.h", "isic_hip_randgraph_ragged.h",
-                                                      "isic_hip_moments_ragged.h", "isic_hip_gpr.h", "isic_hip_h2.h",
-                                                      "isic_hip_radiomics.h")]
+    """Headers isic_hip.h includes for opt-in paths beyond the drop-in surface: its ``#include "isic_hip_*.h"`` lines, in
+    order (abi_headers.py; build.py takes its dependencies from the same list)."""
+    return included_headers(header_path())
 
 
 def test_header_path():

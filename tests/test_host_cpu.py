@@ -400,3 +400,22 @@ def test_hand_counted_gemm_loads_are_never_touched_before_their_wait():
     ok = (";;#ASMSTART\nglobal_load_dwordx4 v[10:13], v[2:3], off\n;;#ASMEND\nglobal_store_dwordx4 v[4:5], v[30:33], off\n"
           ";;#ASMSTART\ns_waitcnt vmcnt(1)\n;;#ASMEND\nv_mov_b32_e32 v20, v11\n")
     assert _scan_requested_registers("ok", ok) == 1
+
+
+def test_dynamic_lds_launches_and_abi_header_list_are_written_once():
+    """DESIGN.md "Shared tile primitives": a kernel with dynamic LDS is launched through isic_launch_lds (csrc/common.h),
+    so no other file of csrc/ opts a kernel in on its own; and the opt-in ABI headers are listed once, as the #include
+    lines of include/isic_hip.h, which lib.py and build.py both read through isic_hip/abi_headers.py."""
+    csrc = os.path.join(ROOT, "multimodal-isic_amd", "csrc")
+    users = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))
+                   and "hipFuncSetAttribute" in open(os.path.join(csrc, f), errors="replace").read())
+    assert users == ["common.h"], users
+    from isic_hip import abi_headers, build, lib
+    assert "torch" not in open(abi_headers.__file__).read()
+    header = os.path.join(ROOT, "include", "isic_hip.h")
+    lines = [ln for ln in open(header).read().splitlines() if ln.startswith('#include "isic_hip_')]
+    paths = abi_headers.included_headers(header)
+    assert [os.path.basename(p) for p in paths] == [ln.split('"')[1] for ln in lines]
+    assert len(paths) == len(set(paths)) == 24 and all(os.path.isfile(p) for p in paths)
+    assert lib.extension_header_paths() == paths
+    assert set(paths) | {header} <= set(build.header_deps())

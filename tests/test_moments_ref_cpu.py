@@ -34,7 +34,7 @@ def test_entry_is_declared_in_the_new_header_only_and_exported():
     assert ENTRY in L.extension and ENTRY in L.fn
     assert f"#define ISIC_MOMENTS_MAX_T {R.MAX_T}\n" in open(os.path.join(inc, "isic_hip_moments.h")).read()
     from isic_hip import build
-    assert "isic_hip_moments.h" in open(build.__file__).read()
+    assert "isic_hip_moments.h" in map(os.path.basename, build.header_deps())
 
 
 def test_argument_checks_without_a_device():
