@@ -23,9 +23,10 @@ extern "C" {
  * clamp >= 0, diagonal = +inf, the k smallest of every row ascending, ties to the lower index; LOCAL ids to nn_idx int64
  * [total_nodes, k], -1 (and +inf in nn_dist float [total_nodes, k], optional) where a row has fewer than k candidates.
  * A graph of N nodes stages ceil(N/16)*16 rows and multiplies ceil(N/16)^2 tiles; every dot product takes the k-slices in
- * the MFMA order of isic_knn_graph's Gram kernel and the norms are the Gram diagonal, so both outputs equal isic_knn_graph's
- * bit for bit.  A graph is taken by the smallest workgroup that holds it (<= 64 nodes: 4 waves, <= 128: 8, <= 208: 13; one
- * launch per class up to max_nodes, which must be >= the largest graph).
+ * the MFMA order of isic_knn_graph's Gram kernel, and the norms (the Gram diagonal), the distance and the selection are the
+ * same code as that kernel's (csrc/knn_tile.inc), so both outputs equal isic_knn_graph's bit for bit.
+ * A graph is taken by the smallest workgroup that holds it (<= 64 nodes: 4 waves, <= 128: 8, <= 208: 13; one launch per
+ * class up to max_nodes, which must be >= the largest graph).
  * Graphs of 0 or 1 node are legal (a single node gets a row of -1).  A graph whose offsets decrease, leave
  * [0, total_nodes] or span more than max_nodes writes nothing and reads no row of x.
  * G == 0 or total_nodes == 0 returns 0 and touches nothing.  ISIC_ERR_BAD_ARG: G, total_nodes or max_nodes negative, D or k

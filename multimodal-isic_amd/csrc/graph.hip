@@ -10,8 +10,11 @@
 // their edge_index order inside a row), every neighbour row is read with one coalesced wave-wide
 // load, every output row written once.  The backward pass is the same kernel on the transposed CSR.
 #include "common.h"
+#include "knn_gram.h"
 
 namespace {
+
+#include "knn_tile.inc"                                       // knn_dist
 
 // ================================================================= k-NN
 // block = (graph, 16 query rows).  distances of the 16 queries to all N nodes of the graph via
@@ -69,10 +72,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ x, c
     for (int r = 0; r < 4; ++r) {
       const int q = r0 + fg * 4 + r;
       float dv = INFINITY;
-      if (q < N && col < N && q != col) {
-        dv = (sqn[lo + q] + sqn[lo + col]) - 2.0f * acc[r];   // 03_build_graphs.py:47
-        dv = fmaxf(dv, 0.f);                                  // :48 clamp(min=0)
-      }
+      if (q < N && col < N && q != col) dv = knn_dist(sqn[lo + q], sqn[lo + col], acc[r]);   // 03_build_graphs.py:47-48
       dist[(fg * 4 + r) * npad + col] = dv;
     }
   }
@@ -470,10 +470,6 @@ __global__ __launch_bounds__(256) void csr_batch_assemble_kernel(
 }
 
 }  // namespace
-
-bool isic_knn_gram_supported(int D, int k, int max_nodes);
-int isic_knn_gram_launch(const float* x, const int64_t* offsets, int G, int D, int k, int64_t* nn_idx, float* nn_dist,
-                         hipStream_t stream);
 
 extern "C" {
 

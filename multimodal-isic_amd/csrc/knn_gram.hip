@@ -20,17 +20,22 @@
 //   * |x_i|^2 is the DIAGONAL of G -- the same MFMA summation order as the dot products, so d[i][i] is exactly 0 before it
 //     is set to +inf and d is symmetric bit for bit; the row norms need no pass of their own.
 //   * summation order of x_i . x_j: identical to knn_kernel's (k-steps of 16, the four MFMAs of a step take k = 4 fg + j).
+//   * the swizzle, the diagonal -> norms, the distances and the selection are knn_tile.inc, the same code that
+//     knn_ragged_kernel (knn_ragged.hip) instantiates for 4 / 8 / 13 tiles: the two kernels are bit-equal by construction.
+//     What is this kernel's own: the persistent loop, the three-stage ring and its counted waits, the result stores.
 #include "common.h"
 #include "mfma_tile.h"
+#include "knn_gram.h"
 
 namespace {
 
-constexpr int KG_ROWS = 208;                 // 13 tiles of 16 nodes
-constexpr int KG_TILES = 13;
+#include "knn_tile.inc"
+
+constexpr int KG_TILES = KT_MAX_TILES;       // every graph gets the whole domain: 13 tiles of 16 nodes
 constexpr int KG_THREADS = KG_TILES * 64;
-constexpr int KG_STAGE = KG_ROWS * 128;      // one K-chunk of 32 floats for every row
+constexpr int KG_STAGE = KT_MAX_NODES * KT_CHUNK_ROW;      // one K-chunk of 32 floats for every row
 constexpr int KG_NST = 3;
-constexpr int KG_LDS = KG_NST * KG_STAGE + KG_ROWS * 4;
+constexpr int KG_LDS = KG_NST * KG_STAGE + KT_MAX_NODES * 4;
 
 struct KnnGramArgs {
   const float* x;
@@ -39,13 +44,6 @@ struct KnnGramArgs {
   float* nn_dist;
   int G, D, k;
 };
-
-template <int CTRL>
-__device__ __forceinline__ float kg_dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int kg_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
 
 template <bool WITH_DIST>
 __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
@@ -60,10 +58,9 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
   const int total = ngr * nchunks;
   if (total <= 0) return;
 
-  // ---- staging: piece t (= 0, 1) of this wave brings rows 16 wave + 8 t + r8; the lane fetches global 16-byte chunk
-  //      p ^ r8 of its row (row & 7 == r8), so that LDS position p of a row holds chunk p ^ (row & 7)
-  const int r8 = lane >> 3, p8 = lane & 7;
-  const unsigned src_chunk = (unsigned)((p8 ^ r8) << 4);
+  // ---- staging: piece h (= 0, 1) of this wave brings rows 16 wave + 8 h + r8, swizzled on the source side (knn_tile.inc)
+  const int r8 = lane >> 3;
+  const unsigned src_chunk = kt_src_chunk(lane);
   int ig = 0, ikc = 0;                                      // (graph ordinal, K-chunk) of the next chunk to ISSUE
   auto issue = [&](int t) {
     const int g = (int)blockIdx.x + ig * (int)gridDim.x;
@@ -84,8 +81,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
   issue(0);
   if (total > 1) issue(1);
 
-  // ---- fragment addresses inside a stage: row 16 c + fr, k-quarter kq (16 floats): chunk (4 kq + fg) ^ (fr & 7)
-  const unsigned foff0 = (unsigned)(fr * 128 + ((fg ^ (fr & 7)) << 4));              // kq = 0; kq = 1: ^ 64
+  const unsigned foff0 = kt_foff0(fr, fg);                  // fragment of tile 0, k-quarter 0; kq = 1: ^ 64
   f32x4 acc[KG_TILES];
 #pragma unroll
   for (int c = 0; c < KG_TILES; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -99,24 +95,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
     else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     __builtin_amdgcn_s_barrier();                           // ... every wave's pieces; and stage (t + 2) % 3 is no longer read
     if (t + 2 < total) issue(t + 2);
-    const unsigned char* st = smem + (t % KG_NST) * KG_STAGE;
-#pragma unroll
-    for (int kq = 0; kq < 2; ++kq) {
-      const unsigned char* q = st + (foff0 ^ (unsigned)(kq << 6));
-      const f32x4 av = *reinterpret_cast<const f32x4*>(q + wave * 2048);
-#pragma unroll
-      for (int c0 = 0; c0 < KG_TILES; c0 += 4) {            // four column tiles at a time: a tile's accumulator is touched
-        f32x4 bv[4];                                        // every fourth MFMA (a dependent MFMA issues ~6 slots late)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (c0 + i < KG_TILES) bv[i] = *reinterpret_cast<const f32x4*>(q + (c0 + i) * 2048);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (c0 + i < KG_TILES) acc[c0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[i][j], acc[c0 + i], 0, 0, 0);
-      }
-    }
+    kt_multiply<KG_TILES, false>(KG_TILES, smem + (t % KG_NST) * KG_STAGE, foff0, wave, acc);   // all 13 x 13 tiles
     if (++ckc < nchunks) continue;
 
     // ================================================================ the graph is complete: distances -> top-k
@@ -125,67 +104,13 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
     ++cg;
     const long long lo = a.offsets[g];
     const int N = (int)(a.offsets[g + 1] - lo);
-    // |x_i|^2 = G[i][i]: tile (wave, wave), row 4 fg + j == column fr
-    {
-      f32x4 dg = acc[0];
-#pragma unroll
-      for (int c = 1; c < KG_TILES; ++c) dg = wave == c ? acc[c] : dg;
-      const float dv = (fr & 3) == 0 ? dg[0] : (fr & 3) == 1 ? dg[1] : (fr & 3) == 2 ? dg[2] : dg[3];
-      if ((fr >> 2) == fg) sqn[wave * 16 + fr] = dv;
-    }
+    kt_store_sqn<KG_TILES>(acc, wave, fr, fg, sqn);
     lds_barrier();
     if (wave * 16 < N) {
-      float sr[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sr[j] = sqn[wave * 16 + fg * 4 + j];
-#pragma unroll
-      for (int c = 0; c < KG_TILES; ++c) {
-        const int col = c * 16 + fr;
-        const float sc = sqn[col];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int q = wave * 16 + fg * 4 + j;
-          float dv = (sr[j] + sc) - 2.0f * acc[c][j];        // 03_build_graphs.py:47
-          dv = fmaxf(dv, 0.f);                               // :48 clamp(min = 0)
-          acc[c][j] = (col < N && col != q) ? dv : INFINITY; // :49 diagonal; columns past the graph
-        }
-      }
+      kt_distances<KG_TILES>(acc, sqn, wave, fr, fg, KG_TILES, N);
       int res_i[4];
       float res_v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { res_i[j] = -1; res_v[j] = INFINITY; }
-      for (int round = 0; round < a.k; ++round) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float bv = acc[0][j];
-          int bc = 0;
-#pragma unroll
-          for (int c = 1; c < KG_TILES; ++c) {               // strict <: the lowest column of this lane wins a tie
-            const bool lt = acc[c][j] < bv;
-            bv = lt ? acc[c][j] : bv;
-            bc = lt ? c : bc;
-          }
-          int bi = bc * 16 + fr;
-          // minimum of (value, index) over the 16 lanes of the DPP row: rotations by 8, 4, 2, 1
-#define KG_STEP(CTRL)                                                        \
-          {                                                                  \
-            const float ov = kg_dpp_f<CTRL>(bv);                             \
-            const int oi = kg_dpp_i<CTRL>(bi);                               \
-            const bool take = ov < bv || (ov == bv && oi < bi);              \
-            bv = take ? ov : bv;                                             \
-            bi = take ? oi : bi;                                             \
-          }
-          KG_STEP(0x128) KG_STEP(0x124) KG_STEP(0x122) KG_STEP(0x121)
-#undef KG_STEP
-          const bool found = bv < INFINITY;
-          if (fr == round) { res_i[j] = found ? bi : -1; res_v[j] = bv; }
-          // the owner of the winner retires it
-          const bool own = (bi & 15) == fr;
-          const int cs = bi >> 4;
-#pragma unroll
-          for (int c = 0; c < KG_TILES; ++c) acc[c][j] = (own && cs == c) ? INFINITY : acc[c][j];
-        }
-      }
+      kt_select<KG_TILES>(acc, fr, a.k, res_i, res_v);
       // lane fr holds neighbour #fr of its four rows: one contiguous run of k indices per row
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -208,7 +133,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_gram_kernel(KnnGramArgs a) {
 
 // fast path of isic_knn_graph (graph.hip): every graph has <= 208 nodes, D % 32 == 0, k <= 16
 bool isic_knn_gram_supported(int D, int k, int max_nodes) {
-  return D % 32 == 0 && D >= 32 && k >= 1 && k <= 16 && max_nodes >= 1 && max_nodes <= KG_ROWS;
+  return max_nodes >= 1 && knn_tile_supported(D, k, max_nodes);
 }
 
 int isic_knn_gram_launch(const float* x, const int64_t* offsets, int G, int D, int k, int64_t* nn_idx, float* nn_dist,

@@ -7,9 +7,11 @@
 //   * only the waves < nt stage their 16 rows of a K-chunk (LDS-DMA, the XOR-swizzled layout of knn_gram.hip) and multiply,
 //     and only against the column tiles < nt: nt^2 tiles instead of 169.  Every skip is wave-uniform.
 //   * the MFMA sequence of one accumulator is knn_gram_kernel's: K-chunks of 32 floats in order, two quarters, the four
-//     v_mfma_f32_16x16x4_f32 of a quarter take k = 4 fg + j; |x_i|^2 is the Gram diagonal; the distance and the selection
-//     are the same expressions.  Tiles that are not multiplied enter the selection as +inf, which is what knn_gram_kernel
-//     makes of them (columns past the graph), so indices and distances are equal bit for bit (tests/test_knn_ragged_gpu.py).
+//     v_mfma_f32_16x16x4_f32 of a quarter take k = 4 fg + j; the Gram diagonal as |x_i|^2, the distance and the selection
+//     are the same code (knn_tile.inc, instantiated for NW tiles here and for 13 there).  Tiles that are not multiplied
+//     enter the selection as +inf, which is what knn_gram_kernel makes of them (columns past the graph), so indices and
+//     distances are equal bit for bit (tests/test_knn_ragged_gpu.py).  The multiply loop is kt_multiply there and here;
+//     this kernel steps over the tiles at or past nt and holds one quarter's fragments at a time.
 //   * synchronisation is plain: two stages of KC K-chunks (a round); per round every wave waits for ALL its outstanding
 //     memory operations (vmcnt(0)), one s_barrier, then the next round's DMA goes out behind it and overlaps this round's
 //     MFMAs.  A stage is overwritten one barrier after its last reader has its data.  A workgroup takes ONE graph (the grid
@@ -23,8 +25,9 @@
 
 namespace {
 
+#include "knn_tile.inc"
+
 constexpr int KR_STAGES = 2;
-constexpr int KR_MAX_NODES = 208;
 constexpr int KR_MAX_GRAPHS = 1 << 22;                     // one workgroup per graph: G x 832 threads stays below 2^32
 
 struct KnnRaggedArgs {
@@ -36,40 +39,6 @@ struct KnnRaggedArgs {
   int G, D, k, max_nodes;
   int above;                                               // this launch takes the graphs of above < N <= 16 NW nodes
 };
-
-template <int CTRL>
-__device__ __forceinline__ float kr_dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int kr_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-
-// One K-chunk of a row stripe against the nt column tiles of its graph (wave-uniform, 1 <= nt <= NW): knn_gram_kernel's loop,
-// four column tiles at a time so that a tile's accumulator is touched every fourth MFMA; tiles at or past nt are stepped over.
-template <int NW>
-__device__ __forceinline__ void kr_multiply(int nt, const unsigned char* st, unsigned foff0, int wave, f32x4 (&acc)[NW]) {
-#pragma unroll
-  for (int kq = 0; kq < 2; ++kq) {
-    __builtin_amdgcn_sched_barrier(0);                     // one quarter's fragments in registers at a time
-    const unsigned char* q = st + (foff0 ^ (unsigned)(kq << 6));
-    const f32x4 av = *reinterpret_cast<const f32x4*>(q + wave * 2048);
-#pragma unroll
-    for (int c0 = 0; c0 < NW; c0 += 4) {
-      if (c0 >= nt) break;
-      f32x4 bv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (c0 + i < NW) bv[i] = *reinterpret_cast<const f32x4*>(q + (c0 + i < nt ? c0 + i : c0) * 2048);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (c0 + i < NW) {
-            if (c0 + i < nt) acc[c0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[i][j], acc[c0 + i], 0, 0, 0);
-          }
-    }
-  }
-}
 
 template <int NW, int KC, bool WITH_DIST>
 // at most 128 registers: 4 / 2 / 1 workgroups per CU (the 4-wave one by its 33 KB of LDS, the others by their waves)
@@ -85,12 +54,10 @@ void knn_ragged_kernel(KnnRaggedArgs a) {
   const int fr = lane & 15, fg = lane >> 4;
   const int nchunks = a.D >> 5;
   const int nrounds = (nchunks + KC - 1) / KC;
-  // staging: piece h (= 0, 1) of this wave brings rows 16 wave + 8 h + r8; the lane fetches global 16-byte chunk p ^ r8 of
-  // its row (row & 7 == r8), so that LDS position p of a row holds chunk p ^ (row & 7)
-  const int r8 = lane >> 3, p8 = lane & 7;
-  const unsigned src_chunk = (unsigned)((p8 ^ r8) << 4);
-  // fragment addresses inside a stage: row 16 c + fr, k-quarter kq (16 floats): chunk (4 kq + fg) ^ (fr & 7)
-  const unsigned foff0 = (unsigned)(fr * 128 + ((fg ^ (fr & 7)) << 4));              // kq = 0; kq = 1: ^ 64
+  // staging: piece h (= 0, 1) of this wave brings rows 16 wave + 8 h + r8, swizzled on the source side (knn_tile.inc)
+  const int r8 = lane >> 3;
+  const unsigned src_chunk = kt_src_chunk(lane);
+  const unsigned foff0 = kt_foff0(fr, fg);               // fragment of tile 0, k-quarter 0; kq = 1: ^ 64
 
   const int g = (int)blockIdx.x;                         // one workgroup per graph: the grid is G
   const long long lo = a.offsets[g], hi = a.offsets[g + 1];
@@ -133,71 +100,17 @@ void knn_ragged_kernel(KnnRaggedArgs a) {
     if (!active) continue;
 #pragma unroll 1
     for (int s = 0; s < KC; ++s)                           // the K-chunks in their order: the summation order of knn_gram_kernel
-      if (r * KC + s < nchunks) kr_multiply<NW>(nt, smem + (r % KR_STAGES) * STAGE + s * CHUNK, foff0, wave, acc);
+      if (r * KC + s < nchunks) kt_multiply<NW, true>(nt, smem + (r % KR_STAGES) * STAGE + s * CHUNK, foff0, wave, acc);
   }
 
   // ================================================================ the graph is complete: distances -> top-k
-  // |x_i|^2 = G[i][i]: tile (wave, wave), row 4 fg + j == column fr
-  if (active) {
-    f32x4 dg = acc[0];
-#pragma unroll
-    for (int c = 1; c < NW; ++c) dg = wave == c ? acc[c] : dg;
-    const float dv = (fr & 3) == 0 ? dg[0] : (fr & 3) == 1 ? dg[1] : (fr & 3) == 2 ? dg[2] : dg[3];
-    if ((fr >> 2) == fg) sqn[wave * 16 + fr] = dv;
-  }
+  if (active) kt_store_sqn<NW>(acc, wave, fr, fg, sqn);
   lds_barrier();
   if (active) {
-    float sr[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sr[j] = sqn[wave * 16 + fg * 4 + j];
-#pragma unroll
-    for (int c = 0; c < NW; ++c) {
-      const int col = c * 16 + fr;
-      const float sc = c < nt ? sqn[col] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int q = wave * 16 + fg * 4 + j;
-        float dv = (sr[j] + sc) - 2.0f * acc[c][j];        // 03_build_graphs.py:47
-        dv = fmaxf(dv, 0.f);                               // :48 clamp(min = 0)
-        acc[c][j] = (col < N && col != q) ? dv : INFINITY; // :49 diagonal; columns past the graph
-      }
-    }
+    kt_distances<NW>(acc, sqn, wave, fr, fg, nt, N);
     int res_i[4];
     float res_v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { res_i[j] = -1; res_v[j] = INFINITY; }
-    for (int round = 0; round < a.k; ++round) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float bv = acc[0][j];
-        int bc = 0;
-#pragma unroll
-        for (int c = 1; c < NW; ++c) {                     // strict <: the lowest column of this lane wins a tie
-          const bool lt = acc[c][j] < bv;
-          bv = lt ? acc[c][j] : bv;
-          bc = lt ? c : bc;
-        }
-        int bi = bc * 16 + fr;
-        // minimum of (value, index) over the 16 lanes of the DPP row: rotations by 8, 4, 2, 1
-#define KR_STEP(CTRL)                                                        \
-        {                                                                  \
-          const float ov = kr_dpp_f<CTRL>(bv);                             \
-          const int oi = kr_dpp_i<CTRL>(bi);                               \
-          const bool take = ov < bv || (ov == bv && oi < bi);              \
-          bv = take ? ov : bv;                                             \
-          bi = take ? oi : bi;                                             \
-        }
-        KR_STEP(0x128) KR_STEP(0x124) KR_STEP(0x122) KR_STEP(0x121)
-#undef KR_STEP
-        const bool found = bv < INFINITY;
-        if (fr == round) { res_i[j] = found ? bi : -1; res_v[j] = bv; }
-        // the owner of the winner retires it
-        const bool own = (bi & 15) == fr;
-        const int cs = bi >> 4;
-#pragma unroll
-        for (int c = 0; c < NW; ++c) acc[c][j] = (own && cs == c) ? INFINITY : acc[c][j];
-      }
-    }
+    kt_select<NW>(acc, fr, a.k, res_i, res_v);
     // lane fr holds neighbour #fr of its four rows: one contiguous run of k indices per row
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -277,7 +190,7 @@ extern "C" {
 int isic_knn_graph_ragged(const float* x, const int64_t* offsets, int G, int D, int k, int max_nodes,
                           int64_t total_nodes, int64_t* nn_idx, float* nn_dist, void* stream) {
   ISIC_CHECK_ARG(G >= 0 && D > 0 && k > 0 && max_nodes >= 0 && total_nodes >= 0);
-  if (D % 32 != 0 || D < 32 || k > 16 || max_nodes > KR_MAX_NODES || G > KR_MAX_GRAPHS) return ISIC_ERR_UNSUPPORTED;
+  if (!knn_tile_supported(D, k, max_nodes) || G > KR_MAX_GRAPHS) return ISIC_ERR_UNSUPPORTED;
   if (G == 0 || total_nodes == 0) return ISIC_OK;
   ISIC_CHECK_ARG(x && offsets && nn_idx);
   if (max_nodes == 0) return ISIC_OK;                      // no graph may own a node: nothing to write

@@ -9,19 +9,27 @@ from .lib import ERR_UNSUPPORTED, IsicHipError, call
 from .ops import _acc_target, _chk, _f32c, _grad_colsum, _grad_gemm, colsum
 
 
-def knn_indices(x, offsets: BagOffsets, k, return_dist=False):
-    """k nearest neighbours of every node inside its own graph -> LOCAL ids [T, k] (int64),
-    ascending by distance (`03_build_graphs.py:46-50`)."""
+def _knn_launch(entry, x, offsets: BagOffsets, k, return_dist):
+    """Checks, output allocation and the launch that ``isic_knn_graph`` and ``isic_knn_graph_ragged`` share; the former also
+    takes a workspace of one float per node.  ``entry``: a name, or the rule that picks one once D is known."""
     _chk(x)
     x = _f32c(x)
     T, D = x.shape
     if T != offsets.total:
         raise ValueError(f"x has {T} rows but offsets cover {offsets.total}")
+    if callable(entry):
+        entry = entry(D)
     idx = torch.empty((T, k), device=x.device, dtype=torch.int64)
     dist = torch.empty((T, k), device=x.device, dtype=torch.float32) if return_dist else None
-    ws = torch.empty((T,), device=x.device, dtype=torch.float32)
-    call("isic_knn_graph", x, offsets.device, offsets.num_bags, D, int(k), offsets.max_bag, T, idx, dist, ws)
+    ws = (torch.empty((T,), device=x.device, dtype=torch.float32),) if entry == "isic_knn_graph" else ()
+    call(entry, x, offsets.device, offsets.num_bags, D, int(k), offsets.max_bag, T, idx, dist, *ws)
     return (idx, dist) if return_dist else idx
+
+
+def knn_indices(x, offsets: BagOffsets, k, return_dist=False):
+    """k nearest neighbours of every node inside its own graph -> LOCAL ids [T, k] (int64),
+    ascending by distance (`03_build_graphs.py:46-50`)."""
+    return _knn_launch("isic_knn_graph", x, offsets, k, return_dist)
 
 
 KNN_RAGGED_MAX_NODES = 208
@@ -47,21 +55,15 @@ def knn_indices_ragged(x, offsets: BagOffsets, k, return_dist=False):
     Gram kernel sized by each graph, bit-equal to ``knn_indices`` -- where that entry supports the batch (D % 32 == 0,
     k <= 16, up to 2^22 graphs of up to 208 nodes) and the graphs are small enough for it to be the faster one (on average at most
     ``KNN_RAGGED_MAX_MEAN_TILES`` tiles of 16 x 16 nodes), else through ``knn_indices``."""
-    _chk(x)
-    x = _f32c(x)
-    T, D = x.shape
-    if T != offsets.total:
-        raise ValueError(f"x has {T} rows but offsets cover {offsets.total}")
-    import numpy as np
-    n = np.diff(offsets.host)
-    tiles = float((((n + 15) // 16) ** 2).mean()) if n.size else 0.0
-    if not (KNN_RAGGED_USE_SIZED_KERNEL and tiles <= KNN_RAGGED_MAX_MEAN_TILES and offsets.num_bags <= KNN_RAGGED_MAX_GRAPHS
-            and knn_ragged_supported(D, int(k), offsets.max_bag)):
-        return knn_indices(x, offsets, k, return_dist=return_dist)
-    idx = torch.empty((T, k), device=x.device, dtype=torch.int64)
-    dist = torch.empty((T, k), device=x.device, dtype=torch.float32) if return_dist else None
-    call("isic_knn_graph_ragged", x, offsets.device, offsets.num_bags, D, int(k), offsets.max_bag, T, idx, dist)
-    return (idx, dist) if return_dist else idx
+    def entry(D):
+        import numpy as np
+        n = np.diff(offsets.host)
+        tiles = float((((n + 15) // 16) ** 2).mean()) if n.size else 0.0
+        sized = (KNN_RAGGED_USE_SIZED_KERNEL and tiles <= KNN_RAGGED_MAX_MEAN_TILES and offsets.num_bags <= KNN_RAGGED_MAX_GRAPHS
+                 and knn_ragged_supported(D, int(k), offsets.max_bag))
+        return "isic_knn_graph_ragged" if sized else "isic_knn_graph"
+
+    return _knn_launch(entry, x, offsets, k, return_dist)
 
 
 def knn_edge_counts(sizes, k_values):

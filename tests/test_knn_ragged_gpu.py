@@ -1,10 +1,12 @@
 """k-NN graphs among patch sets of unequal size on the MI355X (include/isic_hip_knn_ragged.h, csrc/knn_ragged.hip):
 ``isic_knn_graph_ragged`` bit-equal to ``isic_knn_graph`` (same MFMA order, norms from the Gram diagonal) and against the
-oracle under the tie guard of tests/test_graph_gpu.py; ``isic_knn_edges_ragged`` exactly equal to the per-graph reference
+oracle under the tie guard of tests/test_graph_gpu.py; the tie rule of all three k-NN kernels on exact integer inputs;
+``isic_knn_edges_ragged`` exactly equal to the per-graph reference
 loop (tests/knn_ragged_ref.py); the argument rules at the ABI; and the routes built on the two entries --
 ``build_graph_records(per_graph_k=True)``, ``GraphStore(lesion_only=True, lesion_knn=k)``, ``05_train_gnns.py --lesion-knn``,
 ``04_measure_heterophily.py --lesion-knn`` and the resident pipeline's ``keep`` / ``lesion_knn`` switches."""
 import ctypes
+import functools
 import importlib.util
 import os
 import pickle
@@ -82,6 +84,71 @@ def test_many_small_graphs_and_an_empty_one_bit_for_bit():
     sizes = rng.randint(1, 21, 5000)
     sizes[[0, 2500, 4999]] = 0
     _assert_bit_equal(sizes.tolist(), 32, seed=13)
+
+
+# ------------------------------------------------------------------ the tie rule: equal distances -> the lower index
+TIE_SIZES = (1, 2, 3, 16, 17, 64, 65, 128, 129, 208)
+
+
+@functools.lru_cache(maxsize=None)
+def _tie_batch(sizes, D):
+    """Integer coordinates out of {-2 .. 2} with n // 8 rows of every graph overwritten by copies of other rows: every product
+    and every sum is an integer below 2^24, exact in fp32 in any summation order, so the device's distances ARE the int64
+    ones and nearly every row has equal distances among its first k + 1 neighbours, a quarter of them a distance of 0 off
+    the diagonal.  -> x float32, and per row the other nodes of its graph sorted by (distance, index): the first 16 of them
+    (LOCAL ids, -1 past the n - 1 that exist), their distances (+inf there) and the share of rows of >= 17 nodes with a tie."""
+    rng = np.random.RandomState(1000 * len(sizes) + D)
+    xs, want_i, want_d, tied, rows = [], [], [], 0, 0
+    for n in sizes:
+        xg = rng.randint(-2, 3, (n, D))
+        dup = rng.permutation(n)[:2 * (n // 8)]
+        xg[dup[:n // 8]] = xg[dup[n // 8:]]
+        xg = torch.from_numpy(xg).long()
+        d = ((xg[:, None, :] - xg[None, :, :]) ** 2).sum(-1)                   # int64, exact
+        d[torch.arange(n), torch.arange(n)] = 1 << 40                          # a node is not its own neighbour: sorts last
+        dv, di = torch.sort(d, dim=1, stable=True)                             # stable: equal distances keep the index order
+        kk = min(16, n - 1)
+        wi, wd = torch.full((n, 16), -1, dtype=torch.int64), torch.full((n, 16), float("inf"))
+        wi[:, :kk], wd[:, :kk] = di[:, :kk], dv[:, :kk].float()
+        if n >= 17:
+            tied += int((dv[:, 1:17] == dv[:, :16]).any(1).sum())
+            rows += n
+        xs.append(xg.float()), want_i.append(wi), want_d.append(wd)
+    return torch.cat(xs), torch.cat(want_i), torch.cat(want_d), tied / max(rows, 1)
+
+
+def _assert_tie_rule(sizes, D, run):
+    x, want_i, want_d, tied = _tie_batch(tuple(sizes), D)
+    assert tied >= 0.98, tied                                                  # the inputs do what they are made for
+    offs = _offsets(sizes)
+    for k in (16, 1):
+        got_i, got_d = run(x.to(DEV), offs, k)
+        assert torch.equal(got_i.cpu(), want_i[:, :k]), (D, k, int((got_i.cpu() != want_i[:, :k]).sum()))
+        assert torch.equal(got_d.cpu(), want_d[:, :k]), (D, k, int((got_d.cpu() != want_d[:, :k]).sum()))
+
+
+def _knn_indices_with_dist(x, offs, k):
+    from isic_hip.graph import knn_indices
+    return knn_indices(x, offs, k, return_dist=True)
+
+
+@pytest.mark.parametrize("D", [32, 96])
+def test_tie_rule_of_the_gram_kernel(D):
+    """``topk(largest=False)`` on equal distances: the lower index comes first (03_build_graphs.py:50), which the selection
+    of csrc/knn_tile.inc states as "strict < inside a lane, (value, index) across the lanes"."""
+    _assert_tie_rule(TIE_SIZES, D, _knn_indices_with_dist)
+
+
+@pytest.mark.parametrize("D", [32, 96])
+@pytest.mark.parametrize("count", [6, 8, 10], ids=["4waves", "8waves", "13waves"])
+def test_tie_rule_of_the_ragged_entry(count, D):
+    _assert_tie_rule(TIE_SIZES[:count], D, _ragged)
+
+
+@pytest.mark.parametrize("sizes,D", [((240, 30), 32), ((50, 196), 24)], ids=["above_208_nodes", "D_not_multiple_of_32"])
+def test_tie_rule_of_the_row_tile_kernel(sizes, D):
+    """knn_kernel of csrc/graph.hip (its norms come from a sum of their own: exact here like every other sum)."""
+    _assert_tie_rule(sizes, D, _knn_indices_with_dist)
 
 
 # ------------------------------------------------------------------ against the oracle, with the tie guard
