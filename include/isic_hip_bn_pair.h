@@ -23,10 +23,12 @@ extern "C" {
  * apply: one flat walk; dx is what isic_bn_bwd_apply_mask_bf16(dy, x, relu_mask, ...) writes to dx, dx2 what
  *   isic_bn_bwd_apply_bf16(dz, x2, relu = 0, ...) writes with (sum_dzx2, sum_dz).  dgamma_f32 / dbeta_f32 and
  *   dgamma2_f32 / dbeta2_f32 (each pair optional) get += the sums.  dz itself is not written.
- * Both give the bits of the launches they replace: same launch geometry, thread mapping and expressions.  The pair
- * kernels spell every fused multiply-add as fmaf, the kernels they replace leave the same contractions to the compiler
- * (a * b + c under hipcc's default -ffp-contract=fast), so the equality is with those kernels as the compiler builds them
- * today, not with their source text; tests/test_bn_pair_gpu.py compares the two exactly and would show a drift. */
+ * Both give the bits of the launches they replace, by construction: the pair is the same kernel template as those
+ * launches, instantiated for two norms (same launch geometry and thread mapping), and every value -- the gate, the
+ * accumulation step, the constants, dx -- comes from the same functions of csrc/bn_bwd_math.inc, whose source text spells
+ * out every rounding (contraction off, each fused multiply-add a __builtin_fmaf), so nothing is left to the compiler's
+ * contraction choices.  tests/test_bn_pair_gpu.py compares the two exactly; tests/test_bn_bwd_math_gpu.py compares both
+ * with a numpy emulation of the include. */
 int isic_bn_bwd_reduce_pair_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
                                  const float* rstd, const uint16_t* x2, const float* mean2, const float* rstd2, int64_t rows,
                                  int C, double* sum_dzx, double* sum_dz, double* sum_dzx2, void* stream);

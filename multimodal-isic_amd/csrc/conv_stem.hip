@@ -19,6 +19,7 @@
 #include "slab_sum.inc"
 #include "mfma_tile.h"
 #include "pool_grad.h"
+#include "bn_bwd_math.inc"
 
 namespace {
 
@@ -445,13 +446,6 @@ __device__ __forceinline__ void stem_route4_interior(const isic_pool::Windows& w
     for (int j = 0; j < 4; ++j) out[p][j] = bf16_bits_to_f32(f32_to_bf16_bits(acc[p][j]));
 }
 
-// dY = (D + B*y0) + A*dz with every product and sum rounded by itself: no contraction to fused multiply-adds
-__device__ __forceinline__ float stem_dy_unfused(float kA, float kB, float kD, float y0, float dz) {
-#pragma clang fp contract(off)
-  const float t = kD + kB * y0;
-  return t + kA * dz;
-}
-
 // DMA = true needs an even Win and a 16-byte aligned input; DMA = false stages the patch through registers
 // (fetch_patch / commit_patch) and serves every other shape.
 template <bool DMA>
@@ -565,9 +559,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          // one fused multiply-add in the mask, none in dY = (D + B*y0) + A*dz: the roundings of the two-kernel path
-          const float dz = (fmaf(xv[j], sc[j], sh[j]) > 0.f) ? g[p][j] : 0.f;
-          o[j] = stem_dy_unfused(kA[j], kB[j], kD[j], xv[j], dz);
+          // the mask and dz are the two-kernel path's (isic_bn_bwd_apply_pooled_bf16); dY is NOT: dx_unfused rounds each
+          // product and each sum of (D + B*y0) + A*dz by itself, stem_bn_bwd_apply_kernel makes two fused multiply-adds
+          const float dz = isic_bn_bwd::gate<2>(g[p][j], xv[j], 0.f, sc[j], sh[j], 0u, 0);
+          o[j] = isic_bn_bwd::dx_unfused(kA[j], kB[j], kD[j], xv[j], dz);
           if (!inside) o[j] = in ? o[j] : 0.f;
         }
         *reinterpret_cast<u32x2*>(Ys + (oyl * TW + oxl) * YROW + cg * 16 + H_ * 8) = isic_pack_bf16x4(o);
@@ -613,15 +608,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
   // (after the scalar set-up above: what is first computed inside this divergent branch and used again behind it
   //  comes out of the branch's join as a vector value, tile coordinates and address bases included)
   if (tid < 64) {
-#pragma clang fp contract(off)
-    const float inv_rows = 1.f / (float)((int64_t)a.N * a.Hout * a.Wout);
-    // dY = k1*(dz - k2 - xh*k3), xh = (y0 - mu)*rs  ==  A*dz + B*y0 + D  (three constants); the one fused
-    // multiply-add is written out, nothing else contracts
-    const float rs = b.rstd[tid], mu = b.mean[tid], k1 = b.gamma[tid] * rs;
-    const float k2 = (float)b.dbeta[tid] * inv_rows, k3 = (float)b.dgamma[tid] * inv_rows;
-    cst[0][tid] = k1;
-    cst[1][tid] = (-k1 * k3) * rs;
-    cst[2][tid] = k1 * fmaf(k3 * rs, mu, -k2);
+    // dY = k1*(dz - k2 - xh*k3), xh = (y0 - mu)*rs  ==  A*dz + B*y0 + D: the three constants of the two-kernel path
+    const float inv_rows = isic_bn_bwd::inv_count((int64_t)a.N * a.Hout * a.Wout);
+    isic_bn_bwd::constants(b.mean[tid], b.rstd[tid], b.gamma[tid], (float)b.dgamma[tid], (float)b.dbeta[tid], inv_rows,
+                           cst[0][tid], cst[1][tid], cst[2][tid]);
     cst[3][tid] = b.scale[tid]; cst[4][tid] = b.shift[tid];
   }
   __syncthreads();                                       // constants visible
@@ -698,10 +688,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_wgrad_bn_kernel(StemBnArgs b
   // the fp32 copies of dgamma / dbeta, by block 0.  At the END: a test of the block index inside the divergent branch
   // at the top lets the compiler merge "block index == 0" with the register at that branch's join, which turns the
   // block index -- and with it every tile coordinate and address base of the loop -- into vector values
-  if (bid == 0 && tid < 64 && b.dgamma_f32) {
-    b.dgamma_f32[tid] += (float)b.dgamma[tid];
-    b.dbeta_f32[tid] += (float)b.dbeta[tid];
-  }
+  if (bid == 0 && tid < 64 && b.dgamma_f32) isic_bn_bwd::fold(tid, b.dgamma, b.dbeta, b.dgamma_f32, b.dbeta_f32);
 }
 
 // fp32 [64][7][7][3] (channels_last memory of the OIHW parameter) -> bf16 [64][7][8][4], zero padded

@@ -22,6 +22,7 @@
 #include "slab_sum.inc"
 #include "mfma_tile.h"
 #include "pool_grad.h"
+#include "bn_bwd_math.inc"
 
 namespace {
 
@@ -44,7 +45,8 @@ struct WC64Args {
   int N, H, W, tiles_y, tiles_x, total_tiles, tiles_per_block;
 };
 
-// BNBWD: dY = kA * dz + (kB * c + kD) per channel, dz = relu_mask ? g : 0 (isic_bn_bwd_apply*_bf16, encoder_ops.hip)
+// BNBWD: dY = kA * dz + (kB * c + kD) per channel, dz = relu_mask ? g : 0: the functions of bn_bwd_math.inc, as in
+// isic_bn_bwd_apply*_bf16 (encoder_ops.hip)
 struct WC64BnArgs : WC64Args {        // dy = g, the gradient of the BatchNorm(+ReLU) output
   const unsigned short* c;            // the BatchNorm input (this layer's raw convolution output)
   const unsigned char* mask;          // MODE 3: one bit per element
@@ -187,18 +189,13 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(typename WC64Mode<MODE>:
       const int cg = (int)((lane_p & 127u) >> 4);
       float kA[8], kB[8], kD[8], sc[8], sh[8];
       {
-        const float inv_rows = 1.f / (float)((int64_t)a.N * a.H * a.W);
-        if (blockIdx.x == 0 && p == 0 && a.dgamma_f32) {
-          a.dgamma_f32[lane] += (float)a.dgamma[lane];
-          a.dbeta_f32[lane] += (float)a.dbeta[lane];
-        }
+        const float inv_rows = isic_bn_bwd::inv_count((int64_t)a.N * a.H * a.W);
+        if (blockIdx.x == 0 && p == 0 && a.dgamma_f32) isic_bn_bwd::fold(lane, a.dgamma, a.dbeta, a.dgamma_f32, a.dbeta_f32);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {                 // bn_bwd_apply_kernel's constants, with the one contraction the
-#pragma clang fp contract(off)                        // compiler makes there written out (a * b - c * d has two)
+        for (int j = 0; j < 8; ++j) {
           const int c = cg * 8 + j;
-          const float mu = a.mean[c], rs = a.rstd[c], k1 = a.gamma[c] * rs;
-          const float k2 = (float)a.dbeta[c] * inv_rows, k3 = (float)a.dgamma[c] * inv_rows;
-          kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * __builtin_fmaf(k3 * rs, mu, -k2);
+          isic_bn_bwd::constants(a.mean[c], a.rstd[c], a.gamma[c], (float)a.dgamma[c], (float)a.dbeta[c], inv_rows, kA[j],
+                                 kB[j], kD[j]);
           sc[j] = MODE == 2 ? a.scale[c] : 0.f; sh[j] = MODE == 2 ? a.shift[c] : 0.f;
         }
         // the constants are in registers before the first DMA: the compiler's own wait for their loads (it counts only
@@ -235,21 +232,14 @@ __global__ __launch_bounds__(768) void wgrad_c64_kernel(typename WC64Mode<MODE>:
         for (int j = 0; j < WT_H; ++j) {
           bool ok;
           const long long off = dy_off(tl, j, ok);
-          float g[8], xv[8], yv[8], o[8];
+          float g[8], xv[8], o[8];
           isic_pool::unpack8(rg[S][j], g);
           isic_pool::unpack8(rc[S][j], xv);
-          if constexpr (MODE == 2) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) yv[e] = __builtin_fmaf(xv[e], sc[e], sh[e]);
-          } else {
-            const unsigned m = rm[S][j];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) yv[e] = ((m >> e) & 1u) ? 1.f : 0.f;
-          }
+          const unsigned m = MODE == 3 ? rm[S][j] : 0u;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
-            o[e] = __builtin_fmaf(kA[e], dz, __builtin_fmaf(kB[e], xv[e], kD[e]));   // the apply pass's two FMAs
+            const float dz = isic_bn_bwd::gate<MODE>(g[e], xv[e], 0.f, sc[e], sh[e], m, e);
+            o[e] = isic_bn_bwd::dx(kA[e], kB[e], kD[e], xv[e], dz);
           }
           u32x4 v = isic_pool::pack8(o);
           if (!ok) v = (u32x4){0u, 0u, 0u, 0u};       // padding pixels are zeros in LDS, as the DMA left them

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "pool_grad.h"
+#include "bn_bwd_math.inc"
 
 namespace {
 
@@ -46,11 +47,9 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const unsigned short* __r
   float acc[2][8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { acc[0][j] = 0.f; acc[1][j] = 0.f; }
-  // a block sums a CONTIGUOUS range of rows (DRAM pages walked in order: 5.8 -> 6.2 TB/s for the backward sums)
-  const int64_t per_block = ((rows + gridDim.x - 1) / gridDim.x + rls - 1) / rls * rls;
-  const int64_t r_end = min(rows, ((int64_t)blockIdx.x + 1) * per_block);
+  const isic_bn_bwd::RowRange rr = isic_bn_bwd::block_rows(rows, rls);   // contiguous rows, as the backward sums
 #pragma unroll 4
-  for (int64_t r = (int64_t)blockIdx.x * per_block + rl; r < r_end; r += rls) {
+  for (int64_t r = rr.begin + rl; r < rr.end; r += rls) {
     float f[8];
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + r * C + cg * 8)), f);
 #pragma unroll
@@ -201,210 +200,111 @@ __device__ __forceinline__ void pooled_grad8(const unsigned char* __restrict__ a
   unpack8(pack8(acc), out);
 }
 
-// MODE: where the ReLU mask comes from -- 0 no ReLU, 1 the output y, 2 recomputed from x (scale, shift), 3 mask bits.
+// BatchNorm(+ReLU) backward; the arithmetic is bn_bwd_math.inc's.
+// MODE: where the ReLU mask comes from (isic_bn_bwd::gate) -- 0 no ReLU, 1 the output y, 2 recomputed from x (scale, shift),
+// 3 mask bits.  NORMS = 2: the two norms that meet at a downsample block's output, out = relu(bn2(x) + bn_d(x2)), in one
+// walk -- both receive the same dz, which is then never written out and read back; the launch geometry, the thread ->
+// (row, channel group) mapping and the functions are those of <3, 1> on x followed by <0, 1> on dz and x2, so every
+// partial sum and every output is the value those launches give (tests/test_bn_pair_gpu.py).
 // Compile-time so that each variant only carries the registers it needs (occupancy is what hides the HBM latency here).
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const unsigned short* __restrict__ dy,
-                                                             const unsigned short* __restrict__ x,
-                                                             const unsigned short* __restrict__ y,
-                                                             const unsigned char* __restrict__ relu_mask,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ rstd, int64_t rows, int C,
-                                                             int relu, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift,
-                                                             double* __restrict__ dgamma,
-                                                             double* __restrict__ dbeta) {
-  const int tid = threadIdx.x, cgs = C >> 3, cg = tid % cgs, rl = tid / cgs, rls = 256 / cgs;
-  float acc[2][8], mu[8], rs[8], sc[8], sh[8];
-  constexpr bool from_x = MODE == 2;
-  (void)relu;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    acc[0][j] = 0.f; acc[1][j] = 0.f; mu[j] = mean[cg * 8 + j]; rs[j] = rstd[cg * 8 + j];
-    sc[j] = from_x ? scale[cg * 8 + j] : 0.f; sh[j] = from_x ? shift[cg * 8 + j] : 0.f;
-  }
-  // a block sums a CONTIGUOUS range of rows (not a grid-strided set): DRAM pages are walked in order
-  const int64_t per_block = ((rows + gridDim.x - 1) / gridDim.x + rls - 1) / rls * rls;
-  const int64_t r_end = min(rows, ((int64_t)blockIdx.x + 1) * per_block);
-#pragma unroll 2
-  for (int64_t r = (int64_t)blockIdx.x * per_block + rl; r < r_end; r += rls) {
-    float g[8], xv[8], yv[8];
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + r * C + cg * 8)), g);
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + r * C + cg * 8)), xv);
-    if (from_x) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = xv[j] * sc[j] + sh[j];
-    } else if (MODE == 3) {                                // 1 bit per element instead of re-reading the output
-      const unsigned m = relu_mask[r * (C >> 3) + cg];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = ((m >> j) & 1u) ? 1.f : 0.f;
-    } else if (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(y + r * C + cg * 8), yv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float dz = (MODE != 0 && !(yv[j] > 0.f)) ? 0.f : g[j];
-      acc[0][j] += dz * ((xv[j] - mu[j]) * rs[j]);
-      acc[1][j] += dz;
-    }
-  }
-  double* const dst[2] = {dgamma, dbeta};
-  block_reduce_to_global<2>(acc, C, dst);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
+template <int MODE, int NORMS>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x, const unsigned short* __restrict__ y,
-    const unsigned char* __restrict__ relu_mask,
-    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-    const double* __restrict__ dgamma, const double* __restrict__ dbeta, int64_t rows, int C, int relu,
-    const float* __restrict__ scale, const float* __restrict__ shift,
-    unsigned short* __restrict__ dx, unsigned short* __restrict__ d_residual, float* __restrict__ dgamma_f32,
-    float* __restrict__ dbeta_f32) {
-  const int cgs = C >> 3;
-  constexpr bool from_x = MODE == 2;
-  (void)relu;
-  const int64_t nvec = rows * cgs;
-  const float inv_rows = 1.f / (float)rows;
-  if (blockIdx.x == 0 && dgamma_f32) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      dgamma_f32[c] += (float)dgamma[c];
-      dbeta_f32[c] += (float)dbeta[c];
-    }
-  }
-  // per-thread channel constants (a block starts at a multiple of 256 vectors, 256 % (C/8) == 0): dx = k1*dz - k2 - xh*k3
-  const int cg = threadIdx.x % cgs;
-  // dx = k1*(dz - k2 - xh*k3), xh = (x - mu)*rs  ==  kA*dz + (kB*x + kD): three constants and two FMAs per element
-  float kA[8], kB[8], kD[8], sc[8], sh[8];
+    const unsigned char* __restrict__ relu_mask, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ scale, const float* __restrict__ shift, const unsigned short* __restrict__ x2,
+    const float* __restrict__ mean2, const float* __restrict__ rstd2, int64_t rows, int C, double* __restrict__ sum_dzx,
+    double* __restrict__ sum_dz, double* __restrict__ sum_dzx2) {
+  static_assert(NORMS == 1 || (NORMS == 2 && MODE == 3), "the pair is built for the mask form only");
+  const int tid = threadIdx.x, cgs = C >> 3, cg = tid % cgs, rl = tid / cgs, rls = 256 / cgs;
+  float acc[NORMS + 1][8], mu[8], rs[8], sc[8], sh[8], mu2[8], rs2[8];      // acc: sum dz * xhat, sum dz, sum dz * xhat2
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = cg * 8 + j;
-    const float mu = mean[c], rs = rstd[c], k1 = gamma[c] * rs;
-    const float k2 = (float)dbeta[c] * inv_rows, k3 = (float)dgamma[c] * inv_rows;
-    kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * (k3 * rs * mu - k2);
-    sc[j] = from_x ? scale[c] : 0.f; sh[j] = from_x ? shift[c] : 0.f;
+#pragma unroll
+    for (int a = 0; a <= NORMS; ++a) acc[a][j] = 0.f;
+    mu[j] = mean[c]; rs[j] = rstd[c];
+    sc[j] = MODE == 2 ? scale[c] : 0.f; sh[j] = MODE == 2 ? shift[c] : 0.f;
+    if constexpr (NORMS == 2) { mu2[j] = mean2[c]; rs2[j] = rstd2[c]; }
+  }
+  const isic_bn_bwd::RowRange rr = isic_bn_bwd::block_rows(rows, rls);
+#pragma unroll 2
+  for (int64_t r = rr.begin + rl; r < rr.end; r += rls) {
+    float g[8], xv[8], x2v[8], yv[8] = {};
+    unsigned m = 0;
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + r * C + cg * 8)), g);
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + r * C + cg * 8)), xv);
+    if constexpr (NORMS == 2) unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + r * C + cg * 8)), x2v);
+    if constexpr (MODE == 3) m = relu_mask[r * (C >> 3) + cg];     // 1 bit per element instead of re-reading the output
+    if constexpr (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(y + r * C + cg * 8), yv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float dz = isic_bn_bwd::gate<MODE>(g[j], xv[j], yv[j], sc[j], sh[j], m, j);
+      isic_bn_bwd::accumulate(dz, xv[j], mu[j], rs[j], acc[0][j], acc[1][j]);
+      if constexpr (NORMS == 2) isic_bn_bwd::accumulate(dz, x2v[j], mu2[j], rs2[j], acc[2][j]);
+    }
+  }
+  double* dst[NORMS + 1] = {sum_dzx, sum_dz};
+  if constexpr (NORMS == 2) dst[2] = sum_dzx2;
+  block_reduce_to_global<NORMS + 1>(acc, C, dst);
+}
+
+// dx2, the second norm's output, is formed from (sum_dzx2, sum_dz): both norms share the sum of dz.  d_residual (dz itself,
+// for a residual branch) exists with one norm only.
+template <int MODE, int NORMS>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
+    const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x, const unsigned short* __restrict__ y,
+    const unsigned char* __restrict__ relu_mask, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const double* __restrict__ sum_dzx, const double* __restrict__ sum_dz,
+    const float* __restrict__ scale, const float* __restrict__ shift, const unsigned short* __restrict__ x2,
+    const float* __restrict__ mean2, const float* __restrict__ rstd2, const float* __restrict__ gamma2,
+    const double* __restrict__ sum_dzx2, int64_t rows, int C, unsigned short* __restrict__ dx,
+    unsigned short* __restrict__ d_residual, unsigned short* __restrict__ dx2, float* __restrict__ dgamma_f32,
+    float* __restrict__ dbeta_f32, float* __restrict__ dgamma2_f32, float* __restrict__ dbeta2_f32) {
+  static_assert(NORMS == 1 || (NORMS == 2 && MODE == 3), "the pair is built for the mask form only");
+  const int cgs = C >> 3;
+  const int64_t nvec = rows * cgs;
+  const float inv_rows = isic_bn_bwd::inv_count(rows);
+  if (blockIdx.x == 0) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      if (dgamma_f32) isic_bn_bwd::fold(c, sum_dzx, sum_dz, dgamma_f32, dbeta_f32);
+      if constexpr (NORMS == 2)
+        if (dgamma2_f32) isic_bn_bwd::fold(c, sum_dzx2, sum_dz, dgamma2_f32, dbeta2_f32);
+    }
+  }
+  // per-thread channel constants: a block starts at a multiple of 256 vectors and 256 % (C/8) == 0
+  const int cg = threadIdx.x % cgs;
+  float kA[8], kB[8], kD[8], sc[8], sh[8], kA2[8], kB2[8], kD2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = cg * 8 + j;
+    isic_bn_bwd::constants(mean[c], rstd[c], gamma[c], (float)sum_dzx[c], (float)sum_dz[c], inv_rows, kA[j], kB[j], kD[j]);
+    if constexpr (NORMS == 2)
+      isic_bn_bwd::constants(mean2[c], rstd2[c], gamma2[c], (float)sum_dzx2[c], (float)sum_dz[c], inv_rows, kA2[j], kB2[j], kD2[j]);
+    sc[j] = MODE == 2 ? scale[c] : 0.f; sh[j] = MODE == 2 ? shift[c] : 0.f;
   }
   const int64_t base = (int64_t)blockIdx.x * (256 * FLAT_BWD) + threadIdx.x;     // flat: see bn_apply_kernel
 #pragma unroll
   for (int u = 0; u < FLAT_BWD; ++u) {
     const int64_t i = base + u * 256;
     if (i >= nvec) break;
-    float g[8], xv[8], yv[8], o[8];
+    float g[8], xv[8], x2v[8], yv[8] = {}, o[8], o2[8];
+    unsigned m = 0;
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + i * 8)), g);
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8)), xv);
-    if (from_x) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = xv[j] * sc[j] + sh[j];
-    } else if (MODE == 3) {
-      const unsigned m = relu_mask[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = ((m >> j) & 1u) ? 1.f : 0.f;
-    } else if (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(y + i * 8), yv);
+    if constexpr (NORMS == 2) unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + i * 8)), x2v);
+    if constexpr (MODE == 3) m = relu_mask[i];
+    if constexpr (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(y + i * 8), yv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float dz = (MODE != 0 && !(yv[j] > 0.f)) ? 0.f : g[j];
+      const float dz = isic_bn_bwd::gate<MODE>(g[j], xv[j], yv[j], sc[j], sh[j], m, j);
       g[j] = dz;
-      o[j] = kA[j] * dz + (kB[j] * xv[j] + kD[j]);
+      o[j] = isic_bn_bwd::dx(kA[j], kB[j], kD[j], xv[j], dz);
+      if constexpr (NORMS == 2) o2[j] = isic_bn_bwd::dx(kA2[j], kB2[j], kD2[j], x2v[j], dz);
     }
     // streaming stores: the tensors are far larger than L2 / MALL and are not read again by this kernel
     __builtin_nontemporal_store(pack8(o), reinterpret_cast<u32x4*>(dx + i * 8));
-    if (d_residual) __builtin_nontemporal_store(pack8(g), reinterpret_cast<u32x4*>(d_residual + i * 8));
-  }
-}
-
-// ---------------------------------------------------------------- downsample block: bn2 and the shortcut's BatchNorm together
-// Both norms of a downsample block receive the same gradient dz = mask ? dy : 0 (out = relu(bn2(c2) + bn_d(cd))).  The pair
-// kernels are bn_bwd_reduce_kernel<3> + bn_bwd_reduce_kernel<0> and bn_bwd_apply_kernel<3> + bn_bwd_apply_kernel<0> in one
-// walk each: same launch geometry, same thread -> (row, channel group) mapping, same expressions in the same order, so
-// every partial sum and every output is the value those launches give -- and dz is never written out and read back.
-__global__ __launch_bounds__(256) void bn_bwd_reduce_pair_kernel(const unsigned short* __restrict__ dy,
-                                                                  const unsigned short* __restrict__ x,
-                                                                  const unsigned char* __restrict__ relu_mask,
-                                                                  const float* __restrict__ mean,
-                                                                  const float* __restrict__ rstd,
-                                                                  const unsigned short* __restrict__ x2,
-                                                                  const float* __restrict__ mean2,
-                                                                  const float* __restrict__ rstd2, int64_t rows, int C,
-                                                                  double* __restrict__ sum_dzx, double* __restrict__ sum_dz,
-                                                                  double* __restrict__ sum_dzx2) {
-  const int tid = threadIdx.x, cgs = C >> 3, cg = tid % cgs, rl = tid / cgs, rls = 256 / cgs;
-  float acc[3][8], mu[8], rs[8], mu2[8], rs2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    acc[0][j] = 0.f; acc[1][j] = 0.f; acc[2][j] = 0.f;
-    mu[j] = mean[cg * 8 + j]; rs[j] = rstd[cg * 8 + j]; mu2[j] = mean2[cg * 8 + j]; rs2[j] = rstd2[cg * 8 + j];
-  }
-  const int64_t per_block = ((rows + gridDim.x - 1) / gridDim.x + rls - 1) / rls * rls;   // contiguous rows: bn_bwd_reduce_kernel
-  const int64_t r_end = min(rows, ((int64_t)blockIdx.x + 1) * per_block);
-#pragma unroll 2
-  for (int64_t r = (int64_t)blockIdx.x * per_block + rl; r < r_end; r += rls) {
-    float g[8], xv[8], x2v[8];
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + r * C + cg * 8)), g);
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + r * C + cg * 8)), xv);
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + r * C + cg * 8)), x2v);
-    const unsigned m = relu_mask[r * (C >> 3) + cg];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float dz = ((m >> j) & 1u) ? g[j] : 0.f;
-      // fmaf spelled out: the kernels this replaces compile to one fused multiply-add per term, and a bit-identical sum
-      // must not depend on the compiler contracting every one of these the same way
-      acc[0][j] = fmaf(dz, (xv[j] - mu[j]) * rs[j], acc[0][j]);
-      acc[1][j] += dz;
-      acc[2][j] = fmaf(dz, (x2v[j] - mu2[j]) * rs2[j], acc[2][j]);
-    }
-  }
-  double* const dst[3] = {sum_dzx, sum_dz, sum_dzx2};
-  block_reduce_to_global<3>(acc, C, dst);
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(
-    const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x, const unsigned char* __restrict__ relu_mask,
-    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-    const double* __restrict__ sum_dzx, const double* __restrict__ sum_dz, const unsigned short* __restrict__ x2,
-    const float* __restrict__ mean2, const float* __restrict__ rstd2, const float* __restrict__ gamma2,
-    const double* __restrict__ sum_dzx2, int64_t rows, int C, unsigned short* __restrict__ dx,
-    unsigned short* __restrict__ dx2, float* __restrict__ dgamma_f32, float* __restrict__ dbeta_f32,
-    float* __restrict__ dgamma2_f32, float* __restrict__ dbeta2_f32) {
-  const int cgs = C >> 3;
-  const int64_t nvec = rows * cgs;
-  const float inv_rows = 1.f / (float)rows;
-  if (blockIdx.x == 0) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      if (dgamma_f32) { dgamma_f32[c] += (float)sum_dzx[c]; dbeta_f32[c] += (float)sum_dz[c]; }
-      if (dgamma2_f32) { dgamma2_f32[c] += (float)sum_dzx2[c]; dbeta2_f32[c] += (float)sum_dz[c]; }
-    }
-  }
-  const int cg = threadIdx.x % cgs;
-  float kA[8], kB[8], kD[8], kA2[8], kB2[8], kD2[8];      // as in bn_bwd_apply_kernel, once per norm; sum dz is shared
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    const float k2 = (float)sum_dz[c] * inv_rows;
-    {
-      const float mu = mean[c], rs = rstd[c], k1 = gamma[c] * rs, k3 = (float)sum_dzx[c] * inv_rows;
-      kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * fmaf(k3 * rs, mu, -k2);       // fmaf: see bn_bwd_reduce_pair_kernel
-    }
-    {
-      const float mu = mean2[c], rs = rstd2[c], k1 = gamma2[c] * rs, k3 = (float)sum_dzx2[c] * inv_rows;
-      kA2[j] = k1; kB2[j] = -k1 * k3 * rs; kD2[j] = k1 * fmaf(k3 * rs, mu, -k2);
-    }
-  }
-  const int64_t base = (int64_t)blockIdx.x * (256 * FLAT_BWD) + threadIdx.x;     // flat: see bn_apply_kernel
-#pragma unroll
-  for (int u = 0; u < FLAT_BWD; ++u) {
-    const int64_t i = base + u * 256;
-    if (i >= nvec) break;
-    float g[8], xv[8], x2v[8], o[8], o2[8];
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + i * 8)), g);
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8)), xv);
-    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x2 + i * 8)), x2v);
-    const unsigned m = relu_mask[i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float dz = ((m >> j) & 1u) ? g[j] : 0.f;
-      o[j] = fmaf(kA[j], dz, fmaf(kB[j], xv[j], kD[j]));
-      o2[j] = fmaf(kA2[j], dz, fmaf(kB2[j], x2v[j], kD2[j]));
-    }
-    __builtin_nontemporal_store(pack8(o), reinterpret_cast<u32x4*>(dx + i * 8));
-    __builtin_nontemporal_store(pack8(o2), reinterpret_cast<u32x4*>(dx2 + i * 8));
+    if constexpr (NORMS == 2) __builtin_nontemporal_store(pack8(o2), reinterpret_cast<u32x4*>(dx2 + i * 8));
+    else if (d_residual) __builtin_nontemporal_store(pack8(g), reinterpret_cast<u32x4*>(d_residual + i * 8));
   }
 }
 
@@ -457,9 +357,8 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_reduce_kernel(const unsigned 
       unpack8(xr[p], xv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float dz = (in && xv[j] * sc[j] + sh[j] > 0.f) ? g[p][j] : 0.f;
-        acc[0][j] += dz * ((xv[j] - mu[j]) * rs[j]);
-        acc[1][j] += dz;
+        const float dz = in ? isic_bn_bwd::gate<2>(g[p][j], xv[j], 0.f, sc[j], sh[j], 0u, 0) : 0.f;
+        isic_bn_bwd::accumulate(dz, xv[j], mu[j], rs[j], acc[0][j], acc[1][j]);
       }
     }
   }
@@ -474,21 +373,15 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_apply_kernel(
     const float* __restrict__ scale, const float* __restrict__ shift, unsigned short* __restrict__ dx,
     float* __restrict__ dgamma_f32, float* __restrict__ dbeta_f32) {
   const int C = geom.C, cgs = C >> 3;
-  const float inv_rows = 1.f / (float)((int64_t)N * geom.H * geom.W);
-  if (blockIdx.x == 0 && dgamma_f32) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      dgamma_f32[c] += (float)dgamma[c];
-      dbeta_f32[c] += (float)dbeta[c];
-    }
-  }
+  const float inv_rows = isic_bn_bwd::inv_count((int64_t)N * geom.H * geom.W);
+  if (blockIdx.x == 0 && dgamma_f32)
+    for (int c = threadIdx.x; c < C; c += blockDim.x) isic_bn_bwd::fold(c, dgamma, dbeta, dgamma_f32, dbeta_f32);
   const int cg = threadIdx.x % cgs;           // (the grid stride is a multiple of C/8)
-  float kA[8], kB[8], kD[8], sc[8], sh[8];              // as in bn_bwd_apply_kernel
+  float kA[8], kB[8], kD[8], sc[8], sh[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = cg * 8 + j;
-    const float mu = mean[c], rs = rstd[c], k1 = gamma[c] * rs;
-    const float k2 = (float)dbeta[c] * inv_rows, k3 = (float)dgamma[c] * inv_rows;
-    kA[j] = k1; kB[j] = -k1 * k3 * rs; kD[j] = k1 * (k3 * rs * mu - k2);
+    isic_bn_bwd::constants(mean[c], rstd[c], gamma[c], (float)dgamma[c], (float)dbeta[c], inv_rows, kA[j], kB[j], kD[j]);
     sc[j] = scale[c]; sh[j] = shift[c];
   }
   const int Hb = (geom.H + 1) >> 1, Wb = (geom.W + 1) >> 1;
@@ -515,8 +408,8 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_apply_kernel(
       unpack8(xr[p], xv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float dz = (xv[j] * sc[j] + sh[j] > 0.f) ? g[p][j] : 0.f;
-        o[j] = kA[j] * dz + (kB[j] * xv[j] + kD[j]);
+        const float dz = isic_bn_bwd::gate<2>(g[p][j], xv[j], 0.f, sc[j], sh[j], 0u, 0);
+        o[j] = isic_bn_bwd::dx(kA[j], kB[j], kD[j], xv[j], dz);
       }
       __builtin_nontemporal_store(pack8(o), reinterpret_cast<u32x4*>(dx + off));
     }
@@ -910,6 +803,48 @@ inline int grid_for(int64_t n, int block, int cap = 8192) {
 }
 inline bool bn_c_ok(int C) { return C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0; }
 
+// The flat BatchNorm-backward passes: every isic_bn_bwd_reduce* / _apply* entry but the pooled ones checks its own
+// arguments and launches through these.  `mode`: bn_bwd_reduce_kernel's MODE; x2 != nullptr: the pair (mode 3 only).
+int launch_bn_bwd_reduce(int mode, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const uint8_t* relu_mask,
+                         const float* mean, const float* rstd, const float* scale, const float* shift, const uint16_t* x2,
+                         const float* mean2, const float* rstd2, int64_t rows, int C, double* sum_dzx, double* sum_dz,
+                         double* sum_dzx2, void* stream) {
+  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
+  const int rls = 256 / (C / 8);
+  const dim3 grid(grid_for(rows, rls * 8, 2048));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), dy, x, y, relu_mask, mean, rstd, scale, shift, x2, mean2,
+                       rstd2, rows, C, sum_dzx, sum_dz, sum_dzx2);
+  };
+  if (x2) go(bn_bwd_reduce_kernel<3, 2>);
+  else if (mode == 0) go(bn_bwd_reduce_kernel<0, 1>);
+  else if (mode == 1) go(bn_bwd_reduce_kernel<1, 1>);
+  else if (mode == 2) go(bn_bwd_reduce_kernel<2, 1>);
+  else go(bn_bwd_reduce_kernel<3, 1>);
+  return isic_launch_status();
+}
+
+int launch_bn_bwd_apply(int mode, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const uint8_t* relu_mask,
+                        const float* mean, const float* rstd, const float* gamma, const double* sum_dzx, const double* sum_dz,
+                        const float* scale, const float* shift, const uint16_t* x2, const float* mean2, const float* rstd2,
+                        const float* gamma2, const double* sum_dzx2, int64_t rows, int C, uint16_t* dx, uint16_t* d_residual,
+                        uint16_t* dx2, float* dgamma_f32, float* dbeta_f32, float* dgamma2_f32, float* dbeta2_f32,
+                        void* stream) {
+  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
+  const dim3 grid(grid_for(rows * (C / 8), 256 * FLAT_BWD, STREAM_CAP));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), dy, x, y, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz,
+                       scale, shift, x2, mean2, rstd2, gamma2, sum_dzx2, rows, C, dx, d_residual, dx2, dgamma_f32, dbeta_f32,
+                       dgamma2_f32, dbeta2_f32);
+  };
+  if (x2) go(bn_bwd_apply_kernel<3, 2>);
+  else if (mode == 0) go(bn_bwd_apply_kernel<0, 1>);
+  else if (mode == 1) go(bn_bwd_apply_kernel<1, 1>);
+  else if (mode == 2) go(bn_bwd_apply_kernel<2, 1>);
+  else go(bn_bwd_apply_kernel<3, 1>);
+  return isic_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -987,24 +922,15 @@ int isic_bn_bwd_reduce_bf16(const uint16_t* dy, const uint16_t* x, const uint16_
   ISIC_CHECK_ARG(dy && x && mean && rstd && dgamma && dbeta && rows > 0 && C > 0);
   ISIC_CHECK_ARG((scale == nullptr) == (shift == nullptr));
   ISIC_CHECK_ARG(!relu || y || scale);
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;
-  const int rls = 256 / (C / 8);
-  const dim3 grid(grid_for(rows, rls * 8, 2048));
-#define ISIC_REDUCE(M) hipLaunchKernelGGL(bn_bwd_reduce_kernel<M>, grid, dim3(256), 0, as_stream(stream), dy, x, y, nullptr, \
-                                          mean, rstd, rows, C, relu, scale, shift, dgamma, dbeta)
-  if (!relu) ISIC_REDUCE(0); else if (scale) ISIC_REDUCE(2); else ISIC_REDUCE(1);
-#undef ISIC_REDUCE
-  return isic_launch_status();
+  return launch_bn_bwd_reduce(!relu ? 0 : scale ? 2 : 1, dy, x, y, nullptr, mean, rstd, scale, shift, nullptr, nullptr, nullptr,
+                              rows, C, dgamma, dbeta, nullptr, stream);
 }
 
 int isic_bn_bwd_reduce_mask_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
                                  const float* rstd, int64_t rows, int C, double* dgamma, double* dbeta, void* stream) {
   ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && dgamma && dbeta && rows > 0 && C > 0);
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;
-  const int rls = 256 / (C / 8);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<3>, dim3(grid_for(rows, rls * 8, 2048)), dim3(256), 0, as_stream(stream), dy, x,
-                     nullptr, relu_mask, mean, rstd, rows, C, 1, nullptr, nullptr, dgamma, dbeta);
-  return isic_launch_status();
+  return launch_bn_bwd_reduce(3, dy, x, nullptr, relu_mask, mean, rstd, nullptr, nullptr, nullptr, nullptr, nullptr, rows, C,
+                              dgamma, dbeta, nullptr, stream);
 }
 
 int isic_bn_bwd_reduce_pooled_bf16(const uint8_t* argmax, const uint16_t* dy_pooled, const uint16_t* x, const float* mean,
@@ -1028,14 +954,9 @@ int isic_bn_bwd_apply_bf16(const uint16_t* dy, const uint16_t* x, const uint16_t
   ISIC_CHECK_ARG((scale == nullptr) == (shift == nullptr));
   ISIC_CHECK_ARG(!relu || y || scale);
   ISIC_CHECK_ARG((dgamma_f32 == nullptr) == (dbeta_f32 == nullptr));
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
-  const int64_t nvec = rows * (C / 8);
-  const dim3 grid(grid_for(nvec, 256 * FLAT_BWD, STREAM_CAP));
-#define ISIC_APPLY(M) hipLaunchKernelGGL(bn_bwd_apply_kernel<M>, grid, dim3(256), 0, as_stream(stream), dy, x, y, nullptr, mean, \
-                                         rstd, gamma, dgamma, dbeta, rows, C, relu, scale, shift, dx, d_residual, dgamma_f32, dbeta_f32)
-  if (!relu) ISIC_APPLY(0); else if (scale) ISIC_APPLY(2); else ISIC_APPLY(1);
-#undef ISIC_APPLY
-  return isic_launch_status();
+  return launch_bn_bwd_apply(!relu ? 0 : scale ? 2 : 1, dy, x, y, nullptr, mean, rstd, gamma, dgamma, dbeta, scale, shift, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, rows, C, dx, d_residual, nullptr, dgamma_f32, dbeta_f32, nullptr,
+                             nullptr, stream);
 }
 
 int isic_bn_bwd_apply_mask_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
@@ -1044,12 +965,9 @@ int isic_bn_bwd_apply_mask_bf16(const uint16_t* dy, const uint16_t* x, const uin
                                 float* dbeta_f32, void* stream) {
   ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && gamma && dgamma && dbeta && dx && rows > 0 && C > 0 && C % 8 == 0);
   ISIC_CHECK_ARG((dgamma_f32 == nullptr) == (dbeta_f32 == nullptr));
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
-  const int64_t nvec = rows * (C / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<3>, dim3(grid_for(nvec, 256 * FLAT_BWD, STREAM_CAP)), dim3(256), 0, as_stream(stream), dy, x, nullptr,
-                     relu_mask, mean, rstd, gamma, dgamma, dbeta, rows, C, 1, nullptr, nullptr, dx, d_residual, dgamma_f32,
-                     dbeta_f32);
-  return isic_launch_status();
+  return launch_bn_bwd_apply(3, dy, x, nullptr, relu_mask, mean, rstd, gamma, dgamma, dbeta, nullptr, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, rows, C, dx, d_residual, nullptr, dgamma_f32, dbeta_f32, nullptr, nullptr,
+                             stream);
 }
 
 int isic_bn_bwd_reduce_pair_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
@@ -1057,11 +975,8 @@ int isic_bn_bwd_reduce_pair_bf16(const uint16_t* dy, const uint16_t* x, const ui
                                  int C, double* sum_dzx, double* sum_dz, double* sum_dzx2, void* stream) {
   ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && x2 && mean2 && rstd2 && sum_dzx && sum_dz && sum_dzx2 && rows > 0 &&
                  C > 0);
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;
-  const int rls = 256 / (C / 8);
-  hipLaunchKernelGGL(bn_bwd_reduce_pair_kernel, dim3(grid_for(rows, rls * 8, 2048)), dim3(256), 0, as_stream(stream), dy, x,
-                     relu_mask, mean, rstd, x2, mean2, rstd2, rows, C, sum_dzx, sum_dz, sum_dzx2);
-  return isic_launch_status();
+  return launch_bn_bwd_reduce(3, dy, x, nullptr, relu_mask, mean, rstd, nullptr, nullptr, x2, mean2, rstd2, rows, C, sum_dzx,
+                              sum_dz, sum_dzx2, stream);
 }
 
 int isic_bn_bwd_apply_pair_bf16(const uint16_t* dy, const uint16_t* x, const uint8_t* relu_mask, const float* mean,
@@ -1072,12 +987,8 @@ int isic_bn_bwd_apply_pair_bf16(const uint16_t* dy, const uint16_t* x, const uin
   ISIC_CHECK_ARG(dy && x && relu_mask && mean && rstd && gamma && sum_dzx && sum_dz && x2 && mean2 && rstd2 && gamma2 &&
                  sum_dzx2 && dx && dx2 && rows > 0 && C > 0 && C % 8 == 0);
   ISIC_CHECK_ARG((dgamma_f32 == nullptr) == (dbeta_f32 == nullptr) && (dgamma2_f32 == nullptr) == (dbeta2_f32 == nullptr));
-  if (!bn_c_ok(C)) return ISIC_ERR_UNSUPPORTED;   // per-thread channel constants: C/8 must divide the 256-thread block
-  const int64_t nvec = rows * (C / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_pair_kernel, dim3(grid_for(nvec, 256 * FLAT_BWD, STREAM_CAP)), dim3(256), 0,
-                     as_stream(stream), dy, x, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, x2, mean2, rstd2, gamma2, sum_dzx2,
-                     rows, C, dx, dx2, dgamma_f32, dbeta_f32, dgamma2_f32, dbeta2_f32);
-  return isic_launch_status();
+  return launch_bn_bwd_apply(3, dy, x, nullptr, relu_mask, mean, rstd, gamma, sum_dzx, sum_dz, nullptr, nullptr, x2, mean2, rstd2,
+                             gamma2, sum_dzx2, rows, C, dx, nullptr, dx2, dgamma_f32, dbeta_f32, dgamma2_f32, dbeta2_f32, stream);
 }
 
 int isic_bn_bwd_apply_pooled_bf16(const uint8_t* argmax, const uint16_t* dy_pooled, const uint16_t* x, const float* mean,
