@@ -600,8 +600,6 @@ int isic_bn_bwd_apply_pooled_bf16(const uint8_t* argmax, const uint16_t* dy_pool
 /* Global average pool NHWC bf16 -> [N,C] fp32, and backward -> bf16. */
 int isic_avgpool_fwd_bf16(const uint16_t* x, float* y, int N, int HW, int C, void* stream);
 int isic_avgpool_bwd_bf16(const float* dy, uint16_t* dx, int N, int HW, int C, void* stream);
-/* a += b on bf16 tensors (gradient join of a residual block); n % 8 == 0. */
-int isic_add_bf16(uint16_t* a, const uint16_t* b, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------- ViT-S/16 patch encoder, fp16 (BASELINE.json configs[4])
  * The reference's frozen encoder is an un-vendored ConvMAE conv-ViT (save_latent.py:42-60: eval(), no_grad,

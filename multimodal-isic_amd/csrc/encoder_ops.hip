@@ -726,17 +726,6 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, unsigned short*
   }
 }
 
-__global__ void add_bf16_kernel(unsigned short* __restrict__ a, const unsigned short* __restrict__ b, int64_t nvec) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-    float fa[8], fb[8];
-    unpack8(*reinterpret_cast<const u32x4*>(a + i * 8), fa);
-    unpack8(*reinterpret_cast<const u32x4*>(b + i * 8), fb);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fa[j] += fb[j];
-    *reinterpret_cast<u32x4*>(a + i * 8) = pack8(fa);
-  }
-}
-
 // NCHW (fp32 or bf16) -> NHWC with C padded to 4, bf16.  One thread per output pixel.
 __global__ void nchw_to_nhwc4_kernel(const void* __restrict__ in, int in_is_bf16, unsigned short* __restrict__ out,
                                      int64_t npix_total, int C, int64_t HW) {
@@ -1040,6 +1029,7 @@ int isic_bn_relu_maxpool3x3s2_fwd_sel_bf16(const uint16_t* x, const float* scale
 int isic_maxpool3x3s2_bwd_bf16(const uint8_t* argmax, const uint16_t* dy, uint16_t* dx, int N, int H, int W, int C,
                                int Ho, int Wo, void* stream) {
   ISIC_CHECK_ARG(argmax && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0);
+  ISIC_CHECK_ARG(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1);
   const int64_t nvec = (int64_t)N * H * W * (C / 8);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(nvec, 256)), dim3(256), 0, as_stream(stream), argmax, dy, dx, N,
                      H, W, C, Ho, Wo);
@@ -1057,13 +1047,6 @@ int isic_avgpool_bwd_bf16(const float* dy, uint16_t* dx, int N, int HW, int C, v
   const int64_t total = (int64_t)N * HW * C;
   hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), dy, dx, total, HW,
                      C);
-  return isic_launch_status();
-}
-
-int isic_add_bf16(uint16_t* a, const uint16_t* b, int64_t n, void* stream) {
-  ISIC_CHECK_ARG(a && b && n >= 0 && n % 8 == 0);
-  if (n == 0) return ISIC_OK;
-  hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, as_stream(stream), a, b, n / 8);
   return isic_launch_status();
 }
 

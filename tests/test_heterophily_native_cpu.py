@@ -18,7 +18,7 @@ def test_spectral_entry_points_are_exported_and_declared():
         assert name in L.public and hasattr(cdll, name), name
     assert int(re.search(r"#define ISIC_SPECTRAL_MAX_NODES (\d+)", text).group(1)) == 196
     assert int(re.search(r"#define ISIC_SEGMENT_MAX_LEN (\d+)", text).group(1)) == 16384
-    assert len(L.public) == 97
+    assert len(L.public) == 96
     assert L.fn["isic_abi_version"]() == 1
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from encoder_ops_ref import pool_restatement as _pool_restatement
 from test_encoder_gpu import BF, DEV, bf16_close, from_nhwc, krsc, rb
 
 pytestmark = pytest.mark.gpu
@@ -62,20 +63,6 @@ def test_stem_forward_register_epilogue(shape):
                 bound = 8 * 2.0 ** -24 * vals.abs().sum(0) + 1e-12
                 assert bool((err <= bound).all()), f"stem fused {what} {shape}: {float(err.max()):.3e} > {float(bound.min()):.3e}"
     assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
-
-
-def _pool_restatement(x, scale, shift, Ho, Wo):
-    """relu(x * scale + shift) in fp32 on the fused form, rounded to bf16, 3x3/2 windows scanned row-major with the first
-    maximum winning.  (+ 0.0 makes a -0.0 of the ReLU +0.0, as the device's max does.)"""
-    N, H, W, C = x.shape
-    xf = x.float()
-    f = torch.relu(torch.addcmul(shift.view(1, 1, 1, C), xf, scale.view(1, 1, 1, C))).to(BF).float() + 0.0
-    fp = F.pad(f, (0, 0, 1, 2, 1, 2), value=-1.0)                # outside the image: below every value after the ReLU
-    xp = F.pad(xf, (0, 0, 1, 2, 1, 2), value=float("nan"))
-    taps_f = torch.stack([fp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2, :] for kh in range(3) for kw in range(3)])
-    taps_x = torch.stack([xp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2, :] for kh in range(3) for kw in range(3)])
-    am = taps_f.argmax(dim=0, keepdim=True)                      # the first of several maxima
-    return taps_f.gather(0, am)[0], am[0].to(torch.uint8), taps_x.gather(0, am)[0]
 
 
 @pytest.mark.parametrize("hw", [(16, 16),     # Hp = Wp = 8
